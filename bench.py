@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- Mevents/s to depth frame on synthetic 640x480 / 1 M-event frames (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -15,17 +15,30 @@ N > 1: every rank runs the same workload on its own GPU with its own frames (the
 collective) -> "scaling": "weak"; value = events of all ranks / max-over-ranks time.
 
 How the K steps are timed: W warm-up steps, then a fixed wall-clock pre-warm (PREWARM_S, so that clocks and caches are in
-the same state whatever K and W are), then R blocks of EXACTLY K steps, each bracketed by barrier + synchronize on both
-sides; per block the MAX over ranks is taken and the MEDIAN block is reported (R is chosen so that the blocks together
-last about TARGET_TIMED_S; R, and the fastest / slowest block, are in the JSON line).  ms_per_step = median block / K.
+the same state whatever K and W are), then ONE block of exactly K steps, bracketed by barrier + synchronize on both sides,
+the MAX over ranks taken.  ms_per_step = block / K.
+
+A plain run does only that: set up, warm up, time the K steps, write the outputs (--dump-outputs), print the line.
+--full adds everything else, as before: the parity gate against the CPU oracle, the per-kernel roofline pass (and its
+rocprofv3 counter runs), the CPU baseline, the same frames under other engine settings, the host / ingest legs, the
+compact legs of the other BASELINE configs and, with N > 1, the sharded C-10M frame behind the replicas; and the headline
+is then the MEDIAN of R blocks of exactly K steps each (R chosen so that the blocks together last about TARGET_TIMED_S;
+R and the fastest / slowest block are in the line).
+
+--dump-outputs DIR: after the timed steps, what the last timed step computed -- the depth frames (f32) and BGR frames (u8)
+of its group, as the caller of the timed call receives them -- goes to DIR/*.npy as float32, 64 MB at most in all: an array
+that does not fit whole is written as a fixed, seeded sample of its pixels plus their flat indices (rank 0's outputs).
 
 Other workloads (never mixed into the default line):
     --graph    BASELINE configs[4]: 60 frames x 1 M events replayed from one captured hipGraph: throughput + latency
     --sharded  BASELINE configs[3]: C-10M (1280x720, 10 M events/frame) sharded by event index over the ranks, packed-key
                frame MAX-all-reduced over RCCL; value = events / max-rank time, collective time reported separately
 
-Rank 0 prints ONE JSON line with the extra objects `roofline` (dominant kernel, timed with HIP events attached to its own
-dispatch, BEFORE the timed blocks) and `cpu_baseline` (the NumPy port of the reference path from oracle/, 1 host core).
+(These modes report in full whether or not --full is given.)
+
+Rank 0 prints ONE JSON line; with --full it carries the extra objects `roofline` (dominant kernel, timed with HIP events
+attached to its own dispatch, BEFORE the timed blocks) and `cpu_baseline` (the NumPy port of the reference path from oracle/,
+1 host core).
 """
 from __future__ import annotations
 
@@ -53,7 +66,7 @@ sys.path.insert(0, ROOT)
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200, help="timed steps per block; a step = one group of --batch frames")
+    ap.add_argument("--steps", type=int, default=200, help="timed steps (--full: per block); a step = one group of --batch frames")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--slots", type=int, default=int(os.environ.get("XM_SLOTS", "0")),
                     help="frames in flight per GPU (key frame + state each); default 4 (one stream per hardware queue), "
@@ -107,7 +120,12 @@ def parse_args():
     ap.add_argument("--no-other-configs", action="store_true", help="skip the compact legs of the other BASELINE configs (esl, graph60, sharded_c10m)")
     ap.add_argument("--lib-option", action="append", default=[], metavar="NAME=VALUE",
                     help="variant switch of the library for experiments (xm_debug_option), e.g. XM_COLS=0, XM_K2_PIPE=0; repeatable")
-    ap.add_argument("--single-block", action="store_true", help="one timed block of K steps (no repetition)")
+    ap.add_argument("--single-block", action="store_true", help="--full: one timed block of K steps (no repetition)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: parity gate, roofline pass, CPU baseline, other engine settings, host / ingest legs, "
+                         "the other BASELINE configs, the sharded leg behind N > 1 replicas; median of repeated timed blocks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs to DIR/*.npy (float32, at most 64 MB in all)")
     ap.add_argument("--no-pmc", action="store_true",
                     help="do not measure roofline.traffic in this run (two short child runs under rocprofv3 --pmc, ~30 s); the committed "
                          "profiles/pmc_traffic.json is quoted instead, with its age")
@@ -161,7 +179,7 @@ def dry_run(args, rank, world):
         # XM_BENCH_DRY_LEG = "ok" | "hang:<rank>" | "die:<rank>": a stand-in for the sharded leg behind the replicas -- two
         # collectives, between which the named rank goes to sleep for ever / leaves -- under the very guard the real leg runs under
         mode = os.environ.get("XM_BENCH_DRY_LEG")
-        if mode:
+        if mode and args.full:
             kind, _, who = mode.partition(":")
 
             def fake_leg():
@@ -262,6 +280,9 @@ def main():
         return dry_run(args, rank, world)
     if args.esl_stream_child:
         return esl_stream_child(args, local_rank)
+    if args.dump_outputs and (args.sharded or args.esl or args.graph):
+        print(json.dumps({"error": "--dump-outputs writes the default workload's outputs (not --graph / --sharded / --esl)"}), flush=True)
+        sys.exit(2)
 
     import torch
 
@@ -316,7 +337,7 @@ def main():
             # by event index over the ranks (BASELINE configs[3]) -- is measured behind them on the same ranks (never `value`): every
             # rank takes part, rank 0 keeps the figures.  Rank 0 holds the finished replicas' line by now: whatever happens inside
             # the leg, that line is printed (sharded_leg_guarded).
-            if (world > 1 or os.environ.get("XM_BENCH_FORCE_SHARDED_LEG") == "1") and dist is not None and not args.no_other_modes:
+            if (world > 1 or os.environ.get("XM_BENCH_FORCE_SHARDED_LEG") == "1") and dist is not None and args.full and not args.no_other_modes:
                 import copy  # (XM_BENCH_FORCE_SHARDED_LEG + XM_BENCH_FORCE_DIST: the tests exercise this leg on a one-GPU box)
                 if rank == 0:
                     out["n_gpus"], out["rccl_ranks_seen"] = world, ranks_seen

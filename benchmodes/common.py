@@ -81,6 +81,36 @@ def n_blocks_for(args, est_step_s):
     return int(min(400, max(3, round(TARGET_TIMED_S / max(args.steps * est_step_s, 1e-6)))))
 
 
+DUMP_LIMIT_BYTES = 64_000_000  # --dump-outputs: all files together
+DUMP_SEED = 20240  # the pixel sample of an output that does not fit whole
+
+
+def dump_outputs(dirname, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: arrays = [(name, array of shape (frames, H, W, ...))], in order of precedence.  Each is written as float32,
+    whole (DIR/<name>.npy) while it fits in what is left of `limit`, otherwise as a fixed, seeded sample of its pixels
+    (DIR/<name>_sample.npy, shape (n, ...)) and their flat indices into (frames, H, W) (DIR/<name>_sample_pixel.npy, float64).
+    Returns {file name: bytes}."""
+    os.makedirs(dirname, exist_ok=True)
+    left, written = limit, {}
+    for name, a in arrays:
+        a = np.asarray(a)
+        pixels = int(np.prod(a.shape[:3]))
+        per_pixel = int(np.prod(a.shape[3:], dtype=np.int64)) * 4
+        if pixels * per_pixel <= left - 4096:
+            files = {name: a.astype(np.float32)}
+        else:
+            n = min(pixels, max(0, (left - 8192) // (per_pixel + 8)))
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(pixels, n, replace=False))
+            files = {name + "_sample": a.reshape((pixels,) + a.shape[3:])[idx].astype(np.float32),
+                     name + "_sample_pixel": idx.astype(np.float64)}
+        for fn, v in files.items():
+            path = os.path.join(dirname, fn + ".npy")
+            np.save(path, v)
+            written[fn + ".npy"] = os.path.getsize(path)
+            left -= written[fn + ".npy"]
+    return written
+
+
 def depth_parity(got, ref_depth):
     nz = ref_depth != 0
     rel = float((np.abs(got[nz] - ref_depth[nz]) / ref_depth[nz]).max(initial=0.0))

@@ -11,7 +11,7 @@ import numpy as np
 from .other import other_config_legs
 from .common import leg_clock
 from .common import (BENCH_PY, HBM_PEAK_GBS, PREWARM_S, ROOT, TARGET_TIMED_S, Timer, apply_measured_traffic, cpu_baseline_leg, depth_parity,
-                     n_blocks_for, parity_ok, pipeline_fractions, roofline_dict, roofline_of, traffic_file_age)
+                     dump_outputs, n_blocks_for, parity_ok, pipeline_fractions, roofline_dict, roofline_of, traffic_file_age)
 
 
 # =====================================================================================================================
@@ -99,10 +99,10 @@ def bench_stream(args, torch, dist, dev, rank, local_rank, world):
     step = make_step(eng, depth_out, bgr_out, n_out, B)
 
     leg_clock('frames rendered + uploaded')
-    # ---- parity gate before any timing: first (and last) frame of step 0 against the CPU oracle (rank 0) ----------------
+    # ---- parity gate before any timing (--full): first (and last) frame of step 0 against the CPU oracle (rank 0) ---------
     parity = None
     O = None
-    if rank == 0:
+    if rank == 0 and args.full:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import xmaps_oracle as O  # checker + cpu_baseline only
         step(0)
@@ -126,11 +126,11 @@ def bench_stream(args, torch, dist, dev, rank, local_rank, world):
 
     tm = Timer(torch, dist, dev, eng.sync)
     leg_clock('parity gate')
-    # ---- W warm-up steps, fixed pre-warm, per-kernel profile pass, short re-warm, R timed blocks of exactly K steps ----
+    # ---- W warm-up steps, fixed pre-warm, per-kernel profile pass (--full), short re-warm, timed block(s) of exactly K steps ----
     run_steps(step, args.warmup)
     est = tm.prewarm(step, PREWARM_S)
     roofline = alg = pt = wl = None
-    if rank == 0:
+    if rank == 0 and args.full:
         group = None
         if B:
             offs_p = np.arange(B + 1, dtype=np.uint64) * n_ev
@@ -144,30 +144,72 @@ def bench_stream(args, torch, dist, dev, rank, local_rank, world):
                                             (depth_out[0].data_ptr(), None if bgr_out is None else bgr_out[0].data_ptr()),
                                             tables, camera, bgr_b, world, group)
     est = tm.agree(tm.prewarm(step, 0.1))
-    R = n_blocks_for(args, est)
+    R = n_blocks_for(args, est) if args.full else 1
     el, enq = tm.blocks(lambda: run_steps(step, args.steps), R)
     elapsed = float(np.median(el))
     total_events = float(n_ev) * fps * args.steps * world
     value = total_events / elapsed / 1e6
     ms_per_step = elapsed / args.steps * 1e3
     paths = eng.path_counts()
+    if args.dump_outputs and rank == 0:
+        # the last timed step (index steps - 1 of the block) wrote these output slots; nothing has run since its synchronize
+        last = args.steps - 1
+        o = (last % (n_out // B)) * B if B else last % n_out
+        sl = slice(o, o + max(B, 1))
+        outs = [("depth", depth_out[sl].cpu().numpy())] + ([] if bgr_out is None else [("bgr", bgr_out[sl].cpu().numpy())])
+        dump_outputs(args.dump_outputs, outs)
     # (N > 1: the path's real exchange step -- one 10 M-event frame sharded over the same ranks -- is measured by main() BEHIND this
     #  function, under a wall-clock guard, once rank 0 holds the finished replicas' line: sharded_leg_guarded)
     if rank != 0:
         eng.close()
         return None
+    frames_redone = eng.sorted_fallbacks()
+    out = {
+        "metric": "Mevents/s to depth frame, 640x480, 1M ev/frame", "value": round(value, 2), "unit": "Mevents/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 5),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "int64+f64",
+        "data": "synthetic",
+        "config": {"workload": "C-1M: synthetic 1M events/frame, 640x480 cam/proj, rect 1760x1320, 1xMI355X fused kernels"
+                   + (" (camera view)" if camera else " (projector view)"),
+                   "events_per_frame": n_ev, "frames_per_step": fps, "events_per_step": n_ev * fps, "frames_in_flight": slots,
+                   "outputs": "depth f32" + ("" if bgr_out is None else " + BGR u8"),
+                   "launch": (f"eager; a step = one group of {B} frames through ONE call (xm_process_batch: one set of multi-frame "
+                              f"launches, grid = frames x tiles), {slots // B} groups in flight, launches from the calling thread"
+                              if B else ("one frame per call, XM_FLAG_ADAPTIVE_BATCH (frames arriving while the GPU is busy are submitted as groups)"
+                                         if adaptive else "eager, one frame per call"
+                                         + ("" if args.no_launch_workers else "; XM_FLAG_LAUNCH_WORKERS (a launch thread per slot stream)"))),
+                   "inputs": "SoA x:u16 y:u16 t:i64 resident in HBM",
+                   "distinct_frames_resident": nf, "resident_set_MB": round(resident_mb, 1),
+                   "resident_set_vs_infinity_cache": "exceeds the 256 MiB MALL" if resident_mb > 268.4 else "fits the 256 MiB MALL",
+                   "k1_paths_frames": paths,
+                   "extrema": "XM_FLAG_GENERAL (K0 every frame)" if args.general else
+                              ("XM_FLAG_TIME_SORTED" if args.assume_sorted else
+                               "library default: (t[0], t[n-1]) verified on the device; groups take the column-tile K1 (boundary "
+                               "pass + plain-store u16 frame), single frames the compact 32-bit key frame; failing frames are "
+                               "redone with K0 on the 64-bit path"),
+                   "frames_redone_on_general_path": frames_redone},
+        "timing": {"prewarm_s": PREWARM_S, "blocks": int(R), "block_s_median": round(elapsed, 6),
+                   "block_s_min": round(float(el.min()), 6), "block_s_max": round(float(el.max()), 6),
+                   "note": ("R blocks of exactly `steps` steps, each bracketed by barrier + synchronize, max over ranks per block, "
+                            "median block reported" if args.full else
+                            "one block of exactly `steps` steps, bracketed by barrier + synchronize, max over ranks")
+                           + "; ms_per_step = one step = frames_per_step frames"},
+        "host_enqueue_us_per_step": round(float(np.median(enq)) / args.steps * 1e6, 2),
+    }
+    if not args.full:  # a plain run: the headline and nothing else
+        eng.close()
+        return out
 
     s_frame = elapsed / (args.steps * fps)  # seconds per frame, pipelined
     pipeline_fractions(roofline, alg, pt, wl, value, world, s_frame, fps,
                        helper_runs=bool(paths["general"] or paths["cols"] or args.general))
-    frames_redone = eng.sorted_fallbacks()
     # roofline.traffic from counters of THIS run (two short child runs of this very workload under rocprofv3 --pmc, one group at
     # a time) -- the committed profiles/pmc_traffic.json only when that is not possible, and then with its age
     if world == 1 and B and not args.no_pmc and not getattr(args, "as_leg", False) and os.environ.get("XM_BENCH_PMC_CHILD") != "1":
         from benchmodes.pmc import measure_traffic
         os.environ["XM_BENCH_PMC_CHILD"] = "1"
         try:
-            flags = ["--steps", "6", "--warmup", "2", "--groups-in-flight", "1", "--batch", str(B), "--no-cpu-baseline", "--no-other-modes",
+            flags = ["--full", "--steps", "6", "--warmup", "2", "--groups-in-flight", "1", "--batch", str(B), "--no-cpu-baseline", "--no-other-modes",
                      "--no-host-path", "--no-other-configs", "--single-block", "--no-pmc"] + (["--camera-perspective"] if camera else []) + \
                     (["--no-bgr"] if args.no_bgr else [])
             measured, detail = measure_traffic(BENCH_PY, flags)
@@ -334,37 +376,7 @@ def bench_stream(args, torch, dist, dev, rank, local_rank, world):
 
     if eng is not None:
         eng.close()
-    out = {
-        "metric": "Mevents/s to depth frame, 640x480, 1M ev/frame", "value": round(value, 2), "unit": "Mevents/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 5),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "int64+f64",
-        "data": "synthetic",
-        "config": {"workload": "C-1M: synthetic 1M events/frame, 640x480 cam/proj, rect 1760x1320, 1xMI355X fused kernels"
-                   + (" (camera view)" if camera else " (projector view)"),
-                   "events_per_frame": n_ev, "frames_per_step": fps, "events_per_step": n_ev * fps, "frames_in_flight": slots,
-                   "outputs": "depth f32" + ("" if bgr_out is None else " + BGR u8"),
-                   "launch": (f"eager; a step = one group of {B} frames through ONE call (xm_process_batch: one set of multi-frame "
-                              f"launches, grid = frames x tiles), {slots // B} groups in flight, launches from the calling thread"
-                              if B else ("one frame per call, XM_FLAG_ADAPTIVE_BATCH (frames arriving while the GPU is busy are submitted as groups)"
-                                         if adaptive else "eager, one frame per call"
-                                         + ("" if args.no_launch_workers else "; XM_FLAG_LAUNCH_WORKERS (a launch thread per slot stream)"))),
-                   "inputs": "SoA x:u16 y:u16 t:i64 resident in HBM",
-                   "distinct_frames_resident": nf, "resident_set_MB": round(resident_mb, 1),
-                   "resident_set_vs_infinity_cache": "exceeds the 256 MiB MALL" if resident_mb > 268.4 else "fits the 256 MiB MALL",
-                   "k1_paths_frames": paths,
-                   "extrema": "XM_FLAG_GENERAL (K0 every frame)" if args.general else
-                              ("XM_FLAG_TIME_SORTED" if args.assume_sorted else
-                               "library default: (t[0], t[n-1]) verified on the device; groups take the column-tile K1 (boundary "
-                               "pass + plain-store u16 frame), single frames the compact 32-bit key frame; failing frames are "
-                               "redone with K0 on the 64-bit path"),
-                   "frames_redone_on_general_path": frames_redone},
-        "timing": {"prewarm_s": PREWARM_S, "blocks": int(R), "block_s_median": round(elapsed, 6),
-                   "block_s_min": round(float(el.min()), 6), "block_s_max": round(float(el.max()), 6),
-                   "note": "R blocks of exactly `steps` steps, each bracketed by barrier + synchronize, max over ranks per block, "
-                           "median block reported; ms_per_step = one step = frames_per_step frames"},
-        "roofline": roofline, "cpu_baseline": cpu, "parity": parity,
-        "host_enqueue_us_per_step": round(float(np.median(enq)) / args.steps * 1e6, 2),
-    }
+    out.update({"roofline": roofline, "cpu_baseline": cpu, "parity": parity})
     if other_modes:
         out["other_modes"] = other_modes
     if host_path:

@@ -57,10 +57,18 @@ def _last_json(r):
 
 
 def test_leg_behind_the_replicas_runs_under_the_guard():
-    r = _run(["--gpus", "2", "--steps", "3", "--warmup", "1"], {"XM_BENCH_DRY_LEG": "ok", "XM_BENCH_LEG_TIMEOUT_S": "60"})
+    r = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--full"], {"XM_BENCH_DRY_LEG": "ok", "XM_BENCH_LEG_TIMEOUT_S": "60"})
     assert r.returncode == 0, r.stderr[-2000:]
     line = _last_json(r)
     assert line["n_gpus"] == 2 and line["ranks_seen"] == 2 and line["other_modes"]["one_frame_sharded_over_the_ranks"] == {"dry_leg": "ok"}
+
+
+def test_a_plain_run_has_no_leg_behind_the_replicas():
+    """the sharded leg (and its stand-in here) belongs to --full: a plain run prints the replicas' line alone"""
+    r = _run(["--gpus", "2", "--steps", "3", "--warmup", "1"], {"XM_BENCH_DRY_LEG": "ok", "XM_BENCH_LEG_TIMEOUT_S": "60"})
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = _last_json(r)
+    assert line["n_gpus"] == 2 and line["ranks_seen"] == 2 and line["steps"] == 3 and "other_modes" not in line
 
 
 def test_a_rank_that_hangs_inside_the_leg_does_not_cost_the_line():
@@ -68,7 +76,7 @@ def test_a_rank_that_hangs_inside_the_leg_does_not_cost_the_line():
     guard prints the replicas' line with the leg's error in it and every rank leaves"""
     import time
     t0 = time.time()
-    r = _run(["--gpus", "2", "--steps", "3", "--warmup", "1"], {"XM_BENCH_DRY_LEG": "hang:1", "XM_BENCH_LEG_TIMEOUT_S": "6"}, timeout=120)
+    r = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--full"], {"XM_BENCH_DRY_LEG": "hang:1", "XM_BENCH_LEG_TIMEOUT_S": "6"}, timeout=120)
     assert time.time() - t0 < 90
     line = _last_json(r)
     assert line["n_gpus"] == 2 and line["ranks_seen"] == 2 and line["steps"] == 3
@@ -79,7 +87,7 @@ def test_a_rank_that_hangs_inside_the_leg_does_not_cost_the_line():
 def test_a_rank_that_dies_inside_the_leg_does_not_cost_the_line():
     """rank 1 leaves the process mid-leg: the launcher terminates rank 0 (SIGTERM) or its collective fails -- either way rank 0
     has printed the replicas' line, with the leg's error, before it goes"""
-    r = _run(["--gpus", "2", "--steps", "3", "--warmup", "1"], {"XM_BENCH_DRY_LEG": "die:1", "XM_BENCH_LEG_TIMEOUT_S": "30"}, timeout=180)
+    r = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--full"], {"XM_BENCH_DRY_LEG": "die:1", "XM_BENCH_LEG_TIMEOUT_S": "30"}, timeout=180)
     line = _last_json(r)
     assert line["n_gpus"] == 2 and line["ranks_seen"] == 2
     assert "error" in line["other_modes"]["one_frame_sharded_over_the_ranks"]

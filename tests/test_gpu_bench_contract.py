@@ -1,6 +1,7 @@
 """-m gpu: bench.py keeps its contract with the driver -- the LAST stdout line is one JSON object carrying metric / value /
-unit / n_gpus / steps / warmup / ms_per_step / roofline / cpu_baseline, for the default workload and for the other
-BASELINE configurations' modes.  Runs the real script in a subprocess with short settings."""
+unit / n_gpus / steps / warmup / ms_per_step (a plain run: that and no more; --full: roofline / cpu_baseline and the other
+legs too), for the default workload and for the other BASELINE configurations' modes.  Runs the real script in a subprocess
+with short settings."""
 import json
 import os
 import subprocess
@@ -25,8 +26,8 @@ def _run(*flags, **extra_env):
 
 
 def _default_line():
-    # the line as the driver takes it, with everything in it (other engine settings, the other BASELINE configs, a short CPU leg)
-    return _run("--gpus", "1", "--steps", "20", "--warmup", "5", "--cpu-seconds", "1")
+    # the line with everything in it (other engine settings, the other BASELINE configs, a short CPU leg)
+    return _run("--gpus", "1", "--steps", "20", "--warmup", "5", "--cpu-seconds", "1", "--full")
 
 
 def _run_bench(*flags, **extra_env):
@@ -65,6 +66,41 @@ def test_default_line_as_the_driver_calls_it():
     assert e3["period_chunks"]["Mevents_per_s_end_to_end"] > 500 and e3["period_chunks"]["bytes_per_event_over_pcie"] < 8
 
 
+def test_plain_line_times_exactly_the_given_steps_and_dumps_the_last_one(tmp_path):
+    """a plain run (no --full) is the headline alone: one block of exactly --steps steps, no legs beside it; --dump-outputs
+    writes what the last timed step computed -- the depth frames of its group whole, a seeded sample of their BGR pixels --
+    and that is what the CPU oracle computes for the group's frames"""
+    import numpy as np
+    steps = 7
+    d = _run("--gpus", "1", "--steps", str(steps), "--warmup", "2", "--dump-outputs", str(tmp_path))
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype"):
+        assert k in d, k
+    assert d["steps"] == steps and d["warmup"] == 2 and d["timing"]["blocks"] == 1 and d["value"] > 1000 and d["higher_is_better"]
+    assert d["metric"] == "Mevents/s to depth frame, 640x480, 1M ev/frame" and d["unit"] == "Mevents/s" and d["dtype"] == "int64+f64"
+    for k in ("roofline", "cpu_baseline", "parity", "other_modes", "other_configs", "host_path", "ingest_path"):
+        assert k not in d, k
+    fps = d["config"]["frames_per_step"]
+    assert abs(d["value"] - 1e6 * fps / (d["ms_per_step"] * 1e-3) / 1e6) / d["value"] < 0.01
+    assert abs(d["ms_per_step"] * steps * 1e-3 - d["timing"]["block_s_median"]) < 1e-4
+    files = {f.name: f for f in tmp_path.iterdir()}
+    assert set(files) == {"depth.npy", "bgr_sample.npy", "bgr_sample_pixel.npy"}, files
+    assert sum(f.stat().st_size for f in files.values()) <= 64_000_000
+    depth, bgr, pix = (np.load(files[n]) for n in ("depth.npy", "bgr_sample.npy", "bgr_sample_pixel.npy"))
+    assert depth.dtype == bgr.dtype == np.float32 and pix.dtype == np.float64 and depth.shape == (fps, 480, 640)
+    # the last step is step steps - 1: group (steps - 1) % 4 of the resident frames (4 groups in flight by default)
+    import xmaps_oracle as O
+    from x_maps_amd import synthetic as S
+    tables = S.make_tables(S.C_1M)
+    first = ((steps - 1) % 4) * fps
+    for f in (0, fps - 1):
+        x, y, t, _ = S.to_soa(S.make_events(S.C_1M, frame=first + f))
+        ref = O.process_ev_frame(tables, x.astype(np.int64), y.astype(np.int64), t)
+        assert np.array_equal(depth[f], ref["depth"]), f
+        pf = pix.astype(np.int64) - f * 480 * 640
+        inside = (pf >= 0) & (pf < 480 * 640)
+        assert inside.sum() > 1000 and np.array_equal(bgr[inside], ref["bgr"].reshape(-1, 3)[pf[inside]].astype(np.float32)), f
+
+
 def test_the_default_line_carries_the_other_engine_settings():
     d = _default_line()
     om = d["other_modes"]
@@ -76,11 +112,11 @@ def test_the_default_line_carries_the_other_engine_settings():
 
 def test_one_frame_per_call_mode_still_prints_the_line():
     # without adaptive batching every frame is three launches of its own (compact key frame for lone C-1M frames)
-    d = _run("--batch", "0", "--no-adaptive", "--steps", "40", "--warmup", "5", "--no-cpu-baseline", "--no-other-modes", "--no-host-path")
+    d = _run("--batch", "0", "--no-adaptive", "--steps", "40", "--warmup", "5", "--no-cpu-baseline", "--no-other-modes", "--no-host-path", "--full")
     assert d["config"]["frames_per_step"] == 1 and d["roofline"]["frames_per_launch"] == 1 and d["value"] > 1000
     assert d["parity"]["depth_bit_exact"] and d["config"]["k1_paths_frames"]["key32"] > 0
     # with it (the default of --batch 0) frames that arrive while the GPU is busy go out as groups: the column tiles
-    d = _run("--batch", "0", "--steps", "40", "--warmup", "5", "--no-cpu-baseline", "--no-other-modes", "--no-host-path")
+    d = _run("--batch", "0", "--steps", "40", "--warmup", "5", "--no-cpu-baseline", "--no-other-modes", "--no-host-path", "--full")
     assert d["config"]["frames_per_step"] == 1 and d["value"] > 1000 and "ADAPTIVE" in d["config"]["launch"]
     assert d["parity"]["depth_bit_exact"] and d["config"]["k1_paths_frames"]["cols"] > 0
 
@@ -134,7 +170,7 @@ def _check_roofline(r):
 
 def test_default_and_single_frame_lines_carry_the_three_fractions():
     _check_roofline(_default_line()["roofline"])
-    d = _run("--batch", "0", "--no-adaptive", "--steps", "40", "--warmup", "5", "--no-cpu-baseline", "--no-other-modes", "--no-host-path")
+    d = _run("--batch", "0", "--no-adaptive", "--steps", "40", "--warmup", "5", "--no-cpu-baseline", "--no-other-modes", "--no-host-path", "--full")
     _check_roofline(d["roofline"])
 
 
@@ -143,7 +179,7 @@ def test_multi_gpu_line_carries_the_sharded_frame_beside_the_replicas():
     """With N > 1 ranks the default line reports frame-level replicas (no collective) and, beside it, one C-10M frame sharded by
     event index over the same ranks with the collective time listed separately.  One GPU here: the leg is forced through a
     one-rank process group (RCCL kernels run, nothing crosses xGMI)."""
-    d = _run("--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-host-path", "--no-other-configs", "--no-pmc",
+    d = _run("--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-host-path", "--no-other-configs", "--no-pmc", "--full",
              XM_BENCH_FORCE_DIST="1", XM_BENCH_FORCE_SHARDED_LEG="1")
     sh = d["other_modes"]["one_frame_sharded_over_the_ranks"]
     assert sh["scaling"] == "strong" and sh["value"] > 1000 and sh["parity"]["depth_bit_exact"]

@@ -6,7 +6,7 @@ import ctypes, io, os, sys, contextlib
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np
-sys.argv = ["bench.py", "--no-cpu-baseline", "--no-other-modes", "--no-host-path", "--no-pmc", "--no-other-configs", "--groups-in-flight", "1",
+sys.argv = ["bench.py", "--full", "--no-cpu-baseline", "--no-other-modes", "--no-host-path", "--no-pmc", "--no-other-configs", "--groups-in-flight", "1",
             "--steps", "10", "--warmup", "2"] + sys.argv[1:]
 import bench
 out = io.StringIO()
