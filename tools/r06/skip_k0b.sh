@@ -1,6 +1,7 @@
 #!/bin/bash
 # round 6: what the boundary pass K0b costs in the pipelined C-1M step: a build that stops launching it after eight un-profiled groups.
-# variants/libxmaps_skipk0b.so = the library with these lines in front of K0b's launch in host/xm_batch.hpp (column tiles' branch):
+# variants/libxmaps_skipk0b.so = the library with these lines in front of the launch_cols_bounds call in launch_group
+# (host/xm_batch.hpp, column tiles' branch; built when that call was still an inline K0b launch there):
 #   static const int skip_after = dbg_opt("XM_SKIP_K0B") ? atoi(dbg_opt("XM_SKIP_K0B")) : 0;
 #   static std::atomic<int> groups_seen{0};
 #   if (!(skip_after > 0 && !prof && groups_seen.fetch_add(1) >= skip_after))

@@ -383,34 +383,12 @@ int ingest_issue_frame(xm_ingest* g, uint64_t push_no, u64 n) {
     g->frames_since_clear = 0;
   }
   g->frames_since_clear += 1;
-  const u64 nb = n < 2 ? 2 : n;
-  {  // K0 (general path: the cut frame is sorted whenever the camera stream is, but nothing here relies on it)
-    unsigned gx = grid_for(nb, BLOCK * 4);
-    if (gx > 1024) gx = 1024;
-    hipLaunchKernelGGL((k_minmax_batch<long long, true, false, 1>), dim3(gx, 1), dim3(BLOCK), 0, s, desc);
-  }
-  if (!batch_path(h, n)) {  // sparse frame: one thread per event
-    const unsigned gx = grid_for(nb, BLOCK);
-    if (h->cfg.view == XM_VIEW_PROJECTOR)
-      hipLaunchKernelGGL((k_scatter_direct_batch<long long, true, false, 0>), dim3(gx, 1), dim3(BLOCK), 0, s, desc, h->tb, 0);
-    else
-      hipLaunchKernelGGL((k_scatter_direct_batch<long long, true, false, 1>), dim3(gx, 1), dim3(BLOCK), 0, s, desc, h->tb, 0);
-  } else {
-    const double max_ev = h->tb.xmap_w > 0 ? (h->w_ts - 1.5) * (double)n / (double)h->tb.xmap_w : 0.0;
-    unsigned threads = TILE_THREADS;
-    while (threads > 1024 / TILE_EPT && (double)(threads * TILE_EPT) > max_ev) threads >>= 1;
-    const unsigned gx = grid_for(nb, threads * TILE_EPT);
-    auto launch = [&](auto view_tag) -> int {
-      constexpr int VIEW = decltype(view_tag)::value;
-      auto kern = k_scatter_tiled_batch<long long, true, false, VIEW, false>;
-      int rc = h->ensure_lds(reinterpret_cast<const void*>(kern), h->k1_lds);
-      if (rc) return rc;
-      hipLaunchKernelGGL(kern, dim3(gx, 1), dim3(threads), h->k1_lds, s, desc, h->tb, h->w_ts, h->w_x, 0);
-      return XM_OK;
-    };
-    int rc = h->cfg.view == XM_VIEW_PROJECTOR ? launch(std::integral_constant<int, 0>{}) : launch(std::integral_constant<int, 1>{});
-    if (rc) return rc;
-  }
+  // one EventCD frame in descriptor form: grids from at least two events, the tiled K1's block from the frame itself
+  const FrameGroup one{desc, 1, n < 2 ? 2 : n, n, false};
+  // K0 (general path: the cut frame is sorted whenever the camera stream is, but nothing here relies on it)
+  launch_k0<long long, true, false>(one, s);
+  // K1: tiled where a group of such frames would be, else one thread per event
+  if (int rc = launch_k1<long long, true, false>(h, one, batch_path(h, n), false, false, s)) return rc;
   // the ingest stream must not append over the frame's events (dead, but still in the ring) before K1 has read them: whatever
   // is issued on it from now on waits for this event; what has been issued already fits the room k_ing_segment keeps (`ahead`)
   hipEvent_t ev = g->k1_ev[g->frames_issued % 8];
@@ -430,13 +408,8 @@ int ingest_issue_frame(xm_ingest* g, uint64_t push_no, u64 n) {
     g->t_out_wait_s += ingest_now() - tw;
     HIP_TRY(hipStreamWaitEvent(s, g->out_ev[o], 0));
   }
-  if (h->cfg.view == XM_VIEW_PROJECTOR) {
-    if (h->k2_direct) return fail(XM_ERR_INVALID, "ingest needs the tiled frame kernel (XM_K2_DIRECT is set)");
-    launch_k2_batch<0>(h, s, desc, 1);
-  } else {
-    const u64 px = (u64)h->tb.cam_w * h->tb.cam_h;
-    hipLaunchKernelGGL(k_frame_direct_batch, dim3(grid_for(px, BLOCK), 1), dim3(BLOCK), 0, s, desc, px, h->tb.dlut);
-  }
+  if (h->cfg.view == XM_VIEW_PROJECTOR && h->k2_direct) return fail(XM_ERR_INVALID, "ingest needs the tiled frame kernel (XM_K2_DIRECT is set)");
+  launch_frame_kernel(h, one, KM_KEY64, s);
   // the frame's statistics into its status entry while the slot's counters and the frame's events are still the frame's ...
   hipLaunchKernelGGL(k_ing_publish, dim3(1), dim3(64), 0, s, g->dev.st, desc, (const IngFrameInfo*)(g->d_infos + vi), g->h_status, (u64)push_no);
   HIP_TRY(hipGetLastError());

@@ -103,7 +103,9 @@ int xm_shard_finish(xm_handle* h, const uint64_t* key_frame, uint32_t tag, float
   if (!h || !key_frame) return fail(XM_ERR_INVALID, "NULL argument");
   if (tag == 0 || tag > KEY_MAX_TAG) return fail(XM_ERR_INVALID, "tag must be in [1, 2^19)");
   XM_ENTER(h);
-  launch_frame_kernel(h, (const u64*)key_frame, h->aux_st, tag, depth_out, bgr_out, h->slots[0].stream);
+  const EventsView none;
+  launch_frame_kernel(h, LoneFrame{none, h->aux_st, tag, const_cast<uint64_t*>(key_frame), nullptr, depth_out, bgr_out}, KM_KEY64,
+                      h->slots[0].stream);
   HIP_TRY(hipGetLastError());
   return XM_OK;
 }
@@ -195,23 +197,12 @@ int xm_shard_cols_scatter(xm_handle* h, uint16_t* x, uint16_t* y, int64_t* t, si
   FrameDesc* desc = reinterpret_cast<FrameDesc*>(reinterpret_cast<unsigned char*>(h->d_shard_n) + 64);
   hipLaunchKernelGGL(k_shard_cols_prepare, dim3(1), dim3(256), 0, s, x, y, (long long*)t, (u64)n, (const unsigned char*)gathered_dev,
                      (u64)send_bytes, rank, world, h->tb, (u64)cap_events, mm, frame16, h->aux_st, desc);
-  const int flags = h->cols_flags | COLS_F_EXT_EXTREMA;
-  if (W <= 16)  // (16 lanes per boundary: cols_bounds_per_block)
-    hipLaunchKernelGGL((k_cols_bounds_batch<false, 16>), dim3(grid_for(grid_for(h->tb.xmap_w, W) + 1, cols_bounds_per_block(16)), 1), dim3(256), 0, s,
-                       (const FrameDesc*)desc, h->tb, W, flags, 0);
-  else
-    hipLaunchKernelGGL(k_cols_bounds_batch<false>, dim3(grid_for(grid_for(h->tb.xmap_w, W) + 1, cols_bounds_per_block(32)), 1), dim3(256), 0, s,
-                       (const FrameDesc*)desc, h->tb, W, flags, 0);
-  auto kern = k_scatter_cols_batch<false, true>;  // (the piece starts 8-aligned: 16-byte event loads)
-  const size_t lds = cols_lds_bytes(h, W);
-  int rc;
-  if ((rc = h->ensure_lds(reinterpret_cast<const void*>(kern), lds))) return rc;
-  if (dbg_opt("XM_SHARD_PROFILE"))  // (measurement: HIP events tied to THIS dispatch -- xm_shard_cols_last_k1_ms -- beside the three-launch bracket a caller can take itself)
-    hipExtLaunchKernelGGL(kern, dim3(grid_for(h->tb.xmap_w, W), 1), dim3(cols_threads(h, n_frame_events, W)), (std::uint32_t)lds, s, h->prof_ev[2],
-                          h->prof_ev[3], 0u, (const FrameDesc*)desc, h->tb, W, h->w_x, h->cols_xr_min, flags);
-  else
-    hipLaunchKernelGGL(kern, dim3(grid_for(h->tb.xmap_w, W), 1), dim3(cols_threads(h, n_frame_events, W)), lds, s, (const FrameDesc*)desc, h->tb, W,
-                       h->w_x, h->cols_xr_min, flags);
+  const FrameGroup piece{desc, 1, n_frame_events, n_frame_events, true};  // (the piece starts 8-aligned: 16-byte event loads)
+  launch_cols_bounds<false>(h, piece, W, h->cols_flags | COLS_F_EXT_EXTREMA, s);
+  // (measurement: HIP events tied to THIS dispatch -- xm_shard_cols_last_k1_ms -- beside the three-launch bracket a caller can take itself)
+  const ProfSlots ps{dbg_opt("XM_SHARD_PROFILE") ? h->prof_ev + 2 : nullptr};
+  ps.at(0);
+  if (int rc = launch_tiles_k1<false>(h, piece, W, COLS_F_EXT_EXTREMA, 0, s)) return rc;
   HIP_TRY(hipGetLastError());
   return XM_OK;
 }

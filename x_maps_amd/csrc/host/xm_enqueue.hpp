@@ -1,4 +1,5 @@
-// xm_enqueue.hpp -- which K1 a frame takes (path selection) and the launches of ONE frame (enqueue_frame)
+// xm_enqueue.hpp -- the tiles' launchers (K0b, column / owner-tile K1), which path a frame or a group takes (frame_path), what
+// a slot records once a frame is enqueued, and the launches of ONE frame (enqueue_frame)
 // (part of libxmaps_hip.so's host side: included by ../xmaps_hip.hip, one translation unit; see that file for the order)
 #pragma once
 
@@ -57,73 +58,85 @@ unsigned cols_threads(const xm_handle* h, u64 n, int W, int ept = COLS_EPT) {
   return std::max(128u, std::min(t, (unsigned)COLS_MAX_THREADS));
 }
 
-// K0b: the tile boundaries + column thresholds of the frame (half a wave per boundary), left behind the slot's u16 frame
-void launch_cols_bounds(xm_handle* h, const EventsView& ev, uint16_t* frame16, int W, hipStream_t stream) {
-  const int split = h->own_mode ? own_set(h, W).halo : 0;  // owner tiles: two boundaries per tile (tile = W columns + a halo behind them)
+// K0b: the tile boundaries + column thresholds of the frame(s), left behind the u16 frame.  Column tiles: one boundary per tile, 16
+// lanes each on tiles of <= 16 columns, else 32 (cols_bounds_per_block); owner tiles: two per tile (its first column, the end of its
+// halo behind it), 32 lanes.  flags: k_cols_bounds_batch's (a lone frame's kernel has none)
+template <bool AOS, typename F>
+void launch_cols_bounds(xm_handle* h, const F& fr, int W, int flags, hipStream_t stream) {
+  const int split = h->own_mode ? own_set(h, W).halo : 0;
   const unsigned nb = (split ? 2u : 1u) * grid_for(h->tb.xmap_w, W);
-  const bool g16 = !split && W <= 16;  // (16 lanes per boundary on the column tiles: cols_bounds_per_block)
-  const unsigned gx = grid_for(nb + 1, cols_bounds_per_block(g16 ? 16 : 32));
-  if (ev.aos && g16)
-    XM_LAUNCH((k_cols_bounds<true, 16>), dim3(gx), dim3(256), 0, stream, ev.x, (const long long*)ev.t, (const uint4*)ev.aos, (u32)ev.n, h->tb, W, frame16, split);
-  else if (ev.aos)
-    XM_LAUNCH(k_cols_bounds<true>, dim3(gx), dim3(256), 0, stream, ev.x, (const long long*)ev.t, (const uint4*)ev.aos, (u32)ev.n, h->tb, W, frame16, split);
-  else if (g16)
-    XM_LAUNCH((k_cols_bounds<false, 16>), dim3(gx), dim3(256), 0, stream, ev.x, (const long long*)ev.t, (const uint4*)ev.aos, (u32)ev.n, h->tb, W, frame16, split);
-  else
-    XM_LAUNCH(k_cols_bounds<false>, dim3(gx), dim3(256), 0, stream, ev.x, (const long long*)ev.t, (const uint4*)ev.aos, (u32)ev.n, h->tb, W, frame16, split);
+  DevTables tb = h->tb;
+  if constexpr (!is_lone<F>) {
+    if (split) own_apply(own_set(h, W), tb);  // (a group's owner-tile K0b takes its plan's tables, a lone frame's the plain ones)
+  }
+  auto go = [&](auto lanes_tag) {
+    constexpr int G = decltype(lanes_tag)::value;
+    const unsigned gx = grid_for(nb + 1, cols_bounds_per_block(G));
+    if constexpr (is_lone<F>)
+      XM_LAUNCH((k_cols_bounds<AOS, G>), dim3(gx), dim3(256), 0, stream, fr.ev.x, (const long long*)fr.ev.t, (const uint4*)fr.ev.aos,
+                (u32)fr.ev.n, tb, W, static_cast<uint16_t*>(fr.frame), split);
+    else
+      XM_LAUNCH((k_cols_bounds_batch<AOS, G>), dim3(gx, fr.n), dim3(256), 0, stream, fr.descs, tb, W, flags, split);
+  };
+  if (!split && W <= 16) go(std::integral_constant<int, 16>{});
+  else go(std::integral_constant<int, 32>{});
 }
 
-int launch_scatter_cols(xm_handle* h, const EventsView& ev, SlotState* st, uint16_t* frame16, int W, hipStream_t stream) {
-  const bool vec16 = !ev.aos && aligned(ev.x, 16) && aligned(ev.y, 16) && aligned(ev.t, 16);
+// K1 on the column tiles (xmaps_k1cols.hpp) or, where the rig's X-map is not injective, on the owner tiles (xmaps_k1own.hpp):
+// grid = tiles (x frames), block from the mean frame (cols_threads).  flags: on top of h->cols_flags; lds_pad: extra dynamic LDS of
+// a column-tile block (XM_COLS_LDS_PAD, experiments: fewer K1 blocks per CU, room for another kernel's -- the groups' launch only)
+template <bool AOS, typename F>
+int launch_tiles_k1(xm_handle* h, const F& fr, int W, int flags, size_t lds_pad, hipStream_t stream) {
+  const bool v16 = !AOS && vec16(fr);
+  const u64 n = fr.n_mean();
+  const dim3 grid(grid_for(h->tb.xmap_w, W), frames(fr));
+  flags |= h->cols_flags;
   if (h->own_mode) {
-    const int ept = own_ept(h, ev.n, W, vec16);
-    auto kern = k_scatter_own<false, false>;
-    if (ev.aos) kern = ept == 4 ? k_scatter_own<true, false, 4> : k_scatter_own<true, false>;
-    else if (vec16) kern = k_scatter_own<false, true>;
-    else if (ept == 4) kern = k_scatter_own<false, false, 4>;
     const xm_handle::OwnSet& os = own_set(h, W);
     DevTables tbo = h->tb;
     own_apply(os, tbo);
+    auto inst = [](auto vec_tag, auto ept_tag) {
+      constexpr bool V = decltype(vec_tag)::value;
+      constexpr int E = decltype(ept_tag)::value;
+      if constexpr (is_lone<F>) return k_scatter_own<AOS, V, E>;
+      else return k_scatter_own_batch<AOS, V, E>;
+    };
+    const int ept = own_ept(h, n, W, v16);
+    auto kern = ept == 4 ? inst(std::false_type{}, std::integral_constant<int, 4>{})
+                         : inst(std::false_type{}, std::integral_constant<int, COLS_EPT>{});
+    if constexpr (!AOS) {
+      if (v16) kern = inst(std::true_type{}, std::integral_constant<int, COLS_EPT>{});
+    }
     const size_t lds = own_lds_bytes(os);
     int rc = h->ensure_lds(reinterpret_cast<const void*>(kern), lds);
     if (rc) return rc;
-    XM_LAUNCH(kern, dim3(grid_for(h->tb.xmap_w, W)), dim3(cols_threads(h, ev.n, W, ept)), lds, stream, ev.x, ev.y, (const long long*)ev.t,
-              (const uint4*)ev.aos, (u32)ev.n, tbo, st, frame16, W, os.halo, h->cols_flags);
+    const dim3 block(cols_threads(h, n, W, ept));
+    if constexpr (is_lone<F>)
+      XM_LAUNCH(kern, grid, block, lds, stream, fr.ev.x, fr.ev.y, (const long long*)fr.ev.t, (const uint4*)fr.ev.aos, (u32)fr.ev.n, tbo,
+                fr.st, static_cast<uint16_t*>(fr.frame), W, os.halo, flags);
+    else
+      XM_LAUNCH(kern, grid, block, lds, stream, fr.descs, tbo, W, os.halo, flags);
     return XM_OK;
   }
-  auto kern = k_scatter_cols<false, false>;
-  if (ev.aos) kern = k_scatter_cols<true, false>;
-  else if (vec16) kern = k_scatter_cols<false, true>;
-  const size_t lds = cols_lds_bytes(h, W);
+  auto inst = [](auto vec_tag) {
+    constexpr bool V = decltype(vec_tag)::value;
+    if constexpr (is_lone<F>) return k_scatter_cols<AOS, V>;
+    else return k_scatter_cols_batch<AOS, V>;
+  };
+  auto kern = inst(std::false_type{});
+  if constexpr (!AOS) {
+    if (v16) kern = inst(std::true_type{});
+  }
+  const size_t lds = cols_lds_bytes(h, W) + lds_pad;
   int rc = h->ensure_lds(reinterpret_cast<const void*>(kern), lds);
   if (rc) return rc;
-  XM_LAUNCH(kern, dim3(grid_for(h->tb.xmap_w, W)), dim3(cols_threads(h, ev.n, W)), lds, stream, ev.x, ev.y, (const long long*)ev.t,
-            (const uint4*)ev.aos, (u32)ev.n, h->tb, st, frame16, W, h->w_x, h->cols_xr_min, h->cols_flags);
+  const dim3 block(cols_threads(h, n, W));
+  if constexpr (is_lone<F>)
+    XM_LAUNCH(kern, grid, block, lds, stream, fr.ev.x, fr.ev.y, (const long long*)fr.ev.t, (const uint4*)fr.ev.aos, (u32)fr.ev.n, h->tb,
+              fr.st, static_cast<uint16_t*>(fr.frame), W, h->w_x, h->cols_xr_min, flags);
+  else
+    XM_LAUNCH(kern, grid, block, lds, stream, fr.descs, h->tb, W, h->w_x, h->cols_xr_min, flags);
   return XM_OK;
-}
-
-void launch_frame_kernel(xm_handle* h, const u64* key_frame, SlotState* st, u32 tag_override, float* depth,
-                         uint8_t* bgr, hipStream_t stream, const unsigned char* dirty = nullptr, int kmode = KM_KEY64) {
-  KeyCells cells{key_frame, 0};
-  const bool key32 = kmode == KM_KEY32;
-  if (h->cfg.view == XM_VIEW_PROJECTOR && !h->k2_direct && kmode == KM_COLS) {
-    launch_k2<2>(h, stream, key_frame, st, tag_override, nullptr, depth, bgr);
-  } else if (h->cfg.view == XM_VIEW_PROJECTOR && !h->k2_direct && key32) {
-    launch_k2<1>(h, stream, key_frame, st, tag_override, nullptr, depth, bgr);
-  } else if (h->cfg.view == XM_VIEW_PROJECTOR && !h->k2_direct) {
-    launch_k2<0>(h, stream, key_frame, st, tag_override, dirty, depth, bgr);
-  } else if (h->cfg.view == XM_VIEW_PROJECTOR) {
-    const u64 px = (u64)h->tb.proj_w * h->tb.proj_h;
-    XM_LAUNCH((k_frame_proj<KeyCells, 0>), dim3(grid_for(px, BLOCK)), dim3(BLOCK), 0, stream, cells, h->tb, st,
-              tag_override, depth, bgr);
-  } else if (key32) {  // camera view, compact frame: (event index + 1) << 12 | disparity, zeroed as it is read
-    XM_LAUNCH(k_frame_cam32, dim3(grid_for(h->tb.cam_w, CAM32_T), grid_for(h->tb.cam_h, CAM32_T)), dim3(BLOCK), 0, stream,
-              reinterpret_cast<u32*>(const_cast<u64*>(key_frame)), h->tb.cam_w, h->tb.cam_h, st, h->tb.dlut, depth, bgr);
-  } else {
-    const u64 px = (u64)h->tb.cam_w * h->tb.cam_h;
-    XM_LAUNCH((k_frame_direct<KeyCells>), dim3(grid_for(px, BLOCK)), dim3(BLOCK), 0, stream, cells, px,
-              h->tb.p03, h->tb.z_near, h->tb.z_far, st, tag_override, 1, h->tb.dlut, depth, bgr);
-  }
 }
 
 int check_events(const EventsView& ev) {
@@ -141,13 +154,7 @@ int check_events(const EventsView& ev) {
   return XM_OK;
 }
 
-// enqueue K0 -> K1 -> K2 for one frame on a slot.  All pointers are device pointers.
-// dense enough for the tiled K1?  (the same rule as launch_scatter_tv)
-bool tiled_path(const xm_handle* h, u64 n) {
-  const double max_ev = h->tb.xmap_w > 0 ? (h->w_ts - 1.5) * (double)n / (double)h->tb.xmap_w : 0.0;
-  return !h->k1_direct && h->w_ts > 0 && h->w_x > 0 && max_ev >= 1024.0;
-}
-
+// ---- which path a frame or a group takes -----------------------------------------------------------------------------------------
 bool sorted_path(const xm_handle* h, const EventsView& ev) {
   // the verified (t[0], t[n-1]) shortcut: both K1 kernels take it (tiled, and one thread per event for sparse frames)
   return (h->time_sorted || (h->try_sorted && !h->capturing)) && !ev.use_p && ev.n > 0;
@@ -162,14 +169,72 @@ bool key32_path(const xm_handle* h, const EventsView& ev, bool sorted) {
   return ev.n / (u64)(1024 / TILE_EPT * TILE_EPT) < (1ull << KEY32_TILE_BITS);  // tiles of >= 1024 events
 }
 
-// may this (sorted-path) frame use the column tiles?  Same preconditions as the compact key frame (automatic redo at hand)
-// + int64 time stamps; returns the tile width W (0: no)
-int cols_path(const xm_handle* h, const EventsView& ev, bool sorted, bool group = true) {
-  if (!group && !h->cols_single) return 0;
-  if (!sorted || !h->cols_ok || !h->try_sorted || h->capturing || h->key32_pause.load(std::memory_order_relaxed) > 0 ||
-      h->k2_direct || h->k2_flags || ev.use_p || (!ev.aos && ev.t_dtype != XM_T_INT64))
-    return 0;
-  return cols_width(h, ev.n);
+// the column tiles' conditions on a frame: int64 time stamps, no polarity column, dense enough for a tile width of its own
+bool cols_events(const xm_handle* h, const EventsView& ev) {
+  return !ev.use_p && (ev.aos || ev.t_dtype == XM_T_INT64) && cols_width(h, ev.n) != 0;
+}
+
+// can this group of frames go through the multi-frame kernels?  (dense enough for the tiled K1, tiled K2 available)
+bool batch_path(const xm_handle* h, u64 n_mean) {
+  return tiled_path(h, n_mean) && !(h->cfg.view == XM_VIEW_PROJECTOR && h->k2_direct) && !h->k2_flags;
+}
+
+struct FramePath {
+  bool per_frame = false;  // a group without a multi-frame path (untiled K2): frame by frame through enqueue_frame
+  bool sorted = false;     // the verified (t[0], t[n-1]) shortcut: no K0
+  bool direct = false;     // a group too sparse for the tiles: the one-thread-per-event K1 between the multi-frame K0 and K2
+  int cols_w = 0;          // column / owner tiles of this width (0: none)
+  bool dev_redo = false;   // a captured group on the column tiles: the redo decided on the device (launch_group)
+  bool key32 = false;      // the compact key frame
+  u64 n_max = 0, n_mean = 0;
+  bool vec16 = true;       // every SoA frame's columns 16-byte aligned
+  int kmode() const { return cols_w ? KM_COLS : key32 ? KM_KEY32 : KM_KEY64; }
+  int counter() const { return cols_w ? 3 : key32 ? 2 : sorted ? 1 : 0; }  // index into h->path_counts
+};
+
+// The path of a lone frame (group = false) or of a group of n frames.  A group adds its own conditions on top of a lone frame's:
+// the multi-frame kernels, or the one-thread-per-event K1 (>= 2 frames), or none; one tile width for all its frames (from the mean
+// frame) and one layout (AoS / SoA); and while it is being captured (can_redo: descriptors for the redo at hand, >= 2 frames --
+// a lone frame's seven launches, four of them returning at once, take longer than K0 -> K1 -> K2) the column tiles with the
+// redo decided on the device.  A lone frame takes the column tiles only under cols_single.
+FramePath frame_path(const xm_handle* h, const EventsView* evs, int n, bool allow_sorted, bool group = false, bool can_redo = false) {
+  FramePath p;
+  u64 n_sum = 0;
+  bool one_layout = true;
+  p.sorted = allow_sorted && n > 0;
+  for (int f = 0; f < n; ++f) {
+    const EventsView& ev = evs[f];
+    p.n_max = std::max<u64>(p.n_max, ev.n);
+    n_sum += ev.n;
+    if (!ev.aos) p.vec16 = p.vec16 && ev_vec16(ev);
+    p.sorted = p.sorted && sorted_path(h, ev);
+    one_layout = one_layout && (ev.aos != nullptr) == (evs[0].aos != nullptr);
+  }
+  p.n_mean = n ? n_sum / (u64)n : 0;
+  if (group) {
+    // frames too sparse for the tiled K1 (the reference's own recordings: ~150 k events over 1080 time columns): the multi-frame
+    // K0 and K2 with the one-thread-per-event K1 in between -- three launches per group instead of three per frame
+    const bool tiled = batch_path(h, p.n_mean);
+    p.direct = !tiled && !(h->cfg.view == XM_VIEW_PROJECTOR && (h->k2_direct || !h->d_k2_tiles[1])) && !h->k2_flags && n >= 2 &&
+               p.n_max < (1ull << 31);
+    p.per_frame = !tiled && !p.direct;
+    if (p.per_frame) return p;
+  }
+  auto tile_width = [&] {
+    int W = one_layout ? cols_width(h, p.n_mean) : 0;
+    for (int f = 0; f < n && W; ++f)
+      if (!cols_events(h, evs[f])) W = 0;
+    return W;
+  };
+  // the column tiles need the automatic redo at hand on the host, as the compact key frame does
+  if (p.sorted && (group || h->cols_single) && h->cols_ok && h->try_sorted && !h->capturing &&
+      h->key32_pause.load(std::memory_order_relaxed) <= 0 && !h->k2_direct && !h->k2_flags)
+    p.cols_w = tile_width();
+  else if (group && can_redo && n >= 2 && h->capturing && !p.direct && h->cols_ok && !h->k2_direct && !h->k2_flags)
+    p.dev_redo = (p.cols_w = tile_width()) != 0;
+  p.key32 = p.sorted && !p.cols_w && !p.direct;
+  for (int f = 0; f < n && p.key32; ++f) p.key32 = key32_path(h, evs[f], p.sorted);
+  return p;
 }
 
 // keep the slot's compact frame unambiguous for a frame with tag `tag` (4-bit tags repeat every 15 frames)
@@ -195,16 +260,33 @@ void key32_note(xm_handle* h, bool failed) {
   }
 }
 
+// the compact paths' pause (key32_note) counts down by the frames enqueued: one per lone frame, a group's all at once
+void key32_pause_tick(xm_handle* h, int frames) {
+  int v = h->key32_pause.load(std::memory_order_relaxed);
+  while (v > 0 && !h->key32_pause.compare_exchange_weak(v, std::max(0, v - frames), std::memory_order_relaxed)) {
+  }
+}
+
+// frame `ev` was enqueued on slot s along path p: what the slot's redo and statistics read later, and the path counters.  A group
+// hands its tags to the API at once (api_tag); a lone frame's caller does that itself.
+void note_enqueued(xm_handle* h, Slot& s, const EventsView& ev, const FramePath& p, bool group) {
+  s.host_tag += 1;
+  if (group) s.api_tag = s.host_tag;
+  s.any_frame = true;
+  s.last_n = ev.n;
+  s.last_sorted = p.sorted || p.cols_w != 0;  // (no K0 either on a captured group's column tiles; a lone frame's are sorted)
+  s.last_key32 = p.key32 || p.cols_w;
+  s.last_cols = p.cols_w != 0;
+  s.last_t_dtype = ev.aos ? XM_T_INT64 : ev.t_dtype;
+  h->path_counts[p.counter()].fetch_add(1, std::memory_order_relaxed);
+  if (p.key32 || p.cols_w) key32_note(h, false);
+}
+
+// enqueue K0 -> K1 -> K2 for one frame on a slot.  All pointers are device pointers.
 int enqueue_frame(xm_handle* h, Slot& s, const EventsView& ev, float* depth, uint8_t* bgr, hipEvent_t* prof,
                   bool allow_sorted = true, hipStream_t stream_override = nullptr) {
-  const bool sorted = allow_sorted && sorted_path(h, ev);
-  const int cols_w = cols_path(h, ev, sorted, false);
-  const bool use32 = !cols_w && key32_path(h, ev, sorted);
-  {
-    int v = h->key32_pause.load(std::memory_order_relaxed);
-    while (v > 0 && !h->key32_pause.compare_exchange_weak(v, v - 1, std::memory_order_relaxed)) {
-    }
-  }
+  const FramePath p = frame_path(h, &ev, 1, allow_sorted);
+  key32_pause_tick(h, 1);
   hipStream_t stream = stream_override ? stream_override : s.stream;
   if (s.pending_batch_ev) {  // the slot's previous frame ran inside a multi-frame launch, maybe on another stream
     if (s.pending_batch_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, s.pending_batch_ev, 0));
@@ -219,39 +301,32 @@ int enqueue_frame(xm_handle* h, Slot& s, const EventsView& ev, float* depth, uin
 #else
   constexpr int skip = 0;
 #endif
-  // prof = 6 events {start0, stop0, start1, stop1, start2, stop2} attached to the three dispatch packets
-  if (prof) g_prof = ProfCtx{prof[0], prof[1]};
-  if (!(skip & 1) && !sorted) launch_minmax(ev, s.st, 0, stream);
-  if (!(skip & 1) && cols_w) launch_cols_bounds(h, ev, s.frame16, cols_w, stream);  // K0b takes K0's place (and its profile events)
-  if (use32) {
-    int rc = key32_prepare(h, s, s.host_tag + 1, stream);
-    if (rc) return rc;
-  }
-  if (prof) g_prof = ProfCtx{prof[2], prof[3]};
-  if (!(skip & 2)) {
-    int rc = cols_w ? launch_scatter_cols(h, ev, s.st, s.frame16, cols_w, stream)
-                    : launch_scatter(h, ev, s.st, 0, 0, 0, 0, use32 ? reinterpret_cast<u64*>(s.key32) : s.key_frame, s.dirty, stream,
-                                     sorted, nullptr, use32);
-    if (rc) {
-      g_prof = ProfCtx{};
-      return rc;
+  const ProfSlots ps{prof};
+  void* out = p.cols_w ? (void*)s.frame16 : p.key32 ? (void*)s.key32 : (void*)s.key_frame;
+  const LoneFrame fr{ev, s.st, 0, out, s.dirty, depth, bgr};
+  ps.at(0);
+  int rc = with_event_types(ev, [&](auto ty) -> int {
+    using E = decltype(ty);
+    if (!(skip & 1) && !p.sorted) launch_k0<typename E::T, E::AOS, E::HAS_P>(fr, stream);
+    if constexpr (tile_types<E>) {
+      if (!(skip & 1) && p.cols_w) launch_cols_bounds<E::AOS>(h, fr, p.cols_w, 0, stream);  // K0b takes K0's place (and its profile events)
     }
-  }
-  if (prof) g_prof = ProfCtx{prof[4], prof[5]};
-  if (!(skip & 4))
-    launch_frame_kernel(h, cols_w ? reinterpret_cast<const u64*>(s.frame16) : use32 ? reinterpret_cast<const u64*>(s.key32) : s.key_frame,
-                        s.st, 0, depth, bgr, stream, h->k2_flags ? s.dirty : nullptr, cols_w ? KM_COLS : use32 ? KM_KEY32 : KM_KEY64);
-  g_prof = ProfCtx{};
+    if (p.key32) {
+      const int rc_k = key32_prepare(h, s, s.host_tag + 1, stream);
+      if (rc_k) return rc_k;
+    }
+    ps.at(1);
+    if (skip & 2) return XM_OK;
+    if constexpr (tile_types<E>) {
+      if (p.cols_w) return launch_tiles_k1<E::AOS>(h, fr, p.cols_w, 0, 0, stream);
+    }
+    return launch_k1<typename E::T, E::AOS, E::HAS_P>(h, fr, tiled_path(h, ev.n), p.key32, p.sorted, stream);
+  });
+  if (rc) return rc;
+  ps.at(2);
+  if (!(skip & 4)) launch_frame_kernel(h, fr, p.kmode(), stream);
   HIP_TRY(hipGetLastError());
-  s.last_key32 = use32 || cols_w;
-  s.last_cols = cols_w != 0;
-  h->path_counts[cols_w ? 3 : use32 ? 2 : sorted ? 1 : 0].fetch_add(1, std::memory_order_relaxed);
-  if (use32 || cols_w) key32_note(h, false);
-  s.host_tag += 1;
-  s.any_frame = true;
-  s.last_n = ev.n;
-  s.last_sorted = sorted;
-  s.last_t_dtype = ev.aos ? XM_T_INT64 : ev.t_dtype;
+  note_enqueued(h, s, ev, p, false);
   if (!stream_override) s.eager_dirty = true;
   return XM_OK;
 }

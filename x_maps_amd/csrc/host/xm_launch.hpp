@@ -1,145 +1,214 @@
-// xm_launch.hpp -- kernel dispatch: K0 / K1 / K2 launch helpers of every variant (general, tiled, column tiles, owner tiles, pipelined K2)
+// xm_launch.hpp -- kernel dispatch: the two forms a launch takes its frames in, the (aos, use_p, t_dtype) dispatch, and the
+// launchers of K0 (extrema), K1 (tiled / one thread per event) and K2 (every view and key format, pipelined K2)
 // (part of libxmaps_hip.so's host side: included by ../xmaps_hip.hip, one translation unit; see that file for the order)
 #pragma once
 
 namespace {
 
-// ---- kernel dispatch ---------------------------------------------------------------------------------
-template <typename T, bool AOS, bool HAS_P>
-void launch_minmax_t(const EventsView& ev, SlotState* st, u32 tag_override, hipStream_t stream) {
-  const u64 n = ev.n;
-  const bool vec2 = !AOS && sizeof(T) == 8 && std::is_same<T, long long>::value && aligned(ev.t, 16) &&
-                    (!HAS_P || aligned(ev.p, 4));
-  // ~2048 events per thread-block iteration keeps every CU busy without drowning the 32 atomic slots
-  const unsigned per_block = BLOCK * (vec2 ? 2 * K0_UN : 4);  // VEC2: K0_UN loads x 2 events per thread per sweep
-  unsigned grid = grid_for(n, per_block);
-  if (grid > 1024) grid = 1024;
-  if constexpr (std::is_same<T, long long>::value && !AOS) {
-    if (vec2) {
-      XM_LAUNCH((k_minmax<T, false, HAS_P, 2>), dim3(grid), dim3(BLOCK), 0, stream, (const T*)ev.t, ev.p,
-                (const uint4*)nullptr, n, st, tag_override);
-      return;
-    }
+// ---- the two forms a launch takes its frames in ------------------------------------------------------------------------
+// A lone frame passes its events as the kernels' own arguments (nothing to upload on the latency path); a group passes n
+// descriptors in device memory, frame = blockIdx.y (K2: blockIdx.z).  Every launcher serves both forms: the kernel instance,
+// grid, block and dynamic LDS come from one rule; only the frame dimension and the per-frame pointers differ.
+struct LoneFrame {
+  const EventsView& ev;
+  SlotState* st;
+  u32 tag_override;
+  void* frame = nullptr;  // K1's output, K2's input: the 64-bit / compact key frame, or the column tiles' u16 frame
+  unsigned char* dirty = nullptr;
+  float* depth = nullptr;
+  uint8_t* bgr = nullptr;
+  u64 idx_offset = 0, mm_lo = 0, mm_hi = 0;  // shards: global index of the first event, the frame's extrema
+  const void* mm_ext = nullptr;              // sharded mode: {tmin, -tmax} in device memory (NULL: mm_lo / mm_hi)
+  u64 n_max() const { return ev.n; }
+  u64 n_mean() const { return ev.n; }
+};
+struct FrameGroup {
+  const FrameDesc* descs;
+  int n;                        // frames
+  u64 events_max, events_mean;  // the largest frame (grids) and the mean frame (block sizes)
+  bool all_vec16;               // every SoA frame's columns 16-byte aligned (ev_vec16)
+  u64 n_max() const { return events_max; }
+  u64 n_mean() const { return events_mean; }
+};
+template <typename F>
+constexpr bool is_lone = std::is_same<F, LoneFrame>::value;
+unsigned frames(const LoneFrame&) { return 1; }
+unsigned frames(const FrameGroup& g) { return (unsigned)g.n; }
+
+// SoA columns that take 16-byte loads
+bool ev_vec16(const EventsView& ev) {
+  return !ev.aos && aligned(ev.x, 16) && aligned(ev.y, 16) && aligned(ev.t, 16) && (!ev.use_p || aligned(ev.p, 16));
+}
+bool vec16(const LoneFrame& f) { return ev_vec16(f.ev); }
+bool vec16(const FrameGroup& g) { return g.all_vec16; }
+
+// prof = 6 events {start0, stop0, start1, stop1, start2, stop2} attached to the dispatch packets of K0 / K0b, K1, K2 (g_prof);
+// cleared when the frame's or group's launches are issued, on every return
+struct ProfSlots {
+  const hipEvent_t* prof;
+  void at(int i) const {
+    if (prof) g_prof = ProfCtx{prof[2 * i], prof[2 * i + 1]};
   }
-  XM_LAUNCH((k_minmax<T, AOS, HAS_P, 1>), dim3(grid), dim3(BLOCK), 0, stream, (const T*)ev.t, ev.p,
-            (const uint4*)ev.aos, n, st, tag_override);
+  ~ProfSlots() { g_prof = ProfCtx{}; }
+};
+
+// ---- (aos, use_p, t_dtype) -> template arguments -------------------------------------------------------------------------------
+// fn(EvTypes<T, AOS, HAS_P>{}) for the eight event layouts the kernels are instantiated for (AoS EventCD: int64 time stamps)
+template <typename T_, bool AOS_, bool HAS_P_>
+struct EvTypes {
+  using T = T_;
+  static constexpr bool AOS = AOS_, HAS_P = HAS_P_;
+};
+template <typename Fn>
+auto with_event_types(const EventsView& ev, Fn&& fn) {
+  if (ev.aos) return ev.use_p ? fn(EvTypes<long long, true, true>{}) : fn(EvTypes<long long, true, false>{});
+  switch (ev.t_dtype) {
+    case XM_T_INT64: return ev.use_p ? fn(EvTypes<long long, false, true>{}) : fn(EvTypes<long long, false, false>{});
+    case XM_T_FLOAT32: return ev.use_p ? fn(EvTypes<float, false, true>{}) : fn(EvTypes<float, false, false>{});
+    default: return ev.use_p ? fn(EvTypes<double, false, true>{}) : fn(EvTypes<double, false, false>{});
+  }
+}
+// the layouts of the column / owner tiles (and of a captured group's redo): int64 time stamps, no polarity column
+template <typename E>
+constexpr bool tile_types = std::is_same<typename E::T, long long>::value && !E::HAS_P;
+
+// ---- K0 (extrema) ---------------------------------------------------------------------------------------------------------------
+// blocks per frame: ~2048 events per thread-block iteration keeps every CU busy without drowning the 32 atomic slots (VEC2: K0_UN
+// loads x 2 events per thread per sweep); a grid-stride kernel, so the grid is capped
+unsigned k0_blocks(u64 n, bool vec2, unsigned cap) {
+  const unsigned g = grid_for(n, BLOCK * (vec2 ? 2 * K0_UN : 4));
+  return g > cap ? cap : g;
+}
+// VEC2 (16-byte loads of int64 SoA time stamps): a lone frame needs its t (and p) aligned, a group every column of every frame
+bool k0_vec2(const LoneFrame& f) { return aligned(f.ev.t, 16) && (!f.ev.use_p || aligned(f.ev.p, 4)); }
+bool k0_vec2(const FrameGroup& g) { return g.all_vec16; }
+
+// COND = 1: the redo node of a captured group (cap = 64: usually every block returns at once)
+template <typename T, bool AOS, bool HAS_P, int COND = 0, typename F>
+void launch_k0(const F& fr, hipStream_t stream, unsigned cap = 1024) {
+  auto go = [&](auto vec_tag) {
+    constexpr int VEC = decltype(vec_tag)::value;
+    const unsigned gx = k0_blocks(fr.n_max(), VEC == 2, cap);
+    if constexpr (is_lone<F>)
+      XM_LAUNCH((k_minmax<T, AOS, HAS_P, VEC>), dim3(gx), dim3(BLOCK), 0, stream, (const T*)fr.ev.t, fr.ev.p,
+                (const uint4*)(VEC == 2 ? nullptr : fr.ev.aos), fr.ev.n, fr.st, fr.tag_override);
+    else
+      XM_LAUNCH((k_minmax_batch<T, AOS, HAS_P, VEC, COND>), dim3(gx, fr.n), dim3(BLOCK), 0, stream, fr.descs);
+  };
+  if constexpr (!AOS && std::is_same<T, long long>::value) {
+    if (k0_vec2(fr)) return go(std::integral_constant<int, 2>{});
+  }
+  go(std::integral_constant<int, 1>{});
 }
 
 void launch_minmax(const EventsView& ev, SlotState* st, u32 tag_override, hipStream_t stream) {
-  if (ev.aos) {
-    if (ev.use_p) launch_minmax_t<long long, true, true>(ev, st, tag_override, stream);
-    else launch_minmax_t<long long, true, false>(ev, st, tag_override, stream);
-    return;
-  }
-  const bool hp = ev.use_p;
-  switch (ev.t_dtype) {
-    case XM_T_INT64:
-      hp ? launch_minmax_t<long long, false, true>(ev, st, tag_override, stream)
-         : launch_minmax_t<long long, false, false>(ev, st, tag_override, stream);
-      break;
-    case XM_T_FLOAT32:
-      hp ? launch_minmax_t<float, false, true>(ev, st, tag_override, stream)
-         : launch_minmax_t<float, false, false>(ev, st, tag_override, stream);
-      break;
-    default:
-      hp ? launch_minmax_t<double, false, true>(ev, st, tag_override, stream)
-         : launch_minmax_t<double, false, false>(ev, st, tag_override, stream);
-  }
+  with_event_types(ev, [&](auto ty) {
+    using E = decltype(ty);
+    launch_k0<typename E::T, E::AOS, E::HAS_P>(LoneFrame{ev, st, tag_override}, stream);
+  });
 }
 
-struct ScatterArgs {
-  xm_handle* h;
-  const EventsView* ev;
-  const DevTables* tb;
-  int view;
-  SlotState* st;
-  u32 tag_override;
-  u64 idx_offset, mm_lo, mm_hi;
-  const void* mm_ext;  // sharded mode: {tmin, -tmax} in device memory (NULL: mm_lo / mm_hi)
-  u64* frame;
-  unsigned char* dirty;
-  hipStream_t stream;
-  int w_ts, w_x;
-  size_t lds;
-  bool direct;
-  bool sorted;
-  bool key32;
-};
+// ---- K1 (scatter): tiled, or one thread per event --------------------------------------------------------------------------------
+// The tiled kernel pays a fixed price per block (copy the bands, clear + scan w_ts * xmap_h slots), so it needs blocks of >= 1024
+// events whose time slice still fits the LDS window of w_ts X-map columns.  A frame of n events spreads over xmap_w columns: a
+// block of E events spans about E * xmap_w / n of them.  Dense frames (C-1M: 1 M events / 640 columns) get 4096-event blocks;
+// sparse ones (ESL-like: 150 K events / 1080 columns, < 1 event per slot, nothing to de-duplicate) go to the one-thread-per-event
+// kernel, whose cost is proportional to n.
+double k1_block_events(const xm_handle* h, u64 n) {  // the most events a block of a frame of n events may take
+  return h->tb.xmap_w > 0 ? (h->w_ts - 1.5) * (double)n / (double)h->tb.xmap_w : 0.0;
+}
+bool tiled_path(const xm_handle* h, u64 n) {  // dense enough for the tiled K1?
+  return !h->k1_direct && h->w_ts > 0 && h->w_x > 0 && k1_block_events(h, n) >= 1024.0;
+}
+unsigned k1_threads(const xm_handle* h, u64 n) {  // the tiled K1's block for frames of n events
+  const double max_ev = k1_block_events(h, n);
+  unsigned threads = TILE_THREADS;
+  while (threads > 1024 / TILE_EPT && (double)(threads * TILE_EPT) > max_ev) threads >>= 1;  // smallest block: 1024 events
+  return threads;
+}
 
-template <typename T, bool AOS, bool HAS_P, int VIEW>
-int launch_scatter_tv(const ScatterArgs& a) {
-  const EventsView& ev = *a.ev;
-  const u64 n = ev.n;
-  const bool vec16 = !AOS && aligned(ev.x, 16) && aligned(ev.y, 16) && aligned(ev.t, 16) && (!HAS_P || aligned(ev.p, 16));
-  const bool vec = !AOS && aligned(ev.x, 8) && aligned(ev.y, 8) && aligned(ev.t, 16) && (!HAS_P || aligned(ev.p, 8));
-  // The tiled kernel pays a fixed price per block (copy the bands, clear + scan w_ts * xmap_h slots), so it needs blocks
-  // of >= 1024 events whose time slice still fits the LDS window of w_ts X-map columns.  A frame of n events spreads over
-  // xmap_w columns: a block of E events spans about E * xmap_w / n of them.  Dense frames (C-1M: 1 M events / 640
-  // columns) get 4096-event blocks; sparse ones (ESL-like: 150 K events / 1080 columns, < 1 event per slot, nothing to
-  // de-duplicate) go to the one-thread-per-event kernel, whose cost is proportional to n.
-  const double max_ev = a.tb->xmap_w > 0 ? (a.w_ts - 1.5) * (double)n / (double)a.tb->xmap_w : 0.0;
-  if (!a.direct && a.w_ts > 0 && a.w_x > 0 && max_ev >= 1024.0) {
+// tiled: the tiled kernel (key32: onto the compact key frame), else one thread per event.  COND = 1: the redo node of a captured
+// group (projector view, 64-bit keys, at most 32 blocks per frame)
+template <typename T, bool AOS, bool HAS_P, int COND = 0, typename F>
+int launch_k1(xm_handle* h, const F& fr, bool tiled, bool key32, bool sorted, hipStream_t stream) {
+  auto go = [&](auto view_tag) -> int {
+    constexpr int VIEW = decltype(view_tag)::value;
+    if (!tiled) {
+      if constexpr (is_lone<F>) {
+        const EventsView& ev = fr.ev;
+        const bool vec = !AOS && aligned(ev.x, 8) && aligned(ev.y, 8) && aligned(ev.t, 16) && (!HAS_P || aligned(ev.p, 8));
+        if constexpr (AOS)
+          XM_LAUNCH((k_scatter<T, true, HAS_P, 1, VIEW>), dim3(grid_for(ev.n, BLOCK)), dim3(BLOCK), 0, stream,
+                    (const uint16_t*)nullptr, (const uint16_t*)nullptr, (const T*)nullptr, (const int16_t*)nullptr,
+                    (const uint4*)ev.aos, ev.n, fr.idx_offset, h->tb, fr.st, fr.tag_override, fr.mm_lo, fr.mm_hi, fr.mm_ext,
+                    (u64*)fr.frame, fr.dirty, sorted ? 1 : 0);
+        else if (vec)
+          XM_LAUNCH((k_scatter<T, false, HAS_P, 4, VIEW>), dim3(grid_for(ev.n, BLOCK * 4)), dim3(BLOCK), 0, stream, ev.x, ev.y,
+                    (const T*)ev.t, ev.p, (const uint4*)nullptr, ev.n, fr.idx_offset, h->tb, fr.st, fr.tag_override, fr.mm_lo,
+                    fr.mm_hi, fr.mm_ext, (u64*)fr.frame, fr.dirty, sorted ? 1 : 0);
+        else
+          XM_LAUNCH((k_scatter<T, false, HAS_P, 1, VIEW>), dim3(grid_for(ev.n, BLOCK)), dim3(BLOCK), 0, stream, ev.x, ev.y,
+                    (const T*)ev.t, ev.p, (const uint4*)nullptr, ev.n, fr.idx_offset, h->tb, fr.st, fr.tag_override, fr.mm_lo,
+                    fr.mm_hi, fr.mm_ext, (u64*)fr.frame, fr.dirty, sorted ? 1 : 0);
+      } else {  // grid = (blocks of the largest frame, frames)
+        XM_LAUNCH((k_scatter_direct_batch<T, AOS, HAS_P, VIEW>), dim3(grid_for(fr.n_max(), BLOCK), fr.n), dim3(BLOCK), 0, stream,
+                  fr.descs, h->tb, sorted ? 1 : 0);
+      }
+      return XM_OK;
+    }
+    auto inst = [](auto vec_tag, auto key32_tag) {
+      constexpr bool V = decltype(vec_tag)::value, K = decltype(key32_tag)::value;
+      if constexpr (is_lone<F>) return k_scatter_tiled<T, AOS, HAS_P, VIEW, V, K>;
+      else return k_scatter_tiled_batch<T, AOS, HAS_P, VIEW, V, K, COND>;
+    };
     // vector-load variant: 16-byte aligned SoA columns with int64 t (the EventCD time type); everything else takes the
     // lane-strided loads (any alignment)
     constexpr bool kHasVec = !AOS && std::is_same<T, long long>::value;
-    auto kern = k_scatter_tiled<T, AOS, HAS_P, VIEW, false>;
+    const bool v16 = kHasVec && vec16(fr);
+    auto kern = inst(std::false_type{}, std::false_type{});
     if constexpr (kHasVec) {
-      if (vec16) kern = k_scatter_tiled<T, AOS, HAS_P, VIEW, true>;
+      if (v16) kern = inst(std::true_type{}, std::false_type{});
     }
-    if (a.key32) {  // compact key frame (a.frame points at it)
-      kern = k_scatter_tiled<T, AOS, HAS_P, VIEW, false, true>;
-      if constexpr (kHasVec) {
-        if (vec16) kern = k_scatter_tiled<T, AOS, HAS_P, VIEW, true, true>;
+    if constexpr (COND == 0) {
+      if (key32) {
+        kern = inst(std::false_type{}, std::true_type{});
+        if constexpr (kHasVec) {
+          if (v16) kern = inst(std::true_type{}, std::true_type{});
+        }
       }
     }
     // raise the kernel's dynamic-LDS cap once per (handle = device, kernel instantiation); gfx950: 160 KB / CU
-    {
-      int rc_lds = a.h->ensure_lds(reinterpret_cast<const void*>(kern), a.lds);
-      if (rc_lds) return rc_lds;
+    int rc = h->ensure_lds(reinterpret_cast<const void*>(kern), h->k1_lds);
+    if (rc) return rc;
+    // block size from the mean frame: a sparser frame of a group only sends more of its events down the direct path in the kernel
+    const unsigned threads = k1_threads(h, fr.n_mean());
+    unsigned gx = grid_for(fr.n_max(), threads * TILE_EPT);
+    if (COND == 1) gx = std::min(gx, 32u);
+    if constexpr (is_lone<F>) {
+      const EventsView& ev = fr.ev;
+      XM_LAUNCH(kern, dim3(gx), dim3(threads), h->k1_lds, stream, ev.x, ev.y, (const T*)ev.t, ev.p, (const uint4*)ev.aos, ev.n,
+                fr.idx_offset, h->tb, fr.st, fr.tag_override, fr.mm_lo, fr.mm_hi, fr.mm_ext, (u64*)fr.frame, fr.dirty, h->w_ts,
+                h->w_x, sorted ? 1 : 0);
+    } else {
+      XM_LAUNCH(kern, dim3(gx, fr.n), dim3(threads), h->k1_lds, stream, fr.descs, h->tb, h->w_ts, h->w_x, sorted ? 1 : 0);
     }
-    unsigned threads = TILE_THREADS;
-    while (threads > 1024 / TILE_EPT && (double)(threads * TILE_EPT) > max_ev) threads >>= 1;  // smallest block: 1024 events
-    XM_LAUNCH(kern, dim3(grid_for(n, threads * TILE_EPT)), dim3(threads), a.lds, a.stream, ev.x, ev.y,
-              (const T*)ev.t, ev.p, (const uint4*)ev.aos, n, a.idx_offset, *a.tb, a.st, a.tag_override,
-              a.mm_lo, a.mm_hi, a.mm_ext, a.frame, a.dirty, a.w_ts, a.w_x, a.sorted ? 1 : 0);
     return XM_OK;
-  }
-  if constexpr (AOS) {
-    XM_LAUNCH((k_scatter<T, true, HAS_P, 1, VIEW>), dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, a.stream,
-              (const uint16_t*)nullptr, (const uint16_t*)nullptr, (const T*)nullptr, (const int16_t*)nullptr,
-              (const uint4*)ev.aos, n, a.idx_offset, *a.tb, a.st, a.tag_override, a.mm_lo, a.mm_hi, a.mm_ext, a.frame, a.dirty,
-              a.sorted ? 1 : 0);
-  } else if (vec) {
-    XM_LAUNCH((k_scatter<T, false, HAS_P, 4, VIEW>), dim3(grid_for(n, BLOCK * 4)), dim3(BLOCK), 0, a.stream,
-              ev.x, ev.y, (const T*)ev.t, ev.p, (const uint4*)nullptr, n, a.idx_offset, *a.tb, a.st,
-              a.tag_override, a.mm_lo, a.mm_hi, a.mm_ext, a.frame, a.dirty, a.sorted ? 1 : 0);
-  } else {
-    XM_LAUNCH((k_scatter<T, false, HAS_P, 1, VIEW>), dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, a.stream, ev.x,
-              ev.y, (const T*)ev.t, ev.p, (const uint4*)nullptr, n, a.idx_offset, *a.tb, a.st, a.tag_override,
-              a.mm_lo, a.mm_hi, a.mm_ext, a.frame, a.dirty, a.sorted ? 1 : 0);
-  }
+  };
+  if (COND == 1 || h->cfg.view == XM_VIEW_PROJECTOR) return go(std::integral_constant<int, 0>{});
+  if constexpr (COND == 0) return go(std::integral_constant<int, 1>{});
   return XM_OK;
-}
-
-template <typename T, bool AOS, bool HAS_P>
-int launch_scatter_t(const ScatterArgs& a) {
-  return a.view == XM_VIEW_PROJECTOR ? launch_scatter_tv<T, AOS, HAS_P, 0>(a) : launch_scatter_tv<T, AOS, HAS_P, 1>(a);
 }
 
 int launch_scatter(xm_handle* h, const EventsView& ev, SlotState* st, u32 tag_override, u64 idx_offset, u64 mm_lo,
                    u64 mm_hi, u64* frame, unsigned char* dirty, hipStream_t stream, bool sorted = false,
                    const void* mm_ext = nullptr, bool key32 = false) {
-  ScatterArgs a{h, &ev, &h->tb, h->cfg.view, st, tag_override, idx_offset, mm_lo, mm_hi, mm_ext, frame, dirty, stream,
-                h->w_ts, h->w_x, h->k1_lds, h->k1_direct, sorted, key32};
-  if (ev.aos) return ev.use_p ? launch_scatter_t<long long, true, true>(a) : launch_scatter_t<long long, true, false>(a);
-  switch (ev.t_dtype) {
-    case XM_T_INT64: return ev.use_p ? launch_scatter_t<long long, false, true>(a) : launch_scatter_t<long long, false, false>(a);
-    case XM_T_FLOAT32: return ev.use_p ? launch_scatter_t<float, false, true>(a) : launch_scatter_t<float, false, false>(a);
-    default: return ev.use_p ? launch_scatter_t<double, false, true>(a) : launch_scatter_t<double, false, false>(a);
-  }
+  const LoneFrame fr{ev, st, tag_override, frame, dirty, nullptr, nullptr, idx_offset, mm_lo, mm_hi, mm_ext};
+  return with_event_types(ev, [&](auto ty) -> int {
+    using E = decltype(ty);
+    return launch_k1<typename E::T, E::AOS, E::HAS_P>(h, fr, tiled_path(h, ev.n), key32, sorted, stream);
+  });
 }
 
-// ---- column-tile K1 (xmaps_k1cols.hpp) ------------------------------------------------------------------------------------------
 // kmode of a frame: 0 = 64-bit key frame (general), 1 = compact 32-bit key frame, 2 = column tiles + plain u16 frame
 enum { KM_KEY64 = 0, KM_KEY32 = 1, KM_COLS = 2 };
 
@@ -242,6 +311,38 @@ void launch_k2_batch(xm_handle* h, hipStream_t stream, const FrameDesc* d_descs,
   else
     XM_LAUNCH((k_frame_proj_tiled_batch<FMT, COND, 2>), grid, dim3(K2_TX * K2_TY), k2_lds_bytes(h, 2), stream, d_descs, h->tb,
               (const ulonglong2*)h->d_zero16, h->k2_tile_cap[1]);
+}
+
+// K2 of a frame or a group by view and key format (kmode).  Projector view: the tiled frame kernel (a lone frame: k2_ppt(h, 1);
+// under XM_K2_DIRECT the per-pixel kernel, under XM_K2_FLAGS with the dirty map); camera view: k_frame_cam32 on the compact key
+// frame, k_frame_direct otherwise
+template <typename F>
+void launch_frame_kernel(xm_handle* h, const F& fr, int kmode, hipStream_t stream) {
+  const bool proj = h->cfg.view == XM_VIEW_PROJECTOR, key32 = kmode == KM_KEY32;
+  const u64 px = (u64)h->tb.cam_w * h->tb.cam_h;
+  const dim3 g32(grid_for(h->tb.cam_w, CAM32_T), grid_for(h->tb.cam_h, CAM32_T), frames(fr));
+  if constexpr (is_lone<F>) {
+    const u64* keys = static_cast<const u64*>(fr.frame);
+    const KeyCells cells{keys, 0};
+    if (proj && h->k2_direct)
+      XM_LAUNCH((k_frame_proj<KeyCells, 0>), dim3(grid_for((u64)h->tb.proj_w * h->tb.proj_h, BLOCK)), dim3(BLOCK), 0, stream, cells,
+                h->tb, fr.st, fr.tag_override, fr.depth, fr.bgr);
+    else if (proj && kmode == KM_COLS) launch_k2<2>(h, stream, keys, fr.st, fr.tag_override, nullptr, fr.depth, fr.bgr);
+    else if (proj && key32) launch_k2<1>(h, stream, keys, fr.st, fr.tag_override, nullptr, fr.depth, fr.bgr);
+    else if (proj) launch_k2<0>(h, stream, keys, fr.st, fr.tag_override, h->k2_flags ? fr.dirty : nullptr, fr.depth, fr.bgr);
+    else if (key32)  // camera view, compact frame: (event index + 1) << 12 | disparity, zeroed as it is read
+      XM_LAUNCH(k_frame_cam32, g32, dim3(BLOCK), 0, stream, static_cast<u32*>(fr.frame), h->tb.cam_w, h->tb.cam_h, fr.st, h->tb.dlut,
+                fr.depth, fr.bgr);
+    else
+      XM_LAUNCH((k_frame_direct<KeyCells>), dim3(grid_for(px, BLOCK)), dim3(BLOCK), 0, stream, cells, px, h->tb.p03, h->tb.z_near,
+                h->tb.z_far, fr.st, fr.tag_override, 1, h->tb.dlut, fr.depth, fr.bgr);
+  } else {
+    if (proj && kmode == KM_COLS) launch_k2_batch<2>(h, stream, fr.descs, fr.n);
+    else if (proj && key32) launch_k2_batch<1>(h, stream, fr.descs, fr.n);
+    else if (proj) launch_k2_batch<0>(h, stream, fr.descs, fr.n);
+    else if (key32) XM_LAUNCH(k_frame_cam32_batch, g32, dim3(BLOCK), 0, stream, fr.descs, h->tb.cam_w, h->tb.cam_h, h->tb.dlut);
+    else XM_LAUNCH(k_frame_direct_batch, dim3(grid_for(px, BLOCK), fr.n), dim3(BLOCK), 0, stream, fr.descs, px, h->tb.dlut);
+  }
 }
 
 size_t cols_lds_bytes(const xm_handle* h, int W) {  // mirrors the carve-up at the top of scatter_cols_body
