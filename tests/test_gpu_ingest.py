@@ -380,6 +380,27 @@ def test_the_ring_wraps_many_times(launch_thread):
     _check_frames(tb, got, tf.frames)
 
 
+@pytest.mark.parametrize("launch_thread", [True, False])
+def test_a_launch_side_error_reaches_the_caller_and_the_ingest_closes(launch_thread):
+    """XM_K2_DIRECT=1 (read by xm_create) makes a projector-view ingest refuse the first frame it cuts, on the host, before the
+    frame's K2 is launched.  The error reaches the caller -- from the launch thread through its error latch, or from the caller's
+    own call without one -- and the ingest closes: nothing waits for the frame that failed."""
+    xm_option("XM_K2_DIRECT", "1")
+    tb = S.make_tables(S.C_TINY)
+    pk = _packets(_tiny_stream(6, seed=23), int(1e6 / 60 / 4))
+    tf = IO.TriggerFinderOracle(60)
+    for p in pk:
+        tf.process_events(IO.polarity_filter(p))
+    assert len(tf.frames) >= 1
+    with XMapsEngine(tb) as eng:
+        ing = DeviceIngest(eng, 60, capacity_events=1 << 13, max_packet_events=1 << 11, result_ring=8, launch_thread=launch_thread)
+        with pytest.raises(ValueError, match="ingest needs the tiled frame kernel"):
+            for p in pk:
+                ing.push(p)
+            ing.flush()
+        ing.close()
+
+
 def test_packets_of_any_size_and_empty_packets():
     """the same stream in packets of 1 .. 7000 events (several blocks of 2048 per packet, blocks that keep nothing, pauses at
     block and packet borders) with empty pushes in between: the trigger finder sees the same buffer at every decision only if

@@ -408,7 +408,7 @@ void xm_destroy(xm_handle* h) {
   for (auto& w : h->workers) {
     Job stop;
     stop.kind = Job::STOP;
-    post_job(w.get(), stop);
+    w->q.post(stop);
   }
   for (auto& w : h->workers)
     if (w->th.joinable()) w->th.join();

@@ -212,8 +212,7 @@ static int ingest_push_words(xm_ingest* g, xm_evt3* d, int format, const void* w
     // use the same decoder: its state index and buffers are not to be touched from two threads) -- and the records then go to
     // the launch side like a packet that is already on the device
     if (g->threaded) {
-      const unsigned long long posted = ingest_posted(g);
-      while (g->q_done.load(std::memory_order_acquire) < posted && !g->q_error.load(std::memory_order_relaxed)) __builtin_ia32_pause();
+      g->launch_q.wait_done(ingest_posted(g), &g->err);
       if ((rc = ingest_take_error(g))) return rc;
     }
     size_t n = 0;

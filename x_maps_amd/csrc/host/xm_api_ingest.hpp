@@ -78,14 +78,12 @@ struct xm_ingest {
   };
   std::thread out_th;
   bool out_threaded = false;
-  std::atomic<bool> out_stop{false}, out_sleeping{false};
-  std::mutex out_mu;
-  std::condition_variable out_cv;
+  std::atomic<bool> out_stop{false};
+  Doorbell out_bell;                   // out_posted / out_stop have changed
   OutJob out_ring[8];                  // (the launch side never runs more than NOUT frames ahead of out_done)
   std::atomic<uint64_t> out_posted{0}; // frames handed to the out side
   std::atomic<uint64_t> out_done{0};   // frames whose copies + sequence number have been ENQUEUED on the out stream (out_ev[o] recorded)
-  std::atomic<int> out_error{0};
-  std::string out_error_text;
+  FirstError out_err;                  // the out side's first error: it stays (every later call of the launch side reports it)
   bool streams_borrowed = false;       // the four streams are the process's set for the device (ingest_stream_set), else own_streams
   hipStream_t own_streams[4] = {nullptr, nullptr, nullptr, nullptr};
   bool out_on_frame_stream = false;    // "XM_INGEST_OUT_SERIAL" = 1: copies + sequence number ALWAYS on the frame stream, in order with the frames' kernels (A/B)
@@ -160,14 +158,8 @@ struct xm_ingest {
     bool arrived = false;              // the copy side has issued the packet's H2D copy / the chunk's decoding and recorded copied_ev[k]
     uint64_t push_no = 0;              // number of the push (from 1; the caller's count = the launch side's `issued` + 1 when its turn comes)
   };
-  static constexpr unsigned QCAP = 64;
-  Job queue[QCAP];
-  std::atomic<unsigned long long> q_head{0}, q_tail{0}, q_done{0};
-  std::atomic<int> q_error{0};
-  std::string q_error_text;
-  std::mutex q_mu;
-  std::condition_variable q_cv;
-  std::atomic<bool> q_sleeping{false};
+  JobQueue<Job, 64> launch_q;
+  FirstError err;                      // the first error of the launch and copy threads (the caller's next call reports it)
   std::thread th;
   bool threaded = false;
   // Copy side (round 5): a second thread IN FRONT of the launch thread issues what brings a packet to the device -- the H2D copy
@@ -175,11 +167,7 @@ struct xm_ingest {
   // order, to the launch thread, which then issues one stream-wait and the ingest kernels.  With the activity filter the launch
   // thread's 7 runtime calls per packet were what bounded the stream (profiles/r05_ingest.md); now 2-4 of them run beside the rest.
   // "XM_INGEST_NO_COPY_THREAD": the launch thread does both (A/B).
-  Job cqueue[QCAP];
-  std::atomic<unsigned long long> c_head{0}, c_tail{0};
-  std::atomic<bool> c_sleeping{false};
-  std::mutex c_mu;
-  std::condition_variable c_cv;
+  JobQueue<Job, 64> copy_q;
   std::thread copy_th;
   bool copy_threaded = false;
   uint64_t posted = 0;                 // pushes accepted so far (the caller's count)
@@ -318,18 +306,9 @@ void ingest_out_main(xm_ingest* g) {
   for (;;) {
     // A frame's copy should start the moment its K2 is on the stream (with one frame per packet the copies are what bounds the
     // pipe: a sleeping thread's wake-up would go straight into the frame period): spin for about a millisecond before sleeping.
-    for (int i = 0; g->out_posted.load(std::memory_order_acquire) == n; ++i) {
-      if (g->out_stop.load(std::memory_order_acquire)) return;
-      if (i < 40000) {
-        __builtin_ia32_pause();
-        continue;
-      }
-      std::unique_lock<std::mutex> lk(g->out_mu);
-      g->out_sleeping.store(true, std::memory_order_seq_cst);
-      g->out_cv.wait(lk, [&] { return g->out_stop.load(std::memory_order_acquire) || g->out_posted.load(std::memory_order_acquire) != n; });
-      g->out_sleeping.store(false, std::memory_order_relaxed);
-      i = 0;
-    }
+    g->out_bell.wait([&] { return g->out_posted.load(std::memory_order_acquire) != n || g->out_stop.load(std::memory_order_acquire); },
+                     40000);
+    if (g->out_posted.load(std::memory_order_acquire) == n) return;  // (stopped, every frame taken)
     {  // frames below out_done are done (the launch side took them itself while this thread slept): their entries may be gone
       const uint64_t d = g->out_done.load(std::memory_order_acquire);
       if (d > n) {
@@ -339,37 +318,30 @@ void ingest_out_main(xm_ingest* g) {
     }
     const xm_ingest::OutJob j = g->out_ring[n % 8];
     // (a frame the launch side took itself -- out_serial_now -- is only counted: its entry says so, or holds another frame by now)
-    if (j.frame_no == n && !j.serial && !g->out_error.load(std::memory_order_relaxed)) {
-      const int rc = ingest_out_frame(g, j);
-      if (rc) {
-        g->out_error_text = g_err;  // (thread-local text of this thread)
-        g->out_error.store(rc, std::memory_order_release);
-      }
-    }
+    if (j.frame_no == n && !j.serial && !g->out_err.code(std::memory_order_relaxed)) g->out_err.note(ingest_out_frame(g, j), g_err);
     n += 1;
     for (uint64_t cur = g->out_done.load(std::memory_order_acquire); cur < n;)
       if (g->out_done.compare_exchange_weak(cur, n, std::memory_order_release)) break;
   }
 }
 
+// the out side's error, if it has one (it stays)
+int ingest_out_error(xm_ingest* g) {
+  std::string text;
+  const int e = g->out_err.peek(&text);
+  return e ? fail(e, "ingest, out side: %s", text.c_str()) : XM_OK;
+}
+
 // frames below `upto` have their out work enqueued
 int ingest_out_drain_upto(xm_ingest* g, uint64_t upto) {
-  while (g->out_done.load(std::memory_order_acquire) < upto) {
-    if (g->out_error.load(std::memory_order_acquire)) break;
-    __builtin_ia32_pause();
-  }
-  if (g->out_error.load(std::memory_order_acquire)) return fail(g->out_error.load(), "ingest, out side: %s", g->out_error_text.c_str());
-  return XM_OK;
+  while (g->out_done.load(std::memory_order_acquire) < upto && !g->out_err.code()) __builtin_ia32_pause();
+  return ingest_out_error(g);
 }
 
 // every frame issued so far has its out-stream work enqueued
 int ingest_out_drain(xm_ingest* g) {
-  while (g->out_done.load(std::memory_order_acquire) < g->frames_issued) {
-    if (g->out_error.load(std::memory_order_acquire)) break;
-    std::this_thread::yield();
-  }
-  if (g->out_error.load(std::memory_order_acquire)) return fail(g->out_error.load(), "ingest, out side: %s", g->out_error_text.c_str());
-  return XM_OK;
+  while (g->out_done.load(std::memory_order_acquire) < g->frames_issued && !g->out_err.code()) std::this_thread::yield();
+  return ingest_out_error(g);
 }
 
 // K0 -> K1 -> K2 -> statistics for the frame that packet `push_no` cut (n events), on the frame stream; its copies to the out side
@@ -402,7 +374,7 @@ int ingest_issue_frame(xm_ingest* g, uint64_t push_no, u64 n) {
     // (the event must have been RECORDED by the out side before this stream can be told to wait for it)
     const double tw = ingest_now();
     while (g->out_done.load(std::memory_order_acquire) + xm_ingest::NOUT <= f) {
-      if (g->out_error.load(std::memory_order_acquire)) return fail(g->out_error.load(), "ingest, out side: %s", g->out_error_text.c_str());
+      if (g->out_err.code()) return ingest_out_error(g);
       __builtin_ia32_pause();
     }
     g->t_out_wait_s += ingest_now() - tw;
@@ -427,10 +399,7 @@ int ingest_issue_frame(xm_ingest* g, uint64_t push_no, u64 n) {
   if (g->out_threaded && !job.serial) {
     g->out_ring[f % 8] = job;
     g->out_posted.store(f + 1, std::memory_order_seq_cst);
-    if (g->out_sleeping.load(std::memory_order_seq_cst)) {
-      std::lock_guard<std::mutex> lk(g->out_mu);
-      g->out_cv.notify_one();
-    }
+    g->out_bell.ring();
   } else {
     int rc = g->out_threaded ? ingest_out_drain_upto(g, f) : XM_OK;  // (frames posted before the mode changed come first)
     if (!rc) rc = ingest_out_frame(g, job);
@@ -542,7 +511,7 @@ int ingest_process(xm_ingest* g, int k, size_t n, const uint4* hp, const u32* n_
     const IngestStatus* stp = g->h_status + (fe - 1) % (uint64_t)g->ring;
     unsigned spins = 0;
     while (__atomic_load_n(&stp->seq, __ATOMIC_ACQUIRE) < fe) {
-      if (g->out_error.load(std::memory_order_acquire)) return fail(g->out_error.load(), "ingest, out side: %s", g->out_error_text.c_str());
+      if (g->out_err.code()) return ingest_out_error(g);
       __builtin_ia32_pause();
       if ((++spins & 0xfff) == 0) (void)hipStreamQuery(g->out_stream);
     }
@@ -620,136 +589,75 @@ int ingest_run_job(xm_ingest* g, const xm_ingest::Job& j) {
 
 void ingest_thread_main(xm_ingest* g) {
   (void)hipSetDevice(g->h->cfg.device);
-  const auto note = [&](int rc) {
-    if (rc != XM_OK && g->q_error.load(std::memory_order_relaxed) == 0) {
-      g->q_error_text = g_err;  // thread-local text of this thread
-      g->q_error.store(rc, std::memory_order_release);
-    }
+  // Nothing to launch: verdicts first -- a frame's kernels go out the moment its packet's verdict arrives (a live camera's
+  // packets are milliseconds apart: the frame must not wait for the next one) -- then spin a little, then sleep.  Never
+  // asleep with a verdict outstanding (it is at most a few ten microseconds away).
+  const auto idle = [g](unsigned long long i) {
+    if (g->next_verdict > g->issued) return true;
+    g->err.note(ingest_handle_verdicts(g, 0), g_err);
+    if (g->err.code(std::memory_order_relaxed)) g->next_verdict = g->issued + 1;  // (do not spin on a failed stream)
+    if ((i & 0x3ff) == 0x3ff) (void)hipStreamQuery(g->stream);  // (a query makes the runtime hand over what it may still hold back)
+    return false;
   };
   for (;;) {
-    unsigned long long t = g->q_tail.load(std::memory_order_relaxed);
-    if (t == g->q_head.load(std::memory_order_acquire)) {
-      // Nothing to launch: verdicts first -- a frame's kernels go out the moment its packet's verdict arrives (a live camera's
-      // packets are milliseconds apart: the frame must not wait for the next one) -- then spin a little, then sleep.  Never
-      // asleep with a verdict outstanding (it is at most a few ten microseconds away).
-      bool got = false;
-      for (int i = 0; !got; ++i) {
-        if (g->next_verdict <= g->issued) {
-          note(ingest_handle_verdicts(g, 0));
-          if (g->q_error.load(std::memory_order_relaxed)) g->next_verdict = g->issued + 1;  // (do not spin on a failed stream)
-          if ((i & 0x3ff) == 0x3ff) (void)hipStreamQuery(g->stream);  // (a query makes the runtime hand over what it may still hold back)
-          if (i >= 1 << 20) i = 0;
-        } else if (i >= 20000) {
-          break;
-        }
-        __builtin_ia32_pause();
-        got = t != g->q_head.load(std::memory_order_acquire);
-      }
-      if (!got) {
-        std::unique_lock<std::mutex> lk(g->q_mu);
-        g->q_sleeping.store(true, std::memory_order_seq_cst);
-        g->q_cv.wait(lk, [&] { return t != g->q_head.load(std::memory_order_acquire); });
-        g->q_sleeping.store(false, std::memory_order_relaxed);
-      }
-    }
-    const xm_ingest::Job j = g->queue[t % xm_ingest::QCAP];
-    g->q_tail.store(t + 1, std::memory_order_release);
+    const xm_ingest::Job j = g->launch_q.take(20000, idle);
     if (j.kind != 2) {
       const double cj = ingest_now();
-      // the job queued behind this one, if it is a packet whose copy / decoding the copy side has issued already (its slot of the
-      // queue is not reused before q_tail passes it)
+      // the job queued behind this one, if it is a packet whose copy / decoding the copy side has issued already
       g->next_job = nullptr;
-      if ((j.kind == 0 || j.kind == 1 || j.kind == 3) && g->q_head.load(std::memory_order_acquire) > t + 1) {
-        const xm_ingest::Job& c = g->queue[(t + 1) % xm_ingest::QCAP];
-        if ((c.kind == 0 || c.kind == 1) && c.arrived && c.n) g->next_job = &c;
+      if (j.kind == 0 || j.kind == 1 || j.kind == 3) {
+        const xm_ingest::Job* c = g->launch_q.next();
+        if (c && (c->kind == 0 || c->kind == 1) && c->arrived && c->n) g->next_job = c;
       }
-      note(ingest_run_job(g, j));
+      g->err.note(ingest_run_job(g, j), g_err);
       g->next_job = nullptr;
       g->t_jobs_s += ingest_now() - cj;
     }
-    g->q_done.store(t + 1, std::memory_order_release);
+    g->launch_q.finish();
     if (j.kind == 2) return;
   }
 }
 
-// into the launch thread's queue (from the caller, or -- with a copy thread -- from that one: a single producer either way)
-unsigned long long ingest_post_launch(xm_ingest* g, const xm_ingest::Job& j) {
-  const unsigned long long hd = g->q_head.load(std::memory_order_relaxed);
-  while (hd - g->q_tail.load(std::memory_order_acquire) >= xm_ingest::QCAP) __builtin_ia32_pause();  // queue full: back-pressure
-  g->queue[hd % xm_ingest::QCAP] = j;
-  g->q_head.store(hd + 1, std::memory_order_seq_cst);
-  if (g->q_sleeping.load(std::memory_order_seq_cst)) {
-    std::lock_guard<std::mutex> lk(g->q_mu);
-    g->q_cv.notify_one();
-  }
-  return hd + 1;
-}
-
 // The caller's door: the copy thread's queue when there is one (every job passes through it and is forwarded IN ORDER, so a job's
-// number is the same in both queues and q_done counts them alike), else the launch thread's.
+// number is the same in both queues and the launch queue's count of finished jobs counts them alike), else the launch thread's.
 unsigned long long ingest_post(xm_ingest* g, const xm_ingest::Job& j) {
-  if (!g->copy_threaded) return ingest_post_launch(g, j);
-  const unsigned long long hd = g->c_head.load(std::memory_order_relaxed);
-  while (hd - g->c_tail.load(std::memory_order_acquire) >= xm_ingest::QCAP) __builtin_ia32_pause();
-  g->cqueue[hd % xm_ingest::QCAP] = j;
-  g->c_head.store(hd + 1, std::memory_order_seq_cst);
-  if (g->c_sleeping.load(std::memory_order_seq_cst)) {
-    std::lock_guard<std::mutex> lk(g->c_mu);
-    g->c_cv.notify_one();
-  }
-  return hd + 1;
+  return (g->copy_threaded ? g->copy_q : g->launch_q).post(j);
 }
 
 // jobs handed in so far (the caller's count)
 unsigned long long ingest_posted(const xm_ingest* g) {
-  return g->copy_threaded ? g->c_head.load(std::memory_order_acquire) : g->q_head.load(std::memory_order_acquire);
+  return (g->copy_threaded ? g->copy_q : g->launch_q).posted();
 }
 
 void ingest_copy_thread_main(xm_ingest* g) {
   (void)hipSetDevice(g->h->cfg.device);
   for (;;) {
-    const unsigned long long t = g->c_tail.load(std::memory_order_relaxed);
-    for (int i = 0; t == g->c_head.load(std::memory_order_acquire); ++i) {
-      if (i < 20000) {
-        __builtin_ia32_pause();
-        continue;
-      }
-      std::unique_lock<std::mutex> lk(g->c_mu);
-      g->c_sleeping.store(true, std::memory_order_seq_cst);
-      g->c_cv.wait(lk, [&] { return t != g->c_head.load(std::memory_order_acquire); });
-      g->c_sleeping.store(false, std::memory_order_relaxed);
-    }
-    xm_ingest::Job j = g->cqueue[t % xm_ingest::QCAP];
-    g->c_tail.store(t + 1, std::memory_order_release);
-    if ((j.kind == 0 || j.kind == 1) && !g->q_error.load(std::memory_order_relaxed)) {
+    xm_ingest::Job j = g->copy_q.take(20000);
+    if ((j.kind == 0 || j.kind == 1) && !g->err.code(std::memory_order_relaxed)) {
       const int rc = j.kind == 0 ? ingest_copy_records(g, j.k, j.n, (const uint4*)j.host) : ingest_copy_evt3(g, j.dec, j.k, j.host, j.n, j.pinned);
       if (rc != XM_OK) {
-        if (g->q_error.load(std::memory_order_relaxed) == 0) {
-          g->q_error_text = g_err;  // thread-local text of this thread
-          g->q_error.store(rc, std::memory_order_release);
-        }
+        g->err.note(rc, g_err);
         j.kind = 5;  // (nothing arrived: the launch side only counts the job)
       }
       j.arrived = true;
     }
-    ingest_post_launch(g, j);
+    g->launch_q.post(j);
     if (j.kind == 2) return;
   }
 }
 
 int ingest_take_error(xm_ingest* g) {
-  const int e = g->q_error.load(std::memory_order_acquire);
-  if (!e) return XM_OK;
-  g->q_error.store(0, std::memory_order_release);
-  return fail(e, "%s (reported by the ingest's launch thread)", g->q_error_text.c_str());
+  std::string text;
+  const int e = g->err.take(&text);
+  return e ? fail(e, "%s (reported by the ingest's launch thread)", text.c_str()) : XM_OK;
 }
 
 // hand a job to the launch thread (or run it here); wait: until it has run
 int ingest_submit(xm_ingest* g, const xm_ingest::Job& j, bool wait) {
   if (!g->threaded) return ingest_run_job(g, j);
-  const unsigned long long idx = ingest_post(g, j);
+  const unsigned long long n = ingest_post(g, j);
   if (wait) {
-    while (g->q_done.load(std::memory_order_acquire) < idx) __builtin_ia32_pause();
+    g->launch_q.wait_done(n);
     return ingest_take_error(g);
   }
   return XM_OK;
@@ -763,7 +671,7 @@ int ingest_wait_entry(xm_ingest* g, int k) {
   if (!g->threaded) return ingest_handle_verdicts(g, need);
   const double c0 = ingest_now();
   g->stage_waits += 1;
-  while (g->handled.load(std::memory_order_acquire) < need && !g->q_error.load(std::memory_order_relaxed)) __builtin_ia32_pause();
+  while (g->handled.load(std::memory_order_acquire) < need && !g->err.code(std::memory_order_relaxed)) __builtin_ia32_pause();
   g->push_wait_s += ingest_now() - c0;
   return ingest_take_error(g);
 }
@@ -946,11 +854,8 @@ void xm_ingest_destroy(xm_ingest* g) {
   }
   if (g->out_threaded) {  // (behind the launch thread: nobody posts any more; the queue is drained before the thread leaves)
     (void)ingest_out_drain(g);  // (every posted frame is taken before the thread is told to leave)
-    {
-      std::lock_guard<std::mutex> lk(g->out_mu);
-      g->out_stop.store(true, std::memory_order_seq_cst);
-    }
-    g->out_cv.notify_all();
+    g->out_stop.store(true, std::memory_order_seq_cst);
+    g->out_bell.ring();
     if (g->out_th.joinable()) g->out_th.join();
     g->out_threaded = false;
   }
@@ -1214,7 +1119,7 @@ int xm_ingest_backlog(xm_ingest* g, int wait_below, uint64_t* backlog) {
         int rc = ingest_handle_verdicts(g, g->next_verdict);
         if (rc) return rc;
       } else {
-        if (g->q_error.load(std::memory_order_relaxed)) return ingest_take_error(g);
+        if (g->err.code(std::memory_order_relaxed)) return ingest_take_error(g);
         for (int k = 0; k < 64; ++k) __builtin_ia32_pause();
       }
       waited = true;

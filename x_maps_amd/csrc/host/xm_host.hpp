@@ -1,4 +1,4 @@
-// xm_host.hpp -- error reporting, device scratch, slots, launch workers' queues, the handle, launch / profile macros
+// xm_host.hpp -- error reporting, device scratch, slots, launch workers, the handle, launch / profile macros
 // (part of libxmaps_hip.so's host side: included by ../xmaps_hip.hip, one translation unit; see that file for the order)
 #pragma once
 
@@ -126,14 +126,8 @@ struct Job {
 };
 
 struct Worker {
-  static constexpr unsigned CAP = 256;  // jobs in flight per stream (the producer waits when full)
-  Job ring[CAP];
-  std::atomic<unsigned long long> head{0}, tail{0}, done{0};  // produced / taken / finished
-  std::atomic<int> error{0};  // first failing return code of a job (reported by the next xm_sync)
-  std::string error_text;
-  std::mutex mu;
-  std::condition_variable cv;
-  std::atomic<bool> sleeping{false};
+  JobQueue<Job, 256> q;  // jobs in flight per stream (the producer waits when full)
+  FirstError err;        // first failing return code of a job (reported by the next xm_sync)
   std::thread th;
 };
 

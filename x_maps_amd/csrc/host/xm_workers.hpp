@@ -10,50 +10,17 @@ Slot& pick_slot(xm_handle* h) {
   return h->slots[h->last_slot];
 }
 
-// XM_FLAG_TRY_SORTED: did the (t[0], t[n-1]) shortcut hold for the slot's last asynchronous frame?  The kernels answer in
-// pinned host memory (no API call when the frame has finished, which it has when a slot comes round again); a frame that
-// failed is redone here on the general path, into the same output buffers, before anything else happens on the slot.
 // ---- worker threads --------------------------------------------------------------------------------------------------
 void worker_main(xm_handle* h, Worker* w) {
   (void)hipSetDevice(h->cfg.device);
   for (;;) {
-    unsigned long long t = w->tail.load(std::memory_order_relaxed);
-    if (t == w->head.load(std::memory_order_acquire)) {  // empty: spin a little, then sleep
-      bool got = false;
-      for (int i = 0; i < 20000 && !got; ++i) {
-        __builtin_ia32_pause();
-        got = t != w->head.load(std::memory_order_acquire);
-      }
-      if (!got) {
-        std::unique_lock<std::mutex> lk(w->mu);
-        w->sleeping.store(true, std::memory_order_seq_cst);
-        w->cv.wait(lk, [&] { return t != w->head.load(std::memory_order_acquire); });
-        w->sleeping.store(false, std::memory_order_relaxed);
-      }
-    }
-    const Job j = w->ring[t % Worker::CAP];
-    w->tail.store(t + 1, std::memory_order_release);
+    const Job j = w->q.take(20000);
     if (j.kind == Job::STOP) {
-      w->done.store(t + 1, std::memory_order_release);
+      w->q.finish();
       return;
     }
-    const int rc = enqueue_frame(h, h->slots[j.slot], j.ev, j.depth, j.bgr, nullptr, j.allow_sorted);
-    if (rc != XM_OK && w->error.load(std::memory_order_relaxed) == 0) {
-      w->error_text = g_err;  // thread-local text of this worker
-      w->error.store(rc, std::memory_order_release);
-    }
-    w->done.store(t + 1, std::memory_order_release);
-  }
-}
-
-void post_job(Worker* w, const Job& j) {
-  const unsigned long long hd = w->head.load(std::memory_order_relaxed);
-  while (hd - w->tail.load(std::memory_order_acquire) >= Worker::CAP) __builtin_ia32_pause();  // ring full: back-pressure
-  w->ring[hd % Worker::CAP] = j;
-  w->head.store(hd + 1, std::memory_order_seq_cst);
-  if (w->sleeping.load(std::memory_order_seq_cst)) {
-    std::lock_guard<std::mutex> lk(w->mu);
-    w->cv.notify_one();
+    w->err.note(enqueue_frame(h, h->slots[j.slot], j.ev, j.depth, j.bgr, nullptr, j.allow_sorted), g_err);  // (this thread's text)
+    w->q.finish();
   }
 }
 
@@ -63,13 +30,10 @@ int drain_workers(xm_handle* h, int only = -1) {
   for (size_t i = 0; i < h->workers.size(); ++i) {
     if (only >= 0 && (int)i != only) continue;
     Worker* w = h->workers[i].get();
-    const unsigned long long hd = w->head.load(std::memory_order_acquire);
-    while (w->done.load(std::memory_order_acquire) < hd) __builtin_ia32_pause();
-    const int e = w->error.load(std::memory_order_acquire);
-    if (e && rc == XM_OK) {
-      rc = fail(e, "%s (reported by the launch worker of stream %zu)", w->error_text.c_str(), i);
-      w->error.store(0, std::memory_order_release);
-    }
+    w->q.wait_done(w->q.posted());
+    std::string text;
+    if (rc == XM_OK)
+      if (const int e = w->err.take(&text)) rc = fail(e, "%s (reported by the launch worker of stream %zu)", text.c_str(), i);
   }
   return rc;
 }
@@ -83,6 +47,9 @@ int drain_workers(xm_handle* h, int only = -1) {
     if (!(h)->pending.empty() && (rc_enter_ = flush_pending(h))) return rc_enter_;  \
   } while (0)
 
+// XM_FLAG_TRY_SORTED: did the (t[0], t[n-1]) shortcut hold for the slot's last asynchronous frame?  The kernels answer in
+// pinned host memory (no API call when the frame has finished, which it has when a slot comes round again); a frame that
+// failed is redone here on the general path, into the same output buffers, before anything else happens on the slot.
 #ifndef XM_POLL_FIRST_US
 #define XM_POLL_FIRST_US 30
 #define XM_POLL_NEXT_US 100
@@ -126,7 +93,7 @@ int resolve_prev(xm_handle* h, Slot& s, bool* redone = nullptr) {
     j.bgr = s.prev.bgr;
     j.allow_sorted = false;
     s.api_tag = s.api_tag >= KEY_MAX_TAG ? 1 : s.api_tag + 1;
-    post_job(h->workers[s.worker].get(), j);
+    h->workers[s.worker]->q.post(j);
     if (redone) *redone = true;
     return XM_OK;
   }
@@ -181,7 +148,7 @@ int process_common(xm_handle* h, EventsView ev, int mem, float* depth_out, uint8
     j.depth = depth_out;
     j.bgr = bgr_out;
     s.api_tag = s.api_tag >= KEY_MAX_TAG ? 1 : s.api_tag + 1;
-    post_job(h->workers[s.worker].get(), j);
+    h->workers[s.worker]->q.post(j);
     if (s.h_flags) {
       s.prev.valid = true;
       s.prev.check = h->try_sorted && sorted_path(h, ev);

@@ -37,7 +37,8 @@
 using namespace xm;
 
 // The host side is one translation unit, split by concern (each file closes the namespaces / linkage blocks it opens):
-#include "host/xm_host.hpp"         // errors, slots, workers' queues, the handle, launch macros
+#include "host/xm_queue.hpp"        // the host threads' job queues and first-error latches (standard C++ only)
+#include "host/xm_host.hpp"         // errors, slots, launch workers, the handle, launch macros
 #include "host/xm_launch.hpp"       // launch helpers of every kernel variant
 #include "host/xm_own_plan.hpp"     // owner-tile tables (host analysis in xm_create)
 #include "host/xm_enqueue.hpp"      // path selection + the launches of one frame
