@@ -6,16 +6,16 @@
 struct xm_evt3 {
   xm_handle* h = nullptr;
   int device = 0;  // (kept here: the decoder may be destroyed after its handle)
-  hipStream_t stream = nullptr;
+  Stream stream;
   size_t max_words = 0, max_events = 0;
   int format = 3;                // 3: 16-bit EVT 3.0 words; 2: 32-bit EVT 2.0 words
   size_t word_bytes = 2;
-  uint16_t* h_words = nullptr;   // pinned staging (max_words * word_bytes)
-  uint16_t* d_words = nullptr;
-  Evt3Scan* d_agg = nullptr;
-  Evt3State* d_state = nullptr;  // [2]: in / out, swapped per chunk
-  Evt3State* h_state = nullptr;  // pinned: the chunk's event count comes back here
-  uint4* d_out = nullptr;        // records of the last xm_evt3_decode
+  PinnedMem<uint16_t> h_words;   // pinned staging (max_words * word_bytes)
+  DevMem<uint16_t> d_words;
+  DevMem<Evt3Scan> d_agg;
+  DevMem<Evt3State> d_state;     // [2]: in / out, swapped per chunk
+  PinnedMem<Evt3State> h_state;  // pinned: the chunk's event count comes back here
+  DevMem<uint4> d_out;           // records of the last xm_evt3_decode
   int cur = 0;
   int wait_tb = 0;               // xm_evt3_wait_for_time_base: events in front of the stream's first TIME_HIGH word are not emitted
 };
@@ -38,8 +38,8 @@ int evt3_enqueue(xm_evt3* d, const void* words_host, size_t n_words, bool pinned
   Evt3State* st_in = d->d_state + d->cur;
   Evt3State* st_out = d->d_state + (d->cur ^ 1);
   if (d->format == 2) {
-    const u32* w32 = reinterpret_cast<const u32*>(d->d_words);
-    Evt2Scan* agg = reinterpret_cast<Evt2Scan*>(d->d_agg);
+    const u32* w32 = reinterpret_cast<const u32*>(d->d_words.get());
+    Evt2Scan* agg = reinterpret_cast<Evt2Scan*>(d->d_agg.get());
     hipLaunchKernelGGL(k_evt2_aggregate, dim3(nb), dim3(EVT3_THREADS), 0, stream, w32, n, agg);
     hipLaunchKernelGGL(k_evt2_prefix, dim3(1), dim3(EVT3_THREADS), 0, stream, nb, agg, (const Evt3State*)st_in, st_out, count_out, d->wait_tb);
     hipLaunchKernelGGL(k_evt2_emit, dim3(nb), dim3(EVT3_THREADS), 0, stream, w32, n, (const Evt2Scan*)agg, (const Evt3State*)st_in, out,
@@ -104,7 +104,7 @@ static int evt_create(xm_handle* h, int format, size_t max_words, size_t max_eve
   if (!h || !out) return fail(XM_ERR_INVALID, "NULL argument");
   *out = nullptr;
   XM_ENTER(h);
-  xm_evt3* d = new (std::nothrow) xm_evt3();
+  Owned<xm_evt3, xm_evt3_destroy> d(new (std::nothrow) xm_evt3());
   if (!d) return fail(XM_ERR_NOMEM, "out of host memory");
   d->h = h;
   d->device = h->cfg.device;
@@ -112,31 +112,19 @@ static int evt_create(xm_handle* h, int format, size_t max_words, size_t max_eve
   d->word_bytes = format == 2 ? 4 : 2;
   d->max_words = max_words ? max_words : (size_t)1 << 20;
   d->max_events = max_events ? max_events : (format == 2 ? d->max_words : 2 * d->max_words);
-  if (d->max_words >= 0x7fffffffull || d->max_events >= 0x7fffffffull) {
-    delete d;
-    return fail(XM_ERR_INVALID, "max_words and max_events must be < 2^31");
-  }
+  if (d->max_words >= 0x7fffffffull || d->max_events >= 0x7fffffffull) return fail(XM_ERR_INVALID, "max_words and max_events must be < 2^31");
   const size_t nb = grid_for(d->max_words, EVT3_PER_BLOCK);
-#define EV_TRY(expr)                                                             \
-  do {                                                                           \
-    hipError_t e_ = (expr);                                                      \
-    if (e_ != hipSuccess) {                                                      \
-      int rc_ = fail(XM_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-      xm_evt3_destroy(d);                                                        \
-      return rc_;                                                                \
-    }                                                                            \
-  } while (0)
-  EV_TRY(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
-  EV_TRY(hipHostMalloc((void**)&d->h_words, d->max_words * d->word_bytes, hipHostMallocDefault));
-  EV_TRY(hipHostMalloc((void**)&d->h_state, sizeof(Evt3State), hipHostMallocDefault));
-  EV_TRY(hipMalloc((void**)&d->d_words, d->max_words * d->word_bytes + 64));
-  EV_TRY(hipMalloc((void**)&d->d_agg, (nb + 1) * sizeof(Evt3Scan)));
-  EV_TRY(hipMalloc((void**)&d->d_state, 2 * sizeof(Evt3State)));
-  EV_TRY(hipMemsetAsync(d->d_state, 0, 2 * sizeof(Evt3State), d->stream));  // (on the decoder's stream: it does not wait for the default one)
-  EV_TRY(hipStreamSynchronize(d->stream));
-  EV_TRY(hipMalloc((void**)&d->d_out, d->max_events * 16));
-#undef EV_TRY
-  *out = d;
+  const size_t n16 = d->max_words * d->word_bytes / sizeof(uint16_t);
+  HIP_TRY(d->stream.create(hipStreamNonBlocking));
+  HIP_TRY(d->h_words.alloc(n16, hipHostMallocDefault));
+  HIP_TRY(d->h_state.alloc(1, hipHostMallocDefault));
+  HIP_TRY(d->d_words.alloc(n16, 64));
+  HIP_TRY(d->d_agg.alloc(nb + 1));
+  HIP_TRY(d->d_state.alloc(2));
+  HIP_TRY(hipMemsetAsync(d->d_state, 0, 2 * sizeof(Evt3State), d->stream));  // (on the decoder's stream: it does not wait for the default one)
+  HIP_TRY(hipStreamSynchronize(d->stream));
+  HIP_TRY(d->d_out.alloc(d->max_events));
+  *out = d.release();
   return XM_OK;
 }
 
@@ -147,13 +135,6 @@ void xm_evt3_destroy(xm_evt3* d) {
   if (!d) return;
   (void)hipSetDevice(d->device);
   if (d->stream) (void)hipStreamSynchronize(d->stream);
-  if (d->h_words) (void)hipHostFree(d->h_words);
-  if (d->h_state) (void)hipHostFree(d->h_state);
-  if (d->d_words) (void)hipFree(d->d_words);
-  if (d->d_agg) (void)hipFree(d->d_agg);
-  if (d->d_state) (void)hipFree(d->d_state);
-  if (d->d_out) (void)hipFree(d->d_out);
-  if (d->stream) (void)hipStreamDestroy(d->stream);
   delete d;
 }
 

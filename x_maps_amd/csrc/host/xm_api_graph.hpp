@@ -19,7 +19,7 @@ static int graph_capture_batched(xm_handle* h, xm_graph* g, const uint16_t* x, c
   const int G = two ? ns / 2 : std::min(ns, n_frames);
   g->h_descs.resize(2 * (size_t)n_frames);  // [n_frames] the frames, [n_frames] the same frames on their slots' 64-bit key frames
   for (auto& d : g->h_descs) d = FrameDesc{};  // (valid = 0: unused entries are skipped by every kernel)
-  HIP_TRY(hipMalloc((void**)&g->d_descs, sizeof(FrameDesc) * 2 * n_frames));
+  HIP_TRY(g->d_descs.alloc(2 * (size_t)n_frames));
   hipStream_t origin = h->gstreams[0], second = two ? h->gstreams[1] : nullptr;
   int rc = XM_OK;
   hipError_t e = hipSuccess;
@@ -86,7 +86,7 @@ int xm_graph_create(xm_handle* h, const uint16_t* x, const uint16_t* y, const vo
     s.pending_batch_ev = nullptr;
     s.eager_dirty = false;
   }
-  xm_graph* g = new (std::nothrow) xm_graph();
+  Owned<xm_graph, xm_graph_destroy> g(new (std::nothrow) xm_graph());
   if (!g) return fail(XM_ERR_NOMEM, "out of host memory");
   g->h = h;
   g->n_frames = n_frames;
@@ -105,16 +105,11 @@ int xm_graph_create(xm_handle* h, const uint16_t* x, const uint16_t* y, const vo
   // Graphs are captured on (and launched from) default-priority streams of their own: launched from the slots'
   // high-priority streams the replay ran its branches one after the other (28 instead of 61 Gevents/s).
   if (h->gstreams.empty()) {
-    h->gstreams.assign(std::max(ns, 2), nullptr);
-    for (auto& gs : h->gstreams) {
-      hipError_t ce = hipStreamCreateWithFlags(&gs, hipStreamNonBlocking);
-      if (ce != hipSuccess) {
-        delete g;
-        return fail(XM_ERR_HIP, "hipStreamCreateWithFlags: %s", hipGetErrorString(ce));
-      }
-    }
+    std::vector<Stream> gs(std::max(ns, 2));
+    for (Stream& s : gs) HIP_TRY(s.create(hipStreamNonBlocking));
+    h->gstreams = std::move(gs);
   }
-  int rc = graph_capture_batched(h, g, x, y, t, p, t_dtype, offsets_host, n_frames, depth_out, bgr_out);
+  int rc = graph_capture_batched(h, g.get(), x, y, t, p, t_dtype, offsets_host, n_frames, depth_out, bgr_out);
   for (int i = 0; i < ns; ++i) {  // capture only recorded launches: the slots are where they were
     Slot& s = h->slots[i];
     s.host_tag = saved[i].host_tag; s.api_tag = saved[i].api_tag; s.any_frame = saved[i].any_frame;
@@ -126,11 +121,8 @@ int xm_graph_create(xm_handle* h, const uint16_t* x, const uint16_t* y, const vo
     hipError_t e = hipGraphInstantiate(&g->exec, g->graph, nullptr, nullptr, 0);
     if (e != hipSuccess) rc = fail(XM_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
   }
-  if (rc != XM_OK) {
-    xm_graph_destroy(g);
-    return rc;
-  }
-  *out = g;
+  if (rc != XM_OK) return rc;
+  *out = g.release();
   return XM_OK;
 }
 
@@ -193,8 +185,7 @@ void xm_graph_destroy(xm_graph* g) {
   if (!g) return;
   if (g->exec) (void)hipGraphExecDestroy(g->exec);
   if (g->graph) (void)hipGraphDestroy(g->graph);
-  if (g->d_descs) (void)hipFree(g->d_descs);
-  delete g;
+  delete g;  // (d_descs goes with it)
 }
 
 

@@ -33,20 +33,38 @@ struct xm_frame_pool {
   bool closed = false;                 // the ingest is gone: a released buffer is freed
 };
 
+namespace {
+struct ActMem {  // owner of the activity filter's device state (xmaps_ingest.hpp: ActDev holds the views the kernels take)
+  DevMem<long long> last_ts; DevMem<uint2> cells;
+  DevMem<unsigned char> keep; DevMem<u32> ctl;
+};
+}  // namespace
+
 struct xm_ingest {
   xm_handle* h = nullptr;
   xm_ingest_config cfg{};
-  hipStream_t stream = nullptr;        // ingest kernels
+  Stream streams[4];                   // borrowed from the process's set for the device (ingest_stream_set), else the ingest's own
+  hipStream_t stream = nullptr;        // views of streams[0..3]: ingest kernels
   hipStream_t frame_stream = nullptr;  // K0 / K1 / K2 / publish of the frames that were cut
   hipStream_t copy_stream = nullptr;   // H2D of packet k+1 runs beside the kernels of packet k
   hipStream_t out_stream = nullptr;    // DMA of a finished frame to the pinned result ring + its sequence number, beside the next frame's
                                        // kernels (two out streams taking turns were slower: two 6 MB copies at once share the link)
+  static constexpr int NOUT = 3;       // device-side output frames (K2 writes them, a DMA copy takes them to the pinned result ring)
+  static constexpr int STAGE = 16;     // staging (pinned host -> device), a small ring so that the copy of packet k+1 does not wait for packet k's kernels
+  Event k2_ev[NOUT];                   // frame stream: K2 has written output frame o (the out stream's DMA waits for it)
+  Event out_ev[NOUT];                  // out stream: output frame o has left for the result ring (the next K2 into it waits for that)
+  Event copied_ev[STAGE];              // per staging entry: its H2D has finished (the ingest stream waits for it)
+  Event k1_ev[8];                      // frame stream: K1 of a frame has run (the ingest stream waits for it before appending more)
   u64 capacity = 0, max_packet = 0;    // capacity: a power of two (the request rounded up)
   double period = 0.0;
   long long act_thresh = 0;
   int ahead = 0;                       // packets the ingest stream may run ahead of the handled verdicts
   // device
-  IngestDev dev{};                     // what every ingest kernel gets by value (ring, pause ring, state, result ring, ...)
+  IngestDev dev{};                     // what every ingest kernel gets by value (ring, pause ring, state, result ring, ...): views of ...
+  DevMem<uint4> d_buf;                 // ... these owners
+  DevMem<u64> d_pring, d_key_frame;
+  DevMem<IngBlk> d_blk; DevMem<IngestState> d_st; DevMem<SlotState> d_slot;
+  ActMem act_mem;                      // (owner of the activity filter's state; act_base and dev.act are views of it)
   // Activity filter: TWO sets of per-(bucket, pixel) cells + control words, taken in turn by the packets (set = staging entry & 1):
   // the first pass of packet p (k_act_first: fills the packet's cells) then depends on nothing of packet p - 1 -- only on packet
   // p - 2 having emptied the set (k_ing_append) and reset its flags (k_ing_segment).  When packet p is already on its way to the
@@ -57,16 +75,13 @@ struct xm_ingest {
   // that arrives alone (a live camera) gets its first pass as a launch of its own in front of its k_ing_count, as in round 5.
   ActDev act_base{};                   // set 0 (dev.act is pointed at the packet's set before its kernels are launched)
   static constexpr int VRING = 64;     // per-packet rings: frame descriptor, frame info (device), verdict (pinned host)
-  FrameDesc* d_descs = nullptr;
-  IngFrameInfo* d_infos = nullptr;
-  IngVerdict* h_verdicts = nullptr;    // pinned host ...
-  IngVerdict* d_verdicts = nullptr;    // ... and the address the device writes it at
+  DevMem<FrameDesc> d_descs;
+  DevMem<IngFrameInfo> d_infos;
+  PinnedMem<IngVerdict> h_verdicts;    // pinned host ...
+  IngVerdict* d_verdicts = nullptr;    // ... and (a view) the address the device writes it at
   double push_t[VRING] = {};           // when the xm_ingest_push* call of packet p entered (steady clock), p % VRING
   uint64_t entry_frame[VRING] = {};    // frame number + 1 that the packet which used the ring entry last cut (0: none): the entry is
                                        // read by that frame's K2 / publishing launches, so it is reused only once the frame is out
-  static constexpr int NOUT = 3;       // device-side output frames (K2 writes them, a DMA copy takes them to the pinned result ring)
-  hipEvent_t k2_ev[NOUT] = {};         // frame stream: K2 has written output frame o (the out stream's DMA waits for it)
-  hipEvent_t out_ev[NOUT] = {};        // out stream: output frame o has left for the result ring (the next K2 into it waits for that)
   // The out stream's work is enqueued by a thread of its own (with a launch thread; inline without): hipMemcpyAsync of a second
   // copy onto a stream whose previous copy is still running BLOCKS its caller in the HIP 7.0 runtime PyTorch bundles (seen: 160 us
   // per frame, 7 ms per 43 frames, whenever the copies ran slower than the frames came) -- it must not be the launch thread.
@@ -84,8 +99,6 @@ struct xm_ingest {
   std::atomic<uint64_t> out_posted{0}; // frames handed to the out side
   std::atomic<uint64_t> out_done{0};   // frames whose copies + sequence number have been ENQUEUED on the out stream (out_ev[o] recorded)
   FirstError out_err;                  // the out side's first error: it stays (every later call of the launch side reports it)
-  bool streams_borrowed = false;       // the four streams are the process's set for the device (ingest_stream_set), else own_streams
-  hipStream_t own_streams[4] = {nullptr, nullptr, nullptr, nullptr};
   bool out_on_frame_stream = false;    // "XM_INGEST_OUT_SERIAL" = 1: copies + sequence number ALWAYS on the frame stream, in order with the frames' kernels (A/B)
   // Launch side: the frames cut from now on leave on the frame stream.  Set while the packets are EVT 3.0 chunks decoded on the
   // device (typically one frame per chunk: there the in-order form measured 1000 Mev/s against 840-920 on the out stream,
@@ -109,23 +122,21 @@ struct xm_ingest {
   const void* next_job = nullptr;      // launch side: the job queued behind the one being run, if it is a packet that has arrived (else NULL)
   double t_out_wait_s = 0.0;           // XM_INGEST_TRACE: launch side waiting for the out side to have enqueued frame f - NOUT
   double t_out_s = 0.0;                // XM_INGEST_TRACE: host seconds the out side spent enqueuing
-  float* d_out_depth[NOUT] = {};
-  uint8_t* d_out_bgr[NOUT] = {};
-  float** d_depth_ring = nullptr;      // the NOUT pointers above, in device memory (k_ing_segment picks one per frame)
-  uint8_t** d_bgr_ring = nullptr;
-  // staging (pinned host -> device), a small ring so that the copy of packet k+1 does not wait for packet k's kernels
-  static constexpr int STAGE = 16;
-  uint4* h_pkt[STAGE] = {};
-  uint4* d_pkt[STAGE] = {};
-  u32* d_pkt_n = nullptr;              // [STAGE] event counts of chunks decoded on the device (written by the decoder's prefix kernel,
+  DevMem<float> d_out_depth[NOUT];
+  DevMem<uint8_t> d_out_bgr[NOUT];
+  DevMem<float*> d_depth_ring;         // the NOUT pointers above, in device memory (k_ing_segment picks one per frame)
+  DevMem<uint8_t*> d_bgr_ring;
+  PinnedMem<uint4> h_pkt[STAGE];
+  DevMem<uint4> d_pkt[STAGE];
+  DevMem<u32> d_pkt_n;                 // [STAGE] event counts of chunks decoded on the device (written by the decoder's prefix kernel,
                                        // read by the ingest kernels of the packet: one cell per staging entry, free when the entry is)
-  hipEvent_t copied_ev[STAGE] = {};    // per staging entry: its H2D has finished (the ingest stream waits for it)
   uint64_t pkt_push[STAGE] = {};       // number of the push that used the entry last (0: never): free once that push's verdict is in
   int pkt_next = 0;
-  hipEvent_t k1_ev[8] = {};            // frame stream: K1 of a frame has run (the ingest stream waits for it before appending more)
   // results (pinned host, written by the kernels)
   int ring = 0;
-  IngestStatus* h_status = nullptr;
+  PinnedMem<IngestStatus> h_status;
+  // (raw on purpose: a ring slot's buffers leave with a frame and are replaced from the pool -- xm_ingest_poll_owned: ownership
+  //  crosses the C ABI, as with the pool's own)
   std::vector<float*> h_depth;
   std::vector<uint8_t*> h_bgr;
   uint64_t next_seq = 0;               // frames delivered through xm_ingest_poll so far
@@ -183,56 +194,54 @@ namespace {
 // 680-750 (the other way round for one-frame-per-packet EVT 3.0 chunks: 840-890 against 1100-1200) -- measured, not understood
 // (profiles/r04_ingest.md section 5).  Keeping the first set makes every ingest of the process behave like its first one.
 struct IngestStreamSet {
-  hipStream_t s[4] = {nullptr, nullptr, nullptr, nullptr};
-  bool lent = false;
+  hipStream_t s[4] = {nullptr, nullptr, nullptr, nullptr};  // (raw on purpose: created once, never destroyed -- see above)
+  const void* lent_to = nullptr;
 };
 std::mutex g_ing_sets_mu;
 std::map<int, IngestStreamSet> g_ing_sets;
 
-// take = true: borrow the device's set (false when somebody has it); take = false: hand out the borrowed set's array
-bool ingest_stream_set(int device, bool take, hipStream_t** out) {
+// borrow the device's set for `who`: its four streams (created here where they do not exist yet), or NULL when somebody has it
+hipStream_t* ingest_stream_set(int device, const void* who) {
   std::lock_guard<std::mutex> lk(g_ing_sets_mu);
   IngestStreamSet& e = g_ing_sets[device];
-  if (take) {
-    if (e.lent) return false;
-    e.lent = true;
-    return true;
-  }
-  if (out) *out = e.s;
-  return true;
+  if (e.lent_to) return nullptr;
+  e.lent_to = who;
+  return e.s;
 }
 
-void ingest_stream_release(int device) {
+void ingest_stream_release(int device, const void* who) {  // (nothing happens when `who` did not have the set)
   std::lock_guard<std::mutex> lk(g_ing_sets_mu);
-  g_ing_sets[device].lent = false;
+  IngestStreamSet& e = g_ing_sets[device];
+  if (e.lent_to == who) e.lent_to = nullptr;
 }
+
+// The result ring's and the frame pool's pinned buffers (raw on purpose: a buffer leaves with a frame through xm_ingest_poll_owned
+// and comes back through xm_frame_pool_release -- ownership crosses the C ABI; these two are the only places that make / free one)
+hipError_t ring_buf_alloc(void** p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault); }
+void ring_buf_free(void* p) { if (p) (void)hipHostFree(p); }
 
 // the activity filter's device state (xmaps_ingest.hpp: ActDev), for an ingest or for the filter alone (xm_activity_*)
-int act_alloc(ActDev* a, int cam_w, int cam_h, long long thresh, size_t max_packet, int n_sets = 1) {
+int act_alloc(ActMem& m, ActDev* a, int cam_w, int cam_h, long long thresh, size_t max_packet, int n_sets = 1) {
   if (thresh < 0 || thresh >= (1ll << 31) - 2) return fail(XM_ERR_INVALID, "activity threshold must be in [0, 2^31 - 2) us");
   const size_t cam_px = (size_t)cam_w * cam_h;
   *a = ActDev{};
   a->thresh = thresh;
   a->cam_w = cam_w;
   a->cam_h = cam_h;
-  HIP_TRY(hipMalloc((void**)&a->last_ts, cam_px * 8));
-  HIP_TRY(hipMalloc((void**)&a->cells, cam_px * sizeof(uint2) * ACT_NB * (size_t)n_sets));
-  HIP_TRY(hipMalloc((void**)&a->keep, max_packet ? max_packet : 1));
-  HIP_TRY(hipMalloc((void**)&a->ctl, 4 * sizeof(u32) * (size_t)n_sets));
+  HIP_TRY(m.last_ts.alloc(cam_px));
+  HIP_TRY(m.cells.alloc(cam_px * ACT_NB * (size_t)n_sets));
+  HIP_TRY(m.keep.alloc(max_packet ? max_packet : 1));
+  HIP_TRY(m.ctl.alloc(4 * (size_t)n_sets));
+  a->last_ts = m.last_ts.get();
+  a->cells = m.cells.get();
+  a->keep = m.keep.get();
+  a->ctl = m.ctl.get();
   std::vector<long long> init(cam_px, ING_NO_TS);
   HIP_TRY(hipMemcpy(a->last_ts, init.data(), cam_px * 8, hipMemcpyHostToDevice));
   HIP_TRY(hipMemset(a->cells, 0, cam_px * sizeof(uint2) * ACT_NB * (size_t)n_sets));
   HIP_TRY(hipMemset(a->ctl, 0, 4 * sizeof(u32) * (size_t)n_sets));
   HIP_TRY(hipDeviceSynchronize());  // (default-stream work: non-blocking streams do not wait for it)
   return XM_OK;
-}
-
-void act_free(ActDev* a) {
-  if (a->last_ts) (void)hipFree(a->last_ts);
-  if (a->cells) (void)hipFree(a->cells);
-  if (a->keep) (void)hipFree(a->keep);
-  if (a->ctl) (void)hipFree(a->ctl);
-  *a = ActDev{};
 }
 
 inline double ingest_now() {
@@ -686,7 +695,8 @@ int xm_ingest_create(xm_handle* h, const xm_ingest_config* cfg, xm_ingest** out)
   if (cfg->struct_size != sizeof(xm_ingest_config)) return fail(XM_ERR_INVALID, "xm_ingest_config.struct_size mismatch");
   if (cfg->projector_fps <= 0) return fail(XM_ERR_INVALID, "projector_fps must be positive");
   XM_ENTER(h);
-  xm_ingest* g = new (std::nothrow) xm_ingest();
+  Owned<xm_ingest, xm_ingest_destroy> owner(new (std::nothrow) xm_ingest());
+  xm_ingest* const g = owner.get();
   if (!g) return fail(XM_ERR_NOMEM, "out of host memory");
   g->h = h;
   g->cfg = *cfg;
@@ -694,54 +704,45 @@ int xm_ingest_create(xm_handle* h, const xm_ingest_config* cfg, xm_ingest** out)
   g->capacity = 1;
   while (g->capacity < want_cap) g->capacity <<= 1;  // the ring is indexed by (absolute stream index) & (capacity - 1)
   g->max_packet = cfg->max_packet_events ? cfg->max_packet_events : (1u << 19);
-  if (g->capacity >= 0x7fffffffull || g->max_packet * 2 > g->capacity || g->max_packet > (u64)ING_MAX_BLOCKS * ING_EPB) {
-    delete g;
+  if (g->capacity >= 0x7fffffffull || g->max_packet * 2 > g->capacity || g->max_packet > (u64)ING_MAX_BLOCKS * ING_EPB)
     return fail(XM_ERR_INVALID, "capacity must be < 2^31 events and at least twice max_packet_events (itself at most %llu)",
                 (unsigned long long)ING_MAX_BLOCKS * ING_EPB);
-  }
   // packets the ingest stream may run ahead of the frame kernels: each costs one packet's worth of ring (the room rule)
   g->ahead = g->capacity >= 8 * g->max_packet ? (int)std::min<u64>(3, g->capacity / g->max_packet / 4) : 0;
   g->period = 1e6 / (double)cfg->projector_fps;                       // trigger_finder.py: 1e6 / self.projector_fps (float)
   g->act_thresh = cfg->activity_thresh_us > 0 ? cfg->activity_thresh_us : (long long)(1e6 / cfg->projector_fps);  // pipe:65-68
   if (g->cfg.pause_thresh_us <= 0) g->cfg.pause_thresh_us = 40;       // trigger_finder.py:98
   if (g->cfg.min_events_per_frame <= 0) g->cfg.min_events_per_frame = 1000;  // trigger_finder.py:8
-  if (g->cfg.min_events_per_frame < 4) {  // the cut is evs[prev + 2 : next - 2] (trigger_finder.py:172): fewer than 4 events between
-    delete g;                             // two pauses would be an empty frame, on which the reference's t.min() raises
-    return fail(XM_ERR_INVALID, "min_events_per_frame must be >= 4 (the frame is evs[prev + 2 : next - 2])");
-  }
+  // the cut is evs[prev + 2 : next - 2] (trigger_finder.py:172): fewer than 4 events between two pauses would be an empty frame, on
+  // which the reference's t.min() raises
+  if (g->cfg.min_events_per_frame < 4) return fail(XM_ERR_INVALID, "min_events_per_frame must be >= 4 (the frame is evs[prev + 2 : next - 2])");
   if (const char* e = dbg_opt("XM_INGEST_CLEAR_EVERY")) g->clear_every = (uint64_t)std::max(1, atoi(e));  // tests: exercise the tag clear
   g->ring = cfg->result_ring > 0 ? cfg->result_ring : 8;
   const size_t cam_px = (size_t)h->tb.cam_w * h->tb.cam_h;
   const size_t px = (size_t)h->out_w * h->out_h;
-#define ING_TRY(expr)                                                                 \
-  do {                                                                                \
-    hipError_t e_ = (expr);                                                           \
-    if (e_ != hipSuccess) {                                                           \
-      int rc_ = fail(XM_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));      \
-      xm_ingest_destroy(g);                                                           \
-      return rc_;                                                                     \
-    }                                                                                 \
-  } while (0)
   int lo = 0, hi = 0;
-  ING_TRY(hipDeviceGetStreamPriorityRange(&lo, &hi));
+  HIP_TRY(hipDeviceGetStreamPriorityRange(&lo, &hi));
   // "XM_INGEST_PRIOS": four letters h / n / l = the priority pools of the ingest, frame, copy and out stream (A/B; default below).
   // The streams come from the process's set for this device (ingest_stream_set below) when nobody else has it.
   const char* pr = dbg_opt("XM_INGEST_PRIOS");
   if (!pr || strlen(pr) != 4) pr = "hhnh";
   const auto prio_of = [&](char c) { return c == 'l' ? lo : c == 'n' ? (lo + hi) / 2 : hi; };
-  g->streams_borrowed = !dbg_opt("XM_INGEST_OWN_STREAMS") && ingest_stream_set(h->cfg.device, true, nullptr);
-  hipStream_t* set = g->own_streams;
-  if (g->streams_borrowed) (void)ingest_stream_set(h->cfg.device, false, &set);
-  for (int i = 0; i < 4; ++i)
-    if (!set[i]) ING_TRY(hipStreamCreateWithPriority(&set[i], hipStreamNonBlocking, prio_of(pr[i])));
-  g->stream = set[0];        // ingest kernels
-  g->frame_stream = set[1];  // the cut frames' kernels
-  g->copy_stream = set[2];   // H2D of a packet beside the kernels of the previous one
-  g->out_stream = set[3];    // the result frames' copies + sequence numbers
-  for (auto& e : g->copied_ev) ING_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  for (auto& e : g->k1_ev) ING_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  for (auto& e : g->k2_ev) ING_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  for (auto& e : g->out_ev) ING_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  hipStream_t* set = dbg_opt("XM_INGEST_OWN_STREAMS") ? nullptr : ingest_stream_set(h->cfg.device, g);
+  for (int i = 0; i < 4; ++i) {
+    if (!set) HIP_TRY(g->streams[i].create_with_priority(hipStreamNonBlocking, prio_of(pr[i])));
+    else {
+      if (!set[i]) HIP_TRY(hipStreamCreateWithPriority(&set[i], hipStreamNonBlocking, prio_of(pr[i])));  // (the set's: it stays)
+      g->streams[i].borrow(set[i]);
+    }
+  }
+  g->stream = g->streams[0];        // ingest kernels
+  g->frame_stream = g->streams[1];  // the cut frames' kernels
+  g->copy_stream = g->streams[2];   // H2D of a packet beside the kernels of the previous one
+  g->out_stream = g->streams[3];    // the result frames' copies + sequence numbers
+  for (Event& e : g->copied_ev) HIP_TRY(e.create());
+  for (Event& e : g->k1_ev) HIP_TRY(e.create());
+  for (Event& e : g->k2_ev) HIP_TRY(e.create());
+  for (Event& e : g->out_ev) HIP_TRY(e.create());
   if (const char* e = dbg_opt("XM_INGEST_OUT_PIECE")) g->out_piece = std::max<size_t>(2u << 20, (size_t)atoll(e));
   if (const char* e = dbg_opt("XM_INGEST_OUT_SERIAL")) g->out_on_frame_stream = e[0] == '1';
   g->opt_out_no_query = dbg_opt("XM_INGEST_OUT_NO_QUERY") != nullptr;
@@ -754,17 +755,16 @@ int xm_ingest_create(xm_handle* h, const xm_ingest_config* cfg, xm_ingest** out)
   d.room = g->max_packet * (u64)(1 + g->ahead);
   d.mirror = g->capacity / 2;  // frames of up to half the ring are contiguous wherever they start
   d.pcap = g->capacity * 2;    // (a pause per live event + the stale head the trigger finder has not skipped yet)
-  ING_TRY(hipMalloc((void**)&d.buf, (d.cap + d.mirror) * 16));
-  ING_TRY(hipMalloc((void**)&d.pring, d.pcap * 8));
-  ING_TRY(hipMalloc((void**)&d.blk, sizeof(IngBlk) * ING_MAX_BLOCKS));
+  HIP_TRY(g->d_buf.alloc(d.cap + d.mirror));
+  HIP_TRY(g->d_pring.alloc(d.pcap));
+  HIP_TRY(g->d_blk.alloc(ING_MAX_BLOCKS));
+  d.buf = g->d_buf.get();
+  d.pring = g->d_pring.get();
+  d.blk = g->d_blk.get();
   if (cfg->activity_filter) {
-    int rc_ = act_alloc(&d.act, h->tb.cam_w, h->tb.cam_h, g->act_thresh, (size_t)g->max_packet, 2);
+    if (int rc = act_alloc(g->act_mem, &d.act, h->tb.cam_w, h->tb.cam_h, g->act_thresh, (size_t)g->max_packet, 2)) return rc;
     d.act.self_counts = (cfg->flags & XM_INGEST_ACT_SELF) ? 1 : 0;
     g->act_base = d.act;
-    if (rc_) {
-      xm_ingest_destroy(g);
-      return rc_;
-    }
   }
   d.cam_w = h->tb.cam_w;
   d.cam_h = h->tb.cam_h;
@@ -772,58 +772,63 @@ int xm_ingest_create(xm_handle* h, const xm_ingest_config* cfg, xm_ingest** out)
   d.period = g->period;
   d.min_events = (u32)g->cfg.min_events_per_frame;
   d.ring = (u32)g->ring;
-  ING_TRY(hipMalloc((void**)&d.st, sizeof(IngestState)));
-  ING_TRY(hipMemset(d.st, 0, sizeof(IngestState)));
-  ING_TRY(hipMalloc((void**)&g->d_descs, sizeof(FrameDesc) * xm_ingest::VRING));
-  ING_TRY(hipMemset(g->d_descs, 0, sizeof(FrameDesc) * xm_ingest::VRING));
-  ING_TRY(hipMalloc((void**)&g->d_infos, sizeof(IngFrameInfo) * xm_ingest::VRING));
-  ING_TRY(hipMemset(g->d_infos, 0, sizeof(IngFrameInfo) * xm_ingest::VRING));
-  ING_TRY(hipHostMalloc((void**)&g->h_verdicts, sizeof(IngVerdict) * xm_ingest::VRING, hipHostMallocMapped));
+  HIP_TRY(g->d_st.alloc(1));
+  d.st = g->d_st.get();
+  HIP_TRY(hipMemset(d.st, 0, sizeof(IngestState)));
+  HIP_TRY(g->d_descs.alloc(xm_ingest::VRING));
+  HIP_TRY(hipMemset(g->d_descs, 0, sizeof(FrameDesc) * xm_ingest::VRING));
+  HIP_TRY(g->d_infos.alloc(xm_ingest::VRING));
+  HIP_TRY(hipMemset(g->d_infos, 0, sizeof(IngFrameInfo) * xm_ingest::VRING));
+  HIP_TRY(g->h_verdicts.alloc(xm_ingest::VRING, hipHostMallocMapped));
   memset(g->h_verdicts, 0, sizeof(IngVerdict) * xm_ingest::VRING);
-  ING_TRY(hipHostGetDevicePointer((void**)&g->d_verdicts, g->h_verdicts, 0));
-  ING_TRY(hipMalloc((void**)&d.key_frame, h->key_cells * sizeof(u64)));
-  ING_TRY(hipMalloc((void**)&d.slot, sizeof(SlotState)));
-  ING_TRY(hipMemset(d.slot, 0, sizeof(SlotState)));
+  HIP_TRY(hipHostGetDevicePointer((void**)&g->d_verdicts, g->h_verdicts, 0));
+  HIP_TRY(g->d_key_frame.alloc(h->key_cells));
+  HIP_TRY(g->d_slot.alloc(1));
+  d.key_frame = g->d_key_frame.get();
+  d.slot = g->d_slot.get();
+  HIP_TRY(hipMemset(d.slot, 0, sizeof(SlotState)));
   // (a memset of device memory may return before it has run and the ingest's streams do not wait for the default stream:
   //  k_reset_slot initialises the extrema slots inside these bytes -- seen once as a first frame with a wrong time normalisation)
-  ING_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipDeviceSynchronize());
   hipLaunchKernelGGL(k_reset_slot, dim3(1024), dim3(BLOCK), 0, g->frame_stream, d.slot, d.key_frame, (u64)h->key_cells, (unsigned char*)nullptr);
-  ING_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   for (int i = 0; i < xm_ingest::STAGE; ++i) {
     // (the pinned twins h_pkt[] are allocated by the first PAGEABLE push: callers that push pinned packets or RAW words never
     //  pay for 16 x max_packet x 16 bytes of page-locked memory)
-    ING_TRY(hipMalloc((void**)&g->d_pkt[i], g->max_packet * 16));
-    if (!g->d_pkt_n) ING_TRY(hipMalloc((void**)&g->d_pkt_n, xm_ingest::STAGE * sizeof(u32)));
+    HIP_TRY(g->d_pkt[i].alloc(g->max_packet));
   }
-  ING_TRY(hipHostMalloc((void**)&g->h_status, sizeof(IngestStatus) * g->ring, hipHostMallocMapped));
+  HIP_TRY(g->d_pkt_n.alloc(xm_ingest::STAGE));
+  HIP_TRY(g->h_status.alloc(g->ring, hipHostMallocMapped));
   memset(g->h_status, 0, sizeof(IngestStatus) * g->ring);
   g->h_depth.assign(g->ring, nullptr);
   g->h_bgr.assign(g->ring, nullptr);
   g->slot_frame.assign(g->ring, 0);
   for (int i = 0; i < g->ring; ++i) {
-    if (cfg->want_depth) ING_TRY(hipHostMalloc((void**)&g->h_depth[i], px * 4, hipHostMallocDefault));
-    if (cfg->want_bgr) ING_TRY(hipHostMalloc((void**)&g->h_bgr[i], px * 3, hipHostMallocDefault));
+    if (cfg->want_depth) HIP_TRY(ring_buf_alloc((void**)&g->h_depth[i], px * 4));
+    if (cfg->want_bgr) HIP_TRY(ring_buf_alloc((void**)&g->h_bgr[i], px * 3));
   }
   for (int i = 0; i < xm_ingest::NOUT; ++i) {
-    if (cfg->want_depth) ING_TRY(hipMalloc((void**)&g->d_out_depth[i], px * 4));
-    if (cfg->want_bgr) ING_TRY(hipMalloc((void**)&g->d_out_bgr[i], px * 3));
+    if (cfg->want_depth) HIP_TRY(g->d_out_depth[i].alloc(px));
+    if (cfg->want_bgr) HIP_TRY(g->d_out_bgr[i].alloc(px * 3));
   }
-  ING_TRY(hipMalloc((void**)&g->d_depth_ring, sizeof(float*) * xm_ingest::NOUT));
-  ING_TRY(hipMalloc((void**)&g->d_bgr_ring, sizeof(uint8_t*) * xm_ingest::NOUT));
-  ING_TRY(hipMemcpy(g->d_depth_ring, g->d_out_depth, sizeof(float*) * xm_ingest::NOUT, hipMemcpyHostToDevice));
-  ING_TRY(hipMemcpy(g->d_bgr_ring, g->d_out_bgr, sizeof(uint8_t*) * xm_ingest::NOUT, hipMemcpyHostToDevice));
+  float* out_depth[xm_ingest::NOUT];
+  uint8_t* out_bgr[xm_ingest::NOUT];
+  for (int i = 0; i < xm_ingest::NOUT; ++i) out_depth[i] = g->d_out_depth[i], out_bgr[i] = g->d_out_bgr[i];
+  HIP_TRY(g->d_depth_ring.alloc(xm_ingest::NOUT));
+  HIP_TRY(g->d_bgr_ring.alloc(xm_ingest::NOUT));
+  HIP_TRY(hipMemcpy(g->d_depth_ring, out_depth, sizeof out_depth, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(g->d_bgr_ring, out_bgr, sizeof out_bgr, hipMemcpyHostToDevice));
   d.nout = xm_ingest::NOUT;
   // (the first DMA into a pinned buffer is several times slower than the later ones -- seen as 0.2 ms per frame for the first
   //  round through the ring: every entry takes one copy now)
   for (int i = 0; i < g->ring; ++i) {
-    if (cfg->want_depth) ING_TRY(hipMemcpyAsync(g->h_depth[i], g->d_out_depth[i % xm_ingest::NOUT], px * 4, hipMemcpyDeviceToHost, g->out_stream));
-    if (cfg->want_bgr) ING_TRY(hipMemcpyAsync(g->h_bgr[i], g->d_out_bgr[i % xm_ingest::NOUT], px * 3, hipMemcpyDeviceToHost, g->out_stream));
+    if (cfg->want_depth) HIP_TRY(hipMemcpyAsync(g->h_depth[i], g->d_out_depth[i % xm_ingest::NOUT], px * 4, hipMemcpyDeviceToHost, g->out_stream));
+    if (cfg->want_bgr) HIP_TRY(hipMemcpyAsync(g->h_bgr[i], g->d_out_bgr[i % xm_ingest::NOUT], px * 3, hipMemcpyDeviceToHost, g->out_stream));
   }
-  ING_TRY(hipStreamSynchronize(g->out_stream));
+  HIP_TRY(hipStreamSynchronize(g->out_stream));
   d.depth_ring = g->d_depth_ring;
   d.bgr_ring = g->d_bgr_ring;
-  ING_TRY(hipDeviceSynchronize());  // (the memsets above ran on the default stream, which the ingest's non-blocking streams do not wait for)
-#undef ING_TRY
+  HIP_TRY(hipDeviceSynchronize());  // (the memsets above ran on the default stream, which the ingest's non-blocking streams do not wait for)
   if (!(cfg->flags & XM_INGEST_NO_LAUNCH_THREAD)) {
     g->threaded = true;
     g->th = std::thread(ingest_thread_main, g);
@@ -836,7 +841,7 @@ int xm_ingest_create(xm_handle* h, const xm_ingest_config* cfg, xm_ingest** out)
       g->out_th = std::thread(ingest_out_main, g);
     }
   }
-  *out = g;
+  *out = owner.release();
   return XM_OK;
 }
 
@@ -849,15 +854,12 @@ void xm_ingest_destroy(xm_ingest* g) {
     ingest_post(g, stop);
     if (g->copy_th.joinable()) g->copy_th.join();  // (forwards the stop behind everything else, then leaves)
     if (g->th.joinable()) g->th.join();
-    g->threaded = false;
-    g->copy_threaded = false;
   }
   if (g->out_threaded) {  // (behind the launch thread: nobody posts any more; the queue is drained before the thread leaves)
     (void)ingest_out_drain(g);  // (every posted frame is taken before the thread is told to leave)
     g->out_stop.store(true, std::memory_order_seq_cst);
     g->out_bell.ring();
     if (g->out_th.joinable()) g->out_th.join();
-    g->out_threaded = false;
   }
   if (g->copy_stream) (void)hipStreamSynchronize(g->copy_stream);
   if (g->stream) (void)hipStreamSynchronize(g->stream);
@@ -872,53 +874,22 @@ void xm_ingest_destroy(xm_ingest* g) {
     fprintf(stderr, "[ingest] out side (%s): %.3f ms enqueuing %llu frames' copies + sequence numbers; the launch side waited %.3f ms for it\n",
             g->cfg.flags & XM_INGEST_NO_LAUNCH_THREAD ? "inline" : "a thread of its own", g->t_out_s * 1e3, (unsigned long long)g->out_done.load(),
             g->t_out_wait_s * 1e3);
-  IngestDev& d = g->dev;
-  if (d.buf) (void)hipFree(d.buf);
-  if (d.pring) (void)hipFree(d.pring);
-  if (d.blk) (void)hipFree(d.blk);
-  act_free(&g->act_base);
-  d.act = ActDev{};
-  if (d.st) (void)hipFree(d.st);
-  if (d.key_frame) (void)hipFree(d.key_frame);
-  if (d.slot) (void)hipFree(d.slot);
-  if (g->d_descs) (void)hipFree(g->d_descs);
-  if (g->d_infos) (void)hipFree(g->d_infos);
-  if (g->h_verdicts) (void)hipHostFree(g->h_verdicts);
-  if (g->d_pkt_n) (void)hipFree(g->d_pkt_n);
-  if (g->d_depth_ring) (void)hipFree(g->d_depth_ring);
-  if (g->d_bgr_ring) (void)hipFree(g->d_bgr_ring);
-  for (int i = 0; i < xm_ingest::NOUT; ++i) {
-    if (g->d_out_depth[i]) (void)hipFree(g->d_out_depth[i]);
-    if (g->d_out_bgr[i]) (void)hipFree(g->d_out_bgr[i]);
-  }
-  for (int i = 0; i < xm_ingest::STAGE; ++i) {
-    if (g->h_pkt[i]) (void)hipHostFree(g->h_pkt[i]);
-    if (g->d_pkt[i]) (void)hipFree(g->d_pkt[i]);
-  }
-  if (g->h_status) (void)hipHostFree(g->h_status);
-  for (auto p : g->h_depth) if (p) (void)hipHostFree(p);
-  for (auto p : g->h_bgr) if (p) (void)hipHostFree(p);
+  for (auto p : g->h_depth) ring_buf_free(p);
+  for (auto p : g->h_bgr) ring_buf_free(p);
   if (xm_frame_pool* pl = g->pool) {  // spare buffers go now, buffers in consumers' hands when they come back (the last one takes the pool along)
     bool last;
     {
       std::lock_guard<std::mutex> lk(pl->mu);
       pl->closed = true;
       for (auto& v : pl->free_bufs) {
-        for (void* p : v) (void)hipHostFree(p);
+        for (void* p : v) ring_buf_free(p);
         v.clear();
       }
       last = pl->outstanding == 0;
     }
     if (last) delete pl;
-    g->pool = nullptr;
   }
-
-  for (auto& e : g->copied_ev) if (e) (void)hipEventDestroy(e);
-  for (auto& e : g->k1_ev) if (e) (void)hipEventDestroy(e);
-  for (auto& e : g->k2_ev) if (e) (void)hipEventDestroy(e);
-  for (auto& e : g->out_ev) if (e) (void)hipEventDestroy(e);
-  for (auto& s : g->own_streams) if (s) (void)hipStreamDestroy(s);
-  if (g->streams_borrowed) ingest_stream_release(g->h->cfg.device);
+  ingest_stream_release(g->h->cfg.device, g);
   delete g;
 }
 
@@ -941,7 +912,7 @@ static int ingest_push(xm_ingest* g, const void* eventcd16, size_t n, bool pinne
     // first packet instead of one on each of its first 16 packets); callers that push pinned packets or RAW words never pay
     HIP_TRY(hipSetDevice(h->cfg.device));
     for (int i = 0; i < xm_ingest::STAGE; ++i)
-      if (!g->h_pkt[i]) HIP_TRY(hipHostMalloc((void**)&g->h_pkt[i], g->max_packet * 16, hipHostMallocDefault));
+      if (!g->h_pkt[i]) HIP_TRY(g->h_pkt[i].alloc(g->max_packet, hipHostMallocDefault));
   }
   const uint4* hp = pinned ? (const uint4*)eventcd16 : g->h_pkt[k];
   if ((rc = ingest_wait_entry(g, k))) return rc;
@@ -1006,7 +977,7 @@ static int ingest_poll(xm_ingest* g, xm_ingest_frame* out, bool owned) {
           spare[kind] = pl->free_bufs[kind].back();
           pl->free_bufs[kind].pop_back();
         } else if (pl->allocated < pl->cap && hipSetDevice(pl->device) == hipSuccess &&
-                   hipHostMalloc(&spare[kind], pl->bytes[kind], hipHostMallocDefault) == hipSuccess) {
+                   ring_buf_alloc(&spare[kind], pl->bytes[kind]) == hipSuccess) {
           pl->allocated += 1;
         } else {
           (void)hipGetLastError();
@@ -1085,7 +1056,7 @@ void xm_frame_pool_release(xm_frame_pool* pl, void* buffer, int kind) {
       pl->free_bufs[kind].push_back(buffer);
     }
   }
-  if (free_it) (void)hipHostFree(buffer);
+  if (free_it) ring_buf_free(buffer);
   if (last) delete pl;
 }
 
@@ -1206,36 +1177,30 @@ int xm_ingest_host_stats(xm_ingest* g, uint64_t* pushes, double* host_seconds_in
 struct xm_activity {
   xm_handle* h = nullptr;
   int device = 0;
-  hipStream_t stream = nullptr;
+  Stream stream;
   size_t max_packet = 0;
-  ActDev act{};
-  uint4* h_pkt = nullptr;  // pinned staging
-  uint4* d_pkt = nullptr;
-  unsigned char* h_keep = nullptr;
+  ActDev act{};    // views of act_mem
+  ActMem act_mem;
+  PinnedMem<uint4> h_pkt;  // pinned staging
+  DevMem<uint4> d_pkt;
+  PinnedMem<unsigned char> h_keep;
 };
 
 int xm_activity_create(xm_handle* h, int64_t thresh_us, size_t max_packet_events, xm_activity** out) {
   if (!h || !out) return fail(XM_ERR_INVALID, "NULL argument");
   *out = nullptr;
   XM_ENTER(h);
-  xm_activity* f = new (std::nothrow) xm_activity();
+  Owned<xm_activity, xm_activity_destroy> f(new (std::nothrow) xm_activity());
   if (!f) return fail(XM_ERR_NOMEM, "out of host memory");
   f->h = h;
   f->device = h->cfg.device;
   f->max_packet = max_packet_events ? max_packet_events : ((size_t)1 << 19);
-  int rc = act_alloc(&f->act, h->tb.cam_w, h->tb.cam_h, thresh_us, f->max_packet);
-  const auto tr = [&](hipError_t e, const char* what) {
-    if (!rc && e != hipSuccess) rc = fail(XM_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
-  };
-  if (!rc) tr(hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking), "hipStreamCreateWithFlags");
-  if (!rc) tr(hipHostMalloc((void**)&f->h_pkt, f->max_packet * 16, hipHostMallocDefault), "hipHostMalloc");
-  if (!rc) tr(hipHostMalloc((void**)&f->h_keep, f->max_packet, hipHostMallocDefault), "hipHostMalloc");
-  if (!rc) tr(hipMalloc((void**)&f->d_pkt, f->max_packet * 16), "hipMalloc");
-  if (rc) {
-    xm_activity_destroy(f);
-    return rc;
-  }
-  *out = f;
+  if (int rc = act_alloc(f->act_mem, &f->act, h->tb.cam_w, h->tb.cam_h, thresh_us, f->max_packet)) return rc;
+  HIP_TRY(f->stream.create(hipStreamNonBlocking));
+  HIP_TRY(f->h_pkt.alloc(f->max_packet, hipHostMallocDefault));
+  HIP_TRY(f->h_keep.alloc(f->max_packet, hipHostMallocDefault));
+  HIP_TRY(f->d_pkt.alloc(f->max_packet));
+  *out = f.release();
   return XM_OK;
 }
 
@@ -1249,11 +1214,6 @@ void xm_activity_destroy(xm_activity* f) {
   if (!f) return;
   (void)hipSetDevice(f->device);
   if (f->stream) (void)hipStreamSynchronize(f->stream);
-  act_free(&f->act);
-  if (f->h_pkt) (void)hipHostFree(f->h_pkt);
-  if (f->h_keep) (void)hipHostFree(f->h_keep);
-  if (f->d_pkt) (void)hipFree(f->d_pkt);
-  if (f->stream) (void)hipStreamDestroy(f->stream);
   delete f;
 }
 

@@ -30,54 +30,43 @@ int xm_build_x_map(int device, const float* time_map, int height, int width, int
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(XM_ERR_HIP, "no HIP device visible");
   HIP_TRY(hipSetDevice(device));
   const size_t n_in = (size_t)height * width, n_out = (size_t)height * x_map_width;
-  float* d_in = nullptr;
-  int16_t* d_x = nullptr;
-  float* d_d = nullptr;
-  int rc = XM_OK;
-  do {
-    hipError_t e;
-    if ((e = hipMalloc((void**)&d_in, n_in * 4)) != hipSuccess || (e = hipMalloc((void**)&d_x, n_out * 2)) != hipSuccess ||
-        (t_diffs_out && (e = hipMalloc((void**)&d_d, n_out * 4)) != hipSuccess) ||
-        (e = hipMemcpy(d_in, time_map, n_in * 4, hipMemcpyHostToDevice)) != hipSuccess) {
-      rc = fail(XM_ERR_HIP, "xm_build_x_map: %s", hipGetErrorString(e));
-      break;
+  DevMem<float> d_in, d_d;
+  DevMem<int16_t> d_x;
+  hipError_t e;
+  if ((e = d_in.alloc(n_in)) != hipSuccess || (e = d_x.alloc(n_out)) != hipSuccess ||
+      (t_diffs_out && (e = d_d.alloc(n_out)) != hipSuccess) ||
+      (e = hipMemcpy(d_in, time_map, n_in * 4, hipMemcpyHostToDevice)) != hipSuccess) {
+    return fail(XM_ERR_HIP, "xm_build_x_map: %s", hipGetErrorString(e));
+  }
+  int wp = 2;
+  while (wp < width) wp <<= 1;
+  const char* es = dbg_opt("XM_XMAP_SCAN");  // tests: XM_XMAP_SCAN=1 takes the exhaustive scan (read at every call)
+  const bool brute = es && es[0] == '1';
+  if (wp <= 8192 && !brute) {  // rows of up to 8192 columns: the sorted-row kernel (96 KB of LDS at most)
+    const size_t lds = (size_t)wp * sizeof(u64) + (size_t)width * sizeof(float);
+    if (lds > 64 * 1024 &&
+        (e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_build_x_map_sorted), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 (int)lds)) != hipSuccess) {
+      return fail(XM_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
     }
-    int wp = 2;
-    while (wp < width) wp <<= 1;
-    const char* es = dbg_opt("XM_XMAP_SCAN");  // tests: XM_XMAP_SCAN=1 takes the exhaustive scan (read at every call)
-    const bool brute = es && es[0] == '1';
-    if (wp <= 8192 && !brute) {  // rows of up to 8192 columns: the sorted-row kernel (96 KB of LDS at most)
-      const size_t lds = (size_t)wp * sizeof(u64) + (size_t)width * sizeof(float);
-      if (lds > 64 * 1024 &&
-          (e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_build_x_map_sorted), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)lds)) != hipSuccess) {
-        rc = fail(XM_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-        break;
-      }
-      hipLaunchKernelGGL(k_build_x_map_sorted, dim3(height), dim3(BLOCK), lds, 0, d_in, height, width, wp, x_map_width, t_px_scale,
-                         x_offset, 2.0 / (double)num_scanlines, d_x, d_d);
-    } else {
-      const size_t lds = (size_t)width * sizeof(double);
-      if (lds > 64 * 1024 &&
-          (e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_build_x_map), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)lds)) != hipSuccess) {
-        rc = fail(XM_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-        break;
-      }
-      hipLaunchKernelGGL(k_build_x_map, dim3(height), dim3(BLOCK), lds, 0, d_in, height, width, x_map_width, t_px_scale,
-                         x_offset, 2.0 / (double)num_scanlines, d_x, d_d);
+    hipLaunchKernelGGL(k_build_x_map_sorted, dim3(height), dim3(BLOCK), lds, 0, d_in, height, width, wp, x_map_width, t_px_scale,
+                       x_offset, 2.0 / (double)num_scanlines, d_x, d_d);
+  } else {
+    const size_t lds = (size_t)width * sizeof(double);
+    if (lds > 64 * 1024 &&
+        (e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_build_x_map), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 (int)lds)) != hipSuccess) {
+      return fail(XM_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
     }
-    if ((e = hipGetLastError()) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess ||
-        (e = hipMemcpy(x_map_out, d_x, n_out * 2, hipMemcpyDeviceToHost)) != hipSuccess ||
-        (t_diffs_out && (e = hipMemcpy(t_diffs_out, d_d, n_out * 4, hipMemcpyDeviceToHost)) != hipSuccess)) {
-      rc = fail(XM_ERR_HIP, "xm_build_x_map: %s", hipGetErrorString(e));
-      break;
-    }
-  } while (0);
-  if (d_in) (void)hipFree(d_in);
-  if (d_x) (void)hipFree(d_x);
-  if (d_d) (void)hipFree(d_d);
-  return rc;
+    hipLaunchKernelGGL(k_build_x_map, dim3(height), dim3(BLOCK), lds, 0, d_in, height, width, x_map_width, t_px_scale,
+                       x_offset, 2.0 / (double)num_scanlines, d_x, d_d);
+  }
+  if ((e = hipGetLastError()) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess ||
+      (e = hipMemcpy(x_map_out, d_x, n_out * 2, hipMemcpyDeviceToHost)) != hipSuccess ||
+      (t_diffs_out && (e = hipMemcpy(t_diffs_out, d_d, n_out * 4, hipMemcpyDeviceToHost)) != hipSuccess)) {
+    return fail(XM_ERR_HIP, "xm_build_x_map: %s", hipGetErrorString(e));
+  }
+  return XM_OK;
 }
 
 // ---- N4: evaluation metrics -------------------------------------------------------------------------------------
@@ -88,34 +77,24 @@ int xm_eval_stats(int device, const float* estimate, const float* groundtruth, i
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(XM_ERR_HIP, "no HIP device visible");
   HIP_TRY(hipSetDevice(device));
   const u64 n = (u64)height * width;
-  float *d_e = nullptr, *d_g = nullptr;
-  EvalAcc* d_a = nullptr;
-  int rc = XM_OK;
+  DevMem<float> d_e, d_g;
+  DevMem<EvalAcc> d_a;
   EvalAcc a;
   memset(&a, 0, sizeof a);
-  do {
-    hipError_t e;
-    if ((e = hipMalloc((void**)&d_e, n * 4)) != hipSuccess || (e = hipMalloc((void**)&d_g, n * 4)) != hipSuccess ||
-        (e = hipMalloc((void**)&d_a, sizeof(EvalAcc))) != hipSuccess ||
-        (e = hipMemcpy(d_e, estimate, n * 4, hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(d_g, groundtruth, n * 4, hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemset(d_a, 0, sizeof(EvalAcc))) != hipSuccess) {
-      rc = fail(XM_ERR_HIP, "xm_eval_stats: %s", hipGetErrorString(e));
-      break;
-    }
-    unsigned grid = grid_for(n, BLOCK * 8);
-    if (grid > 2048) grid = 2048;
-    hipLaunchKernelGGL((k_eval_stats<1>), dim3(grid), dim3(BLOCK), 0, 0, (const float*)d_e, (const float*)d_g, n, filter, min_depth, max_depth, d_a);
-    hipLaunchKernelGGL((k_eval_stats<2>), dim3(grid), dim3(BLOCK), 0, 0, (const float*)d_e, (const float*)d_g, n, filter, min_depth, max_depth, d_a);
-    if ((e = hipGetLastError()) != hipSuccess || (e = hipMemcpy(&a, d_a, sizeof a, hipMemcpyDeviceToHost)) != hipSuccess) {
-      rc = fail(XM_ERR_HIP, "xm_eval_stats: %s", hipGetErrorString(e));
-      break;
-    }
-  } while (0);
-  if (d_e) (void)hipFree(d_e);
-  if (d_g) (void)hipFree(d_g);
-  if (d_a) (void)hipFree(d_a);
-  if (rc) return rc;
+  hipError_t e;
+  if ((e = d_e.alloc(n)) != hipSuccess || (e = d_g.alloc(n)) != hipSuccess || (e = d_a.alloc(1)) != hipSuccess ||
+      (e = hipMemcpy(d_e, estimate, n * 4, hipMemcpyHostToDevice)) != hipSuccess ||
+      (e = hipMemcpy(d_g, groundtruth, n * 4, hipMemcpyHostToDevice)) != hipSuccess ||
+      (e = hipMemset(d_a, 0, sizeof(EvalAcc))) != hipSuccess) {
+    return fail(XM_ERR_HIP, "xm_eval_stats: %s", hipGetErrorString(e));
+  }
+  unsigned grid = grid_for(n, BLOCK * 8);
+  if (grid > 2048) grid = 2048;
+  hipLaunchKernelGGL((k_eval_stats<1>), dim3(grid), dim3(BLOCK), 0, 0, (const float*)d_e, (const float*)d_g, n, filter, min_depth, max_depth, d_a);
+  hipLaunchKernelGGL((k_eval_stats<2>), dim3(grid), dim3(BLOCK), 0, 0, (const float*)d_e, (const float*)d_g, n, filter, min_depth, max_depth, d_a);
+  if ((e = hipGetLastError()) != hipSuccess || (e = hipMemcpy(&a, d_a, sizeof a, hipMemcpyDeviceToHost)) != hipSuccess) {
+    return fail(XM_ERR_HIP, "xm_eval_stats: %s", hipGetErrorString(e));
+  }
   const double hw = (double)n;
   out->margin = 0.01 * a.sum_gt / (double)a.n_gt_pos;
   out->fillrate = ((double)a.n_close - (double)a.n_gt_zero) / (hw - (double)a.n_gt_zero);
@@ -135,7 +114,7 @@ int xm_host_alloc(xm_handle* h, size_t bytes, void** out) {
   HIP_TRY(hipHostMalloc(out, bytes ? bytes : 16, hipHostMallocDefault));
   return XM_OK;
 }
-int xm_host_free(xm_handle* h, void* p) {
+int xm_host_free(xm_handle* h, void* p) {  // (xm_host_alloc / xm_dev_alloc and their frees stay raw: the caller owns the memory across the C ABI)
   if (!h) return fail(XM_ERR_INVALID, "NULL handle");
   XM_ENTER(h);
   if (p) HIP_TRY(hipHostFree(p));

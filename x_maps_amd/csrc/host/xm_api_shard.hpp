@@ -13,7 +13,7 @@ int xm_shard_minmax(xm_handle* h, const void* t, const int16_t* p, size_t n, int
   if ((rc = rearm_aux(h, s.stream, nullptr, 0))) return rc;
   EventsView ev;
   ev.t = n ? t : (const void*)h->d_lut; ev.p = p; ev.n = n; ev.t_dtype = t_dtype; ev.use_p = p != nullptr;
-  ev.x = (const uint16_t*)h->d_lut; ev.y = ev.x;
+  ev.x = (const uint16_t*)h->d_lut.get(); ev.y = ev.x;
   launch_minmax(ev, h->aux_st, 2, s.stream);
   HIP_TRY(hipGetLastError());
   SlotState hs;
@@ -37,7 +37,7 @@ int xm_shard_minmax_device(xm_handle* h, const void* t, const int16_t* p, size_t
   if ((rc = rearm_aux(h, s.stream, nullptr, 0))) return rc;
   EventsView ev;
   ev.t = n ? t : (const void*)h->d_lut; ev.p = p; ev.n = n; ev.t_dtype = t_dtype; ev.use_p = p != nullptr;
-  ev.x = (const uint16_t*)h->d_lut; ev.y = ev.x;
+  ev.x = (const uint16_t*)h->d_lut.get(); ev.y = ev.x;
   launch_minmax(ev, h->aux_st, 2, s.stream);
   switch (t_dtype) {
     case XM_T_INT64: hipLaunchKernelGGL(k_minmax_export<long long>, dim3(1), dim3(64), 0, s.stream, h->aux_st, 2u, mm_dev); break;
@@ -191,10 +191,10 @@ int xm_shard_cols_scatter(xm_handle* h, uint16_t* x, uint16_t* y, int64_t* t, si
   XM_ENTER(h);
   const int W = cols_width(h, n_frame_events);
   if (!h->cols_ok || h->own_mode || W == 0) return fail(XM_ERR_INVALID, "this rig / frame density does not take the column tiles");
-  if (!h->d_shard_n) HIP_TRY(hipMalloc((void**)&h->d_shard_n, 64 + sizeof(FrameDesc)));
+  if (!h->d_shard_n) HIP_TRY(h->d_shard_n.alloc(8, sizeof(FrameDesc)));
   hipStream_t s = h->slots[0].stream;
-  long long* mm = reinterpret_cast<long long*>(h->d_shard_n);  // {tmin, -tmax} of the frame
-  FrameDesc* desc = reinterpret_cast<FrameDesc*>(reinterpret_cast<unsigned char*>(h->d_shard_n) + 64);
+  long long* mm = reinterpret_cast<long long*>(h->d_shard_n.get());  // {tmin, -tmax} of the frame
+  FrameDesc* desc = reinterpret_cast<FrameDesc*>(reinterpret_cast<unsigned char*>(h->d_shard_n.get()) + 64);
   hipLaunchKernelGGL(k_shard_cols_prepare, dim3(1), dim3(256), 0, s, x, y, (long long*)t, (u64)n, (const unsigned char*)gathered_dev,
                      (u64)send_bytes, rank, world, h->tb, (u64)cap_events, mm, frame16, h->aux_st, desc);
   const FrameGroup piece{desc, 1, n_frame_events, n_frame_events, true};  // (the piece starts 8-aligned: 16-byte event loads)

@@ -24,11 +24,11 @@ struct xm_shard_comm {
   uint64_t n_frame = 0;
   bool cols = false;               // the rig / density takes the column tiles
   size_t cap = 0, send_bytes = 0, reduce_u32 = 0, frame_bytes = 0;
-  unsigned char *send = nullptr, *gathered = nullptr;
-  uint16_t* frame16 = nullptr;
-  uint64_t* key = nullptr;         // packed keys (allocated on first use)
-  void* mm = nullptr;              // {tmin, -tmax}
-  int* flag = nullptr;             // the ranks' verdicts (device)
+  DevMem<unsigned char> send, gathered;
+  DevMem<uint16_t> frame16;
+  DevMem<uint64_t> key;            // packed keys (allocated on first use)
+  DevMem<long long> mm;            // {tmin, -tmax} (16 bytes, int64 or float64)
+  DevMem<int> flag;                // the ranks' verdicts (device)
   u32 tag = 0;
 };
 
@@ -52,12 +52,6 @@ void xm_shard_comm_destroy(xm_shard_comm* c) {
     (void)xm_sync(c->h);
   }
   if (c->comm && c->rccl.CommDestroy) (void)c->rccl.CommDestroy(c->comm);
-  if (c->send) (void)hipFree(c->send);
-  if (c->gathered) (void)hipFree(c->gathered);
-  if (c->frame16) (void)hipFree(c->frame16);
-  if (c->key) (void)hipFree(c->key);
-  if (c->mm) (void)hipFree(c->mm);
-  if (c->flag) (void)hipFree(c->flag);
   delete c;
 }
 
@@ -66,7 +60,7 @@ int xm_shard_comm_create(xm_handle* h, const void* id, int rank, int world, uint
   *out = nullptr;
   if (world < 1 || rank < 0 || rank >= world) return fail(XM_ERR_INVALID, "bad rank / world");
   XM_ENTER(h);
-  xm_shard_comm* c = new (std::nothrow) xm_shard_comm();
+  Owned<xm_shard_comm, xm_shard_comm_destroy> c(new (std::nothrow) xm_shard_comm());
   if (!c) return fail(XM_ERR_NOMEM, "out of host memory");
   c->h = h;
   c->rank = rank;
@@ -74,8 +68,8 @@ int xm_shard_comm_create(xm_handle* h, const void* id, int rank, int world, uint
   c->n_frame = n_frame_events;
   c->rccl = load_rccl();
   const auto bail = [&](int rc) {
-    const std::string keep = g_err;
-    xm_shard_comm_destroy(c);
+    const std::string keep = g_err;  // (the destroy function's own calls may overwrite it)
+    c.reset();
     return fail(rc, "%s", keep.c_str());
   };
   if (!c->rccl.ok_ranks()) {
@@ -85,14 +79,14 @@ int xm_shard_comm_create(xm_handle* h, const void* id, int rank, int world, uint
   c->cols = xm_shard_cols_info(h, n_frame_events, &c->frame_bytes, &c->reduce_u32, &c->send_bytes, &c->cap) == XM_OK;
   hipError_t e = hipSuccess;
   if (c->cols) {
-    e = hipMalloc((void**)&c->send, c->send_bytes);
-    if (e == hipSuccess) e = hipMalloc((void**)&c->gathered, c->send_bytes * (size_t)world);
-    if (e == hipSuccess) e = hipMalloc((void**)&c->frame16, c->frame_bytes);
+    e = c->send.alloc(c->send_bytes);
+    if (e == hipSuccess) e = c->gathered.alloc(c->send_bytes * (size_t)world);
+    if (e == hipSuccess) e = c->frame16.alloc((c->frame_bytes + 1) / sizeof(uint16_t));
     if (e == hipSuccess) e = hipMemset(c->send, 0, c->send_bytes);
     if (e == hipSuccess) e = hipMemset(c->frame16, 0, c->frame_bytes);
   }
-  if (e == hipSuccess) e = hipMalloc(&c->mm, 16);
-  if (e == hipSuccess) e = hipMalloc((void**)&c->flag, sizeof(int));
+  if (e == hipSuccess) e = c->mm.alloc(2);
+  if (e == hipSuccess) e = c->flag.alloc(1);
   if (e != hipSuccess) {
     (void)fail(XM_ERR_HIP, "device buffers of the shard communicator: %s", hipGetErrorString(e));
     return bail(XM_ERR_HIP);
@@ -105,7 +99,7 @@ int xm_shard_comm_create(xm_handle* h, const void* id, int rank, int world, uint
     (void)fail(XM_ERR_HIP, "ncclCommInitRank(rank %d of %d) failed: %s", rank, world, c->rccl.err(ne));
     return bail(XM_ERR_HIP);
   }
-  *out = c;
+  *out = c.release();
   return XM_OK;
 }
 
@@ -141,7 +135,7 @@ int xm_shard_comm_frame_keys(xm_shard_comm* c, const uint16_t* x, const uint16_t
   xm_handle* h = c->h;
   XM_ENTER(h);
   hipStream_t st = h->slots[0].stream;
-  if (!c->key) HIP_TRY(hipMalloc((void**)&c->key, (size_t)h->key_cells * sizeof(uint64_t)));
+  if (!c->key) HIP_TRY(c->key.alloc(h->key_cells));
   c->tag = c->tag >= 1000 ? 1 : c->tag + 1;  // (the key frame is cleared every frame: any tag in [1, 2^19) would do)
   int rc, e;
   if ((rc = xm_shard_minmax_device(h, t, p, n_own, t_dtype, c->mm))) return rc;

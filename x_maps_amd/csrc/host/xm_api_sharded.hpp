@@ -84,17 +84,17 @@ struct xm_sharded {
     int id = 0;
     xm_handle* h = nullptr;
     void* comm = nullptr;
+    Event ev[4];                   // device 0: around the two all-reduces
     DevBuf x, y, t, p, depth, bgr;
     DevBuf send, gathered;         // columns exchange: this device's header + last events, every device's
-    uint16_t* frame16 = nullptr;   // columns exchange: the plain u16 disparity frame (+ the boundary pass' scratch)
+    DevMem<uint16_t> frame16;      // columns exchange: the plain u16 disparity frame (+ the boundary pass' scratch)
     int flagged = 0;               // columns exchange: this device's piece could not be handled
-    uint64_t* key = nullptr;
-    void* mm = nullptr;            // {tmin, -tmax} of the shard, then of the frame (16 bytes, int64 or float64)
-    hipEvent_t ev[4] = {};         // device 0: around the two all-reduces
+    DevMem<uint64_t> key;
+    DevMem<long long> mm;          // {tmin, -tmax} of the shard, then of the frame (16 bytes, int64 or float64)
     bool peer_only = false;        // this frame: the device itself was fine, it stopped because a peer had failed
     long long mm_back[2] = {0, 0}; // device 0: the frame's {tmin, -tmax} copied back (the copy outlives an early return: not on the stack)
     DevBuf fake_tmp;               // virtual ranks: the reduction's result before it replaces the rank's own buffer
-    const void** fake_ptrs = nullptr;  // virtual ranks: device array of the W ranks' buffers
+    DevMem<const void*> fake_ptrs;     // virtual ranks: device array of the W ranks' buffers
     const void* fake_cur = nullptr;    // virtual ranks: the buffer this rank brings to the collective in flight
     std::thread th;
     int rc = XM_OK;
@@ -211,7 +211,7 @@ int fake_all_reduce(xm_sharded* s, int g, T* buf, size_t count, hipStream_t st) 
   if (hipMemcpyAsync(d.fake_ptrs, ptrs.data(), sizeof(void*) * W, hipMemcpyHostToDevice, st) != hipSuccess) rc = fail(XM_ERR_HIP, "hipMemcpyAsync failed");
   if (!rc) {
     const unsigned gx = (unsigned)std::min<size_t>(4096, (count + 255) / 256);
-    hipLaunchKernelGGL((k_fake_reduce<T, OP>), dim3(gx ? gx : 1), dim3(256), 0, st, (const T* const*)d.fake_ptrs, W, count, (T*)d.fake_tmp.p);
+    hipLaunchKernelGGL((k_fake_reduce<T, OP>), dim3(gx ? gx : 1), dim3(256), 0, st, (const T* const*)d.fake_ptrs.get(), W, count, (T*)d.fake_tmp.p);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) rc = fail(XM_ERR_HIP, "virtual all-reduce kernel failed");
   }
   if (const int agreed = sharded_agree(s, rc)) return sharded_peer_failed(d, agreed, rc);  // (everybody has read everybody's buffer)
@@ -246,7 +246,7 @@ void sharded_frame_on(xm_sharded* s, int g) {
         if (g == 0 && s->depth_out && (rc = d.depth.reserve((size_t)d.h->out_w * d.h->out_h * 4))) return rc;
         if (g == 0 && s->bgr_out && (rc = d.bgr.reserve((size_t)d.h->out_w * d.h->out_h * 3))) return rc;
         if (!d.frame16) {
-          HIP_TRY(hipMalloc((void**)&d.frame16, s->cols_frame_bytes));
+          HIP_TRY(d.frame16.alloc((s->cols_frame_bytes + 1) / sizeof(uint16_t)));
           HIP_TRY(hipMemsetAsync(d.frame16, 0, s->cols_frame_bytes, st));
         }
         dx = (uint16_t*)d.x.p + hr;
@@ -282,7 +282,7 @@ void sharded_frame_on(xm_sharded* s, int g) {
       rc = before_reduce();
       if (const int agreed = sharded_agree(s, rc)) return sharded_peer_failed(d, agreed, rc);
       if (s->fake) {
-        if ((rc = fake_all_reduce<u32, 0>(s, g, (u32*)d.frame16, s->cols_reduce_u32, st))) return rc;
+        if ((rc = fake_all_reduce<u32, 0>(s, g, (u32*)d.frame16.get(), s->cols_reduce_u32, st))) return rc;
       } else if (s->use_rccl) {
         const int e = s->rccl.AllReduce(d.frame16, d.frame16, s->cols_reduce_u32, RcclApi::Int32, RcclApi::Sum, d.comm, st);
         if (e) return fail(XM_ERR_HIP, "ncclAllReduce(SUM, u16 frame) failed: %s", s->rccl.err(e));
@@ -336,7 +336,7 @@ void sharded_frame_on(xm_sharded* s, int g) {
     if (const int agreed = sharded_agree(s, rc)) return sharded_peer_failed(d, agreed, rc);
     if (dbg_fail_at(s, g, 3)) return fail(XM_ERR_HIP, "injected failure (XM_SHARD_FAIL_AT) on device index %d BEHIND the agreement, outside any agreement point", g);
     if (s->fake) {
-      rc = s->t_dtype == XM_T_INT64 ? fake_all_reduce<long long, 2>(s, g, (long long*)d.mm, 2, st) : fake_all_reduce<double, 2>(s, g, (double*)d.mm, 2, st);
+      rc = s->t_dtype == XM_T_INT64 ? fake_all_reduce<long long, 2>(s, g, (long long*)d.mm, 2, st) : fake_all_reduce<double, 2>(s, g, (double*)d.mm.get(), 2, st);
       if (rc) return rc;
     } else if (s->use_rccl) {
       const int e = s->rccl.AllReduce(d.mm, d.mm, 2, s->t_dtype == XM_T_INT64 ? RcclApi::Int64 : RcclApi::Float64, RcclApi::Min, d.comm, st);
@@ -356,7 +356,7 @@ void sharded_frame_on(xm_sharded* s, int g) {
     rc = before_max();
     if (const int agreed = sharded_agree(s, rc)) return sharded_peer_failed(d, agreed, rc);
     if (s->fake) {
-      if ((rc = fake_all_reduce<unsigned long long, 1>(s, g, (unsigned long long*)d.key, d.h->key_cells, st))) return rc;
+      if ((rc = fake_all_reduce<unsigned long long, 1>(s, g, (unsigned long long*)d.key.get(), d.h->key_cells, st))) return rc;
     } else if (s->use_rccl) {
       const int e = s->rccl.AllReduce(d.key, d.key, d.h->key_cells, RcclApi::Uint64, RcclApi::Max, d.comm, st);
       if (e) return fail(XM_ERR_HIP, "ncclAllReduce(MAX, key frame) failed: %s", s->rccl.GetErrorString ? s->rccl.GetErrorString(e) : "?");
@@ -425,16 +425,10 @@ void xm_sharded_destroy(xm_sharded* s) {
     if (d->th.joinable()) d->th.join();
   for (auto& d : s->devs) {
     (void)hipSetDevice(d->id);
-    if (d->h) (void)xm_sync(d->h);
+    if (d->h) (void)xm_sync(d->h);  // (the device thread launched on the handle's streams only)
     if (d->comm && s->rccl.CommDestroy) (void)s->rccl.CommDestroy(d->comm);
-    d->x.release(); d->y.release(); d->t.release(); d->p.release(); d->depth.release(); d->bgr.release();
-    d->send.release(); d->gathered.release(); d->fake_tmp.release();
-    if (d->fake_ptrs) (void)hipFree(d->fake_ptrs);
-    if (d->frame16) (void)hipFree(d->frame16);
-    if (d->key) (void)hipFree(d->key);
-    if (d->mm) (void)hipFree(d->mm);
-    for (auto& e : d->ev) if (e) (void)hipEventDestroy(e);
     if (d->h) xm_destroy(d->h);
+    d.reset();  // the device's own buffers and events, while it is the current device
   }
   delete s;
 }
@@ -449,15 +443,12 @@ int xm_create_sharded(const int* dev_ids, int n_dev, const xm_config* cfg, xm_sh
     for (int j = 0; j < i; ++j)
       if (dev_ids[j] == dev_ids[i]) return fail(XM_ERR_INVALID, "device %d is listed twice", dev_ids[i]);
   }
-  xm_sharded* s = new (std::nothrow) xm_sharded();
+  Owned<xm_sharded, xm_sharded_destroy> s(new (std::nothrow) xm_sharded());
   if (!s) return fail(XM_ERR_NOMEM, "out of host memory");
   std::vector<int> ids(dev_ids, dev_ids + n_dev);
   if (const char* fr = dbg_opt("XM_SHARD_FAKE_RANKS")) {  // tests: W virtual ranks on the one device (see the header comment)
     const int W = atoi(fr);
-    if (n_dev != 1 || W < 1 || W > 64) {
-      delete s;
-      return fail(XM_ERR_INVALID, "XM_SHARD_FAKE_RANKS = %s needs n_dev == 1 and 1 <= W <= 64", fr);
-    }
+    if (n_dev != 1 || W < 1 || W > 64) return fail(XM_ERR_INVALID, "XM_SHARD_FAKE_RANKS = %s needs n_dev == 1 and 1 <= W <= 64", fr);
     s->fake = W > 1;
     ids.assign(W, dev_ids[0]);
     n_dev = W;
@@ -468,10 +459,8 @@ int xm_create_sharded(const int* dev_ids, int n_dev, const xm_config* cfg, xm_sh
   dev_ids = ids.data();
   s->rccl = load_rccl();
   s->use_rccl = !s->fake && s->rccl.ok();
-  if (n_dev > 1 && !s->use_rccl && !s->fake) {
-    delete s;
+  if (n_dev > 1 && !s->use_rccl && !s->fake)
     return fail(XM_ERR_INVALID, "librccl was not found: a sharded handle over %d devices needs it", n_dev);
-  }
   int rc = XM_OK;
   for (int i = 0; i < n_dev && !rc; ++i) {
     s->devs.emplace_back(new xm_sharded::Dev());
@@ -481,11 +470,11 @@ int xm_create_sharded(const int* dev_ids, int n_dev, const xm_config* cfg, xm_sh
     c.device = d.id;
     if ((rc = xm_create(&c, &d.h))) break;
     hipError_t e = hipSetDevice(d.id);
-    if (e == hipSuccess) e = hipMalloc((void**)&d.key, d.h->key_cells * sizeof(uint64_t));
-    if (e == hipSuccess) e = hipMalloc(&d.mm, 16);
-    for (auto& ev : d.ev)
-      if (e == hipSuccess) e = hipEventCreate(&ev);
-    if (e == hipSuccess && s->fake) e = hipMalloc((void**)&d.fake_ptrs, sizeof(void*) * 64);
+    if (e == hipSuccess) e = d.key.alloc(d.h->key_cells);
+    if (e == hipSuccess) e = d.mm.alloc(2);
+    for (Event& ev : d.ev)
+      if (e == hipSuccess) e = ev.create(hipEventDefault);
+    if (e == hipSuccess && s->fake) e = d.fake_ptrs.alloc(64);
     if (e != hipSuccess) rc = fail(XM_ERR_HIP, "device %d: %s", d.id, hipGetErrorString(e));
   }
   if (!rc && s->use_rccl) {  // one communicator per device, all in this process
@@ -496,12 +485,12 @@ int xm_create_sharded(const int* dev_ids, int n_dev, const xm_config* cfg, xm_sh
       for (int i = 0; i < n_dev; ++i) s->devs[i]->comm = comms[i];
   }
   if (rc) {
-    const std::string keep = g_err;
-    xm_sharded_destroy(s);
+    const std::string keep = g_err;  // (the destroy function's own calls may overwrite it)
+    s.reset();
     return fail(rc, "%s", keep.c_str());
   }
-  for (int i = 0; i < n_dev; ++i) s->devs[i]->th = std::thread(sharded_thread_main, s, i);
-  *out = s;
+  for (int i = 0; i < n_dev; ++i) s->devs[i]->th = std::thread(sharded_thread_main, s.get(), i);
+  *out = s.release();
   return XM_OK;
 }
 

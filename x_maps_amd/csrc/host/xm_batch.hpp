@@ -9,7 +9,7 @@ namespace {
 // slots[f] (its own key frame + state), all on ONE stream.  A single frame's launches leave the chip half empty while
 // they ramp up and drain (245 K1 blocks for 256 CUs, each a ~10 us dependent chain); a group's launch keeps every CU fed.
 template <typename T, bool AOS, bool HAS_P>
-int launch_group(xm_handle* h, const FrameGroup& g, const FramePath& p, hipStream_t stream, hipEvent_t* prof,
+int launch_group(xm_handle* h, const FrameGroup& g, const FramePath& p, hipStream_t stream, const Event* prof,
                  const FrameDesc* d_descs_redo) {
   const ProfSlots ps{prof};
   if constexpr (std::is_same<T, long long>::value && !HAS_P) {
@@ -55,7 +55,7 @@ int launch_group(xm_handle* h, const FrameGroup& g, const FramePath& p, hipStrea
 // (eager) -- false when the caller uploads once (graph capture).
 int enqueue_batch(xm_handle* h, const int* slot_idx, const EventsView* evs, float* const* depth, uint8_t* const* bgr,
                   int n_frames, hipStream_t stream, FrameDesc* h_descs, FrameDesc* d_descs, bool upload, bool allow_sorted,
-                  hipEvent_t* prof = nullptr, int* kinds = nullptr, FrameDesc* h_descs_redo = nullptr,
+                  const Event* prof = nullptr, int* kinds = nullptr, FrameDesc* h_descs_redo = nullptr,
                   FrameDesc* d_descs_redo = nullptr) {
   const FramePath p = frame_path(h, evs, n_frames, allow_sorted, true, d_descs_redo != nullptr);
   for (int f = 0; f < n_frames; ++f) {  // order the group after whatever its slots did last on other streams
@@ -94,7 +94,7 @@ int enqueue_batch(xm_handle* h, const int* slot_idx, const EventsView* evs, floa
     FrameDesc& d = h_descs[f];
     const EventsView& ev = evs[f];
     d.x = ev.x; d.y = ev.y; d.t = ev.t; d.p = ev.use_p ? ev.p : nullptr; d.aos = (const uint4*)ev.aos;
-    d.n = ev.n; d.key_frame = p.cols_w ? reinterpret_cast<u64*>(s.frame16) : p.key32 ? reinterpret_cast<u64*>(s.key32) : s.key_frame;
+    d.n = ev.n; d.key_frame = p.cols_w ? reinterpret_cast<u64*>(s.frame16.get()) : p.key32 ? reinterpret_cast<u64*>(s.key32.get()) : s.key_frame.get();
     d.st = s.st; d.depth = depth[f];
     d.bgr = bgr[f]; d.valid = 1; d.pad = 0;
     if (p.dev_redo) {  // the same frame on the slot's 64-bit key frame

@@ -283,7 +283,7 @@ void note_enqueued(xm_handle* h, Slot& s, const EventsView& ev, const FramePath&
 }
 
 // enqueue K0 -> K1 -> K2 for one frame on a slot.  All pointers are device pointers.
-int enqueue_frame(xm_handle* h, Slot& s, const EventsView& ev, float* depth, uint8_t* bgr, hipEvent_t* prof,
+int enqueue_frame(xm_handle* h, Slot& s, const EventsView& ev, float* depth, uint8_t* bgr, const Event* prof,
                   bool allow_sorted = true, hipStream_t stream_override = nullptr) {
   const FramePath p = frame_path(h, &ev, 1, allow_sorted);
   key32_pause_tick(h, 1);

@@ -36,23 +36,21 @@ const char* dbg_opt(const char* name) {
   return it == g_opts.end() ? nullptr : it->second->c_str();
 }
 
-struct DevBuf {  // grow-only device scratch
-  void* p = nullptr;
+struct DevBuf {  // grow-only device scratch: grows by a quarter beyond what was asked for
+  DevMem<unsigned char> mem;
+  void* p = nullptr;  // view of mem
   size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : mem(std::move(o.mem)), p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
   int reserve(size_t bytes) {
     if (bytes <= cap) return XM_OK;
-    if (p) (void)hipFree(p);
     p = nullptr;
     cap = 0;
     size_t want = bytes + bytes / 4 + 256;
-    HIP_TRY(hipMalloc(&p, want));
+    HIP_TRY(mem.alloc(want));
+    p = mem.get();
     cap = want;
     return XM_OK;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
   }
 };
 
@@ -68,13 +66,12 @@ struct EventsView {
 };
 
 struct Slot {
-  hipStream_t stream = nullptr;
-  bool owns_stream = true;
+  Stream stream;      // its own, or borrowed from an earlier slot (slots beyond the hardware-queue count share streams)
   int worker = -1;    // launch worker of this slot's stream (-1: none)
   u32 api_tag = 0;    // tag of the slot's last frame as the API thread counts them (== host_tag once the workers are idle)
   // XM_FLAG_TRY_SORTED: pinned host words the kernels report to ([0] tag of the last frame whose shortcut failed, [1] tag of
   // the last frame whose K2 has started) and what is needed to redo the slot's last asynchronous frame on the general path
-  u32* h_flags = nullptr;
+  PinnedMem<u32> h_flags;
   struct Prev {
     bool valid = false;
     EventsView ev;
@@ -86,22 +83,22 @@ struct Slot {
     u32 tag = 0;
     hipStream_t stream = nullptr;  // the stream the frame's launches went to (the group's stream for xm_process_batch)
   } prev;
-  u64* key_frame = nullptr;
-  u32* key32 = nullptr;            // compact key frame of the verified-sorted projector-view path (see key32_tag)
+  DevMem<u64> key_frame;
+  DevMem<u32> key32;               // compact key frame of the verified-sorted projector-view path (see key32_tag)
   u32 key32_valid_from = 0;        // tag of the frame before which key32 was last cleared: every key in it has a tag in
                                    // [valid_from, valid_from + 15), so the 4-bit tag field is unambiguous
   bool last_key32 = false;         // the slot's last frame took a compact path (key32 or column tiles): a failure counts against it
   bool last_cols = false;          // ... the column tiles (K0b was launched in K0's place)
-  uint16_t* frame16 = nullptr;     // plain u16 disparity frame of the column-tile path (xmaps_k1cols.hpp): rewritten by every frame
-  unsigned char* dirty = nullptr;  // projector view: one flag byte per 128-byte line of key_frame
-  SlotState* st = nullptr;  // device
+  DevMem<uint16_t> frame16;        // plain u16 disparity frame of the column-tile path (xmaps_k1cols.hpp): rewritten by every frame
+  DevMem<unsigned char> dirty;     // projector view: one flag byte per 128-byte line of key_frame
+  SlotState* st = nullptr;  // device: a view into xm_handle::d_states
   u32 host_tag = 0;         // mirrors st->tag_a after the enqueued work has run
   bool any_frame = false;
   bool last_sorted = false;
   uint64_t last_n = 0;
   int last_t_dtype = XM_T_INT64;  // how xm_last_frame_stats decodes t_min / t_max
   // the slot's last frame ran inside a multi-frame launch on ANOTHER stream: work on the slot's own stream waits for this
-  hipEvent_t pending_batch_ev = nullptr;
+  hipEvent_t pending_batch_ev = nullptr;  // view: an event of xm_handle::batch_ev / graph_ev
   hipStream_t pending_batch_stream = nullptr;
   bool eager_dirty = false;  // eager work was enqueued on the slot's own stream since the last synchronisation point
   // staging for XM_MEM_HOST calls
@@ -135,16 +132,28 @@ struct Worker {
 
 struct xm_handle {
   xm_config cfg{};
-  DevTables tb{};
-  u32* d_lut = nullptr;
-  int16_t* d_xmap = nullptr;
-  u32* d_pmap = nullptr;
-  uint2* d_dlut = nullptr;
+  // the handle's own streams and events come before its buffers, which are therefore released first; a Slot orders its own
+  // members the same way (every stream has been synchronised by xm_destroy before any of this runs: see xm_res.hpp)
+  std::vector<Stream> gstreams;  // default-priority streams the hipGraph batches are captured on and launched from
+  Event prof_ev[6];
+  Event fork_ev;
+  std::vector<Event> join_ev;
+  Event k2_chain_ev[16];  // "XM_K2_CHAIN": created on first use (launch_k2_pipe)
+  static constexpr int DESC_RING = 16;
+  Event desc_ev[DESC_RING];  // recorded after the ring entry's upload: the entry may be rewritten once it fired
+  // an event per (stream, ring entry) recorded at the end of a batch: eager work on a slot's own stream waits for it
+  std::vector<std::vector<Event>> batch_ev;  // [distinct stream][8]
+  Event graph_ev[8];  // end-of-replay events (ring), recorded on the graphs' origin stream
+  DevTables tb{};      // what the kernels take by value: every pointer in it is a view of a table owned below
+  DevMem<u32> d_lut;   // owner; tb.lut is the view
+  DevMem<int16_t> d_xmap;
+  DevMem<u32> d_pmap;
+  DevMem<uint2> d_dlut;
   // K2's static per-tile / per-pixel tables for its two geometries: [0] one pixel per thread (16 x 16 tiles), [1] two (32 x 16)
   // ([2]: four pixels per thread, 64 x 16 tiles -- the pipelined kernel on rigs whose patches are small against the tile)
-  int4* d_k2_tiles[3] = {nullptr, nullptr, nullptr};  // [g]: tiles of 16 << g pixels x 16 rows
-  u32* d_k2_pix[3] = {nullptr, nullptr, nullptr};
-  uint16_t* d_k2_pix16[3] = {nullptr, nullptr, nullptr};  // the pipelined K2's copy: u16, rows padded to k2_pix_stride
+  DevMem<int4> d_k2_tiles[3];  // [g]: tiles of 16 << g pixels x 16 rows (owners; tb.k2_tiles1 / tb.k2_tiles view [0] / [1])
+  DevMem<u32> d_k2_pix[3];     // (owners; tb.k2_pix1 / tb.k2_pix view [0] / [1])
+  DevMem<uint16_t> d_k2_pix16[3];  // the pipelined K2's copy: u16, rows padded to k2_pix_stride
   int k2_pix_stride = 0;
   int k2_consec = -1;  // k_frame_proj_pipe<PPT, true>: PPT consecutive pixels per thread; -1 = where it measured faster (PPT = 4), XM_K2_CONSEC=0|1 forces
   int k2_tile_cap[3] = {K2_TILE_MAX, K2_TILE_MAX, K2_TILE_MAX};  // cells of the largest K2 patch (multiple of 8)
@@ -159,30 +168,26 @@ struct xm_handle {
   // k2_per_cu_max blocks per CU, and the following groups' boundary pass and K1 in what it leaves (profiles/r05_own_tiles.md)
   bool k2_chain = false;
   std::mutex k2_chain_mu;
-  hipEvent_t k2_chain_ev[16] = {};
   unsigned k2_chain_n = 0;
   bool k2_pipe_force = false;   // XM_K2_PIPE=2 (tests): also for groups too small for the pipeline to matter
   bool k2_pipe = true, k2_pipe_rig_ok = false;  // (rig_ok: every tile's patch fits the pipelined loader, rect_h % 8 == 0)
-  ulonglong2* d_zero16 = nullptr;  // 16 zero bytes: what K2 reads instead of a clean key-frame line
-  SlotState* d_states = nullptr;  // n_slots + 1 (last = aux state for stage / shard calls)
-  SlotState* aux_st = nullptr;
-  u64* d_shard_n = nullptr;  // shards on the column tiles: the piece's own event count (device) + its FrameDesc behind it
+  DevMem<ulonglong2> d_zero16;  // 16 zero bytes: what K2 reads instead of a clean key-frame line
+  DevMem<SlotState> d_states;  // n_slots + 1 (last = aux state for stage / shard calls)
+  SlotState* aux_st = nullptr;  // view: the last entry of d_states
+  DevMem<u64> d_shard_n;  // shards on the column tiles: the piece's own event count (device) + its FrameDesc behind it
   std::vector<Slot> slots;
   int next_slot = 0;
   int last_slot = 0;
   size_t key_cells = 0;   // cells of the fused path's key frame (rect or camera frame)
   int out_w = 0, out_h = 0;
-  u64* stage_frame = nullptr;  // lazily allocated scratch for the stage API (max(rect, cam) cells)
+  DevMem<u64> stage_frame;  // lazily allocated scratch for the stage API (max(rect, cam) cells)
   size_t stage_cells = 0;
-  hipEvent_t prof_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  hipEvent_t fork_ev = nullptr;
   // K1 tiling: LDS windows (time columns / camera columns) and the dynamic LDS they need; 0 = direct kernel
   int w_ts = 0, w_x = 0;
   size_t k1_lds = 0;
   bool k1_direct = false, k2_direct = false;
   bool k2_flags = false;      // XM_K2_FLAGS=1: K1 marks dirty 128-byte lines of the key frame, K2 skips clean ones.
                               // Measured: K2 fetches 37 % fewer bytes but is not faster (it is latency, not bandwidth bound)
-  std::vector<hipStream_t> gstreams;  // default-priority streams the hipGraph batches are captured on and launched from
   std::vector<std::unique_ptr<Worker>> workers;  // one per slot stream (empty: launches happen in the calling thread)
   bool key32_ok = false;      // the rig qualifies for the compact key frame (projector view, rect_h % 4 == 0, disparities < 4096)
   // column-tile K1 (xmaps_k1cols.hpp): the rig qualifies (projector view, cell(row, column) injective, no int16 wrap in the
@@ -205,11 +210,11 @@ struct xm_handle {
     bool ok = false, all_in = false;
     int w = 0, halo = 0, extras = 0;
     int r_lo = 0, hr = 0, hrp = 0, rp = 0, grouped = 0, nxs_max = 0, extra_max = 0;
-    uint16_t* d_xmap_own = nullptr;
-    uint16_t* d_xmap_extra = nullptr;
-    int4* d_tiles = nullptr;
-    u32* d_bm = nullptr;
-    u32* d_extra_cells = nullptr;
+    DevMem<uint16_t> d_xmap_own;
+    DevMem<uint16_t> d_xmap_extra;
+    DevMem<int4> d_tiles;
+    DevMem<u32> d_bm;
+    DevMem<u32> d_extra_cells;
   } own[OWN_PLANS];
   int own_ept_forced = 0;  // "XM_OWN_EPT" (experiments): 4 = four events per thread where a tile then fits one pass
   // XM_FLAG_ADAPTIVE_BATCH: asynchronous device-pointer frames are submitted as GROUPS (multi-frame launches) whenever the GPU
@@ -223,7 +228,7 @@ struct xm_handle {
   };
   std::vector<Deferred> pending;
   int ab_max = 0;                                  // 0: off
-  hipEvent_t ab_inflight[4] = {nullptr, nullptr, nullptr, nullptr};  // end-of-group events of the last four groups submitted this way
+  hipEvent_t ab_inflight[4] = {nullptr, nullptr, nullptr, nullptr};  // views (events of batch_ev): end-of-group events of the last four groups submitted this way
   uint64_t ab_groups = 0, ab_frames = 0;
   std::atomic<uint64_t> path_counts[4] = {};  // frames enqueued per K1 variant (xm_path_counts)
   // (atomics: with XM_FLAG_LAUNCH_WORKERS the launch threads and the API thread all pass through enqueue_frame)
@@ -233,21 +238,15 @@ struct xm_handle {
   bool try_sorted = false;    // XM_FLAG_TRY_SORTED
   bool capturing = false;     // inside xm_graph_create's stream capture (no host-side redo possible there)
   uint64_t sorted_fallbacks = 0;
-  std::vector<hipEvent_t> join_ev;
   // multi-frame launches (xm_process_batch, batched hipGraphs, ingest): frame descriptors.  Eager batches stage them
   // through a ring of pinned host entries -> device entries (one memcpy per batch, stream-ordered before its kernels).
-  static constexpr int DESC_RING = 16;
-  FrameDesc* h_descs = nullptr;   // pinned  [DESC_RING][n_slots]
-  FrameDesc* d_descs = nullptr;   // device  [DESC_RING][n_slots]
-  hipEvent_t desc_ev[DESC_RING] = {};  // recorded after the ring entry's upload: the entry may be rewritten once it fired
+  PinnedMem<FrameDesc> h_descs;  // pinned  [DESC_RING][n_slots]
+  DevMem<FrameDesc> d_descs;     // device  [DESC_RING][n_slots]
   bool desc_used[DESC_RING] = {};
   int desc_next = 0;
   uint64_t batch_counter = 0;
-  // an event per (stream, ring entry) recorded at the end of a batch: eager work on a slot's own stream waits for it
-  std::vector<std::vector<hipEvent_t>> batch_ev;  // [distinct stream][8]
-  std::vector<hipStream_t> streams;               // distinct slot streams
+  std::vector<hipStream_t> streams;  // views: the distinct slot streams
   std::vector<int> batch_ev_next;
-  hipEvent_t graph_ev[8] = {};  // end-of-replay events (ring), recorded on the graphs' origin stream
   unsigned graph_ev_next = 0;
   // dynamic-LDS caps already raised on this handle's device, per kernel function (launch workers call concurrently)
   std::mutex lds_mu;
@@ -262,7 +261,7 @@ struct xm_graph {
   std::vector<u32> frames_on_slot;
   int n_frames = 0;
   std::vector<FrameDesc> h_descs;  // batched capture: the frames' descriptors (static for the graph's lifetime)
-  FrameDesc* d_descs = nullptr;
+  DevMem<FrameDesc> d_descs;
 };
 
 int flush_pending(xm_handle* h);  // XM_FLAG_ADAPTIVE_BATCH: submit the frames held back (defined beside xm_process_batch)

@@ -45,7 +45,7 @@ bool vec16(const FrameGroup& g) { return g.all_vec16; }
 // prof = 6 events {start0, stop0, start1, stop1, start2, stop2} attached to the dispatch packets of K0 / K0b, K1, K2 (g_prof);
 // cleared when the frame's or group's launches are issued, on every return
 struct ProfSlots {
-  const hipEvent_t* prof;
+  const Event* prof;
   void at(int i) const {
     if (prof) g_prof = ProfCtx{prof[2 * i], prof[2 * i + 1]};
   }
@@ -289,8 +289,8 @@ bool launch_k2_pipe(xm_handle* h, hipStream_t stream, const FrameDesc* d_descs, 
   }
 #undef XM_K2P_LAUNCH
   if (chain_lock.owns_lock()) {
-    hipEvent_t& ev = h->k2_chain_ev[h->k2_chain_n % 16];
-    if (!ev) (void)hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    Event& ev = h->k2_chain_ev[h->k2_chain_n % 16];
+    if (!ev) (void)ev.create();
     if (ev && hipEventRecord(ev, stream) == hipSuccess) h->k2_chain_n += 1;
   }
   h->k2_pipe_frames += (uint64_t)n_frames;

@@ -285,18 +285,17 @@ int own_setup(xm_handle* h, const xm_config* cfg, int xr_min) {
   OwnPlan pls[OWN_PLANS];
   own_plans(cfg, h->tb.xmap_h, xr_min, pls);
   if (!pls[0].ok) return XM_OK;
-  const auto up = [](auto** dst, const auto& v) -> hipError_t {
-    typedef typename std::remove_reference<decltype(v)>::type::value_type E;
-    hipError_t e = hipMalloc((void**)dst, v.size() * sizeof(E) + 64);
-    return e != hipSuccess ? e : hipMemcpy(*dst, v.data(), v.size() * sizeof(E), hipMemcpyHostToDevice);
+  const auto up = [](auto& dst, const auto& v) -> hipError_t {
+    hipError_t e = dst.alloc(v.size(), 64);
+    return e != hipSuccess ? e : hipMemcpy(dst.get(), v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice);
   };
   for (int i = 0; i < OWN_PLANS; ++i) {
     const OwnPlan& pl = pls[i];
     if (!pl.ok) continue;
     xm_handle::OwnSet& os = h->own[i];
-    HIP_TRY(up(&os.d_xmap_own, pl.packed));
-    HIP_TRY(up(&os.d_xmap_extra, pl.xextra));
-    HIP_TRY(up(&os.d_tiles, pl.tiles));
+    HIP_TRY(up(os.d_xmap_own, pl.packed));
+    HIP_TRY(up(os.d_xmap_extra, pl.xextra));
+    HIP_TRY(up(os.d_tiles, pl.tiles));
     {  // per tile ONE table, read by 16-byte loads at the head of the tile.  Per-row ownership: per row the band's first column before
        // the frame's shear (an event's band column = cell column - that) | the row's ownership mask << 16.  Per 8-row group: per
        // group that column | the band's first column in the sheared frame << 16, then per group the band columns the tile owns.
@@ -314,9 +313,9 @@ int own_setup(xm_handle* h, const xm_config* cfg, int xr_min) {
             tab[(size_t)t * words + e] = (u32)(uint16_t)(int16_t)org | (pl.masks[k] << 16);
           }
         }
-      HIP_TRY(up(&os.d_bm, tab));
+      HIP_TRY(up(os.d_bm, tab));
     }
-    HIP_TRY(up(&os.d_extra_cells, pl.extra_flat));
+    HIP_TRY(up(os.d_extra_cells, pl.extra_flat));
     os.extras = (int)pl.extra_flat.size() - 1;
     os.w = pl.W; os.halo = pl.halo; os.all_in = pl.all_in;
     os.r_lo = pl.r_lo; os.hr = pl.hr; os.hrp = pl.hrp; os.rp = pl.rp; os.grouped = pl.grouped ? 1 : 0;

@@ -256,9 +256,7 @@ int process_common(xm_handle* h, EventsView ev, int mem, float* depth_out, uint8
 int ensure_stage_frame(xm_handle* h) {
   const size_t need = std::max((size_t)h->tb.rect_w * h->tb.rect_h, (size_t)h->tb.cam_w * h->tb.cam_h);
   if (h->stage_frame && h->stage_cells >= need) return XM_OK;
-  if (h->stage_frame) (void)hipFree(h->stage_frame);
-  h->stage_frame = nullptr;
-  HIP_TRY(hipMalloc((void**)&h->stage_frame, need * sizeof(u64)));
+  HIP_TRY(h->stage_frame.alloc(need));
   h->stage_cells = need;
   return XM_OK;
 }

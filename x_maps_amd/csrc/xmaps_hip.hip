@@ -38,12 +38,14 @@ using namespace xm;
 
 // The host side is one translation unit, split by concern (each file closes the namespaces / linkage blocks it opens):
 #include "host/xm_queue.hpp"        // the host threads' job queues and first-error latches (standard C++ only)
+#include "host/xm_res.hpp"          // owners of device / pinned memory, streams and events (RAII)
 #include "host/xm_host.hpp"         // errors, slots, launch workers, the handle, launch macros
 #include "host/xm_launch.hpp"       // launch helpers of every kernel variant
 #include "host/xm_own_plan.hpp"     // owner-tile tables (host analysis in xm_create)
 #include "host/xm_enqueue.hpp"      // path selection + the launches of one frame
 #include "host/xm_batch.hpp"        // multi-frame launches (groups)
 #include "host/xm_workers.hpp"      // redo of failed shortcuts, launch workers, single-frame entry
+#include "host/xm_create.hpp"       // the stages of xm_create
 #include "host/xm_api_engine.hpp"   // xm_create .. xm_process_batch, adaptive batching
 #include "host/xm_api_graph.hpp"    // hipGraph batches
 #include "host/xm_api_stage.hpp"    // debug + stage API
