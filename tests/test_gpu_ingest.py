@@ -14,44 +14,9 @@ from x_maps_amd import XMapsEngine
 from x_maps_amd import synthetic as S
 from x_maps_amd.ingest import DeviceIngest
 
+from ingest_helpers import Window, _check_frames, _packets, _processor_params, _tiny_stream  # noqa: F401  (other modules take them from here too)
+
 pytestmark = pytest.mark.gpu
-
-
-def _packets(stream, packet_us):
-    edges = np.arange(stream["t"][0], stream["t"][-1] + packet_us, packet_us)
-    cuts = np.searchsorted(stream["t"], edges)
-    return [stream[a:b] for a, b in zip(cuts[:-1], cuts[1:])]
-
-
-def _tiny_stream(n_frames, seed, per_frame=2600, neg=0.1, gap_noise=3):
-    cfg = S.C_TINY
-    rng = np.random.default_rng(seed)
-    chunks = []
-    for f in range(n_frames):
-        start = 2_000_000 + f * 16_600
-        tt = np.unique(np.concatenate((np.sort(rng.integers(0, 13_000, per_frame)) + start, np.arange(start, start + 13_000, 25))))
-        ev = np.zeros(len(tt), S.EVENT_CD_DTYPE)
-        ev["t"] = tt
-        ev["x"] = np.clip((tt - start) / 13_000 * cfg.cam_w + rng.normal(0, 1.5, len(tt)), 0, cfg.cam_w - 1).astype(np.uint16)
-        ev["y"] = rng.integers(0, cfg.cam_h, len(tt))
-        ev["p"] = rng.random(len(tt)) >= neg
-        parts = [ev]
-        if gap_noise and f % gap_noise == gap_noise - 1:
-            nz = np.zeros(1, S.EVENT_CD_DTYPE)
-            nz["t"], nz["x"], nz["y"], nz["p"] = start + 14_500, 5, 5, 1
-            parts.append(nz)
-        chunks.append(np.concatenate(parts))
-    return np.concatenate(chunks)
-
-
-def _check_frames(tb, got, want_frames, camera=False):
-    assert len(got) == len(want_frames), (len(got), len(want_frames))
-    for fr, evs in zip(got, want_frames):
-        assert (fr.n_events, fr.t_first, fr.t_last) == (len(evs), int(evs["t"][0]), int(evs["t"][-1])), (fr.seq, fr.lost, fr.overflow)
-        x, y, t, _ = S.to_soa(evs)
-        ref = O.process_ev_frame(tb, x.astype(np.int64), y.astype(np.int64), t, camera_perspective=camera)
-        assert fr.n_inliers == int(ref["mask"].sum()) and fr.n_index_errors == 0 and not fr.lost and fr.overflow == 0
-        assert np.array_equal(fr.depth, ref["depth"]) and np.array_equal(fr.bgr, ref["bgr"]), fr.seq
 
 
 def test_golden_trigger_stream_is_cut_on_the_device_like_the_reference(golden_dir):
@@ -155,19 +120,11 @@ def test_pipe_with_device_ingest_calls_back_with_the_same_frames():
 
     def run(device_ingest):
         shown = []
-
-        class Window:
-            def should_close(self):
-                return False
-
-            def show_async(self, img):
-                shown.append(img)
-
         params = RuntimeParams(camera_width=cfg.cam_w, camera_height=cfg.cam_h, projector_width=cfg.proj_w,
                                projector_height=cfg.proj_h, projector_fps=60, z_near=0.1, z_far=1.2, calib=None,
                                projector_time_map=None, no_frame_dropping=True, camera_perspective=False, tables=tb,
                                device_ingest=device_ingest)
-        with DepthReprojectionProcessor(params, window=Window()) as proc:
+        with DepthReprojectionProcessor(params, window=Window(shown)) as proc:
             for p in pk:
                 proc.process_events(p)
             proc.flush()
@@ -177,13 +134,6 @@ def test_pipe_with_device_ingest_calls_back_with_the_same_frames():
     assert len(a) == len(b) >= 3
     for x, y in zip(a, b):
         assert np.array_equal(x, y)
-
-
-def _processor_params(tb, cfg=S.C_TINY, **kw):
-    from x_maps_amd.depth_reprojection_processor import RuntimeParams
-    return RuntimeParams(camera_width=cfg.cam_w, camera_height=cfg.cam_h, projector_width=cfg.proj_w, projector_height=cfg.proj_h,
-                         projector_fps=60, z_near=0.1, z_far=1.2, calib=None, projector_time_map=None, no_frame_dropping=True,
-                         camera_perspective=False, tables=tb, **kw)
 
 
 def test_default_params_take_the_device_ingest_and_hand_out_frames_of_the_consumers_own():
@@ -198,16 +148,8 @@ def test_default_params_take_the_device_ingest_and_hand_out_frames_of_the_consum
     pk = _packets(stream, int(1e6 / 60 / 4))
 
     def run(**kw):
-        shown = []
-
-        class Window:
-            def should_close(self):
-                return False
-
-            def show_async(self, img):
-                shown.append(img)  # (kept: never copied)
-
-        with DepthReprojectionProcessor(_processor_params(tb, **kw), window=Window()) as proc:
+        shown = []  # (the window keeps every frame: never copied)
+        with DepthReprojectionProcessor(_processor_params(tb, **kw), window=Window(shown)) as proc:
             assert (proc._pipe.ingest is not None) == kw.get("device_ingest", True)
             for p in pk:
                 proc.process_events(p)
@@ -297,15 +239,7 @@ def test_a_frame_event_filter_moves_the_stream_to_the_host_chain_and_back():
     pk = _packets(stream, int(1e6 / 60 / 4))
     third = len(pk) // 3
     shown = []
-
-    class Window:
-        def should_close(self):
-            return False
-
-        def show_async(self, img):
-            shown.append(img)
-
-    with DepthReprojectionProcessor(_processor_params(tb), window=Window()) as proc:
+    with DepthReprojectionProcessor(_processor_params(tb), window=Window(shown)) as proc:
         pipe = proc._pipe
         for p in pk[:third]:
             proc.process_events(p)

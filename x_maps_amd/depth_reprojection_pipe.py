@@ -110,6 +110,8 @@ class DepthReprojectionPipe:
         self._raw_dev, self._raw_host = {}, {}  # EVT 3.0 / 2.0 decoders (process_evt3_words / process_evt2_words), created on first use
         self._own_act_filter = None
         self._host_chain_active = False
+        self._ingest_failed = False  # an ingest call has raised: the error has reached the caller, close() does not ask again
+        self._closed = False
         if self.activity_filter is None and getattr(p, "activity_filter", True):
             _warn_activity_rule_unpinned()
         # a caller-supplied activity filter (Metavision's own, where the SDK is installed) runs on the host: so does the chain
@@ -148,8 +150,7 @@ class DepthReprojectionPipe:
         if want_host != self._host_chain_active:
             self._host_chain_active = want_host
             if want_host:
-                self.ingest.flush()
-                self._deliver_ingest_frames()
+                self.flush()
                 self.ingest.reset()
                 self._ensure_host_chain()
                 if self._own_act_filter is not None:
@@ -171,9 +172,15 @@ class DepthReprojectionPipe:
             self.frame_callback(fr.bgr)
 
     def flush(self):
-        if self.ingest is not None:
-            self.ingest.flush()
-            self._deliver_ingest_frames()
+        """Device ingest: wait for the packets pushed so far and deliver the frames they produced.  Never needed for
+        correctness -- reset() and close() do the same -- only to see the frames sooner."""
+        if self.ingest is not None and not self._ingest_failed:
+            try:
+                self.ingest.flush()
+                self._deliver_ingest_frames()
+            except BaseException:
+                self._ingest_failed = True
+                raise
 
     def process_evt3_words(self, words):
         """A chunk of a recording's EVT 3.0 words (x_maps_amd.evt3.read_raw_words) instead of an EventCD packet: decoded on the
@@ -207,8 +214,12 @@ class DepthReprojectionPipe:
                     push(piece[len(piece) // 2:])
                     return
                 self._deliver_ingest_frames()
-            for a in range(0, len(w), dev.max_words):
-                push(w[a:a + dev.max_words])
+            try:
+                for a in range(0, len(w), dev.max_words):
+                    push(w[a:a + dev.max_words])
+            except BaseException:
+                self._ingest_failed = True
+                raise
             return
         host = self._raw_host.get(fmt)
         if host is None:
@@ -220,8 +231,13 @@ class DepthReprojectionPipe:
 
     def process_events(self, evs):
         if self._use_ingest():
-            self.ingest.push(evs)
-            self._deliver_ingest_frames()
+            # asynchronous: the frames this packet cuts are delivered by a later call -- at the latest by reset() / close()
+            try:
+                self.ingest.push(evs)
+                self._deliver_ingest_frames()
+            except BaseException:
+                self._ingest_failed = True
+                raise
             return
         pos = evs[evs["p"] == 1]  # PolarityFilterAlgorithm(1), pipe:43,114
         if self.activity_filter is not None:
@@ -296,6 +312,9 @@ class DepthReprojectionPipe:
         self.stats_printer.log(f"Selected event filter: {new_filter}")
 
     def reset(self):
+        # the frames cut so far belong to the old stream and were shown by now in the reference (its callback is synchronous):
+        # deliver them before the stream starts over
+        self.flush()
         self.trigger_finder.reset()
         if self.ingest is not None:
             self.ingest.reset()  # (buffered events and the activity filter's history: the stream starts over)
@@ -305,15 +324,25 @@ class DepthReprojectionPipe:
     replay_group = 16  # frames per group of process_ev_frames
 
     def close(self):
-        if getattr(self, "_replay_engine", None) is not None:
-            self._replay_engine.close()
-            self._replay_engine = None
-        for dev in getattr(self, "_raw_dev", {}).values():  # (before the engine they belong to)
-            dev.close()
-        self._raw_dev = {}
-        if self.ingest is not None:
-            self.ingest.close()
-        if self._own_act_filter is not None:
-            self._own_act_filter.close()
-            self._own_act_filter = None
-        self.calib_maps.engine.close()
+        """Delivers the frames the device ingest still holds (every frame cut from the packets pushed so far reaches
+        frame_callback: the reference's loop has no flush), then releases everything.  A second call does nothing.  When the
+        last frames cannot be had (a launch-side error nobody has seen yet) everything is released all the same and the error is
+        raised once, here."""
+        if getattr(self, "_closed", False):
+            return
+        self._closed = True
+        try:
+            self.flush()  # (before the decoders, the ingest and its result ring go: views are delivered while they are valid)
+        finally:
+            if getattr(self, "_replay_engine", None) is not None:
+                self._replay_engine.close()
+                self._replay_engine = None
+            for dev in getattr(self, "_raw_dev", {}).values():  # (before the engine they belong to)
+                dev.close()
+            self._raw_dev = {}
+            if self.ingest is not None:
+                self.ingest.close()
+            if self._own_act_filter is not None:
+                self._own_act_filter.close()
+                self._own_act_filter = None
+            self.calib_maps.engine.close()

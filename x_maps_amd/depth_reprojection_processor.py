@@ -47,6 +47,9 @@ class RuntimeParams:
     # arrays (the pinned buffers their DMA filled).  THE DEFAULT since round 6 -- the same frames as the host chain, which stays
     # as the opt-out (False: NumPy polarity mask + one GPU call per packet for the activity filter + the NumPy trigger finder,
     # 20 x slower) and takes over by itself while a frame event filter (key E) or a caller-supplied activity filter is selected.
+    # DELIVERY: a frame reaches frame_callback from a later process_events call than the one that cut it, at the latest from
+    # reset() / close() / the end of the `with` block; same frames, same order, none lost (with no_frame_dropping: whatever the
+    # packets' sizes and ingest_result_ring).  flush() only brings them forward.
     device_ingest: bool = True
     # The activity-noise filter behind the polarity filter, on every packet, as the reference runs it unconditionally
     # (depth_reprojection_pipe.py:65-67,116-117): kernels of the device ingest, or one GPU call per packet in front of the host's
@@ -126,9 +129,26 @@ class DepthReprojectionProcessor:
             self._window.set_keyboard_callback(self.keyboard_cb)
         return self
 
-    def __exit__(self, *exc_info):
-        self.stats_printer.print_stats()
-        self._pipe.close()
+    def __exit__(self, exc_type=None, exc=None, tb=None):
+        # The reference's loop has no flush(): the frames the device ingest still holds are delivered here, before the statistics
+        # are printed ("frames shown" counts them).  An error of that last delivery is raised once everything is released --
+        # unless an exception is leaving the block already: that one goes on, this one is logged.
+        err = None
+        try:
+            self._pipe.flush()
+        except Exception as e:
+            err = e
+        try:
+            self.stats_printer.print_stats()
+        finally:
+            try:
+                self._pipe.close()
+            except Exception as e:
+                err = err or e
+        if err is not None:
+            if exc_type is None:
+                raise err
+            self.stats_printer.log(f"the last frames were not delivered: {err!r}")
         return False
 
     def keyboard_cb(self, key, scancode=None, action=None, mods=None):
@@ -166,7 +186,8 @@ class DepthReprojectionProcessor:
         self.stats_printer.print_stats_if_needed()
 
     def flush(self):
-        """Device ingest: wait for the packets pushed so far and deliver the frames they produced."""
+        """Device ingest: wait for the packets pushed so far and deliver the frames they produced now.  Optional: reset() and
+        leaving the `with` block deliver them too, no frame is lost without it."""
         self._pipe.flush()
 
     def reset(self):

@@ -83,10 +83,10 @@ class DeviceIngest:
         self.max_packet = int(max_packet_events) or (1 << 19)
         self.shape = (engine.out_h, engine.out_w)
         self._views = {}
-        # lossless: a caller that polls after every push never loses a frame to the result ring being lapped -- at most one frame
-        # is cut per push, so after result_ring - 1 pushes without a synchronisation the next push waits for the GPU first (the
-        # frames cut so far are then published and the caller's poll behind this push picks them up).  Off: the reference's own
-        # behaviour under load -- frames the host did not fetch in time are dropped and reported (`lost`).
+        # lossless: no frame is lost to the result ring being lapped, however the caller packs its events and however rarely it
+        # polls -- at most one frame is cut per packet, and a packet is handed to the library only while the frames not polled yet
+        # and the packets still in flight leave room in the ring (_backpressure).  Off: the reference's own behaviour under load --
+        # frames the host did not fetch in time are dropped and reported (`lost`).
         self._lossless = bool(lossless)
         self._ring = int(result_ring) if int(result_ring) > 0 else 8
         self._fr = N.xm_ingest_frame()
@@ -95,11 +95,13 @@ class DeviceIngest:
         self._pool = C.c_void_p(None)   # the pool of the frame polled last (NULL unless its buffers left the ring with it)
         self._pool_ref = C.byref(self._pool)
         self._pool_seen = None          # ... of this ingest, once a frame has left with its buffers
+        self._parked = []               # lossless: frames polled by the back-pressure, handed out by the next poll()
 
     def close(self):
         if getattr(self, "_g", None) is not None and self._g.value:
             self._lib.xm_ingest_destroy(self._g)
             self._g = C.c_void_p(None)
+        self._parked = []
 
     def __del__(self):
         try:
@@ -116,33 +118,51 @@ class DeviceIngest:
 
     def push(self, evs: np.ndarray):
         """One packet of EventCD records; larger packets are split (every piece is a packet of its own for the trigger
-        finder's once-per-packet decision, like feeding the reference smaller packets)."""
+        finder's once-per-packet decision, like feeding the reference smaller packets).  lossless: the back-pressure is applied in
+        front of every piece, so no packing of the events can lap the result ring."""
         if evs.dtype != EVENT_CD_DTYPE:
             evs = evs.astype(EVENT_CD_DTYPE)
         evs = np.ascontiguousarray(evs)
-        self._backpressure(max(1, -(-len(evs) // self.max_packet)))
         if len(evs) == 0:
+            self._backpressure()
             N.check(self._lib.xm_ingest_push(self._g, None, 0))
             return
         for a in range(0, len(evs), self.max_packet):
             part = evs[a:a + self.max_packet]
+            self._backpressure()
             N.check(self._lib.xm_ingest_push(self._g, C.c_void_p(part.ctypes.data), len(part)))
 
     def push_pinned(self, evs: np.ndarray):
         """A packet that already lives in pinned host memory (XMapsEngine.host_empty): no staging copy."""
         assert evs.dtype == EVENT_CD_DTYPE and evs.flags.c_contiguous
-        self._backpressure(max(1, -(-len(evs) // self.max_packet)))
+        if len(evs) == 0:
+            self._backpressure()
         for a in range(0, len(evs), self.max_packet):
             part = evs[a:a + self.max_packet]
+            self._backpressure()
             N.check(self._lib.xm_ingest_push_pinned(self._g, C.c_void_p(part.ctypes.data), len(part)))
 
-    def _backpressure(self, n_pushes):
-        """lossless: frames not polled yet + packets whose verdict is still out (each may cut one) stay below the result ring's
-        size.  Waits for verdicts only (xm_ingest_backlog) -- nothing is synchronised, the GPU's pipeline stays full.  What
-        waiting cannot settle are frames the caller has not polled: the contract is a caller that polls after every push."""
+    def _backpressure(self, n_pushes=1):
+        """lossless, in front of every packet handed to the library (a piece of a split push, a chunk of raw words): frames not
+        polled yet + packets whose verdict is still out (each may cut one frame) + this packet stay below the result ring's size.
+        The usual case -- a caller that polls after every push, a ring with room -- waits for verdicts at most
+        (xm_ingest_backlog): nothing is synchronised, the GPU's pipeline stays full.  What waiting for verdicts cannot settle are
+        frames nobody has polled (the pieces of one large push, a caller that polls rarely) and frames that are issued but not
+        published while no packet is in flight: those are polled here and parked -- the caller's next poll() returns them first, in
+        order -- after a flush if they are not out yet.  That path synchronises; it is taken only where a frame would be lost
+        otherwise."""
         if not self._lossless:
             return
-        N.check(self._lib.xm_ingest_backlog(self._g, max(1, self._ring - n_pushes), C.byref(self._backlog)))
+        room = max(1, self._ring - n_pushes)
+        N.check(self._lib.xm_ingest_backlog(self._g, room, C.byref(self._backlog)))
+        if self._backlog.value < room:
+            return
+        self._parked += self._poll_now(True)
+        N.check(self._lib.xm_ingest_backlog(self._g, room, C.byref(self._backlog)))
+        if self._backlog.value < room:
+            return
+        self.flush()
+        self._parked += self._poll_now(True)
 
     def _view(self, ptr, shape, ctype):
         """NumPy view of one buffer of the pinned result ring (built once per buffer, from the address: np.ctypeslib.as_array on
@@ -161,6 +181,12 @@ class DeviceIngest:
         over it is dropped; only when the pool is exhausted is the frame copied out of the ring instead).  copy=False: views into
         the pinned result ring, valid until `result_ring` - 1 further frames have been cut (the lifetime xm_ingest_frame
         documents)."""
+        if self._parked:  # (frames the back-pressure took out of the ring: the caller's own arrays whatever `copy` says)
+            out, self._parked = self._parked, []
+            return out + self._poll_now(copy)
+        return self._poll_now(copy)
+
+    def _poll_now(self, copy: bool) -> list[IngestFrame]:
         out = []
         fr = self._fr
         h, w = self.shape
