@@ -4,6 +4,8 @@
 //   2. a producer that pauses longer than the consumer spins: the consumer sleeps and is woken again and again, no job is lost
 //   3. wait_done returns once the job is done, and early once an error has been noted
 //   4. FirstError: two threads note at once while a third reads: one code comes out, with its own text
+//   5. the hand-over of the ingest's out side: the producer runs some jobs itself -- behind wait_done of everything it posted
+//      before -- and posts them marked as done; what both sides write is never written by two at once, and job n stays frame n - 1
 // Prints "ok" and exits 0; any failed check exits 1 (a lost wake-up hangs: the test's time limit catches that).
 #include "../../x_maps_amd/csrc/host/xm_queue.hpp"
 
@@ -194,11 +196,56 @@ void first_error_races() {
   }
 }
 
+void producer_takes_some_itself() {
+  struct OutJob {
+    unsigned long long frame = 0;
+    bool done = false, stop = false;
+  };
+  JobQueue<OutJob, 8> q;
+  FirstError err;
+  unsigned long long frames_out = 0;  // (plain on purpose: the queue alone orders the two sides' writes)
+  std::thread c([&] {
+    for (;;) {
+      const OutJob j = q.take(64);
+      if (!j.stop && !j.done) {
+        CHECK(frames_out == j.frame);
+        frames_out = j.frame + 1;
+      }
+      q.finish();
+      if (j.stop) return;
+    }
+  });
+  const unsigned long long n = 100000, ahead = 3;
+  unsigned r = 2463534242u;
+  bool self = false;
+  for (unsigned long long f = 0; f < n; ++f) {
+    r = r * 1103515245u + 12345u;
+    if ((r >> 16) % 16 == 0) self = !self;  // (the mode changes every few frames, as between records and EVT chunks)
+    if ((r >> 20) % 512 == 0) std::this_thread::sleep_for(std::chrono::microseconds(100));  // (the consumer falls asleep)
+    if (f >= ahead) q.wait_done(f - ahead + 1, &err);  // at most `ahead` frames in front of the finished ones
+    OutJob j;
+    j.frame = f;
+    if (self) {
+      q.wait_done(f, &err);  // the frames posted before come first
+      CHECK(frames_out == f);
+      frames_out = f + 1;
+      j.done = true;
+    }
+    CHECK(q.post(j) == f + 1);
+  }
+  OutJob stop;
+  stop.stop = true;
+  q.wait_done(q.post(stop));
+  c.join();
+  CHECK(frames_out == n && err.code() == 0);
+}
+
 int main() {
   order_under_load();
   sleep_and_wake();
   wait_done_and_errors();
   first_error_races();
+  producer_takes_some_itself();
   std::printf("ok\n");
   return 0;
 }

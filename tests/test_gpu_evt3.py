@@ -206,6 +206,47 @@ def test_words_and_records_take_turns_on_one_ingest():
         assert np.array_equal(a.depth, b.depth) and np.array_equal(a.bgr, b.bgr)
 
 
+@pytest.mark.parametrize("launch_thread", [True, False])
+def test_records_and_chunks_alternate_on_every_frame_with_a_result_ring_of_two(launch_thread):
+    """one packet per frame period; the packets that cut the odd frames (the CPU chain says which) arrive as EVT 3.0 chunks, all
+    others as records: the frames leave through the out thread and in order on the frame stream ALTERNATELY (without a launch
+    thread: all inline).  A result ring of 2 with back-pressure instead of flushes: the hand-over between the two ways runs while
+    frames are in flight.  == the CPU chain (oracle/ingest_oracle.py) frame by frame, no frame lost"""
+    import ingest_oracle as IO
+    from ingest_helpers import _check_frames, _packets, _tiny_stream
+    from x_maps_amd.ingest import DeviceIngest
+    tb = S.make_tables(S.C_TINY)
+    packets = [pk for pk in _packets(_tiny_stream(26, seed=5), 16_600) if len(pk)]
+    tf = IO.TriggerFinderOracle(60)
+    cut_by = []  # per frame: the number (from 1) of the push that cuts it
+    for i, pk in enumerate(packets):
+        tf.process_events(IO.polarity_filter(pk))
+        cut_by += [i + 1] * (len(tf.frames) - len(cut_by))
+    assert 16 <= len(tf.frames) <= 22 and len(set(cut_by)) == len(cut_by)
+    as_chunk = set(cut_by[1::2])
+    with XMapsEngine(tb) as eng, \
+            DeviceIngest(eng, 60, capacity_events=1 << 15, max_packet_events=1 << 12, result_ring=2, launch_thread=launch_thread,
+                         lossless=True) as ing, \
+            evt3.DeviceEvt3Decoder(eng, max_words=8 << 12) as dec:
+        got, keep = [], []
+        for i, pk in enumerate(packets):
+            if i + 1 in as_chunk:
+                w = evt3.encode_evt3(pk)
+                pw = eng.host_empty(w.shape, np.uint16)  # (pinned, count left on the device: the push waits for nothing)
+                pw[:] = w
+                keep.append(pw)
+                dec.push(ing, pw, pinned=True, count=False)
+            else:
+                ing.push(pk)
+            got += ing.poll()
+        ing.flush()
+        got += ing.poll()
+    _check_frames(tb, got, tf.frames)  # (asserts `not lost` for every frame)
+    assert [(f.seq, f.push_seq) for f in got] == list(enumerate(cut_by))
+    if launch_thread:  # a frame that left in order has no publish time of the out thread's (xmaps.h: push_to_publish_us)
+        assert [f.push_to_publish_us == 0 for f in got] == [n in as_chunk for n in cut_by]
+
+
 def test_a_raw_file_through_the_processor(tmp_path):
     """DepthReprojectionProcessor.process_evt3_words (device ingest: words decoded on the GPU; host ingest: on the host) shows the
     same frames as process_events on the decoded packets"""

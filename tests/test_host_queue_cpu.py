@@ -1,7 +1,8 @@
 """The host threads' hand-over (x_maps_amd/csrc/host/xm_queue.hpp: the job queue of the launch workers and of the ingest's
-launch and copy threads, the out thread's wait and wake-up, the first-error latch) built alone with ThreadSanitizer and stressed
-by tests/c_host/queue_stress.cpp: order, no lost job or wake-up, wait_done on work and on an error, one error with its own text
-when two threads fail at once.  Host code only: no GPU."""
+copy, launch and out threads, the first-error latch) built alone with ThreadSanitizer and stressed by
+tests/c_host/queue_stress.cpp: order, no lost job or wake-up, wait_done on work and on an error, one error with its own text
+when two threads fail at once, and the out side's form of the queue -- a producer that runs some of the jobs itself and posts
+them as done.  Host code only: no GPU."""
 import os
 import shutil
 import subprocess

@@ -1,5 +1,6 @@
-// xm_api_evt3.hpp -- C-ABI: EVT 3.0 / EVT 2.0 words -> EventCD records on the device (xmaps_evt3.hpp, xmaps_evt2.hpp), alone or
-// straight into the ingest.  One decoder object for both encodings (`format`): same buffers, same state record, same three launches.
+// xm_api_evt3.hpp -- C-ABI: EVT 3.0 / EVT 2.0 words -> EventCD records on the device (xmaps_evt3.hpp, xmaps_evt2.hpp).  One decoder
+// object for both encodings (`format`): same buffers, same state record, same three launches.  Straight into the ingest:
+// xm_ingest_push_evt3 / _evt2 (xm_api_ingest.hpp), which enqueue the same launches (evt3_enqueue) from the ingest's copy side.
 // (part of libxmaps_hip.so's host side: included by ../xmaps_hip.hip, one translation unit; see that file for the order)
 #pragma once
 
@@ -70,30 +71,6 @@ int evt3_run(xm_evt3* d, const void* words_host, size_t n_words, bool pinned, ui
   if (*n_events > out_cap) return fail(XM_ERR_TOO_MANY, "the chunk decodes to %zu events, room for %zu (decoder state unchanged: decode it again in smaller pieces)", *n_events, out_cap);
   d->cur ^= 1;
   return XM_OK;
-}
-
-// one chunk of words, the copy side: H2D + the three decode launches on the decoder's stream + the event behind them
-int ingest_words_to_events(const xm_evt3* d) { return d && d->format == 2 ? 1 : 12; }
-
-int ingest_copy_evt3(xm_ingest* g, xm_evt3* d, int k, const void* words, size_t n_words, bool pinned) {
-  if (n_words) {
-    int rc = evt3_enqueue(d, words, n_words, pinned, g->d_pkt[k], (size_t)g->max_packet, d->stream, g->d_pkt_n + k);
-    if (rc) return rc;
-    HIP_TRY(hipEventRecord(g->copied_ev[k], d->stream));
-    d->cur ^= 1;
-  }
-  return XM_OK;
-}
-
-// ... the launch side: everything behind it, nothing waited for: the ingest's kernels read the chunk's event count on the device
-int ingest_issue_evt3(xm_ingest* g, xm_evt3* d, int k, const void* words, size_t n_words, bool pinned, bool arrived) {
-  g->out_serial_now = !g->opt_evt3_out_stream;  // (see xm_ingest::out_serial_now)
-  int rc0 = arrived ? XM_OK : ingest_copy_evt3(g, d, k, words, n_words, pinned);
-  if (rc0) return rc0;
-  if (n_words) HIP_TRY(hipStreamWaitEvent(g->stream, g->copied_ev[k], 0));
-  // (upper bound of the chunk's events for the host's bookkeeping: an EVT 3.0 vector word yields up to 12, everything else at most one)
-  const size_t bound = std::min<size_t>((size_t)g->max_packet, n_words * (d->format == 2 ? 1 : 12));
-  return ingest_process(g, k, n_words ? bound : 0, nullptr, n_words ? g->d_pkt_n + k : nullptr);
 }
 
 }  // namespace
@@ -167,60 +144,6 @@ int xm_evt3_decode(xm_evt3* d, const uint16_t* words_host, size_t n_words, const
 }
 int xm_evt2_decode(xm_evt3* d, const uint32_t* words_host, size_t n_words, const void** events_dev, size_t* n_events) {
   return evt_decode(d, 2, words_host, n_words, events_dev, n_events);
-}
-
-// The chunk is decoded on the DECODER's stream into the packet slot (free: its previous packet has been consumed) while the frame
-// kernels of the packets before it keep running on the ingest's stream.  n_events != NULL: the decoding is waited for and the
-// chunk's event count returned (and checked against max_packet_events: XM_ERR_TOO_MANY leaves decoder and ingest as they were).
-// n_events == NULL: nothing is waited for -- the ingest's kernels read the count from device memory (round 4); a chunk that
-// decodes to more than max_packet_events events is truncated to that many and the excess counted in the frames' `overflow`;
-// the words are handed to the ingest's launch thread like a packet of records (pageable words: the call returns once they have been copied).
-static int ingest_push_words(xm_ingest* g, xm_evt3* d, int format, const void* words_host, size_t n_words, int words_pinned, size_t* n_events) {
-  if (!g || !d || (n_words && !words_host)) return fail(XM_ERR_INVALID, "NULL argument");
-  if (d->format != format) return fail(XM_ERR_INVALID, "this decoder was created for EVT %d.0 words", d->format);
-  if (g->h != d->h) return fail(XM_ERR_INVALID, "the decoder and the ingest belong to different handles");
-  if (n_words > d->max_words) return fail(XM_ERR_TOO_MANY, "chunk of %zu words exceeds max_words %zu", n_words, d->max_words);
-  const double c0 = ingest_now();
-  HIP_TRY(hipSetDevice(g->h->cfg.device));
-  int rc = ingest_take_error(g);
-  if (rc) return rc;
-  const int k = g->pkt_next;
-  if ((rc = ingest_wait_entry(g, k))) return rc;  // the staging entry's previous packet has been consumed
-  xm_ingest::Job j;
-  j.k = k;
-  if (n_events) {
-    // the decoder runs here, on its own stream -- once the launch thread is done with every chunk handed to it before (those
-    // use the same decoder: its state index and buffers are not to be touched from two threads) -- and the records then go to
-    // the launch side like a packet that is already on the device
-    if (g->threaded) {
-      g->launch_q.wait_done(ingest_posted(g), &g->err);
-      if ((rc = ingest_take_error(g))) return rc;
-    }
-    size_t n = 0;
-    rc = evt3_run(d, words_host, n_words, words_pinned != 0, g->d_pkt[k], (size_t)g->max_packet, d->stream, &n);
-    *n_events = n;
-    if (rc) return rc;  // (XM_ERR_TOO_MANY: neither the decoder nor the ingest has advanced -- push the chunk again in halves)
-    j.kind = 3; j.n = n;
-  } else {
-    j.kind = 1; j.n = n_words; j.host = words_host; j.dec = d; j.pinned = words_pinned != 0;
-  }
-  g->pkt_next = (k + 1) % xm_ingest::STAGE;
-  g->posted += 1;
-  j.push_no = g->posted;
-  g->pkt_push[k] = g->posted;
-  g->push_t[g->posted % xm_ingest::VRING] = c0;
-  // (pageable words are copied by the launch side: wait until it has done so)
-  rc = ingest_submit(g, j, j.kind == 1 && !j.pinned);
-  g->push_host_s += ingest_now() - c0;
-  g->push_calls += 1;
-  return rc;
-}
-
-int xm_ingest_push_evt3(xm_ingest* g, xm_evt3* d, const uint16_t* words_host, size_t n_words, int words_pinned, size_t* n_events) {
-  return ingest_push_words(g, d, 3, words_host, n_words, words_pinned, n_events);
-}
-int xm_ingest_push_evt2(xm_ingest* g, xm_evt3* d, const uint32_t* words_host, size_t n_words, int words_pinned, size_t* n_events) {
-  return ingest_push_words(g, d, 2, words_host, n_words, words_pinned, n_events);
 }
 
 }  // extern "C"

@@ -53,6 +53,11 @@ using namespace xm;
 #include "host/xm_api_sharded.hpp"  // one frame over several GPUs of one process (RCCL communicators owned by the handle)
 #include "host/xm_api_shardcomm.hpp"  // one rank of a frame sharded over several processes: the library drives RCCL itself
 #include "host/xm_api_filters.hpp"  // frame event filters, pause detection
-#include "host/xm_api_ingest.hpp"   // device-side ingest
-#include "host/xm_api_evt3.hpp"     // EVT 3.0 decoder on the device (alone / in front of the ingest)
+#include "host/xm_api_activity.hpp" // the activity filter alone; its device state (shared with the ingest)
+#include "host/xm_api_evt3.hpp"     // EVT 3.0 / 2.0 decoder on the device
+#include "host/xm_ingest_state.hpp" // device-side ingest: its state by owning thread, the jobs its threads hand each other
+#include "host/xm_ingest_out.hpp"   // ... the out side (result copies, sequence numbers) and the frame pool
+#include "host/xm_ingest_launch.hpp"  // ... the launch and copy sides (packets, verdicts, frames), the caller's door to them
+#include "host/xm_ingest_create.hpp"  // ... the stages of xm_ingest_create
+#include "host/xm_api_ingest.hpp"   // ... its C entry points (records, and EVT words through the decoder)
 #include "host/xm_api_misc.hpp"     // X-map builder, evaluation metrics, memory helpers
