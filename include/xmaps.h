@@ -568,6 +568,24 @@ int xm_ingest_backlog(xm_ingest* g, int wait_below, uint64_t* backlog);
  * over it: a caller that copies a frame out of the ring asks this AFTER the copy (the ring is lapped only when the host falls
  * result_ring - 1 frames behind; never in a pipe that polls after every push with result_ring >= 3) */
 int xm_ingest_frame_valid(xm_ingest* g, uint64_t seq);
+/* Frame event filters (the reference's key E, python/frame_event_filter.py) as a stage of the ingest: `filter` = 0 (none) or
+ * XM_FILTER_*, with xm_frame_event_filter's semantics for both values of intended_semantics.  The frames cut by packets pushed
+ * AFTER the call go through the filter on the device, between the cut and the frame kernels (ordered like a push: nothing is
+ * flushed, nothing is reset; the filter selected when a packet is handed in is the one its frame gets, as in the reference).
+ * Cells: (y, x) on the cam_height x cam_width sensor; XM_FILTER_FIRST_PER_YT: (y, xr) with xr from the handle's rectify table
+ * (cam_mapx_i16), on a map as wide as the frame's own max(xr) + 1, a negative xr wrapping like NumPy's negative index.  An
+ * event whose cell lies outside the map (x >= cam_width, y >= cam_height, a column still negative after the wrap: the reference
+ * raises IndexError) is left out and counted in the frame's n_index_errors.
+ * xm_ingest_frame of a filtered frame: n_events / t_first / t_last are the CUT frame's (what the trigger finder reports),
+ * n_inliers / n_index_errors the filtered frame's; xm_ingest_last_frame_kept gives the survivors' count.
+ * XM_ERR_INVALID (nothing changes): an unknown filter; XM_FILTER_FIRST_PER_YT on a rig whose cell map, cam_height x (largest
+ * entry of cam_mapx_i16 + 1), would exceed XM_INGEST_YT_MAX_CELLS cells.  The stage's scratch (two u32 maps of that many
+ * cells, a survivors buffer) is allocated by the first call that selects a filter. */
+#define XM_INGEST_YT_MAX_CELLS (1u << 22)
+int xm_ingest_set_frame_filter(xm_ingest* g, int filter, int intended_semantics);
+/* events of the frame most recently returned by xm_ingest_poll* that survived the frame event filter (= its n_events when none
+ * was selected) */
+int xm_ingest_last_frame_kept(xm_ingest* g, uint64_t* n_kept);
 int xm_ingest_flush(xm_ingest* g); /* wait for everything pushed so far */
 int xm_ingest_reset(xm_ingest* g); /* RobustTriggerFinder.reset(): discard the buffered events (and the activity filter's
                                      * per-pixel history: the stream starts over) */

@@ -204,6 +204,7 @@ static int ingest_poll(xm_ingest* g, xm_ingest_frame* out, bool owned) {
   out->overflow = v.overflow;
   out->push_seq = v.push_seq;
   out->push_to_publish_us = v.latency_us;
+  ca.last_kept = v.n_used;
   ca.next_seq += 1;
   return 1;
 }
@@ -261,6 +262,61 @@ int xm_ingest_frame_valid(xm_ingest* g, uint64_t seq) {
   // (k_ing_publish zeroes the slot's sequence number before anything of the next frame is written into the slot's buffers: the
   //  frame kernels' K2 writes device memory, the copy into this slot comes behind k_ing_publish on the frame stream's event)
   return __atomic_load_n(&g->fx.h_status[seq % (uint64_t)g->fx.ring].seq, __ATOMIC_ACQUIRE) == seq + 1 ? 1 : 0;
+}
+
+int xm_ingest_last_frame_kept(xm_ingest* g, uint64_t* n_kept) {
+  if (!g || !n_kept) return fail(XM_ERR_INVALID, "NULL argument");
+  *n_kept = g->ca.last_kept;
+  return XM_OK;
+}
+
+// the frame-filter stage's scratch, once (IngestFrameFilter): sized for every filter the rig's LUT allows
+static int ingest_frame_filter_alloc(xm_ingest* g) {
+  IngestFrameFilter& ff = g->ff;
+  const IngestFixed& fx = g->fx;
+  const xm_handle* h = fx.h;
+  ff.cells_xy = (u32)h->tb.cam_w * (u32)h->tb.cam_h;
+  ff.yt_w = h->lut_xr_max + 1;
+  ff.yt_wrap = h->cols_xr_min < 0;
+  const u64 cells_yt = ff.yt_w > 0 ? (u64)ff.yt_w * (u64)h->tb.cam_h : 0;
+  ff.yt_ok = cells_yt > 0 && cells_yt <= ING_YT_MAX_CELLS;
+  ff.cells_yt = ff.yt_ok ? (u32)cells_yt : 0u;
+  const size_t cells = std::max(ff.cells_xy, ff.cells_yt), blocks = (cells + FF_BLOCK - 1) / FF_BLOCK;
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  for (Event& e : ff.read_ev) HIP_TRY(e.create());
+  HIP_TRY(ff.d_last.alloc(cells));
+  HIP_TRY(ff.d_first.alloc(cells));
+  HIP_TRY(ff.d_sums.alloc(blocks));
+  HIP_TRY(ff.d_survivors.alloc(std::max<size_t>((size_t)fx.dev.mirror, cells)));
+  HIP_TRY(ff.d_descs.alloc(ING_VRING));
+  HIP_TRY(ff.d_infos.alloc(ING_VRING));
+  HIP_TRY(ff.d_ctl.alloc(1));
+  HIP_TRY(hipMemset(ff.d_last, 0, cells * sizeof(u32)));
+  HIP_TRY(hipMemset(ff.d_first, 0, cells * sizeof(u32)));
+  HIP_TRY(hipMemset(ff.d_sums, 0, blocks * sizeof(u32)));
+  HIP_TRY(hipMemset(ff.d_descs, 0, sizeof(FrameDesc) * ING_VRING));
+  HIP_TRY(hipMemset(ff.d_infos, 0, sizeof(FrameFilterInfo) * ING_VRING));
+  HIP_TRY(hipMemset(ff.d_ctl, 0, sizeof(FrameFilterCtl)));
+  HIP_TRY(hipDeviceSynchronize());  // (default-stream memsets: the ingest's non-blocking streams do not wait for them)
+  ff.ready = true;
+  return XM_OK;
+}
+
+int xm_ingest_set_frame_filter(xm_ingest* g, int filter, int intended_semantics) {
+  if (!g) return fail(XM_ERR_INVALID, "NULL argument");
+  if (filter != 0 && (filter < FILTER_FIRST_PER_YT || filter > FILTER_MEAN_PER_XY)) return fail(XM_ERR_INVALID, "unknown filter %d", filter);
+  int rc = ingest_take_error(g);
+  if (rc) return rc;
+  if (filter && !g->ff.ready && (rc = ingest_frame_filter_alloc(g))) return rc;
+  if (filter == FILTER_FIRST_PER_YT && !g->ff.yt_ok)
+    return fail(XM_ERR_INVALID, "FirstEventPerYT: a cell map of %d rows x %d columns (the rectify LUT's largest entry + 1) exceeds %llu cells",
+                g->fx.h->tb.cam_h, g->ff.yt_w, (unsigned long long)ING_YT_MAX_CELLS);
+  // ordered like a push: the packets handed in before this call keep the filter they were pushed under
+  IngestJob j;
+  j.kind = JobKind::set_filter;
+  j.filter = filter;
+  j.intended = intended_semantics ? 1 : 0;
+  return ingest_submit(g, j, false);
 }
 
 int xm_ingest_flush(xm_ingest* g) {

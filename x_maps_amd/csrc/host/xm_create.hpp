@@ -212,6 +212,7 @@ int classify_rig(xm_handle* h, const CreateOpts& o) {
   // disp >= 0 <=> xp - x_offset >= xr, which is what makes "dead" X-map cells recognisable
   const bool no_wrap = (long)xp_max - xr_min - cfg->x_offset <= 32767 && (long)xp_min - xr_max - cfg->x_offset >= -32768;
   h->cols_xr_min = xr_min;
+  h->lut_xr_max = xr_max;
   bool injective = false;
   if (cfg->view == XM_VIEW_PROJECTOR && no_wrap && cfg->rect_width <= 65536) {
     DevMem<u32> d_dup;

@@ -7,20 +7,58 @@ namespace {
 
 // ---- frames ---------------------------------------------------------------------------------------------------------------
 
-// K0 -> K1 -> K2 -> statistics for the frame that packet `push_no` cut (n events), on the frame stream; its copies to the out side
+// the frame-filter stage's arguments for verdict entry vi under `filter` (FILTER_*) with the semantics `intended`
+FrameFilterDev ingest_frame_filter_dev(const xm_ingest* g, int vi, int filter, int intended) {
+  const IngestFrameFilter& ff = g->ff;
+  const xm_handle* h = g->fx.h;
+  const bool yt = filter == FILTER_FIRST_PER_YT;
+  FrameFilterDev f{};
+  f.cut = g->fx.d_descs + vi;
+  f.out = ff.d_descs + vi;
+  f.info = ff.d_infos + vi;
+  f.ctl = ff.d_ctl;
+  f.last = ff.d_last;
+  f.first = ff.d_first;
+  f.sums = ff.d_sums;
+  f.survivors = ff.d_survivors;
+  f.lut = h->tb.lut;
+  f.cam_w = h->tb.cam_w;
+  f.cam_h = h->tb.cam_h;
+  f.map_w = yt ? ff.yt_w : h->tb.cam_w;
+  f.n_cells = yt ? ff.cells_yt : ff.cells_xy;
+  f.filter = filter;
+  f.use_first = intended && filter != FILTER_LAST_PER_XY;
+  f.wrap = yt && ff.yt_wrap;
+  return f;
+}
+
+// [frame event filter ->] K0 -> K1 -> K2 -> statistics for the frame that packet `push_no` cut (n events), on the frame stream; its
+// copies to the out side
 int ingest_issue_frame(xm_ingest* g, uint64_t push_no, u64 n) {
   const IngestFixed& fx = g->fx;
   IngestLaunch& la = g->la;
   xm_handle* h = fx.h;
   hipStream_t s = fx.frame_stream;
   const int vi = (int)(push_no % ING_VRING);
-  const FrameDesc* desc = fx.d_descs + vi;
+  const FrameDesc* cut = fx.d_descs + vi;
+  // the filter the packet was pushed under: its stage leaves the entry's second descriptor (the survivors, <= n of them), on
+  // which everything below runs; n stays the bound of the grids.  No filter: the launches below and nothing else
+  const int flt = la.push_filter[vi] & 7;
+  const FrameDesc* desc = flt ? g->ff.d_descs + vi : cut;
   if (la.frames_since_clear >= fx.clear_every) {  // (stream-ordered behind every frame so far)
     hipLaunchKernelGGL(k_reset_slot, dim3(1024), dim3(BLOCK), 0, s, fx.dev.slot, fx.dev.key_frame, (u64)h->key_cells, (unsigned char*)nullptr);
     la.frames_since_clear = 0;
   }
   la.frames_since_clear += 1;
   // one EventCD frame in descriptor form: grids from at least two events, the tiled K1's block from the frame itself
+  if (flt) {
+    launch_frame_filter(ingest_frame_filter_dev(g, vi, flt, la.push_filter[vi] >> 3), n, s);
+    // the stage's last launch is the last reader of the cut frame in the ring (K0 / K1 read the survivors): the ingest stream waits
+    // for it instead of for K1
+    hipEvent_t ev = g->ff.read_ev[la.frames_issued % 8];
+    HIP_TRY(hipEventRecord(ev, s));
+    HIP_TRY(hipStreamWaitEvent(fx.stream, ev, 0));
+  }
   const FrameGroup one{desc, 1, n < 2 ? 2 : n, n, false};
   // K0 (general path: the cut frame is sorted whenever the camera stream is, but nothing here relies on it)
   launch_k0<long long, true, false>(one, s);
@@ -28,9 +66,11 @@ int ingest_issue_frame(xm_ingest* g, uint64_t push_no, u64 n) {
   if (int rc = launch_k1<long long, true, false>(h, one, batch_path(h, n), false, false, s)) return rc;
   // the ingest stream must not append over the frame's events (dead, but still in the ring) before K1 has read them: whatever
   // is issued on it from now on waits for this event; what has been issued already fits the room k_ing_segment keeps (`ahead`)
-  hipEvent_t ev = fx.k1_ev[la.frames_issued % 8];
-  HIP_TRY(hipEventRecord(ev, s));
-  HIP_TRY(hipStreamWaitEvent(fx.stream, ev, 0));
+  if (!flt) {
+    hipEvent_t ev = fx.k1_ev[la.frames_issued % 8];
+    HIP_TRY(hipEventRecord(ev, s));
+    HIP_TRY(hipStreamWaitEvent(fx.stream, ev, 0));
+  }
   // K2 writes device output frame o = frame number % ING_NOUT (k_ing_segment put its address into the descriptor) -- once the DMA
   // of the frame that used it last has left
   const uint64_t f = la.frames_issued;
@@ -45,7 +85,8 @@ int ingest_issue_frame(xm_ingest* g, uint64_t push_no, u64 n) {
   if (h->cfg.view == XM_VIEW_PROJECTOR && h->k2_direct) return fail(XM_ERR_INVALID, "ingest needs the tiled frame kernel (XM_K2_DIRECT is set)");
   launch_frame_kernel(h, one, KM_KEY64, s);
   // the frame's statistics into its status entry while the slot's counters and the frame's events are still the frame's ...
-  hipLaunchKernelGGL(k_ing_publish, dim3(1), dim3(64), 0, s, fx.dev.st, desc, (const IngFrameInfo*)(fx.d_infos + vi), (IngestStatus*)fx.h_status, (u64)push_no);
+  hipLaunchKernelGGL(k_ing_publish, dim3(1), dim3(64), 0, s, fx.dev.st, desc, (const IngFrameInfo*)(fx.d_infos + vi), (IngestStatus*)fx.h_status, (u64)push_no,
+                     flt ? cut : (const FrameDesc*)nullptr, flt ? &(g->ff.d_infos + vi)->n_dropped : (u32*)nullptr);
   HIP_TRY(hipGetLastError());
   // ... device -> pinned result ring by DMA and the entry's sequence number behind it on the OUT stream: a 6 MB frame is 140 us
   // on the link, during which the frame stream already runs the next frame's kernels (on one stream the frames came out one DMA
@@ -55,7 +96,7 @@ int ingest_issue_frame(xm_ingest* g, uint64_t push_no, u64 n) {
   job.frame_no = f;
   job.slot = (int)(f % (uint64_t)fx.ring);
   job.o = o;
-  job.desc = desc;
+  job.desc = cut;
   job.t_push = la.push_t[vi];
   job.serial = fx.out_on_frame_stream || la.out_serial_now;
   if (int rc = ingest_out_hand_over(g, job)) return rc;
@@ -175,6 +216,7 @@ int ingest_process(xm_ingest* g, const IngestJob& j, size_t n, const u32* n_dev 
     la.entry_frame[vi] = 0;
   }
   la.push_t[vi] = j.t_push;
+  la.push_filter[vi] = (unsigned char)(la.filter | (la.intended ? 8 : 0));
   la.dev.desc = fx.d_descs + vi;
   la.dev.info = fx.d_infos + vi;
   la.dev.verdict = fx.d_verdicts + vi;
@@ -259,6 +301,10 @@ int ingest_run_job(xm_ingest* g, const IngestJob& j) {
     case JobKind::words: return ingest_issue_evt3(g, j);
     case JobKind::on_device: return ingest_process(g, j, j.n);
     case JobKind::flush: return ingest_finish(g);
+    case JobKind::set_filter:
+      g->la.filter = j.filter;
+      g->la.intended = j.intended;
+      break;
     case JobKind::stop:
     case JobKind::count_only: break;
   }

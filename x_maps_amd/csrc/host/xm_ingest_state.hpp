@@ -20,7 +20,8 @@
 // Every hand-over between them is a JobQueue (xm_queue.hpp): caller -> copy thread -> launch thread -> out thread.
 // The ingest stream may be `ahead` packets in front of the verdict the thread has handled last (0 on small rings: each packet's
 // verdict is awaited before the next is issued); k_ing_segment's room rule keeps that many packets' worth of the ring free, and
-// the ingest stream waits (on the device) for K1 of a frame before anything issued after it appends.  XM_INGEST_NO_LAUNCH_THREAD:
+// the ingest stream waits (on the device) for K1 of a frame -- for a frame under a frame event filter: for the filter stage's last
+// read of it -- before anything issued after it appends.  XM_INGEST_NO_LAUNCH_THREAD:
 // the caller does the work of all three threads inside xm_ingest_push* (and waits for each packet's verdict).
 
 namespace {
@@ -69,6 +70,7 @@ enum class JobKind : int {
   on_device,   // records that are in d_pkt[k] already (a chunk the caller decoded itself: xm_ingest_push_evt3 with n_events)
   flush,       // every verdict in, every frame's kernels launched and run
   count_only,  // nothing arrived (the copy side failed): the launch side only counts the job
+  set_filter,  // the frame event filter for the frames cut by the packets behind this job (xm_ingest_set_frame_filter)
 };
 inline bool carries_packet(JobKind k) { return k == JobKind::records || k == JobKind::words || k == JobKind::on_device; }
 inline bool copy_side_has_work(JobKind k) { return k == JobKind::records || k == JobKind::words; }
@@ -84,6 +86,7 @@ struct IngestJob {
   bool arrived = false;              // the copy side has issued the packet's H2D copy / the chunk's decoding and recorded copied_ev[k]
   uint64_t push_no = 0;              // number of the push (from 1; the caller's count = the launch side's `issued` + 1 when its turn comes)
   double t_push = 0.0;               // when the xm_ingest_push* call entered (steady clock)
+  int filter = 0, intended = 0;      // set_filter: FILTER_* (0: none) and its semantics
 };
 
 // launch side -> out thread: one cut frame.  Every cut frame is posted, so frame f is job f + 1 of the out queue.
@@ -166,6 +169,25 @@ struct IngestFixed {
   uint64_t clear_every = KEY_MAX_TAG - 16;  // ("XM_INGEST_CLEAR_EVERY": tests exercise the clear)
 };
 
+// Frame event filters (N3) on the frame stream (xmaps_ingest_filter.hpp).  Scratch, made ONCE by the caller's first
+// xm_ingest_set_frame_filter that selects a filter, before it posts the set_filter job: the launch side looks at it only for
+// packets behind that job (the job queue orders the two), and nothing of it changes afterwards.
+constexpr u64 ING_YT_MAX_CELLS = XM_INGEST_YT_MAX_CELLS;  // (include/xmaps.h)
+struct IngestFrameFilter {
+  bool ready = false;
+  bool yt_ok = false;                  // cam_h x (LUT's largest entry + 1) cells fit ING_YT_MAX_CELLS
+  bool yt_wrap = false;                // the LUT has a negative entry: FirstEventPerYT's columns may wrap at the frame's own width
+  int yt_w = 0;                        // the LUT's largest entry + 1
+  u32 cells_xy = 0, cells_yt = 0;
+  Event read_ev[8];                    // frame stream: the stage's last read of a cut frame has run (the ingest stream waits for it
+                                       // before appending more, as it waits for K1 of an unfiltered frame)
+  DevMem<u32> d_last, d_first, d_sums; // the cell maps (u32 per cell, zero between frames) and the per-block counts
+  DevMem<uint4> d_survivors;           // max(frame capacity, cells) records
+  DevMem<FrameDesc> d_descs;           // [ING_VRING] the entries' second descriptors
+  DevMem<FrameFilterInfo> d_infos;     // [ING_VRING]
+  DevMem<FrameFilterCtl> d_ctl;
+};
+
 // Caller side: the thread that calls xm_ingest_push* / poll* / backlog / flush (one at a time, by the API's contract).
 struct IngestCaller {
   uint64_t posted = 0;                 // pushes accepted so far
@@ -174,6 +196,7 @@ struct IngestCaller {
   PinnedMem<uint4> h_pkt[ING_STAGE];   // the entries' pinned twins (pageable pushes only; the other threads see them as IngestJob::host)
   uint64_t next_seq = 0;               // frames delivered through xm_ingest_poll so far
   xm_frame_pool* pool = nullptr;       // made by the first xm_ingest_poll_owned
+  uint64_t last_kept = 0;              // IngestStatus::n_used of the frame xm_ingest_poll* returned last (xm_ingest_last_frame_kept)
   // host time spent inside xm_ingest_push* (what the calling thread pays per packet), for xm_ingest_host_stats
   double push_host_s = 0.0, push_wait_s = 0.0;
   uint64_t push_calls = 0, stage_waits = 0;
@@ -189,6 +212,8 @@ struct IngestLaunch {
   uint64_t entry_frame[ING_VRING] = {};  // frame number + 1 that the packet which used the ring entry last cut (0: none): the entry is
                                        // read by that frame's K2 / publishing launches, so it is reused only once the frame is out
   double push_t[ING_VRING] = {};       // IngestJob::t_push of packet p, p % ING_VRING, until its verdict says whether it cut a frame
+  int filter = 0, intended = 0;        // the frame event filter selected by the last set_filter job (0: none) ...
+  unsigned char push_filter[ING_VRING] = {};  // ... and what packet p was pushed under: filter | intended << 3 (its frame's filter)
   IngestDev dev{};                     // = IngestFixed::dev with the CURRENT packet's desc / info / verdict / act: passed by value to its kernels
   int act_toggle = 0;                  // the set of cells the next non-empty packet takes (ingest_act_set)
   uint64_t act_fused_push = 0;         // the packet whose k_act_first went out with its predecessor's k_ing_count (k_ing_count_act)
@@ -243,6 +268,7 @@ struct IngestShared {
 
 struct xm_ingest {
   IngestFixed fx;
+  IngestFrameFilter ff;
   IngestCaller ca;
   IngestLaunch la;
   IngestOutSide out;

@@ -345,6 +345,19 @@ void launch_frame_kernel(xm_handle* h, const F& fr, int kmode, hipStream_t strea
   }
 }
 
+// ---- the ingest's frame-filter stage (xmaps_ingest_filter.hpp) ----------------------------------------------------------------
+// One cut frame through the selected filter: events -> cells -> survivors in raster order + the second descriptor.  n_bound: the
+// verdict's event count (the cut frame's length: the event passes' grids; the survivors' upper bound for K0 / K1 behind this).
+// The cell passes take one block per FF_BLOCK cells of the fixed map; the width pass goes out only where a column can wrap.
+unsigned ff_cell_blocks(const FrameFilterDev& f) { return grid_for(f.n_cells, FF_BLOCK); }
+void launch_frame_filter(const FrameFilterDev& f, u64 n_bound, hipStream_t stream) {
+  const unsigned ge = grid_for(n_bound < 1 ? 1 : n_bound, FF_THREADS), gc = ff_cell_blocks(f);
+  if (f.wrap) XM_LAUNCH(k_ff_width, dim3(ge), dim3(FF_THREADS), 0, stream, f);
+  XM_LAUNCH(k_ff_scatter, dim3(ge), dim3(FF_THREADS), 0, stream, f);
+  XM_LAUNCH(k_ff_count, dim3(gc), dim3(FF_BLOCK), 0, stream, f);
+  XM_LAUNCH(k_ff_emit, dim3(gc), dim3(FF_BLOCK), 0, stream, f, (u32)gc);
+}
+
 size_t cols_lds_bytes(const xm_handle* h, int W) {  // mirrors the carve-up at the top of scatter_cols_body
   const size_t lut_q = ((size_t)h->w_x * h->tb.cam_h + 3) / 4 + 1 + 64, xm_q = ((size_t)W * h->tb.xmap_h + 7) / 8 + 1 + 64,
                slot_q = ((size_t)W * h->tb.xmap_h + 3) / 4;

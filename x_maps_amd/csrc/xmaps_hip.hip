@@ -7,6 +7,7 @@
 #include "xmaps_k1own.hpp"
 #include "xmaps_k2pipe.hpp"
 #include "xmaps_ingest.hpp"
+#include "xmaps_ingest_filter.hpp"
 #include "xmaps_evt3.hpp"
 #include "xmaps_evt2.hpp"
 

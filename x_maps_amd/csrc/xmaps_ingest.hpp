@@ -48,6 +48,11 @@
 //     k_act_mark, or by k_ing_count's blocks one after the other) -- slow (~20 ms per million events) and exact.
 // The keep flags go to a byte per event (the ingest: k_ing_count computes them as it counts, k_ing_append reads them and clears the
 // cells the packet used; the filter alone: k_act_mark / k_act_update).
+//
+// Frame event filters (N3: the reference's key E, python/frame_event_filter.py): a stage of its own on the frame stream, between the
+// cut and K0, for the frames cut while one is selected (xm_ingest_set_frame_filter) -- xmaps_ingest_filter.hpp.  It reads the cut
+// frame's descriptor, writes a second one over the surviving events, and the frame kernels and k_ing_publish run on that; the ring
+// is released behind the stage's last read of it instead of behind K1.  With no filter selected nothing of it is launched.
 #pragma once
 #include "xmaps_kernels.hpp"
 
@@ -790,9 +795,13 @@ __global__ __launch_bounds__(ING_THREADS) void k_ing_segment(IngestDev d, Ingest
 
 // after the frame kernels (same stream, before the next frame's kernels touch the slot's counters): the frame's statistics into
 // its entry of the pinned status ring -- everything but the sequence number, which k_ing_publish_seq writes once the frame's
-// outputs have arrived in host memory
+// outputs have arrived in host memory.  A frame that went through the frame-filter stage (xmaps_ingest_filter.hpp): `desc` is its second
+// descriptor (the survivors: n_used, n_inliers and n_index_errors are theirs), `cut` the one k_ing_segment wrote (n_events stays the cut
+// frame's, like t_first / t_last) and `filter_dropped` the events the filter left out because their cell lies outside its map
+// (added to n_index_errors, and left zero for the entry's next frame); both NULL otherwise
 __global__ __launch_bounds__(64) void k_ing_publish(IngestState* st, const FrameDesc* __restrict__ desc, const IngFrameInfo* __restrict__ info,
-                                                    IngestStatus* ring_status, u64 push_seq) {
+                                                    IngestStatus* ring_status, u64 push_seq, const FrameDesc* __restrict__ cut,
+                                                    u32* filter_dropped) {
   if (!desc->valid) return;
   const SlotState* s = desc->st;
   const u32 tag = s->tag_a, parity = tag & 1;
@@ -814,7 +823,11 @@ __global__ __launch_bounds__(64) void k_ing_publish(IngestState* st, const Frame
   //  look at it fails -- the new one follows only when the frame's outputs have arrived, a whole copy later)
   __hip_atomic_store(&out->seq, (u64)0, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   __threadfence_system();
-  out->n_events = desc->n;
+  if (filter_dropped) {
+    oob += *filter_dropped;
+    *filter_dropped = 0u;
+  }
+  out->n_events = cut ? cut->n : desc->n;
   out->t_first = info->t_first;
   out->t_last = info->t_last;
   out->n_inliers = inl;

@@ -2727,20 +2727,12 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_filter_scan_sums(u32* __restrict
   if (threadIdx.x == 0) *total = carry;
 }
 
-__global__ __launch_bounds__(SCAN_BLOCK) void k_filter_emit(const uint4* __restrict__ aos, const u32* __restrict__ first_idx,
-                                                            const u32* __restrict__ last_idx, const u32* __restrict__ pos,
-                                                            const u32* __restrict__ sums, u32 n_cells, int map_w, int filter,
-                                                            int intended, uint4* __restrict__ out) {
-  const u32 i = blockIdx.x * SCAN_BLOCK + threadIdx.x;
-  if (i >= n_cells) return;
-  const u32 li = last_idx[i];
-  if (!li) return;
-  const u32 o = sums[blockIdx.x] + pos[i];
-  const uint4 last = aos[li - 1];
-  const uint4 first = intended ? aos[first_idx[i]] : last;
+// The record a filter hands on for one occupied cell (cell_x, y): `last` / `first` are the cell's events with the largest /
+// smallest index in the frame (first == last unless `intended`).  Shared by k_filter_emit and the ingest's frame-filter stage
+// (xmaps_ingest_filter.hpp): the int32 maps of the reference, p = True, FirstEventPerYT carries the surviving event's own x.
+__device__ inline uint4 filter_record(int filter, const uint4& first, const uint4& last, int cell_x, int y) {
   const int t_first = (int)first.z, t_last = (int)last.z;  // low 32 bits = the reference's int32 maps
-  int t32, x = (int)(i % (u32)map_w);
-  const int y = (int)(i / (u32)map_w);
+  int t32, x = cell_x;
   if (filter == FILTER_LAST_PER_XY) t32 = t_last;
   else if (filter == FILTER_MEAN_PER_XY) t32 = (int)((u32)t_last + (u32)t_first) >> 1;  // int32 wrap, floor division by 2
   else t32 = t_first;
@@ -2751,7 +2743,20 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_filter_emit(const uint4* __restr
   rec.y = 1u;  // p = True
   rec.z = (u32)((u64)t64 & 0xffffffffull);
   rec.w = (u32)((u64)t64 >> 32);
-  out[o] = rec;
+  return rec;
+}
+
+__global__ __launch_bounds__(SCAN_BLOCK) void k_filter_emit(const uint4* __restrict__ aos, const u32* __restrict__ first_idx,
+                                                            const u32* __restrict__ last_idx, const u32* __restrict__ pos,
+                                                            const u32* __restrict__ sums, u32 n_cells, int map_w, int filter,
+                                                            int intended, uint4* __restrict__ out) {
+  const u32 i = blockIdx.x * SCAN_BLOCK + threadIdx.x;
+  if (i >= n_cells) return;
+  const u32 li = last_idx[i];
+  if (!li) return;
+  const uint4 last = aos[li - 1];
+  const uint4 first = intended ? aos[first_idx[i]] : last;
+  out[sums[blockIdx.x] + pos[i]] = filter_record(filter, first, last, (int)(i % (u32)map_w), (int)(i / (u32)map_w));
 }
 
 // =====================================================================================================

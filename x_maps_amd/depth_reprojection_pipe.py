@@ -10,7 +10,8 @@ runs six NumPy/Numba/OpenCV stages; here it is one C-ABI call (xm_process_frame_
 and the frame handed to `frame_callback` is a fresh (H, W, 3) uint8 BGR array exactly as before.
 The packet side mirrors pipe:110-119: polarity filter -> activity-noise filter -> trigger finder -- by default (round 6) as
 kernels of the device ingest (RuntimeParams.device_ingest: process_events(packet) stages the packet and returns; the frames
-arrive through frame_callback as the consumer's own arrays), or on the host (the opt-out, and whenever a frame event filter or a
+arrive through frame_callback as the consumer's own arrays; with RuntimeParams.device_frame_filters a selected frame event filter
+is a stage of that ingest, too), or on the host (the opt-out, and whenever a frame event filter -- without that parameter -- or a
 caller-supplied activity filter is selected) with x_maps_amd.activity_filter.ActivityNoiseFilterAlgorithm (the same kernels behind one call);
 Metavision's own filter is a binary of the SDK, so the rule is this build's definition (oracle/ingest_oracle.py).
 Out of scope in this build: the timing watchdog.
@@ -110,6 +111,9 @@ class DepthReprojectionPipe:
         self._raw_dev, self._raw_host = {}, {}  # EVT 3.0 / 2.0 decoders (process_evt3_words / process_evt2_words), created on first use
         self._own_act_filter = None
         self._host_chain_active = False
+        self._device_frame_filters = bool(getattr(p, "device_frame_filters", False))
+        self._ingest_filter = (0, False)  # what the ingest has been told (DeviceIngest.set_frame_filter)
+        self._ingest_filter_refused = False
         self._ingest_failed = False  # an ingest call has raised: the error has reached the caller, close() does not ask again
         self._closed = False
         if self.activity_filter is None and getattr(p, "activity_filter", True):
@@ -146,7 +150,21 @@ class DepthReprojectionPipe:
         clean start on either side (a switch is a user pressing E: the frames around it are not comparable anyway)."""
         if self.ingest is None:
             return False
-        want_host = not isinstance(self.ev_filter_proc.selected_filter(), NoFilter)
+        sel = self.ev_filter_proc.selected_filter()
+        want_host = not isinstance(sel, NoFilter)
+        if self._device_frame_filters:
+            # RuntimeParams.device_frame_filters: the filter is a stage of the ingest -- the stream stays where it is, the ingest is
+            # told which filter the packets from now on are pushed under; only a filter it refuses takes the host chain
+            want = (int(getattr(sel, "filter_id", 0)), bool(getattr(sel, "intended_semantics", False))) if want_host else (0, False)
+            if want != self._ingest_filter:
+                try:
+                    self.ingest.set_frame_filter(*want)
+                    self._ingest_filter_refused = False
+                except ValueError as e:
+                    self._ingest_filter_refused = True
+                    self.stats_printer.log(f"{sel}: not available on the device ingest ({e}); the host chain takes the stream")
+                self._ingest_filter = want
+            want_host = want_host and self._ingest_filter_refused
         if want_host != self._host_chain_active:
             self._host_chain_active = want_host
             if want_host:
@@ -166,6 +184,8 @@ class DepthReprojectionPipe:
                 continue
             self.stats_printer.count("trig ✅")
             self.stats_printer.add_metric("frame len [ms]", (fr.t_last - fr.t_first) / 1000)
+            if self._device_frame_filters and fr.n_events:
+                self.stats_printer.add_metric("frame evs filtered out [%]", 100 - fr.n_kept / fr.n_events * 100)
             self.last_ingest_frame = fr
             # a fresh array copied out of the pinned result ring, or (RuntimeParams.ingest_frame_views) a view into it that stays
             # valid until ingest_result_ring - 1 further frames have been produced

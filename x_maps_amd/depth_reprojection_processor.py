@@ -65,6 +65,11 @@ class RuntimeParams:
     # (Since round 6 the default frames cost no host copy either -- xm_ingest_poll_owned --, so views only save the pool.)
     ingest_frame_views: bool = False
     ingest_result_ring: int = 16
+    # device ingest only: a frame event filter (key E) runs as a stage of the ingest, on the device between the cut and the frame
+    # kernels (DeviceIngest.set_frame_filter), instead of moving the stream to the host chain while it is selected.  Same frames;
+    # nothing is reset at the switch (the reference does not reset either).  Off by default: the pipe behaves as before.  A filter
+    # the ingest refuses (FirstEventPerYT on a rig whose cell map would be too large) still takes the host chain, and says so.
+    device_frame_filters: bool = False
     # process_evt3_words / process_evt2_words: events in front of a recording's first EVT_TIME_HIGH word are dropped (a reader that
     # waits for the first time base) instead of emitted at time base 0.  Which of the two Metavision's reader does is unpinned
     # (tools/pin_thirdparty.py decides); it matters for the first few words of a file only.

@@ -37,6 +37,7 @@ class IngestFrame:
     bgr: np.ndarray | None
     push_seq: int = 0  # number (from 1) of the push whose packet cut the frame
     push_to_publish_us: float = 0.0  # the library's own clock: that push call entered -> the frame's sequence number published
+    n_kept: int = 0  # events that survived the frame event filter (set_frame_filter); = n_events when none was selected
 
 
 class _OwnedBuffer:
@@ -96,6 +97,8 @@ class DeviceIngest:
         self._pool_ref = C.byref(self._pool)
         self._pool_seen = None          # ... of this ingest, once a frame has left with its buffers
         self._parked = []               # lossless: frames polled by the back-pressure, handed out by the next poll()
+        self._kept = C.c_uint64(0)
+        self._kept_ref = C.byref(self._kept)
 
     def close(self):
         if getattr(self, "_g", None) is not None and self._g.value:
@@ -131,6 +134,12 @@ class DeviceIngest:
             part = evs[a:a + self.max_packet]
             self._backpressure()
             N.check(self._lib.xm_ingest_push(self._g, C.c_void_p(part.ctypes.data), len(part)))
+
+    def set_frame_filter(self, filter_id: int, intended_semantics: bool = False):
+        """The frame event filter (x_maps_amd.frame_event_filter.XM_FILTER_*; 0: none) for the frames cut by the packets pushed from
+        now on: applied on the device between the cut and the frame kernels.  Ordered like a push -- nothing is flushed or reset.
+        ValueError: an unknown filter, or FirstEventPerYT on a rig whose (y, xr) cell map would be too large (nothing changes)."""
+        N.check(self._lib.xm_ingest_set_frame_filter(self._g, int(filter_id), int(bool(intended_semantics))))
 
     def push_pinned(self, evs: np.ndarray):
         """A packet that already lives in pinned host memory (XMapsEngine.host_empty): no staging copy."""
@@ -199,6 +208,10 @@ class DeviceIngest:
                 break
             depth = bgr = None
             lost = bool(fr.lost)
+            n_kept = 0
+            if not lost:
+                lib.xm_ingest_last_frame_kept(self._g, self._kept_ref)
+                n_kept = int(self._kept.value)
             if copy and fr.owned:
                 pool, rel = self._pool.value, lib.xm_frame_pool_release
                 self._pool_seen = pool
@@ -216,7 +229,7 @@ class DeviceIngest:
                 if copy and not lost and (depth is not None or bgr is not None) and not lib.xm_ingest_frame_valid(self._g, fr.seq):
                     lost, depth, bgr = True, None, None  # the ring was lapped while the frame was being copied out: a torn copy is no frame
             out.append(IngestFrame(int(fr.seq), int(fr.n_events), int(fr.t_first), int(fr.t_last), int(fr.n_inliers),
-                                   int(fr.n_index_errors), int(fr.live_after), int(fr.overflow), lost, depth, bgr, int(fr.push_seq), float(fr.push_to_publish_us)))
+                                   int(fr.n_index_errors), int(fr.live_after), int(fr.overflow), lost, depth, bgr, int(fr.push_seq), float(fr.push_to_publish_us), n_kept))
         return out
 
     def pool_stats(self) -> dict:
