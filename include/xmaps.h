@@ -658,6 +658,43 @@ int xm_evt2_create(xm_handle* h, size_t max_words, size_t max_events, xm_raw_dec
 int xm_evt2_decode(xm_raw_decoder* d, const uint32_t* words_host, size_t n_words, const void** events_dev, size_t* n_events);
 int xm_ingest_push_evt2(xm_ingest* g, xm_raw_decoder* d, const uint32_t* words_host, size_t n_words, int words_pinned, size_t* n_events);
 
+/* ---- time surfaces in, depth maps and point clouds out ("next" row N4) --------------------------------------------------
+ * The reference's offline evaluation (python/eval/compute_depth_x_maps.py:79-131) for a GROUP of camera time surfaces in one
+ * device call: each surface is [cam_height][cam_width] row-major, XM_T_FLOAT32 or XM_T_FLOAT64, 0 = no event.  Per surface:
+ * lo / hi over the non-zero entries; every pixel v -> v' = ((double)v - lo) / (hi - lo), negatives to 0 -- the surface is
+ * widened to float64 BEFORE it is normalised, whatever its dtype (the reference normalises float32 files in float32: the time
+ * stamps can differ in the last bit; an existing property of this build, pinned by golden G7); a pixel is an event iff v' > 0
+ * (the pixel holding lo lands on 0 and is dropped, as in the reference); (t_min, t_max) = extrema of the events' v'; then A1 ->
+ * A2 -> both inlier masks -> A5 per pixel and ONE plain store of depth[y][x] (0 where no inlier event).  A surface holds at most
+ * one event per pixel and in camera view an event's frame cell is its own pixel: no key frame, no atomics, no clear --
+ * xm_path_counts does not move.  Results equal the stage calls (xm_stage_rectify .. xm_stage_disparity_to_depth,
+ * xm_stage_rectify_f32, xm_stage_point_cloud) on the events of time_surface_to_events (x_maps_amd/eval_depth.py) bit for bit.
+ * None of the kernels waits for another block of its launch: every dependency between blocks is a kernel boundary.
+ * Camera-view handles only.  Defined, not errors: an all-zero surface and a surface with fewer than two distinct non-zero
+ * values (hi == lo) have no events -- an all-zero depth map, n_inliers 0, visible in the statistics.  Surfaces that hold NaN or
+ * +-inf are out of contract (results undefined); they neither fault nor write out of bounds. */
+typedef struct xm_surface_stats {
+  uint64_t n_nonzero;      /* pixels != 0                                                                 */
+  uint64_t n_events;       /* pixels with v' > 0                                                          */
+  uint64_t n_inliers;      /* events that passed both inlier masks = valid rows of the surface's cloud    */
+  uint64_t n_index_errors; /* as xm_frame_stats.n_index_errors                                            */
+  double lo, hi;           /* extrema of the non-zero entries (0, 0 for an all-zero surface)              */
+  double t_min, t_max;     /* extrema of the events' v' (0, 0 without events)                             */
+} xm_surface_stats;
+/* The float rectify maps ([cam_height][cam_width] row-major, CamProjMaps.disp_cam_map{x,y}_f32) and the 4x4 float64 Q
+ * (row-major; cast to float32 like the reference), copied to the device once.  Needed only when clouds are wanted. */
+int xm_surface_set_cloud_tables(xm_handle* h, const float* mapx_f32, const float* mapy_f32, const double* Q);
+/* depth_out: f32 [n_surfaces][cam_height][cam_width].  cloud_out (may be NULL): f32 [n_surfaces][cam_height * cam_width][3] -- a
+ * fixed stride per surface, of which the first n_inliers rows are valid: the inlier events in raster order (the order of
+ * xr_f[mask]) through construct_point_cloud (cam_proj_calibration.py:319-331; disparity 0 gives the reference's inf / nan).
+ * stats_out (may be NULL): xm_surface_stats[n_surfaces], host memory for XM_MEM_HOST, device memory for XM_MEM_DEVICE.
+ * mem == XM_MEM_HOST: synchronous (only the valid cloud rows are copied back).  XM_MEM_DEVICE: enqueued on the next slot's stream,
+ * xm_sync() waits; buffers stay valid and untouched until then.  Scratch is allocated by the first call and grown when a larger
+ * group arrives.  XM_ERR_INVALID: a handle that is not XM_VIEW_CAMERA, cloud_out without xm_surface_set_cloud_tables, a dtype
+ * other than the two float types, n_surfaces <= 0. */
+int xm_process_time_surfaces(xm_handle* h, const void* surfaces, int dtype, int n_surfaces, int mem, float* depth_out,
+                             float* cloud_out, xm_surface_stats* stats_out);
+
 /* ---- pinned host memory for XM_MEM_HOST_PINNED ------------------------------------------------------------- */
 int xm_host_alloc(xm_handle* h, size_t bytes, void** out);
 int xm_host_free(xm_handle* h, void* p);

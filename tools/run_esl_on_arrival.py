@@ -109,11 +109,14 @@ def write_ply(path, pts):
         f.write(pts.tobytes())
 
 
-def depth_from_scans(object_dir, eval_calib, proj_w, proj_h, num_scans=0, start_scan=0, point_clouds=False, device=0, tables=None):
-    """Part B, first half: compute_depth_x_maps.py:22-133.  -> report"""
+def depth_from_scans(object_dir, eval_calib, proj_w, proj_h, num_scans=0, start_scan=0, point_clouds=False, device=0, tables=None,
+                     surfaces_on_device=False, group=8):
+    """Part B, first half: compute_depth_x_maps.py:22-133.  -> report
+    surfaces_on_device: the scans go through the time-surface entry in groups of `group` (surfaces in, depth maps and clouds out
+    in one device call each) instead of one scan at a time through the stage sequence; same files."""
     from x_maps_amd import calibration as C
     from x_maps_amd.cam_proj_calibration import CamProjMaps
-    from x_maps_amd.eval_depth import compute_depth_from_time_surface
+    from x_maps_amd.eval_depth import compute_depth_from_time_surface, compute_depths_from_time_surfaces
     from x_maps_amd.x_maps_disparity import XMapsDisparity
     names = sorted(glob.glob(os.path.join(object_dir, "scans_np", "*.npy")))
     if not names:
@@ -132,15 +135,29 @@ def depth_from_scans(object_dir, eval_calib, proj_w, proj_h, num_scans=0, start_
     t_setup = time.perf_counter() - t0
     last = len(names) if not num_scans else min(len(names), start_scan + num_scans)
     per, skipped, filled = [], 0, []
-    try:
-        for i in range(start_scan, last):
-            surf = np.load(names[i])
+    def results():
+        if not surfaces_on_device:
+            for i in range(start_scan, last):
+                surf = np.load(names[i])
+                c0 = time.perf_counter()
+                depth, cloud = compute_depth_from_time_surface(maps, xd, surf, want_point_cloud=point_clouds)
+                yield i, depth, cloud, time.perf_counter() - c0
+            return
+        for g0 in range(start_scan, last, max(1, group)):
+            idx = range(g0, min(last, g0 + max(1, group)))
+            surfs = [np.load(names[i]) for i in idx]
             c0 = time.perf_counter()
-            depth, cloud = compute_depth_from_time_surface(maps, xd, surf, want_point_cloud=point_clouds)
+            out = compute_depths_from_time_surfaces(maps, surfs, want_point_cloud=point_clouds)
+            dt = (time.perf_counter() - c0) / len(idx)
+            for i, (depth, cloud) in zip(idx, out):
+                yield i, depth, cloud, dt
+
+    try:
+        for i, depth, cloud, seconds in results():
             if depth is None:  # "Skip camera npy file ... since it is empty" (:132)
                 skipped += 1
                 continue
-            per.append(time.perf_counter() - c0)
+            per.append(seconds)
             np.save(os.path.join(depth_dir, "scans" + str(i).zfill(3) + ".npy"), depth)
             filled.append(float((depth > 0).mean()))
             if point_clouds:
@@ -172,6 +189,9 @@ def main(argv=None):
     ap.add_argument("--num-scans", type=int, default=0, help="part B: scans to process (0 = all)")
     ap.add_argument("--start-scan", type=int, default=0)
     ap.add_argument("--point-clouds", action="store_true")
+    ap.add_argument("--surfaces-on-device", action="store_true",
+                    help="part B: the scans go through the time-surface entry in groups (one device call per group)")
+    ap.add_argument("--surface-group", type=int, default=8, help="scans per group with --surfaces-on-device")
     ap.add_argument("--min-depth", type=float, default=20)
     ap.add_argument("--max-depth", type=float, default=500, help="eval/x-map-eval.sh:72 passes 500 (the table script's own default is 120)")
     ap.add_argument("--save-frames", type=int, default=0, help="part A: keep the first N BGR frames as frame_NNN.npy beside --out")
@@ -199,7 +219,8 @@ def main(argv=None):
         if not a.eval_calib:
             ap.error("--scans needs --eval-calib (the ESL dataset's calib.yaml)")
         report["depth_from_scans"] = depth_from_scans(a.scans, a.eval_calib, a.projector_width, a.projector_height, a.num_scans,
-                                                      a.start_scan, a.point_clouds, a.device)
+                                                      a.start_scan, a.point_clouds, a.device,
+                                                      surfaces_on_device=a.surfaces_on_device, group=a.surface_group)
         if "error" not in report["depth_from_scans"]:
             from x_maps_amd.eval_table import x_maps_table_row
             row = x_maps_table_row(a.scans, a.min_depth, a.max_depth, device=a.device)

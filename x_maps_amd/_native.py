@@ -130,6 +130,11 @@ class xm_eval_result(C.Structure):
                 ("perc_10", C.c_double), ("margin", C.c_double), ("n_valid", C.c_uint64), ("n_gt_zero", C.c_uint64)]
 
 
+class xm_surface_stats(C.Structure):
+    _fields_ = [("n_nonzero", C.c_uint64), ("n_events", C.c_uint64), ("n_inliers", C.c_uint64), ("n_index_errors", C.c_uint64),
+                ("lo", C.c_double), ("hi", C.c_double), ("t_min", C.c_double), ("t_max", C.c_double)]
+
+
 # every symbol include/xmaps.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -231,6 +236,8 @@ SYMBOLS = {
     "xm_ingest_push_evt2": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_int, C.POINTER(C.c_size_t)]),
     "xm_eval_stats": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.POINTER(xm_eval_result)]),
     "xm_build_x_map": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "xm_surface_set_cloud_tables": (C.c_int, [_P, _P, _P, _P]),
+    "xm_process_time_surfaces": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "xm_stream": (_P, [_P, C.c_int]),
     "xm_host_alloc": (C.c_int, [_P, C.c_size_t, C.POINTER(_P)]),
     "xm_host_free": (C.c_int, [_P, _P]),

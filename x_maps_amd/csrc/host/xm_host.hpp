@@ -105,6 +105,18 @@ struct Slot {
   DevBuf ev_x, ev_y, ev_t, ev_p, ev_aos, out_depth, out_bgr, dbg[5];
 };
 
+// The time-surface entry (xm_api_surface.hpp): cloud tables + grow-only scratch, allocated by the first call.  One set per handle:
+// a call's launches wait for the previous call's (`done`, recorded on the stream that one ran on) before they touch it.
+struct SurfaceScratch {
+  Event done;
+  hipStream_t last_stream = nullptr;  // view: the slot stream of the most recent call (nullptr: none in flight since xm_sync)
+  DevMem<float> mapx, mapy;           // float rectify maps [cam_h][cam_w] (xm_surface_set_cloud_tables)
+  Mat4f q{};
+  bool has_cloud_tables = false;
+  DevBuf part1, part2, seg_cnt, seg_off, wave_oob, code, stats;  // device-side intermediates of a group
+  DevBuf in, depth, cloud;                                         // staging of XM_MEM_HOST calls
+};
+
 // ---- launch workers -------------------------------------------------------------------------------------------
 // A kernel launch costs the calling thread ~2.7 us in the HIP runtime, three launches per frame; with the GPU at ~12 us per
 // frame that single thread is what bounds the asynchronous device-pointer path (tools/only_kernel_eager.sh: 3.2 us per call
@@ -182,6 +194,7 @@ struct xm_handle {
   int out_w = 0, out_h = 0;
   DevMem<u64> stage_frame;  // lazily allocated scratch for the stage API (max(rect, cam) cells)
   size_t stage_cells = 0;
+  SurfaceScratch surf;      // xm_process_time_surfaces
   // K1 tiling: LDS windows (time columns / camera columns) and the dynamic LDS they need; 0 = direct kernel
   int w_ts = 0, w_x = 0;
   size_t k1_lds = 0;

@@ -10,6 +10,7 @@
 #include "xmaps_ingest_filter.hpp"
 #include "xmaps_evt3.hpp"
 #include "xmaps_evt2.hpp"
+#include "xmaps_surface.hpp"
 
 #include <hip/hip_ext.h>
 
@@ -62,3 +63,4 @@ using namespace xm;
 #include "host/xm_ingest_create.hpp"  // ... the stages of xm_ingest_create
 #include "host/xm_api_ingest.hpp"   // ... its C entry points (records, and EVT words through the decoder)
 #include "host/xm_api_misc.hpp"     // X-map builder, evaluation metrics, memory helpers
+#include "host/xm_api_surface.hpp"  // a group of camera time surfaces -> depth maps + point clouds (the evaluation caller's entry)

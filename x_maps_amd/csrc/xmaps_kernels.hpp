@@ -2371,13 +2371,9 @@ __global__ __launch_bounds__(BLOCK) void k_stage_rectify_f32(const uint16_t* __r
 struct Mat4f {
   float m[16];
 };
-__global__ __launch_bounds__(BLOCK) void k_point_cloud(const float* __restrict__ xpr, const float* __restrict__ ypr,
-                                                       const float* __restrict__ disp, u64 n, Mat4f Q,
-                                                       float* __restrict__ cloud) {
-  const u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x;
-  if (i >= n) return;
-  const float d = disp[i];
-  const float p0 = xpr[i] + d, p1 = ypr[i], p2 = -d;
+// one point (shared with the time-surface path, xmaps_surface.hpp: the same float32 operations in the same order)
+__device__ inline void point_from_disparity(const Mat4f& Q, float xpr, float ypr, float d, float (&out)[3]) {
+  const float p0 = xpr + d, p1 = ypr, p2 = -d;
   float r[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
@@ -2387,9 +2383,20 @@ __global__ __launch_bounds__(BLOCK) void k_point_cloud(const float* __restrict__
     acc = acc + Q.m[4 * k + 3];
     r[k] = acc;
   }
-  cloud[3 * i + 0] = r[0] / r[3];
-  cloud[3 * i + 1] = -(r[1] / r[3]);
-  cloud[3 * i + 2] = -(r[2] / r[3]);
+  out[0] = r[0] / r[3];
+  out[1] = -(r[1] / r[3]);
+  out[2] = -(r[2] / r[3]);
+}
+__global__ __launch_bounds__(BLOCK) void k_point_cloud(const float* __restrict__ xpr, const float* __restrict__ ypr,
+                                                       const float* __restrict__ disp, u64 n, Mat4f Q,
+                                                       float* __restrict__ cloud) {
+  const u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= n) return;
+  float p[3];
+  point_from_disparity(Q, xpr[i], ypr[i], disp[i], p);
+  cloud[3 * i + 0] = p[0];
+  cloud[3 * i + 1] = p[1];
+  cloud[3 * i + 2] = p[2];
 }
 
 // A2 on caller-supplied rectified coordinates

@@ -33,6 +33,24 @@ class FrameStats:
                           float(s.t_min), float(s.t_max), tuple(float(v) for v in s.gpu_ms), int(s.n_unsorted))
 
 
+@dataclass
+class SurfaceStats:
+    """xm_surface_stats of one time surface (process_time_surfaces)."""
+    n_nonzero: int = 0
+    n_events: int = 0
+    n_inliers: int = 0
+    n_index_errors: int = 0
+    lo: float = 0.0
+    hi: float = 0.0
+    t_min: float = 0.0
+    t_max: float = 0.0
+
+    @staticmethod
+    def from_c(s: N.xm_surface_stats) -> "SurfaceStats":
+        return SurfaceStats(int(s.n_nonzero), int(s.n_events), int(s.n_inliers), int(s.n_index_errors), float(s.lo), float(s.hi),
+                            float(s.t_min), float(s.t_max))
+
+
 def _ptr(a) -> C.c_void_p:
     if a is None:
         return C.c_void_p(None)
@@ -131,6 +149,9 @@ class XMapsEngine:
         # packed-key frame as laid out in HBM: camera view row-major [y][x]; projector view column-major [col][row]
         self.key_shape = (cam_h, cam_w) if camera_perspective else (self.rect_w, self.rect_h)
         self.t_px_scale = xmap.shape[1] - 1
+        # process_time_surfaces(want_cloud=True): the float rectify maps and Q go to the device with the first such call
+        self._has_cloud_tables = False
+        self._cloud_tables = tuple(tables.get(k) for k in ("cam_mapx_f32", "cam_mapy_f32", "Q"))
 
     # ---- lifetime ------------------------------------------------------------------------------
     def close(self):
@@ -439,6 +460,56 @@ class XMapsEngine:
         src = np.ascontiguousarray(disp, dtype=np.float32)
         out = np.empty(src.shape + (3,), np.uint8)
         N.check(self._lib.xm_stage_colorize_depth_from_disp(self._h, _ptr(src), src.shape[0], src.shape[1], _ptr(out)))
+        return out
+
+    # ---- time surfaces in, depth maps + point clouds out (the offline evaluation caller) --------------------
+    def set_cloud_tables(self, mapx_f32, mapy_f32, Q):
+        """The float rectify maps [cam_h][cam_w] and the 4x4 Q the point clouds of process_time_surfaces need."""
+        mx = np.ascontiguousarray(mapx_f32, dtype=np.float32)
+        my = np.ascontiguousarray(mapy_f32, dtype=np.float32)
+        Q = np.ascontiguousarray(Q, dtype=np.float64)
+        if mx.shape != (self.cam_h, self.cam_w) or my.shape != mx.shape:
+            raise ValueError(f"float rectify maps must be ({self.cam_h}, {self.cam_w})")
+        if Q.shape != (4, 4):
+            raise ValueError("Q must be 4x4")
+        N.check(self._lib.xm_surface_set_cloud_tables(self._h, _ptr(mx), _ptr(my), _ptr(Q)))
+        self._has_cloud_tables = True
+
+    def process_time_surfaces(self, surfaces, want_cloud=False):
+        """A group of camera time surfaces (a list of [cam_h][cam_w] arrays or one 3-D array; float32 or float64, 0 = no
+        event) in ONE device call -> [(depth f32 [cam_h][cam_w], cloud f32 [n_inliers][3] | None, SurfaceStats)] per surface.
+        A list of mixed dtypes is cast to float64 (exact).  Camera-view engines only.  Defined: an all-zero surface and one
+        with fewer than two distinct non-zero values have no events (zero depth, empty cloud)."""
+        if isinstance(surfaces, np.ndarray):
+            grp = surfaces if surfaces.ndim == 3 else surfaces[None]
+        else:
+            arrs = [np.asarray(a) for a in surfaces]
+            if not arrs:
+                raise ValueError("no surfaces")
+            dt = np.float32 if all(a.dtype == np.float32 for a in arrs) else np.float64
+            for a in arrs:
+                if a.shape != (self.cam_h, self.cam_w):
+                    raise ValueError(f"a time surface must be ({self.cam_h}, {self.cam_w}), got {a.shape}")
+            grp = np.stack([a.astype(dt, copy=False) for a in arrs])
+        if grp.ndim != 3 or grp.shape[1:] != (self.cam_h, self.cam_w) or grp.shape[0] == 0:
+            raise ValueError(f"time surfaces must be (n, {self.cam_h}, {self.cam_w}), got {grp.shape}")
+        if grp.dtype not in (np.float32, np.float64):
+            grp = grp.astype(np.float64)
+        grp = np.ascontiguousarray(grp)
+        if want_cloud and not self._has_cloud_tables:
+            if any(t is None for t in self._cloud_tables):
+                raise ValueError("want_cloud needs the tables cam_mapx_f32, cam_mapy_f32 and Q (or set_cloud_tables)")
+            self.set_cloud_tables(*self._cloud_tables)
+        n, px = grp.shape[0], self.cam_h * self.cam_w
+        depth = np.empty((n, self.cam_h, self.cam_w), np.float32)
+        cloud = np.empty((n, px, 3), np.float32) if want_cloud else None
+        st = (N.xm_surface_stats * n)()
+        N.check(self._lib.xm_process_time_surfaces(self._h, _ptr(grp), _T_DTYPES[grp.dtype], n, N.XM_MEM_HOST, _ptr(depth),
+                                                   _ptr(cloud), C.cast(st, C.c_void_p)))
+        out = []
+        for i in range(n):
+            k = int(st[i].n_inliers)
+            out.append((depth[i], cloud[i, :k].copy() if want_cloud else None, SurfaceStats.from_c(st[i])))
         return out
 
     # ---- N3: per-frame de-duplication filters ------------------------------------------------------------

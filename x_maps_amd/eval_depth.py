@@ -6,7 +6,15 @@ compute_disp_map_camera_view, disparity_to_depth_rectified -- and, for the point
 construct_point_cloud.  Raster order means the timestamps are NOT sorted: this goes through the general
 (min/max-reduction) path of the engine, never the time-sorted one.
 
-File handling, the MC3D baseline and the metrics of eval/ are out of scope.
+Two routes: compute_depth_from_time_surface, the reference's stage sequence (or the live path's fused kernels) for one
+surface, with the front half -- normalising, argwhere, the x / y / t columns -- on the host; and
+compute_depths_from_time_surfaces, a GROUP of surfaces in one device call (XMapsEngine.process_time_surfaces: surfaces in,
+depth maps and point clouds out, nothing on the host in between, no atomics; camera view).  Both widen the surface to float64
+before normalising it (the reference normalises a float32 file in float32: the last bit of t can differ; golden G7 pins
+this build's choice), and both give the same depth maps and clouds bit for bit.
+
+Out of scope: file handling, the ESL and MC3D baselines and the ground truth they produce, a projector-view
+surface path.  (The metrics of eval/ are in eval_metrics.py.)
 """
 from __future__ import annotations
 
@@ -36,6 +44,13 @@ def compute_depth_from_time_surface(cam_proj_maps: CamProjMaps, x_maps_disp: XMa
     """-> (depth [cam_h][cam_w] float32, point_cloud [k][3] float32 or None); None, None for an empty surface.
     eval/compute_depth_x_maps.py:99-120.  fused=True runs the three fused kernels of the live path instead of the
     reference's stage sequence (needs cam_proj_maps built with camera_perspective=True); the depth map is identical."""
+    if fused and want_point_cloud:  # depth AND cloud on the device: the group entry with a group of one
+        if not cam_proj_maps.camera_perspective:
+            raise ValueError("fused evaluation needs CamProjMaps(camera_perspective=True)")
+        if not np.any(np.asarray(cam_image) != 0):
+            return None, None
+        depth, cloud, _ = cam_proj_maps.engine.process_time_surfaces([cam_image], want_cloud=True)[0]
+        return depth, cloud
     events = time_surface_to_events(cam_image)
     if events is None:
         return None, None
@@ -54,3 +69,14 @@ def compute_depth_from_time_surface(cam_proj_maps: CamProjMaps, x_maps_disp: XMa
         xr_f, yr_f = cam_proj_maps.rectify_cam_coords_f32(events)
         cloud = cam_proj_maps.construct_point_cloud(xr_f[mask], yr_f[mask], disp)
     return depth, cloud
+
+
+def compute_depths_from_time_surfaces(cam_proj_maps: CamProjMaps, cam_images, want_point_cloud: bool = False):
+    """A group of time surfaces (list of [cam_h][cam_w] arrays or a 3-D array) in one device call ->
+    [(depth, point_cloud or None)] per surface, each as compute_depth_from_time_surface returns it: (None, None) for an
+    all-zero surface.  Needs cam_proj_maps built with camera_perspective=True (and, for clouds, tables with cam_mapx_f32,
+    cam_mapy_f32 and Q)."""
+    if not cam_proj_maps.camera_perspective:
+        raise ValueError("the time-surface entry needs CamProjMaps(camera_perspective=True)")
+    res = cam_proj_maps.engine.process_time_surfaces(cam_images, want_cloud=want_point_cloud)
+    return [(None, None) if st.n_nonzero == 0 else (depth, cloud) for depth, cloud, st in res]
