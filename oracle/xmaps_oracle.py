@@ -326,6 +326,48 @@ def time_surface_to_events(cam_image):
     return yx[:, 1], yx[:, 0], img[img > 0]
 
 
+def process_time_surface(tables, surf):
+    """One camera time surface -> what xm_process_time_surfaces returns for it, from the functions above in the order of
+    python/eval/compute_depth_x_maps.py:83-131: time_surface_to_events -> A1 -> A2 -> camera-view frame -> A5, and the rows
+    of the point cloud's input, xr_f[mask] (raster order of the camera pixels).
+
+    Returns dict(depth f32 [cam_h][cam_w];
+                 x, y, disp (int16), xr_f32, yr_f32: one entry per inlier, raster order (the float rows None without the
+                 tables cam_mapx_f32 / cam_mapy_f32);
+                 event_x, event_y, event_t, mask: the event list the rows were taken from;
+                 stats: the eight fields of xm_surface_stats).
+    The entry's defined results for a surface without events (the reference's caller divides by zero or reduces an empty
+    array there): all-zero -> zero depth, no rows, lo = hi = 0; one distinct non-zero value -> zero depth, no rows,
+    lo == hi == that value.  t_min = t_max = 0 in both.  n_index_errors is always 0: a pixel of the surface is inside the LUT."""
+    mapx, mapy, xmap = tables["cam_mapx_i16"], tables["cam_mapy_i16"], tables["proj_x_map"]
+    cam_h, cam_w = mapx.shape
+    img = np.asarray(surf)
+    if img.shape != (cam_h, cam_w):
+        raise ValueError(f"a time surface must be {(cam_h, cam_w)}, got {img.shape}")
+    nz = img[img != 0].astype(np.float64)
+    lo, hi = (float(nz.min()), float(nz.max())) if nz.size else (0.0, 0.0)
+    none_i, none_f = np.zeros(0, np.int64), np.zeros(0, np.float32)
+    has_f32 = tables.get("cam_mapx_f32") is not None and tables.get("cam_mapy_f32") is not None
+    out = {"depth": np.zeros((cam_h, cam_w), np.float32), "x": none_i, "y": none_i, "disp": np.zeros(0, np.int16),
+           "xr_f32": none_f if has_f32 else None, "yr_f32": none_f if has_f32 else None,
+           "event_x": none_i, "event_y": none_i, "event_t": np.zeros(0, np.float64), "mask": np.zeros(0, bool),
+           "stats": {"n_nonzero": int(nz.size), "n_events": 0, "n_inliers": 0, "n_index_errors": 0,
+                     "lo": lo, "hi": hi, "t_min": 0.0, "t_max": 0.0}}
+    if nz.size == 0 or hi == lo:
+        return out
+    x, y, t = time_surface_to_events(img)
+    xr, yr = rectify_cam_coords_i16(mapx, mapy, x, y)
+    disp, mask = compute_disparity(xr, yr, t, xmap, tables.get("t_px_scale", xmap.shape[1] - 1), tables.get("x_offset", X_OFFSET))
+    frame = disp_map_camera_view(x, y, mask, disp, cam_h, cam_w)
+    out.update(depth=disparity_to_depth_rectified(frame, tables["p03"]), x=x[mask], y=y[mask], disp=disp,
+               event_x=x, event_y=y, event_t=t, mask=mask)
+    if has_f32:
+        xf, yf = rectify_cam_coords_f32(tables["cam_mapx_f32"], tables["cam_mapy_f32"], x, y)
+        out.update(xr_f32=xf[mask], yr_f32=yf[mask])
+    out["stats"].update(n_events=int(len(t)), n_inliers=int(mask.sum()), t_min=float(t.min()), t_max=float(t.max()))
+    return out
+
+
 def generate_linear_projector_time_map(proj_w, proj_h, scan_upwards):
     """Ideal raster time map: x is the slow axis, y the fast one.  python/proj_time_map.py:6-19."""
     ys, xs = np.mgrid[0:proj_h, 0:proj_w]

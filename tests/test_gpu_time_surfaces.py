@@ -9,27 +9,17 @@ import numpy as np
 import pytest
 
 import xmaps_oracle as O
+from time_surface_cases import with_cloud_tables as _with_cloud_tables
 from x_maps_amd.synthetic import C_TINY, RigConfig, make_tables
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-Q_G7 = np.array([[1, 0, 0, -80.5], [0, 1, 0, -60.25], [0, 0, 0, 540.0], [0, 0, -7.75, 0]], dtype=np.float64)
 
 
 def _g7_tables(g):
     return {"cam_mapx_i16": g["mapx"], "cam_mapy_i16": g["mapy"], "proj_x_map": g["xmap"],
             "rect_w": int(g["rect_w"]), "rect_h": int(g["rect_h"]), "p03": float(g["p03"]), "z_near": 0.1, "z_far": 1.0,
             "cam_mapx_f32": g["mapx_f32"], "cam_mapy_f32": g["mapy_f32"], "Q": g["Q"]}
-
-
-def _with_cloud_tables(tb, seed):
-    """float rectify maps as tests/golden/make_golden.py builds them (the i16 LUT + uniform(-0.45, 0.45)) and a Q like G7's"""
-    rng = np.random.default_rng(seed)
-    tb = dict(tb)
-    tb["cam_mapx_f32"] = (tb["cam_mapx_i16"] + rng.uniform(-0.45, 0.45, tb["cam_mapx_i16"].shape)).astype(np.float32)
-    tb["cam_mapy_f32"] = (tb["cam_mapy_i16"] + rng.uniform(-0.45, 0.45, tb["cam_mapy_i16"].shape)).astype(np.float32)
-    tb["Q"] = Q_G7.copy()
-    return tb
 
 
 def _odd_tables():
