@@ -1,5 +1,5 @@
 """-m gpu: the compact key frame of the CAMERA view -- (event index + 1) << 12 | disparity, one u32 per camera pixel, no tag
-(x_maps_amd/csrc/xmaps_kernels.hpp: KEY32_DISP_BITS).  The order field is the event itself, so last-writer-wins holds for every
+(x_maps_amd/csrc/xmaps_common.hpp: KEY32_DISP_BITS).  The order field is the event itself, so last-writer-wins holds for every
 pair of writers of a pixel whatever tile they are in and wherever they sit in the stream (strays included); stale pixels cannot
 show because the frame kernel zeroes every pixel it reads.  Each is exercised here against the CPU oracle, bit for bit."""
 import numpy as np

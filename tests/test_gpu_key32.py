@@ -1,5 +1,5 @@
 """-m gpu: the compact (32-bit) key frame of the verified-sorted projector-view path -- tag4 | tile | disparity, order field
-= tile index (x_maps_amd/csrc/xmaps_kernels.hpp: key32_tag).  Exactness rests on three mechanisms, each exercised here:
+= tile index (x_maps_amd/csrc/xmaps_common.hpp: key32_tag).  Exactness rests on three mechanisms, each exercised here:
 every event of a tile is resolved in LDS (x-noise events fetch their LUT entry from global memory and join the slots),
 events outside a tile's LDS time window mark the frame as failed (automatic redo on the 64-bit path), and the 4-bit tag is
 kept unambiguous by clearing the frame at least every 15 frames of a slot."""

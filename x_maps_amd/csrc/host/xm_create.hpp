@@ -192,7 +192,7 @@ int classify_rig(xm_handle* h, const CreateOpts& o) {
     xp_min = std::min<int>(xp_min, cfg->proj_x_map[i]);
     xp_max = std::max<int>(xp_max, cfg->proj_x_map[i]);
   }
-  {  // does the rig qualify for the compact (32-bit) key frame?  (see key32_tag in xmaps_kernels.hpp)
+  {  // does the rig qualify for the compact (32-bit) key frame?  (see key32_tag in xmaps_common.hpp)
     // (largest disparity: the projector's largest x, never taken below 0, against the LUT's smallest)
     const long max_disp = std::max<long>((long)std::max(xp_max, 0) - xr_min - cfg->x_offset, (long)0 - xr_min - cfg->x_offset);
     // (camera view: (event index + 1) << 12 | disparity on the camera frame -- only the disparity range matters)

@@ -318,7 +318,6 @@ inline unsigned grid_for(u64 items, unsigned per_block) {
 }
 
 inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
-inline long long rec_t_host(const uint4& r) { return (long long)(((u64)r.w << 32) | r.z); }
 
 size_t t_size(int t_dtype) { return t_dtype == XM_T_FLOAT32 ? 4 : 8; }
 

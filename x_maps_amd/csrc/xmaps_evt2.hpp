@@ -13,7 +13,8 @@
 // scan in one block seeded with the previous chunk's state (which also leaves the next state and the chunk's event count),
 // every block re-scans its words from its prefix and writes its records in word order.
 #pragma once
-#include "xmaps_evt3.hpp"
+#include "xmaps_common.hpp"
+#include "xmaps_evt3.hpp"  // Evt3Scan (the decoders share the aggregates' buffer), evt_dropped
 
 namespace xm {
 

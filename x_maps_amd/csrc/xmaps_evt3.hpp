@@ -17,7 +17,7 @@
 // left (which also writes the next state and the chunk's event count) -> every block re-scans its words from its prefix and
 // writes the records in word order, a vector word's events in ascending column order.
 #pragma once
-#include "xmaps_kernels.hpp"
+#include "xmaps_common.hpp"
 
 namespace xm {
 

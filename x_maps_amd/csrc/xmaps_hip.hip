@@ -2,15 +2,16 @@
 // Written for MI355X (gfx950) only: build with
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -shared xmaps_hip.hip -o libxmaps_hip.so
 // -ffp-contract=off keeps the time normalisation (divide, multiply, rint) unfused = bit-exact with NumPy.
-#include "xmaps_kernels.hpp"
-#include "xmaps_k1cols.hpp"
-#include "xmaps_k1own.hpp"
-#include "xmaps_k2pipe.hpp"
-#include "xmaps_ingest.hpp"
-#include "xmaps_ingest_filter.hpp"
-#include "xmaps_evt3.hpp"
-#include "xmaps_evt2.hpp"
-#include "xmaps_surface.hpp"
+// The device side, one header per kernel (each includes what it needs):
+#include "xmaps_kernels.hpp"        // common ABI, K0, K1 direct / event tiles, K2, stage, X-map builder, filters, eval, slots
+#include "xmaps_k1cols.hpp"         // K1 on column tiles + the boundary pass
+#include "xmaps_k1own.hpp"          // K1 on owner tiles
+#include "xmaps_k2pipe.hpp"         // pipelined K2 on the u16 frame
+#include "xmaps_ingest.hpp"         // device-side ingest: activity filter, frame segmentation
+#include "xmaps_ingest_filter.hpp"  // ... the frame event filters as a stage of it
+#include "xmaps_evt3.hpp"           // EVT 3.0 decoder
+#include "xmaps_evt2.hpp"           // EVT 2.0 decoder
+#include "xmaps_surface.hpp"        // time surfaces -> depth maps + point clouds
 
 #include <hip/hip_ext.h>
 

@@ -54,7 +54,7 @@
 // frame's descriptor, writes a second one over the surviving events, and the frame kernels and k_ing_publish run on that; the ring
 // is released behind the stage's last read of it instead of behind K1.  With no filter selected nothing of it is launched.
 #pragma once
-#include "xmaps_kernels.hpp"
+#include "xmaps_common.hpp"
 
 namespace xm {
 
@@ -159,7 +159,6 @@ constexpr u32 ING_F_SEGMENT = 2u;   // k_ing_segment: run the trigger finder (el
 
 constexpr long long ING_NO_TS = (long long)0x8000000000000000ull;
 
-__device__ inline long long rec_t(const uint4& r) { return (long long)(((u64)r.w << 32) | r.z); }
 // (a count on the device: n is the room of the packet's slot -- a chunk that decoded to more has been truncated to that)
 __device__ inline u32 ing_packet_n(const IngestPush& p) {
   if (!p.n_dev) return p.n;

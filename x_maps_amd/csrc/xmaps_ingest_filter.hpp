@@ -4,7 +4,7 @@
 // What the reference does per cut frame while a filter is selected (python/frame_event_filter.py:19-151, applied at
 // python/depth_reprojection_pipe.py:130-139): one output event per cell that fired -- cell = camera pixel (y, x) for the three XY
 // filters, (y, rectified x) for FirstEventPerYT --, handed on in raster order of the cells.  The arithmetic of the record is
-// filter_record (xmaps_kernels.hpp), shared with the synchronous entry point xm_frame_event_filter.
+// filter_record (xmaps_filters.hpp), shared with the synchronous entry point xm_frame_event_filter.
 // Here the cut frame is the FrameDesc k_ing_segment wrote (a pointer into the event ring + a count); the stage writes a SECOND
 // descriptor for the same verdict entry whose events are the survivors in a scratch buffer, and K0 -> K1 -> K2 -> k_ing_publish run on
 // that one unchanged:
@@ -28,6 +28,8 @@
 // the reference's per-frame `max + 1` extents, only the wrap does.
 // k_ff_emit is the last reader of the cut frame in the ring: the ingest stream waits for IT (not for K1) before appending more.
 #pragma once
+#include "xmaps_common.hpp"
+#include "xmaps_filters.hpp"  // filter_record, FILTER_*
 #include "xmaps_ingest.hpp"
 
 namespace xm {

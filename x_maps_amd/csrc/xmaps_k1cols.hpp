@@ -1,5 +1,5 @@
 // xmaps_k1cols.hpp -- K1 "column tiles": the fused per-event kernel of the verified-sorted projector-view path without
-// atomics and without a key.  (gfx950 / MI355X; included by xmaps_hip.hip after xmaps_kernels.hpp)
+// atomics and without a key.  (gfx950 / MI355X; needs xmaps_common.hpp only)
 //
 // What the tiled K1 (k_scatter_tiled) pays for at full occupancy is the chip's L2 atomic request rate: its tiles are
 // runs of 4096 consecutive EVENTS, so a time column of the X-map is flushed by ~1.4 tiles and the frame cell of a
@@ -28,7 +28,7 @@
 //     2640 slots are cleared / scanned per 3125 events instead of 6600 per 4096.
 // Algorithmic bytes are those of K1: 24 B/event.
 #pragma once
-#include "xmaps_kernels.hpp"
+#include "xmaps_common.hpp"
 
 namespace xm {
 
@@ -105,7 +105,7 @@ template <bool AOS>
 __device__ __forceinline__ long long cols_t_at(gp_i64 ts, gp_u4 aos, int i) {
   if constexpr (AOS) {
     const uint4 r = aos[i];
-    return (long long)(((u64)r.w << 32) | r.z);
+    return rec_t(r);
   } else {
     return ts[i];
   }
@@ -114,7 +114,7 @@ __device__ __forceinline__ long long cols_t_at(gp_i64 ts, gp_u4 aos, int i) {
 // K1 never converts a time stamp: for int64 stamps the X-map column is a step function of a = t - tmin, so the frame's
 // columns are described exactly by THRESHOLDS  thr[c] = the smallest a in [0, span + 1] with column(tmin + a) >= c
 // (span = tmax - tmin; span + 1 = "no such a"), computed here with the very conversion that is bit-exact with NumPy
-// (TimeNorm, xmaps_kernels.hpp).  Then  column(t) = #{c' >= 1 : thr[c'] <= a}  and, for a tile of columns [c0, c1):
+// (TimeNorm, xmaps_common.hpp).  Then  column(t) = #{c' >= 1 : thr[c'] <= a}  and, for a tile of columns [c0, c1):
 // event in tile <=> thr[c0] <= a < thr[c1]; its column = c0 + #{interior c' : thr[c'] <= a}: a few 32-bit compares per event
 // instead of the FP64 chain, and half the registers.
 __device__ inline u32 cols_threshold(const TimeNorm<long long>& tn, const long long tmin, const u32 span, const int c, const int S) {
@@ -249,8 +249,8 @@ __device__ __forceinline__ void cols_bounds_body(gp_u16 xs, gp_i64 ts, gp_u4 aos
     t_last = -ext_mm[1];
   } else if constexpr (AOS) {
     const uint4 a = aos[0], b = aos[n - 1];
-    t_first = (T)(((u64)a.w << 32) | a.z);
-    t_last = (T)(((u64)b.w << 32) | b.z);
+    t_first = rec_t<T>(a);
+    t_last = rec_t<T>(b);
   } else {
     t_first = ts[0];
     t_last = ts[n - 1];
@@ -342,7 +342,7 @@ __device__ __forceinline__ void cols_bounds_body(gp_u16 xs, gp_i64 ts, gp_u4 aos
       xk[k] = 0;
       if constexpr (AOS) {
         const uint4 r = aos[act[k] ? q[k] : 0];
-        tv[k] = (T)(((u64)r.w << 32) | r.z);
+        tv[k] = (T)(((u64)r.w << 32) | r.z);  // (not rec_t / rec_x: the call reorders this kernel's code, profiles/device_split_identity.md)
         xk[k] = r.x & 0xffffu;
       } else {
         tv[k] = ts[act[k] ? q[k] : 0];
@@ -452,8 +452,8 @@ __device__ __forceinline__ void scatter_cols_body(gp_u16 xs, gp_u16 ys, gp_i64 t
     t_last = -ext_mm[1];
   } else if constexpr (AOS) {
     const uint4 a = aos[0], b = aos[n - 1];
-    t_first = (T)(((u64)a.w << 32) | a.z);
-    t_last = (T)(((u64)b.w << 32) | b.z);
+    t_first = rec_t<T>(a);
+    t_last = rec_t<T>(b);
   } else {
     t_first = ts[0];
     t_last = ts[n - 1];
@@ -521,7 +521,7 @@ __device__ __forceinline__ void scatter_cols_body(gp_u16 xs, gp_u16 ys, gp_i64 t
           const uint4 r = aos[ic];
           xw[k >> 1] |= (r.x & 0xffff) << ((k & 1) * 16);
           yw[k >> 1] |= (r.x >> 16) << ((k & 1) * 16);
-          tt[k] = (T)(((u64)r.w << 32) | r.z);
+          tt[k] = rec_t<T>(r);
         } else {
           xw[k >> 1] |= (u32)xs[ic] << ((k & 1) * 16);
           yw[k >> 1] |= (u32)ys[ic] << ((k & 1) * 16);
@@ -567,10 +567,7 @@ __device__ __forceinline__ void scatter_cols_body(gp_u16 xs, gp_u16 ys, gp_i64 t
       st->mm[parity][0][0] = TimeCodec<T>::enc(t_first);  // xm_frame_stats.t_min / t_max
       st->mm[parity][0][1] = TimeCodec<T>::enc(t_last);
     }
-    for (int i = tid; i < MM_SLOTS; i += nthreads) {
-      st->mm[parity ^ 1][i][0] = MM_INIT_MIN;
-      st->mm[parity ^ 1][i][1] = MM_INIT_MAX;
-    }
+    rearm_minmax(st, parity, tid, nthreads);
   }
 
   u32 n_in = 0, n_oob = 0;  // per-lane counters (summed over the wave at the end: no ballot + popcount per event)
@@ -770,11 +767,7 @@ __device__ __forceinline__ void scatter_cols_body(gp_u16 xs, gp_u16 ys, gp_i64 t
     }
   }
   XM_CSTAMP(8);
-  if (tid == 0) {
-    XM_GLOBAL u32* c = st->cnt[parity][blk % CNT_SLOTS];
-    if (s_in) __hip_atomic_fetch_add(&c[CNT_INLIER], s_in, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (s_oob) __hip_atomic_fetch_add(&c[CNT_OOB], s_oob, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  if (tid == 0) flush_counts(st->cnt[parity][blk % CNT_SLOTS], s_in, s_oob);
 }
 
 #ifndef XM_COLS_MAX_THREADS

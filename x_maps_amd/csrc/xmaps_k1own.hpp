@@ -2,7 +2,7 @@
 // map is NOT injective -- the reference's own calibration: X_MAP_WIDTH = projector_width = 1080 time columns
 // (x_maps_disparity.py:58-59) land on ~300 columns of the rectified frame (cam_proj_calibration.py:299-303), so up to four
 // consecutive time columns of a row share one cell and the plain column tiles (one slot per (row, column) pair, one owner
-// per cell by injectivity) do not apply.  (gfx950 / MI355X; included by xmaps_hip.hip after xmaps_k1cols.hpp)
+// per cell by injectivity) do not apply.  (gfx950 / MI355X; needs xmaps_common.hpp and xmaps_k1cols.hpp)
 //
 //   * OWNER of a cell = the FIRST time column of its row that maps to it; delta(row, c) = c - owner column (0..7, found once
 //     in xm_create and packed into the top 3 bits of a second copy of the X-map: xp | delta << 13).  Tile T = W time columns
@@ -30,7 +30,8 @@
 //     64-bit general path.
 // Algorithmic bytes are K1's: 24 B/event.
 #pragma once
-#include "xmaps_k1cols.hpp"
+#include "xmaps_common.hpp"
+#include "xmaps_k1cols.hpp"  // gp_* pointer types, COLS_*, cols_threshold, the boundaries of k_cols_bounds
 
 #ifndef XM_OWN_WAVES
 #define XM_OWN_WAVES 1  /* waves per SIMD the 8-events-per-thread kernels are compiled for (experiments: 5, 6) */
@@ -101,8 +102,8 @@ __device__ __forceinline__ void scatter_own_body(gp_u16 xs, gp_u16 ys, gp_i64 ts
   T t_first, t_last;
   if constexpr (AOS) {
     const uint4 a = aos[0], b = aos[n - 1];
-    t_first = (T)(((u64)a.w << 32) | a.z);
-    t_last = (T)(((u64)b.w << 32) | b.z);
+    t_first = rec_t<T>(a);
+    t_last = rec_t<T>(b);
   } else {
     t_first = ts[0];
     t_last = ts[n - 1];
@@ -171,7 +172,7 @@ __device__ __forceinline__ void scatter_own_body(gp_u16 xs, gp_u16 ys, gp_i64 ts
         if constexpr (AOS) {
           const uint4 r = aos[ic];
           xy[k] = r.x;
-          tt[k] = (T)(((u64)r.w << 32) | r.z);
+          tt[k] = rec_t<T>(r);
         } else {
           xy[k] = (u32)xs[ic] | ((u32)ys[ic] << 16);
           tt[k] = ts[ic];
@@ -194,10 +195,7 @@ __device__ __forceinline__ void scatter_own_body(gp_u16 xs, gp_u16 ys, gp_i64 ts
       st->mm[parity][0][0] = TimeCodec<T>::enc(t_first);
       st->mm[parity][0][1] = TimeCodec<T>::enc(t_last);
     }
-    for (int i = tid; i < MM_SLOTS; i += nthreads) {
-      st->mm[parity ^ 1][i][0] = MM_INIT_MIN;
-      st->mm[parity ^ 1][i][1] = MM_INIT_MAX;
-    }
+    rearm_minmax(st, parity, tid, nthreads);
   }
   __syncthreads();  // slots cleared, masks in place
   XM_CSTAMP(2);
@@ -461,11 +459,7 @@ __device__ __forceinline__ void scatter_own_body(gp_u16 xs, gp_u16 ys, gp_i64 ts
     for (int i = tid; i < n_extra; i += nthreads) frame16[xc[i]] = (uint16_t)(slots_x[i] & 0xffffu);
   }
   XM_CSTAMP(8);
-  if (tid == 0) {
-    XM_GLOBAL u32* c = st->cnt[parity][blk % CNT_SLOTS];
-    if (s_in) __hip_atomic_fetch_add(&c[CNT_INLIER], s_in, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (s_oob) __hip_atomic_fetch_add(&c[CNT_OOB], s_oob, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  if (tid == 0) flush_counts(st->cnt[parity][blk % CNT_SLOTS], s_in, s_oob);
 }
 
 template <bool AOS, bool VEC, int EPT = COLS_EPT>

@@ -1,6 +1,6 @@
 // xmaps_k2pipe.hpp -- K2 (dilate o remap -> depth -> u8 -> Turbo BGR, disp_to_depth.py:7-97) for GROUPS of frames on the plain
-// u16 disparity frame of the column / owner tiles, as persistent, software-pipelined blocks.  (gfx950 / MI355X; included by
-// xmaps_hip.hip after xmaps_kernels.hpp)
+// u16 disparity frame of the column / owner tiles, as persistent, software-pipelined blocks.  (gfx950 / MI355X; needs
+// xmaps_common.hpp, xmaps_k2.hpp and xmaps_k1cols.hpp)
 //
 // k_frame_proj_tiled_batch is one block per (tile, frame): a chain of dependent round trips -- frame descriptor + tile record ->
 // the tile's patch of the disparity frame -> (LDS work) -> the per-disparity table -> stores -- with 55 % of the block's lifetime
@@ -17,7 +17,9 @@
 //     the frame's height: an octet is inside or outside as a whole); a rig with a patch of more than 128 rows or more quads than
 //     the loader's registers hold keeps the one-block-per-tile kernel (k2_pipe_tile_ok, checked once in xm_create).
 #pragma once
-#include "xmaps_kernels.hpp"
+#include "xmaps_common.hpp"
+#include "xmaps_k2.hpp"      // K2_TX / K2_TY, k2_rowmax8, the tile tables of k_build_k2_tables
+#include "xmaps_k1cols.hpp"  // XM_CABL (experiment switches), the u16 frame these kernels read
 
 namespace xm {
 

@@ -21,7 +21,8 @@
 // t are an existing property of this build, not of this path).  NaN / +-inf entries are out of contract: they never become extrema
 // (comparisons with NaN are false) and an event's column is bounds-checked like K1's, so they cannot index outside a table.
 #pragma once
-#include "xmaps_kernels.hpp"
+#include "xmaps_common.hpp"
+#include "xmaps_stage.hpp"  // Mat4f, point_from_disparity
 
 namespace xm {
 
