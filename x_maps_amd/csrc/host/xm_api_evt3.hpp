@@ -1,4 +1,4 @@
-// xm_api_evt3.hpp -- C-ABI: EVT 3.0 / EVT 2.0 words -> EventCD records on the device (xmaps_evt3.hpp, xmaps_evt2.hpp).  One decoder
+// xm_api_evt3.hpp -- C-ABI: EVT 3.0 / EVT 2.0 words -> EventCD records on the device (xmaps_evt3.hpp, xmaps_evt2.hpp; xmaps_evt.hpp).  One decoder
 // object for both encodings (`format`): same buffers, same state record, same three launches.  Straight into the ingest:
 // xm_ingest_push_evt3 / _evt2 (xm_api_ingest.hpp), which enqueue the same launches (evt3_enqueue) from the ingest's copy side.
 // (part of libxmaps_hip.so's host side: included by ../xmaps_hip.hip, one translation unit; see that file for the order)
@@ -21,6 +21,8 @@ struct xm_evt3 {
   int wait_tb = 0;               // xm_evt3_wait_for_time_base: events in front of the stream's first TIME_HIGH word are not emitted
 };
 
+static_assert(sizeof(Evt2Scan) <= sizeof(Evt3Scan), "the decoders share the aggregates' buffer (d_agg)");
+
 namespace {
 
 // words (host) -> records at `out` (device, room for out_cap) enqueued on `stream`; the chunk's event count is left in
@@ -35,23 +37,23 @@ int evt3_enqueue(xm_evt3* d, const void* words_host, size_t n_words, bool pinned
     memcpy(d->h_words, words_host, n_words * d->word_bytes);
   }
   HIP_TRY(hipMemcpyAsync(d->d_words, pinned ? words_host : (const void*)d->h_words, n_words * d->word_bytes, hipMemcpyHostToDevice, stream));
-  const u32 n = (u32)n_words, nb = (u32)grid_for(n_words, EVT3_PER_BLOCK);
+  const u32 n = (u32)n_words, nb = (u32)grid_for(n_words, EVT_PER_BLOCK);
   Evt3State* st_in = d->d_state + d->cur;
   Evt3State* st_out = d->d_state + (d->cur ^ 1);
   if (d->format == 2) {
     const u32* w32 = reinterpret_cast<const u32*>(d->d_words.get());
     Evt2Scan* agg = reinterpret_cast<Evt2Scan*>(d->d_agg.get());
-    hipLaunchKernelGGL(k_evt2_aggregate, dim3(nb), dim3(EVT3_THREADS), 0, stream, w32, n, agg);
-    hipLaunchKernelGGL(k_evt2_prefix, dim3(1), dim3(EVT3_THREADS), 0, stream, nb, agg, (const Evt3State*)st_in, st_out, count_out, d->wait_tb);
-    hipLaunchKernelGGL(k_evt2_emit, dim3(nb), dim3(EVT3_THREADS), 0, stream, w32, n, (const Evt2Scan*)agg, (const Evt3State*)st_in, out,
+    hipLaunchKernelGGL(k_evt2_aggregate, dim3(nb), dim3(EVT_THREADS), 0, stream, w32, n, agg);
+    hipLaunchKernelGGL(k_evt2_prefix, dim3(1), dim3(EVT_THREADS), 0, stream, nb, agg, (const Evt3State*)st_in, st_out, count_out, d->wait_tb);
+    hipLaunchKernelGGL(k_evt2_emit, dim3(nb), dim3(EVT_THREADS), 0, stream, w32, n, (const Evt2Scan*)agg, (const Evt3State*)st_in, out,
                        (u32)std::min<size_t>(out_cap, 0xffffffffu), d->wait_tb);
     HIP_TRY(hipGetLastError());
     return XM_OK;
   }
-  hipLaunchKernelGGL(k_evt3_aggregate, dim3(nb), dim3(EVT3_THREADS), 0, stream, (const uint16_t*)d->d_words, n, d->d_agg);
-  hipLaunchKernelGGL(k_evt3_prefix, dim3(1), dim3(EVT3_THREADS), 0, stream, (const uint16_t*)d->d_words, nb, d->d_agg, (const Evt3State*)st_in, st_out,
+  hipLaunchKernelGGL(k_evt3_aggregate, dim3(nb), dim3(EVT_THREADS), 0, stream, (const uint16_t*)d->d_words, n, d->d_agg);
+  hipLaunchKernelGGL(k_evt3_prefix, dim3(1), dim3(EVT_THREADS), 0, stream, (const uint16_t*)d->d_words, nb, d->d_agg, (const Evt3State*)st_in, st_out,
                      count_out, d->wait_tb);
-  hipLaunchKernelGGL(k_evt3_emit, dim3(nb), dim3(EVT3_THREADS), 0, stream, (const uint16_t*)d->d_words, n, (const Evt3Scan*)d->d_agg,
+  hipLaunchKernelGGL(k_evt3_emit, dim3(nb), dim3(EVT_THREADS), 0, stream, (const uint16_t*)d->d_words, n, (const Evt3Scan*)d->d_agg,
                      (const Evt3State*)st_in, out, (u32)std::min<size_t>(out_cap, 0xffffffffu), d->wait_tb);
   HIP_TRY(hipGetLastError());
   return XM_OK;
@@ -90,7 +92,7 @@ static int evt_create(xm_handle* h, int format, size_t max_words, size_t max_eve
   d->max_words = max_words ? max_words : (size_t)1 << 20;
   d->max_events = max_events ? max_events : (format == 2 ? d->max_words : 2 * d->max_words);
   if (d->max_words >= 0x7fffffffull || d->max_events >= 0x7fffffffull) return fail(XM_ERR_INVALID, "max_words and max_events must be < 2^31");
-  const size_t nb = grid_for(d->max_words, EVT3_PER_BLOCK);
+  const size_t nb = grid_for(d->max_words, EVT_PER_BLOCK);
   const size_t n16 = d->max_words * d->word_bytes / sizeof(uint16_t);
   HIP_TRY(d->stream.create(hipStreamNonBlocking));
   HIP_TRY(d->h_words.alloc(n16, hipHostMallocDefault));

@@ -298,6 +298,36 @@ __device__ inline u64 wave_max_u64(u64 v) {
   return v;
 }
 
+__device__ inline double wave_min_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double w = __shfl_xor(v, o, 64);
+    v = w < v ? w : v;
+  }
+  return v;
+}
+__device__ inline double wave_max_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double w = __shfl_xor(v, o, 64);
+    v = w > v ? w : v;
+  }
+  return v;
+}
+__device__ inline u32 wave_sum_u32(u32 v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ inline u32 wave_max_u32(u32 v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const u32 w = __shfl_xor(v, o, 64);
+    v = w > v ? w : v;
+  }
+  return v;
+}
+
 // frame extrema as written by K0: every wave reduces the MM_SLOTS partials itself (128 B, L2-hot) and broadcasts
 // the result through SGPRs (readfirstlane), so everything derived from it is wave-uniform
 __device__ inline u64 uniform_u64(u64 v) {

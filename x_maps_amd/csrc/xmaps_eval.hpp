@@ -61,7 +61,7 @@ __global__ __launch_bounds__(BLOCK) void k_eval_stats(const float* __restrict__ 
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
-    s += __shfl_xor(s, o, 64);
+    s += __shfl_xor(s, o, 64);  // (with the counts in one pass: s alone through wave helpers moves the kernel, profiles/evt_skeleton_identity.md)
 #pragma unroll
     for (int k = 0; k < 7; ++k) c[k] += __shfl_xor(c[k], o, 64);
   }

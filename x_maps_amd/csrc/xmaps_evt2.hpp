@@ -1,7 +1,6 @@
 // xmaps_evt2.hpp -- Prophesee EVT 2.0 words -> EventCD records on the device ("EVT2/EVT3 RAW reader"): the older
-// of the two public RAW encodings, 32-bit little-endian words, one event per CD word.  (gfx950 / MI355X; included by xmaps_hip.hip
-// after xmaps_evt3.hpp, whose state record and three-launch shape it shares.)  x_maps_amd/evt2.py restates the format on the host,
-// oracle/evt2_oracle.py is the independent word-by-word checker.
+// of the two public RAW encodings, 32-bit little-endian words, one event per CD word.  (gfx950 / MI355X; included by xmaps_hip.hip.)
+// x_maps_amd/evt2.py restates the format on the host, oracle/evt2_oracle.py is the independent word-by-word checker.
 //
 //   [31:28] type   0x0 CD_OFF / 0x1 CD_ON   [27:22] t[5:0]   [21:11] x   [10:0] y          one event, p = type
 //                  0x8 EVT_TIME_HIGH        [27:0]  t[33:6]                                the time base of the words behind it
@@ -11,10 +10,11 @@
 // The state at word i is the last TIME_HIGH at or before it (+ the loops among the TIME_HIGH words so far) and the number of CD
 // words before it: an inclusive scan with an associative combine, evaluated like EVT 3.0's -- block aggregates, their exclusive
 // scan in one block seeded with the previous chunk's state (which also leaves the next state and the chunk's event count),
-// every block re-scans its words from its prefix and writes its records in word order.
+// every block re-scans its words from its prefix and writes its records in word order.  The block geometry, the state record
+// (EVT 3.0's: only t_high, t_loops, have_high and n_events are used), the start-of-stream rule and the block scan are
+// xmaps_evt.hpp's, shared with EVT 3.0 (xmaps_evt3.hpp).
 #pragma once
-#include "xmaps_common.hpp"
-#include "xmaps_evt3.hpp"  // Evt3Scan (the decoders share the aggregates' buffer), evt_dropped
+#include "xmaps_evt.hpp"
 
 namespace xm {
 
@@ -23,7 +23,6 @@ struct Evt2Scan {
   u32 n_ev;
   u32 hi_word, n_pre;                       // a TIME_HIGH WORD lies in the range (the seed is not one); events in front of its first one
 };
-static_assert(sizeof(Evt2Scan) <= sizeof(Evt3Scan), "the decoders share the aggregates' buffer");
 
 __device__ __forceinline__ Evt2Scan evt2_identity() {
   Evt2Scan e;
@@ -34,7 +33,7 @@ __device__ __forceinline__ Evt2Scan evt2_identity() {
 }
 
 // a = the earlier range, b = the later one
-__device__ __forceinline__ Evt2Scan evt2_combine(const Evt2Scan& a, const Evt2Scan& b) {
+__device__ __forceinline__ Evt2Scan evt_combine(const Evt2Scan& a, const Evt2Scan& b) {
   Evt2Scan r;
   if (!b.hi_has) {
     r.hi_has = a.hi_has; r.hi_first = a.hi_first; r.hi_last = a.hi_last; r.hi_wraps = a.hi_wraps;
@@ -66,55 +65,36 @@ __device__ __forceinline__ Evt2Scan evt2_seed(const Evt3State& s) {  // the stat
   return e;
 }
 
-// inclusive scan of one element per thread over the block; returns the thread's inclusive result, *block_total = the aggregate
-__device__ __forceinline__ Evt2Scan evt2_block_scan(const Evt2Scan mine, Evt2Scan (*buf)[EVT3_THREADS], Evt2Scan* block_total) {
-  const int tid = threadIdx.x;
-  int cur = 0;
-  buf[0][tid] = mine;
-  __syncthreads();
-  for (int o = 1; o < EVT3_THREADS; o <<= 1) {
-    Evt2Scan v = buf[cur][tid];
-    if (tid >= o) v = evt2_combine(buf[cur][tid - o], v);
-    buf[cur ^ 1][tid] = v;
-    cur ^= 1;
-    __syncthreads();
-  }
-  const Evt2Scan r = buf[cur][tid];
-  *block_total = buf[cur][EVT3_THREADS - 1];
-  __syncthreads();
-  return r;
-}
-
-// 1. the aggregate of every block of EVT3_PER_BLOCK words
-__global__ __launch_bounds__(EVT3_THREADS) void k_evt2_aggregate(const u32* __restrict__ words, u32 n, Evt2Scan* __restrict__ agg) {
-  __shared__ Evt2Scan buf[2][EVT3_THREADS];
-  const u32 i0 = blockIdx.x * EVT3_PER_BLOCK + threadIdx.x * EVT3_IPT;
+// 1. the aggregate of every block of EVT_PER_BLOCK words
+__global__ __launch_bounds__(EVT_THREADS) void k_evt2_aggregate(const u32* __restrict__ words, u32 n, Evt2Scan* __restrict__ agg) {
+  __shared__ Evt2Scan buf[2][EVT_THREADS];
+  const u32 i0 = blockIdx.x * EVT_PER_BLOCK + threadIdx.x * EVT_IPT;
   Evt2Scan acc = evt2_identity();
 #pragma unroll
-  for (int k = 0; k < EVT3_IPT; ++k)
-    if (i0 + k < n) acc = evt2_combine(acc, evt2_element(words[i0 + k]));
+  for (int k = 0; k < EVT_IPT; ++k)
+    if (i0 + k < n) acc = evt_combine(acc, evt2_element(words[i0 + k]));
   Evt2Scan total;
-  (void)evt2_block_scan(acc, buf, &total);
+  (void)evt_block_scan(acc, buf, &total);
   if (threadIdx.x == 0) agg[blockIdx.x] = total;
 }
 
 // 2. one block: exclusive scan of the aggregates, seeded with the previous chunk's state; the chunk's event count and the state
 //    for the next chunk (the EVT 3.0 record: only t_high, t_loops and n_events are used)
-__global__ __launch_bounds__(EVT3_THREADS) void k_evt2_prefix(u32 n_blocks, Evt2Scan* __restrict__ agg, const Evt3State* __restrict__ st_in,
+__global__ __launch_bounds__(EVT_THREADS) void k_evt2_prefix(u32 n_blocks, Evt2Scan* __restrict__ agg, const Evt3State* __restrict__ st_in,
                                                              Evt3State* __restrict__ st_out, u32* __restrict__ count_out, int wait) {
-  __shared__ Evt2Scan buf[2][EVT3_THREADS];
-  __shared__ Evt2Scan s_incl[EVT3_THREADS];
+  __shared__ Evt2Scan buf[2][EVT_THREADS];
+  __shared__ Evt2Scan s_incl[EVT_THREADS];
   const Evt3State s = *st_in;
   Evt2Scan carry = evt2_seed(s);
-  for (u32 b0 = 0; b0 < n_blocks; b0 += EVT3_THREADS) {
+  for (u32 b0 = 0; b0 < n_blocks; b0 += EVT_THREADS) {
     const u32 b = b0 + threadIdx.x;
     const Evt2Scan mine = b < n_blocks ? agg[b] : evt2_identity();
     Evt2Scan total;
-    const Evt2Scan incl = evt2_block_scan(mine, buf, &total);
+    const Evt2Scan incl = evt_block_scan(mine, buf, &total);
     s_incl[threadIdx.x] = incl;
     __syncthreads();
-    if (b < n_blocks) agg[b] = threadIdx.x ? evt2_combine(carry, s_incl[threadIdx.x - 1]) : carry;
-    carry = evt2_combine(carry, total);
+    if (b < n_blocks) agg[b] = threadIdx.x ? evt_combine(carry, s_incl[threadIdx.x - 1]) : carry;
+    carry = evt_combine(carry, total);
     __syncthreads();
   }
   if (threadIdx.x == 0) {
@@ -130,32 +110,32 @@ __global__ __launch_bounds__(EVT3_THREADS) void k_evt2_prefix(u32 n_blocks, Evt2
 }
 
 // 3. the records: every block re-scans its words from its exclusive prefix and writes its events
-__global__ __launch_bounds__(EVT3_THREADS) void k_evt2_emit(const u32* __restrict__ words, u32 n, const Evt2Scan* __restrict__ prefix,
+__global__ __launch_bounds__(EVT_THREADS) void k_evt2_emit(const u32* __restrict__ words, u32 n, const Evt2Scan* __restrict__ prefix,
                                                            const Evt3State* __restrict__ st_in, uint4* __restrict__ out, u32 out_cap, int wait) {
-  __shared__ Evt2Scan buf[2][EVT3_THREADS];
-  __shared__ Evt2Scan s_incl[EVT3_THREADS];
+  __shared__ Evt2Scan buf[2][EVT_THREADS];
+  __shared__ Evt2Scan s_incl[EVT_THREADS];
   const unsigned long long loops0 = st_in->t_loops;
   const u32 have_high = st_in->have_high;
-  const u32 i0 = blockIdx.x * EVT3_PER_BLOCK + threadIdx.x * EVT3_IPT;
-  u32 w[EVT3_IPT];
+  const u32 i0 = blockIdx.x * EVT_PER_BLOCK + threadIdx.x * EVT_IPT;
+  u32 w[EVT_IPT];
   Evt2Scan acc = evt2_identity();
 #pragma unroll
-  for (int k = 0; k < EVT3_IPT; ++k) {
+  for (int k = 0; k < EVT_IPT; ++k) {
     w[k] = i0 + k < n ? words[i0 + k] : 0xE0000000u;  // (OTHERS: skipped)
-    if (i0 + k < n) acc = evt2_combine(acc, evt2_element(w[k]));
+    if (i0 + k < n) acc = evt_combine(acc, evt2_element(w[k]));
   }
   Evt2Scan total;
-  const Evt2Scan incl = evt2_block_scan(acc, buf, &total);
+  const Evt2Scan incl = evt_block_scan(acc, buf, &total);
   s_incl[threadIdx.x] = incl;
   __syncthreads();
   Evt2Scan run = prefix[blockIdx.x];
-  if (threadIdx.x) run = evt2_combine(run, s_incl[threadIdx.x - 1]);
+  if (threadIdx.x) run = evt_combine(run, s_incl[threadIdx.x - 1]);
 #pragma unroll
-  for (int k = 0; k < EVT3_IPT; ++k) {
+  for (int k = 0; k < EVT_IPT; ++k) {
     if (i0 + k >= n) break;
     const u32 before = run.n_ev - evt_dropped(run.n_pre, have_high, wait);
     const Evt2Scan e = evt2_element(w[k]);
-    run = evt2_combine(run, e);
+    run = evt_combine(run, e);
     if (!e.n_ev || before >= out_cap) continue;
     if (wait && !have_high && !run.hi_word) continue;  // in front of the stream's first EVT_TIME_HIGH: not emitted
     const unsigned long long t = ((loops0 + run.hi_wraps) << 34) | ((unsigned long long)run.hi_last << 6) | (unsigned long long)((w[k] >> 22) & 0x3fu);

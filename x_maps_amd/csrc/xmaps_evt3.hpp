@@ -15,20 +15,12 @@
 //   * events emitted so far: a sum (ADDR_X: 1, VECT_*: the population count of its valid bits).
 // Three launches per chunk: block aggregates -> their exclusive scan in one block, seeded with the state the previous chunk
 // left (which also writes the next state and the chunk's event count) -> every block re-scans its words from its prefix and
-// writes the records in word order, a vector word's events in ascending column order.
+// writes the records in word order, a vector word's events in ascending column order.  The block geometry, the state record, the
+// start-of-stream rule and the block scan are xmaps_evt.hpp's, shared with EVT 2.0 (xmaps_evt2.hpp).
 #pragma once
-#include "xmaps_common.hpp"
+#include "xmaps_evt.hpp"
 
 namespace xm {
-
-constexpr int EVT3_THREADS = 256, EVT3_IPT = 8, EVT3_PER_BLOCK = EVT3_THREADS * EVT3_IPT;
-
-struct Evt3State {  // what a chunk hands to the next one (Evt3Decoder's fields in x_maps_amd/evt3.py)
-  u32 y, base_x, base_p, t_high, t_low;
-  u32 have_high;  // a TIME_HIGH word has been seen since the stream started (the "wait for the time base" option drops events before it)
-  unsigned long long t_loops;
-  unsigned long long n_events;  // of the chunk that wrote this state
-};
 
 struct Evt3Scan {
   u32 lo_idx, y_idx, b_idx;  // last TIME_LOW / ADDR_Y / VECT_BASE_X word: index + 1, 0 = none
@@ -49,7 +41,7 @@ __device__ __forceinline__ Evt3Scan evt3_identity() {
 }
 
 // a = the earlier range, b = the later one
-__device__ __forceinline__ Evt3Scan evt3_combine(const Evt3Scan& a, const Evt3Scan& b) {
+__device__ __forceinline__ Evt3Scan evt_combine(const Evt3Scan& a, const Evt3Scan& b) {
   Evt3Scan r;
   r.lo_idx = max(a.lo_idx, b.lo_idx);
   r.y_idx = max(a.y_idx, b.y_idx);
@@ -74,11 +66,6 @@ __device__ __forceinline__ Evt3Scan evt3_combine(const Evt3Scan& a, const Evt3Sc
   return r;
 }
 
-// Start-of-stream rule (an option of the decoder, xm_evt3_wait_for_time_base): events in front of the stream's FIRST TIME_HIGH word
-// carry a time of which only the low 12 bits are known.  Off (default): they are emitted with the high field at its initial 0,
-// like everything else the initial state defines.  On: they are not emitted (a reader that waits for the first time base).
-__device__ __forceinline__ u32 evt_dropped(const u32 n_pre, const u32 have_high, const int wait) { return wait && !have_high ? n_pre : 0u; }
-
 __device__ __forceinline__ Evt3Scan evt3_element(u32 w, u32 i) {  // word w at index i of the chunk
   Evt3Scan e = evt3_identity();
   const u32 typ = w >> 12;
@@ -100,36 +87,16 @@ __device__ __forceinline__ Evt3Scan evt3_seed(const Evt3State& s) {  // the stat
   return e;
 }
 
-// inclusive scan of one element per thread over the block (Hillis-Steele on two LDS buffers); returns the thread's inclusive
-// result, *block_total = the block's aggregate
-__device__ __forceinline__ Evt3Scan evt3_block_scan(const Evt3Scan mine, Evt3Scan (*buf)[EVT3_THREADS], Evt3Scan* block_total) {
-  const int tid = threadIdx.x;
-  int cur = 0;
-  buf[0][tid] = mine;
-  __syncthreads();
-  for (int o = 1; o < EVT3_THREADS; o <<= 1) {
-    Evt3Scan v = buf[cur][tid];
-    if (tid >= o) v = evt3_combine(buf[cur][tid - o], v);
-    buf[cur ^ 1][tid] = v;
-    cur ^= 1;
-    __syncthreads();
-  }
-  const Evt3Scan r = buf[cur][tid];
-  *block_total = buf[cur][EVT3_THREADS - 1];
-  __syncthreads();
-  return r;
-}
-
-// 1. the aggregate of every block of EVT3_PER_BLOCK words
-__global__ __launch_bounds__(EVT3_THREADS) void k_evt3_aggregate(const uint16_t* __restrict__ words, u32 n, Evt3Scan* __restrict__ agg) {
-  __shared__ Evt3Scan buf[2][EVT3_THREADS];
-  const u32 i0 = blockIdx.x * EVT3_PER_BLOCK + threadIdx.x * EVT3_IPT;
+// 1. the aggregate of every block of EVT_PER_BLOCK words
+__global__ __launch_bounds__(EVT_THREADS) void k_evt3_aggregate(const uint16_t* __restrict__ words, u32 n, Evt3Scan* __restrict__ agg) {
+  __shared__ Evt3Scan buf[2][EVT_THREADS];
+  const u32 i0 = blockIdx.x * EVT_PER_BLOCK + threadIdx.x * EVT_IPT;
   Evt3Scan acc = evt3_identity();
 #pragma unroll
-  for (int k = 0; k < EVT3_IPT; ++k)
-    if (i0 + k < n) acc = evt3_combine(acc, evt3_element(words[i0 + k], i0 + k));
+  for (int k = 0; k < EVT_IPT; ++k)
+    if (i0 + k < n) acc = evt_combine(acc, evt3_element(words[i0 + k], i0 + k));
   Evt3Scan total;
-  (void)evt3_block_scan(acc, buf, &total);
+  (void)evt_block_scan(acc, buf, &total);
   if (threadIdx.x == 0) agg[blockIdx.x] = total;
 }
 
@@ -148,23 +115,23 @@ __device__ __forceinline__ void evt3_resolve(const Evt3Scan& r, const Evt3State&
 
 // 2. one block: exclusive scan of the aggregates, seeded with the previous chunk's state; the chunk's event count and the state
 //    for the next chunk
-__global__ __launch_bounds__(EVT3_THREADS) void k_evt3_prefix(const uint16_t* __restrict__ words, u32 n_blocks, Evt3Scan* __restrict__ agg,
+__global__ __launch_bounds__(EVT_THREADS) void k_evt3_prefix(const uint16_t* __restrict__ words, u32 n_blocks, Evt3Scan* __restrict__ agg,
                                                              const Evt3State* __restrict__ st_in, Evt3State* __restrict__ st_out,
                                                              u32* __restrict__ count_out, int wait) {
-  __shared__ Evt3Scan buf[2][EVT3_THREADS];
+  __shared__ Evt3Scan buf[2][EVT_THREADS];
   const Evt3State s = *st_in;
   Evt3Scan carry = evt3_seed(s);
-  for (u32 b0 = 0; b0 < n_blocks; b0 += EVT3_THREADS) {
+  for (u32 b0 = 0; b0 < n_blocks; b0 += EVT_THREADS) {
     const u32 b = b0 + threadIdx.x;
     const Evt3Scan mine = b < n_blocks ? agg[b] : evt3_identity();
     Evt3Scan total;
-    const Evt3Scan incl = evt3_block_scan(mine, buf, &total);
+    const Evt3Scan incl = evt_block_scan(mine, buf, &total);
     // exclusive prefix of block b = carry + (inclusive of b - 1): recompute from the neighbour's inclusive value
-    __shared__ Evt3Scan s_incl[EVT3_THREADS];
+    __shared__ Evt3Scan s_incl[EVT_THREADS];
     s_incl[threadIdx.x] = incl;
     __syncthreads();
-    if (b < n_blocks) agg[b] = threadIdx.x ? evt3_combine(carry, s_incl[threadIdx.x - 1]) : carry;
-    carry = evt3_combine(carry, total);
+    if (b < n_blocks) agg[b] = threadIdx.x ? evt_combine(carry, s_incl[threadIdx.x - 1]) : carry;
+    carry = evt_combine(carry, total);
     __syncthreads();
   }
   if (threadIdx.x == 0) {
@@ -182,32 +149,32 @@ __global__ __launch_bounds__(EVT3_THREADS) void k_evt3_prefix(const uint16_t* __
 }
 
 // 3. the records: every block re-scans its words from its exclusive prefix and writes its events
-__global__ __launch_bounds__(EVT3_THREADS) void k_evt3_emit(const uint16_t* __restrict__ words, u32 n, const Evt3Scan* __restrict__ prefix,
+__global__ __launch_bounds__(EVT_THREADS) void k_evt3_emit(const uint16_t* __restrict__ words, u32 n, const Evt3Scan* __restrict__ prefix,
                                                            const Evt3State* __restrict__ st_in, uint4* __restrict__ out, u32 out_cap, int wait) {
-  __shared__ Evt3Scan buf[2][EVT3_THREADS];
+  __shared__ Evt3Scan buf[2][EVT_THREADS];
   const Evt3State s = *st_in;
-  const u32 i0 = blockIdx.x * EVT3_PER_BLOCK + threadIdx.x * EVT3_IPT;
-  u32 w[EVT3_IPT];
+  const u32 i0 = blockIdx.x * EVT_PER_BLOCK + threadIdx.x * EVT_IPT;
+  u32 w[EVT_IPT];
   Evt3Scan acc = evt3_identity();
 #pragma unroll
-  for (int k = 0; k < EVT3_IPT; ++k) {
+  for (int k = 0; k < EVT_IPT; ++k) {
     w[k] = i0 + k < n ? (u32)words[i0 + k] : 0xE000u;  // (OTHERS: skipped)
-    if (i0 + k < n) acc = evt3_combine(acc, evt3_element(w[k], i0 + k));
+    if (i0 + k < n) acc = evt_combine(acc, evt3_element(w[k], i0 + k));
   }
   Evt3Scan total;
-  const Evt3Scan incl = evt3_block_scan(acc, buf, &total);
+  const Evt3Scan incl = evt_block_scan(acc, buf, &total);
   // exclusive prefix of this thread's first word = block prefix + the threads in front of it
-  __shared__ Evt3Scan s_incl[EVT3_THREADS];
+  __shared__ Evt3Scan s_incl[EVT_THREADS];
   s_incl[threadIdx.x] = incl;
   __syncthreads();
   Evt3Scan run = prefix[blockIdx.x];
-  if (threadIdx.x) run = evt3_combine(run, s_incl[threadIdx.x - 1]);
+  if (threadIdx.x) run = evt_combine(run, s_incl[threadIdx.x - 1]);
 #pragma unroll
-  for (int k = 0; k < EVT3_IPT; ++k) {
+  for (int k = 0; k < EVT_IPT; ++k) {
     if (i0 + k >= n) break;
     const u32 before = run.n_ev - evt_dropped(run.n_pre, s.have_high, wait);
     const Evt3Scan e = evt3_element(w[k], i0 + k);
-    run = evt3_combine(run, e);
+    run = evt_combine(run, e);
     if (!e.n_ev) continue;
     if (wait && !s.have_high && !run.hi_word) continue;  // in front of the stream's first TIME_HIGH word: not emitted
     u32 y, th, tl, base, pol;

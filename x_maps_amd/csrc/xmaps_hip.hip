@@ -9,7 +9,7 @@
 #include "xmaps_k2pipe.hpp"         // pipelined K2 on the u16 frame
 #include "xmaps_ingest.hpp"         // device-side ingest: activity filter, frame segmentation
 #include "xmaps_ingest_filter.hpp"  // ... the frame event filters as a stage of it
-#include "xmaps_evt3.hpp"           // EVT 3.0 decoder
+#include "xmaps_evt3.hpp"           // EVT 3.0 decoder (xmaps_evt.hpp: what it shares with the next one)
 #include "xmaps_evt2.hpp"           // EVT 2.0 decoder
 #include "xmaps_surface.hpp"        // time surfaces -> depth maps + point clouds
 

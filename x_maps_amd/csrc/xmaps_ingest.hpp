@@ -460,8 +460,7 @@ __device__ inline void ing_block_local(const IngestPush& p, const ActDev& act, u
     }
   }
   // block total of the pauses (their order inside the block follows from the ranks: see ing_pause_rank)
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) np += __shfl_xor(np, o, 64);
+  np = wave_sum_u32(np);
   __syncthreads();  // (s.cnt is reused)
   if (lane == 0) s.cnt[0][wave] = np;
   __syncthreads();

@@ -78,11 +78,7 @@ __global__ __launch_bounds__(FF_THREADS) void k_ff_width(FrameFilterDev f) {
     const int x = (int)(r.x & 0xffff), y = (int)(r.x >> 16);
     if (x < f.cam_w && y < f.cam_h) enc = (u32)(ff_xr(f, x, y) + FF_XR_BIAS);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const u32 v = __shfl_xor(enc, o, 64);
-    enc = v > enc ? v : enc;
-  }
+  enc = wave_max_u32(enc);
   if ((threadIdx.x & 63) == 0 && enc) __hip_atomic_fetch_max(&f.ctl->xr_enc, enc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 

@@ -716,7 +716,7 @@ __device__ __forceinline__ void scatter_cols_body(gp_u16 xs, gp_u16 ys, gp_i64 t
   {  // both counters in one word (a lane counts <= 8 events per pass, a tile holds <= 65527 events)
     u32 cnt2 = n_in | (n_oob << 16);
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) cnt2 += __shfl_xor(cnt2, o, 64);
+    for (int o = 32; o > 0; o >>= 1) cnt2 += __shfl_xor(cnt2, o, 64);  // (wave_sum_u32 moves all six k_scatter_cols*: profiles/evt_skeleton_identity.md)
     if (lane == 0) {
       if (cnt2 & 0xffffu) atomicAdd(&s_in, cnt2 & 0xffffu);
       if (cnt2 >> 16) atomicAdd(&s_oob, cnt2 >> 16);

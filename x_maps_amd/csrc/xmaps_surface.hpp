@@ -47,28 +47,6 @@ struct SurfStats {  // == xm_surface_stats (include/xmaps.h)
   double lo, hi, t_min, t_max;
 };
 
-__device__ inline double wave_min_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double w = __shfl_xor(v, o, 64);
-    v = w < v ? w : v;
-  }
-  return v;
-}
-__device__ inline double wave_max_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double w = __shfl_xor(v, o, 64);
-    v = w > v ? w : v;
-  }
-  return v;
-}
-__device__ inline u32 wave_sum_u32(u32 v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // {min, max, count} of a block (BLOCK threads): valid in thread 0
 __device__ inline void surf_block_reduce(double& mn, double& mx, u32& cnt) {
   __shared__ double s_mn[BLOCK / 64], s_mx[BLOCK / 64];

@@ -19,7 +19,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .evt3 import _ffill_index, split_raw_header
+from .evt3 import DeviceEvtDecoder, _ffill_index, raw_format, read_raw_chunks, split_raw_header  # noqa: F401 (a name of this module too)
 from .synthetic import EVENT_CD_DTYPE
 
 T_CD_OFF, T_CD_ON, T_TIME_HIGH = 0x0, 0x1, 0x8
@@ -91,8 +91,7 @@ def encode_evt2(evs: np.ndarray, time_high_every_us: int = 0) -> np.ndarray:
 
 
 def _is_evt2(fields: dict) -> bool:
-    fmt = fields.get("evt", fields.get("format", ""))
-    return fmt.split(";")[0].strip().upper() in _FORMAT_NAMES
+    return raw_format(fields) in _FORMAT_NAMES
 
 
 def read_raw(path: str, chunk_words: int = 1 << 22):
@@ -106,14 +105,7 @@ def read_raw(path: str, chunk_words: int = 1 << 22):
 
 def read_raw_words(path: str, chunk_words: int = 1 << 20):
     """Yields the EVT 2.0 words of a .raw file chunk by chunk, undecoded: for DeviceEvt2Decoder / process_evt2_words."""
-    with open(path, "rb") as f:
-        blob = f.read()
-    fields, off = split_raw_header(blob)
-    if not _is_evt2(fields):
-        raise ValueError(f"{path}: not an EVT 2.0 file (header says {fields.get('evt', fields.get('format'))!r}; EVT 3.0: x_maps_amd.evt3)")
-    words = np.frombuffer(blob, dtype="<u4", offset=off, count=(len(blob) - off) // 4)
-    for a in range(0, len(words), chunk_words):
-        yield words[a:a + chunk_words]
+    return read_raw_chunks(path, _FORMAT_NAMES, "<u4", chunk_words)
 
 
 def write_raw(path: str, evs: np.ndarray, width: int = 640, height: int = 480):
@@ -123,74 +115,8 @@ def write_raw(path: str, evs: np.ndarray, width: int = 640, height: int = 480):
         f.write(encode_evt2(evs).tobytes())
 
 
-class DeviceEvt2Decoder:
+class DeviceEvt2Decoder(DeviceEvtDecoder):
     """The same decoder as three kernels (csrc/xmaps_evt2.hpp): the words cross PCIe as the recording stores them (4-8 bytes per
-    event), the records stay on the device.  Same interface as evt3.DeviceEvt3Decoder."""
+    event), the records stay on the device.  Same interface as evt3.DeviceEvt3Decoder (push: xm_ingest_push_evt2)."""
 
-    def __init__(self, engine, max_words: int = 1 << 20, max_events: int = 0, wait_for_time_base: bool = False):
-        import ctypes as C
-
-        from . import _native as N
-        self._C, self._N, self._e = C, N, engine
-        self._lib = engine._lib
-        self._d = C.c_void_p(None)
-        self.max_words = int(max_words)
-        N.check(self._lib.xm_evt2_create(engine._h, int(max_words), int(max_events), C.byref(self._d)))
-        if wait_for_time_base:
-            N.check(self._lib.xm_evt3_wait_for_time_base(self._d, 1))
-
-    def close(self):
-        if getattr(self, "_d", None) is not None and self._d.value:
-            self._lib.xm_evt3_destroy(self._d)  # (one decoder type serves both encodings)
-            self._d = self._C.c_void_p(None)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def reset(self):
-        self._N.check(self._lib.xm_evt3_reset(self._d))
-
-    def decode_device(self, words: np.ndarray):
-        C = self._C
-        w = np.ascontiguousarray(words, dtype="<u4")
-        ptr, n = C.c_void_p(None), C.c_size_t(0)
-        self._N.check(self._lib.xm_evt2_decode(self._d, C.c_void_p(w.ctypes.data), len(w), C.byref(ptr), C.byref(n)))
-        return int(ptr.value or 0), int(n.value)
-
-    def decode(self, words: np.ndarray) -> np.ndarray:
-        w = np.ascontiguousarray(words, dtype="<u4")
-        parts = []
-        for a in range(0, max(len(w), 1), self.max_words):
-            ptr, n = self.decode_device(w[a:a + self.max_words])
-            ev = np.zeros(n, EVENT_CD_DTYPE)
-            if n:
-                self._e.dev_download(ev, ptr)
-            parts.append(ev)
-        cat = np.zeros(sum(len(e) for e in parts), EVENT_CD_DTYPE)  # (np.concatenate hands back the packed 14-byte layout under NumPy 2)
-        o = 0
-        for e in parts:
-            cat[o:o + len(e)] = e
-            o += len(e)
-        return cat
-
-    def push(self, ingest, words: np.ndarray, pinned: bool = False, count: bool = True):
-        """One chunk = one packet of `ingest` (xm_ingest_push_evt2); see evt3.DeviceEvt3Decoder.push."""
-        C = self._C
-        w = np.ascontiguousarray(words, dtype="<u4")
-        ingest._backpressure(1)
-        if not count:
-            self._N.check(self._lib.xm_ingest_push_evt2(ingest._g, self._d, C.c_void_p(w.ctypes.data), len(w), int(bool(pinned)), None))
-            return None
-        n = C.c_size_t(0)
-        self._N.check(self._lib.xm_ingest_push_evt2(ingest._g, self._d, C.c_void_p(w.ctypes.data), len(w), int(bool(pinned)), C.byref(n)))
-        return int(n.value)
+    _dtype, _create, _decode, _push = "<u4", "xm_evt2_create", "xm_evt2_decode", "xm_ingest_push_evt2"

@@ -24,6 +24,7 @@ import numpy as np
 from .synthetic import EVENT_CD_DTYPE
 
 T_ADDR_Y, T_ADDR_X, T_VECT_BASE_X, T_VECT_12, T_VECT_8, T_TIME_LOW, T_TIME_HIGH = 0x0, 0x2, 0x3, 0x4, 0x5, 0x6, 0x8
+_FORMAT_NAMES = ("3.0", "3", "EVT3", "EVT3.0")
 
 
 def split_raw_header(blob: bytes) -> tuple[dict, int]:
@@ -40,6 +41,25 @@ def split_raw_header(blob: bytes) -> tuple[dict, int]:
         k, _, v = line.partition(" ")
         fields[k] = v
     return fields, off
+
+
+def raw_format(fields: dict, default: str = "") -> str:
+    """The encoding a RAW header names: "% evt 3.0" (older headers) or "% format EVT3;height=720;width=1280" (newer ones): the
+    first token decides."""
+    return fields.get("evt", fields.get("format", default)).split(";")[0].strip().upper()
+
+
+def read_raw_chunks(path: str, names: tuple, dtype: str, chunk_words: int, default: str = ""):
+    """Yields the words of a .raw file chunk by chunk, undecoded, once its header names one of `names` as the encoding (a header
+    that names none counts as `default`): the header check and the word view of both encodings' readers."""
+    with open(path, "rb") as f:
+        blob = f.read()
+    fields, off = split_raw_header(blob)
+    if raw_format(fields, default) not in names:
+        raise ValueError(f"{path}: not an EVT {names[0]} file (header says {fields.get('evt', fields.get('format'))!r})")
+    words = np.frombuffer(blob, dtype=dtype, offset=off, count=(len(blob) - off) // np.dtype(dtype).itemsize)
+    for a in range(0, len(words), chunk_words):
+        yield words[a:a + chunk_words]
 
 
 def _ffill_index(mask: np.ndarray) -> np.ndarray:
@@ -136,16 +156,12 @@ def decode_evt3(words: np.ndarray, wait_for_time_base: bool = False) -> np.ndarr
     return Evt3Decoder(wait_for_time_base).decode(words)
 
 
-class DeviceEvt3Decoder:
-    """The same decoder as three kernels (csrc/xmaps_evt3.hpp: the state machine as scans): the words cross PCIe as the
-    recording stores them, the records stay on the device.
+class DeviceEvtDecoder:
+    """A RAW decoder as three kernels per chunk (csrc/xmaps_evt.hpp): the words cross PCIe as the recording stores them, the records
+    stay on the device.  One native decoder object serves both encodings (csrc/host/xm_api_evt3.hpp); a subclass names the word
+    dtype and the three entry points that differ: DeviceEvt3Decoder below, evt2.DeviceEvt2Decoder."""
 
-        dec = DeviceEvt3Decoder(engine)
-        ptr, n = dec.decode_device(words)       # 16-byte EventCD records in device memory, valid until the next call
-        evs = dec.decode(words)                 # ... copied back (tests)
-        n = dec.push(ingest, words)             # one chunk = one packet of a DeviceIngest (xm_ingest_push_evt3)
-
-    State (row, time, vector base, 24-bit wraps) carries over from chunk to chunk, as in Evt3Decoder."""
+    _dtype = _create = _decode = _push = None
 
     def __init__(self, engine, max_words: int = 1 << 20, max_events: int = 0, wait_for_time_base: bool = False):
         import ctypes as C
@@ -155,13 +171,13 @@ class DeviceEvt3Decoder:
         self._lib = engine._lib
         self._d = C.c_void_p(None)
         self.max_words = int(max_words)
-        N.check(self._lib.xm_evt3_create(engine._h, int(max_words), int(max_events), C.byref(self._d)))
+        N.check(getattr(self._lib, self._create)(engine._h, int(max_words), int(max_events), C.byref(self._d)))
         if wait_for_time_base:  # (Evt3Decoder's option: events in front of the stream's first EVT_TIME_HIGH are not emitted)
             N.check(self._lib.xm_evt3_wait_for_time_base(self._d, 1))
 
     def close(self):
         if getattr(self, "_d", None) is not None and self._d.value:
-            self._lib.xm_evt3_destroy(self._d)
+            self._lib.xm_evt3_destroy(self._d)  # (one decoder type serves both encodings)
             self._d = self._C.c_void_p(None)
 
     def __del__(self):
@@ -182,14 +198,14 @@ class DeviceEvt3Decoder:
 
     def decode_device(self, words: np.ndarray):
         C = self._C
-        w = np.ascontiguousarray(words, dtype="<u2")
+        w = np.ascontiguousarray(words, dtype=self._dtype)
         ptr, n = C.c_void_p(None), C.c_size_t(0)
-        self._N.check(self._lib.xm_evt3_decode(self._d, C.c_void_p(w.ctypes.data), len(w), C.byref(ptr), C.byref(n)))
+        self._N.check(getattr(self._lib, self._decode)(self._d, C.c_void_p(w.ctypes.data), len(w), C.byref(ptr), C.byref(n)))
         return int(ptr.value or 0), int(n.value)
 
     def decode(self, words: np.ndarray) -> np.ndarray:
         out = []
-        w = np.ascontiguousarray(words, dtype="<u2")
+        w = np.ascontiguousarray(words, dtype=self._dtype)
         for a in range(0, max(len(w), 1), self.max_words):
             ptr, n = self.decode_device(w[a:a + self.max_words])
             ev = np.zeros(n, EVENT_CD_DTYPE)
@@ -208,44 +224,40 @@ class DeviceEvt3Decoder:
         staging copy.  count=True: waits for the decoder and returns the chunk's event count; count=False: nothing is waited
         for (the ingest's kernels read the count on the device), returns None."""
         C = self._C
-        w = np.ascontiguousarray(words, dtype="<u2")
+        w = np.ascontiguousarray(words, dtype=self._dtype)
         ingest._backpressure(1)
-        if not count:
-            self._N.check(self._lib.xm_ingest_push_evt3(ingest._g, self._d, C.c_void_p(w.ctypes.data), len(w), int(bool(pinned)), None))
-            return None
-        n = C.c_size_t(0)
-        self._N.check(self._lib.xm_ingest_push_evt3(ingest._g, self._d, C.c_void_p(w.ctypes.data), len(w), int(bool(pinned)), C.byref(n)))
-        return int(n.value)
+        n = C.c_size_t(0) if count else None
+        self._N.check(getattr(self._lib, self._push)(ingest._g, self._d, C.c_void_p(w.ctypes.data), len(w), int(bool(pinned)),
+                                                     C.byref(n) if count else None))
+        return int(n.value) if count else None
+
+
+class DeviceEvt3Decoder(DeviceEvtDecoder):
+    """The same decoder as three kernels (csrc/xmaps_evt3.hpp: the state machine as scans): the words cross PCIe as the
+    recording stores them, the records stay on the device.
+
+        dec = DeviceEvt3Decoder(engine)
+        ptr, n = dec.decode_device(words)       # 16-byte EventCD records in device memory, valid until the next call
+        evs = dec.decode(words)                 # ... copied back (tests)
+        n = dec.push(ingest, words)             # one chunk = one packet of a DeviceIngest (xm_ingest_push_evt3)
+
+    State (row, time, vector base, 24-bit wraps) carries over from chunk to chunk, as in Evt3Decoder."""
+
+    _dtype, _create, _decode, _push = "<u2", "xm_evt3_create", "xm_evt3_decode", "xm_ingest_push_evt3"
 
 
 def read_raw(path: str, chunk_words: int = 1 << 22):
     """Yields EventCD packets of a .raw file (EVT 3.0)."""
-    with open(path, "rb") as f:
-        blob = f.read()
-    fields, off = split_raw_header(blob)
-    fmt = fields.get("evt", fields.get("format", "3.0"))
-    # "% evt 3.0" (older headers) or "% format EVT3;height=720;width=1280" (newer ones): the first token decides
-    if fmt.split(";")[0].strip().upper() not in ("3.0", "3", "EVT3", "EVT3.0"):
-        raise ValueError(f"{path}: only EVT 3.0 is supported (header says {fmt!r})")
-    words = np.frombuffer(blob, dtype="<u2", offset=off, count=(len(blob) - off) // 2)
     dec = Evt3Decoder()
-    for a in range(0, len(words), chunk_words):
-        ev = dec.decode(words[a:a + chunk_words])
+    for w in read_raw_words(path, chunk_words):
+        ev = dec.decode(w)
         if len(ev):
             yield ev
 
 
 def read_raw_words(path: str, chunk_words: int = 1 << 20):
     """Yields the EVT 3.0 words of a .raw file chunk by chunk, undecoded: for DeviceEvt3Decoder / process_evt3_words."""
-    with open(path, "rb") as f:
-        blob = f.read()
-    fields, off = split_raw_header(blob)
-    fmt = fields.get("evt", fields.get("format", "3.0"))
-    if fmt.split(";")[0].strip().upper() not in ("3.0", "3", "EVT3", "EVT3.0"):
-        raise ValueError(f"{path}: only EVT 3.0 is supported (header says {fmt!r})")
-    words = np.frombuffer(blob, dtype="<u2", offset=off, count=(len(blob) - off) // 2)
-    for a in range(0, len(words), chunk_words):
-        yield words[a:a + chunk_words]
+    return read_raw_chunks(path, _FORMAT_NAMES, "<u2", chunk_words, default="3.0")
 
 
 def encode_evt3(evs: np.ndarray, use_vectors: bool = True) -> np.ndarray:
