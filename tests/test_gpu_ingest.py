@@ -69,7 +69,8 @@ def test_filters_and_segmentation_match_the_cpu_chain(camera, activity):
 
 
 def test_activity_filter_with_packets_longer_than_its_threshold():
-    """Packets spanning several thresholds are split into sub-packets on the way in; the result is the same rule."""
+    """Packets spanning several thresholds go in whole: the device cuts their time axis into buckets of one threshold + 1 us
+    (at most 8 on the parallel path); the result is the same rule."""
     tb = S.make_tables(S.C_TINY)
     stream = _tiny_stream(10, seed=21)
     tf = IO.TriggerFinderOracle(60)
@@ -336,7 +337,7 @@ def test_a_launch_side_error_reaches_the_caller_and_the_ingest_closes(launch_thr
 
 
 def test_packets_of_any_size_and_empty_packets():
-    """the same stream in packets of 1 .. 7000 events (several blocks of 2048 per packet, blocks that keep nothing, pauses at
+    """the same stream in packets of 1 .. 7000 events (several blocks of 512 per packet, blocks that keep nothing, pauses at
     block and packet borders) with empty pushes in between: the trigger finder sees the same buffer at every decision only if
     the packets are the same, so the CPU chain gets the very same packets"""
     tb = S.make_tables(S.C_TINY)
