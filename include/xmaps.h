@@ -156,12 +156,13 @@ typedef struct xm_frame_stats {
 } xm_frame_stats;
 
 /* ---- lifetime ---------------------------------------------------------------------------------- */
-/* Variant switches for tests and experiments ("XM_COLS", "XM_K2_PIPE", "XM_K2_PIPE_PPT", "XM_K2_CONSEC", "XM_K2_NLDS_MAX",
+/* Variant switches for tests and experiments ("XM_COLS", "XM_K2_PIPE", "XM_K2_PIPE_PPT", "XM_K2_CONSEC", "XM_K2_LIVE", "XM_K2_NLDS_MAX",
  * "XM_K2_PPT", "XM_K2_FLAGS", "XM_K1_DIRECT", "XM_K2_DIRECT", "XM_KEY32", "XM_OWN_W", "XM_OWN_SHEAR", "XM_OWN_GROUPED",
  * "XM_OWN_ROW_PASSES", "XM_OWN_EPT", "XM_K2_PER_CU", "XM_K2_CHAIN", "XM_WORKERS", "XM_XMAP_SCAN",
  * "XM_INGEST_CLEAR_EVERY", "XM_INGEST_TRACE", "XM_INGEST_OUT_PIECE", "XM_INGEST_OUT_SERIAL", "XM_INGEST_OUT_INLINE",
  * "XM_INGEST_OUT_NO_QUERY", "XM_INGEST_EVT3_OUT_STREAM", "XM_INGEST_OWN_STREAMS", "XM_INGEST_PRIOS", "XM_SHARDED_KEYS"; values as text).  Process-wide, read when a handle / an ingest is created (XM_XMAP_SCAN:
- * at every call).  The library never reads them from the environment.  value == NULL removes an option, name == NULL all. */
+ * at every call).  "XM_K2_LIVE": 0 = the pipelined K2 loads every quad (all ones in its live-slot masks), 1 = the derived masks
+ * (default), 2 = the same and their live fractions on stderr, one line per tile geometry.  The library never reads them from the environment.  value == NULL removes an option, name == NULL all. */
 int xm_debug_option(const char* name, const char* value);
 int xm_api_version(void);
 const char* xm_last_error(void);

@@ -32,6 +32,7 @@ int xm_create(const xm_config* cfg, xm_handle** out) {
   if ((rc = build_k2_tables(h.get(), o))) return rc;
   if ((rc = classify_rig(h.get(), o))) return rc;
   size_k1_windows(h.get(), o);
+  if ((rc = build_k2_live(h.get(), o))) return rc;
   if ((rc = create_slots(h.get(), o))) return rc;
   if ((rc = create_batch_rings(h.get()))) return rc;
   start_workers(h.get(), o);

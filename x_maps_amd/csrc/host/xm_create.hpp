@@ -15,6 +15,7 @@ struct CreateOpts {
   const char* ablate = nullptr;       // "XM_ABLATE" (builds with -DXM_ABLATE only)
   int k2_nlds_max = 2048;             // "XM_K2_NLDS_MAX" (experiments)
   int k1_wx = 16;                     // "XM_K1_WX" (experiments): the LUT band's width in camera columns
+  std::vector<int4> k2_tiles[3];      // the K2 tile records, copied back once (build_k2_tables) for build_k2_live
 };
 
 int validate_config(const xm_config* cfg) {
@@ -53,6 +54,10 @@ void read_create_options(xm_handle* h, CreateOpts& o) {
   if (const char* e = dbg_opt("XM_K2_CHAIN")) h->k2_chain = e[0] != '0';
   if (const char* e = dbg_opt("XM_K2_PER_CU")) h->k2_per_cu_max = std::max(1, atoi(e));
   if (const char* e = dbg_opt("XM_COLS_LDS_PAD")) h->cols_lds_pad = std::max(0, std::min(64 * 1024, atoi(e)));
+  if (const char* e = dbg_opt("XM_K2_LIVE")) {
+    h->k2_live = e[0] != '0';
+    h->k2_live_report = e[0] == '2';
+  }
   if (const char* e = dbg_opt("XM_K2_CONSEC")) h->k2_consec = e[0] != '0' ? 1 : 0;  // experiments / tests: the strided pixel assignment
   o.cols = dbg_opt("XM_COLS");
   const char* e1 = dbg_opt("XM_K1_DIRECT");
@@ -116,7 +121,7 @@ int upload_tables(xm_handle* h) {
 }
 
 // K2's static per-tile patch rectangles and per-pixel offsets, for each of its geometries, and which one the pipelined kernel takes
-int build_k2_tables(xm_handle* h, const CreateOpts& o) {
+int build_k2_tables(xm_handle* h, CreateOpts& o) {
   const xm_config* cfg = &h->cfg;
   if (!h->d_pmap) return XM_OK;
   double mean_cells2 = 0.0;
@@ -147,6 +152,7 @@ int build_k2_tables(xm_handle* h, const CreateOpts& o) {
     int cap = 8;
     bool pipe_ok = (cfg->rect_height & 7) == 0;
     double cells = 0.0;
+    if (g > 0) o.k2_tiles[g] = tiles;  // (build_k2_live)
     for (const int4& r : tiles) {
       if (r.z > 0) cap = std::max(cap, r.z * r.w);
       if (r.z > 0) cells += (double)r.z * r.w;
@@ -287,6 +293,42 @@ void size_k1_windows(xm_handle* h, const CreateOpts& o) {
     h->cols_w_max = wm;
   }
   if (h->cols_w_max < 1 && !h->own_mode) h->cols_ok = false;
+}
+
+// The pipelined K2's live-slot masks (xm_k2_live.hpp), for both of its geometries.  Derived only where this handle's column-tile
+// K1 is the sole writer of the frames that kernel reads: a group's K2 (launch_k2_batch<2> / <2, 2>) reads the slots' frame16,
+// which k_scatter_cols / k_scatter_cols_batch write through cols_cell() with h->tb and h->cols_xr_min, lone frames and groups
+// alike, and which nothing else stores into after the memset of create_slots.  Owner-tile rigs (another flush, a sheared frame),
+// rigs without column tiles and "XM_K2_LIVE"=0 get all ones.  After classify_rig and size_k1_windows: both decide cols_ok.
+int build_k2_live(xm_handle* h, const CreateOpts& o) {
+  const xm_config* cfg = &h->cfg;
+  const bool derive = h->k2_live && h->cols_ok && !h->own_mode && h->k2_pipe_rig_ok;
+  for (int g = 1; g < 3; ++g) {
+    const std::vector<int4>& tiles = o.k2_tiles[g];
+    if (tiles.empty()) {  // (a rig without a projector map has no K2 tables at all; with them, the pipelined kernel must find its masks)
+      if (h->d_k2_tiles[g]) return fail(XM_ERR_INVALID, "no tile records for the pipelined K2's live-slot masks (geometry %d)", g);
+      continue;
+    }
+    std::vector<uint32_t> mask(tiles.size() * (size_t)K2L_WORDS, ~0u);
+    if (derive) {
+      static_assert(K2L_THREADS == K2_TX * K2_TY && K2L_UN == K2P_UN && sizeof(K2LiveTile) == sizeof(int4), "xm_k2_live.hpp restates the loader's geometry");
+      K2LiveRig rig;
+      rig.xmap = cfg->proj_x_map; rig.xmap_w = cfg->xmap_width; rig.xmap_h = cfg->xmap_height;
+      rig.x_offset = cfg->x_offset; rig.xr_min = h->cols_xr_min; rig.rect_w = cfg->rect_width; rig.rect_h = cfg->rect_height;
+      rig.shear_m = h->tb.shear_m; rig.shear_bias = h->tb.shear_bias; rig.shear_extra = h->tb.shear_extra;
+      std::vector<K2LiveTile> recs(tiles.size());
+      for (size_t i = 0; i < tiles.size(); ++i) recs[i] = K2LiveTile{tiles[i].x, tiles[i].y, tiles[i].z, tiles[i].w};
+      k2_live_mask(rig, recs.data(), recs.size(), mask);
+      if (h->k2_live_report) {
+        const K2LiveStats st = k2_live_stats(rig, recs.data(), recs.size());
+        fprintf(stderr, "[xm] K2 live quads, tiles of %d x 16 pixels: frame cells %.4f quads %.4f lines %.4f; loader slots %.4f, their lines %.4f\n",
+                16 << g, st.cells, st.quads, st.lines, st.slot_quads, st.slot_lines);
+      }
+    }
+    HIP_TRY(h->d_k2_live[g].alloc(mask.size() / 4));
+    HIP_TRY(hipMemcpy(h->d_k2_live[g], mask.data(), mask.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  }
+  return XM_OK;
 }
 
 // the slot states, then per slot: its stream, key frames, flags; every slot reset on its own stream

@@ -166,6 +166,11 @@ struct xm_handle {
   DevMem<int4> d_k2_tiles[3];  // [g]: tiles of 16 << g pixels x 16 rows (owners; tb.k2_tiles1 / tb.k2_tiles view [0] / [1])
   DevMem<u32> d_k2_pix[3];     // (owners; tb.k2_pix1 / tb.k2_pix view [0] / [1])
   DevMem<uint16_t> d_k2_pix16[3];  // the pipelined K2's copy: u16, rows padded to k2_pix_stride
+  // the pipelined K2's live-slot masks (xm_k2_live.hpp): per tile, wave and loader register the lanes whose quad some (row, time
+  // column) pair of the column tiles can store into; all ones where that is not known (owner tiles, "XM_K2_LIVE"=0)
+  DevMem<uint4> d_k2_live[3];
+  bool k2_live = true;                 // "XM_K2_LIVE"=0: all ones (the same kernel, for tests and A/B runs)
+  bool k2_live_report = false;         // "XM_K2_LIVE"=2: the derived masks, and their live fractions on stderr (profiles)
   int k2_pix_stride = 0;
   int k2_consec = -1;  // k_frame_proj_pipe<PPT, true>: PPT consecutive pixels per thread; -1 = where it measured faster (PPT = 4), XM_K2_CONSEC=0|1 forces
   int k2_tile_cap[3] = {K2_TILE_MAX, K2_TILE_MAX, K2_TILE_MAX};  // cells of the largest K2 patch (multiple of 8)

@@ -274,7 +274,7 @@ bool launch_k2_pipe(xm_handle* h, hipStream_t stream, const FrameDesc* d_descs, 
 #define XM_K2P_LAUNCH(P, C)                                                                                                          \
   XM_LAUNCH((k_frame_proj_pipe<P, C, COND>), dim3(blocks), dim3(K2_TX * K2_TY), lds, stream, d_descs, (const int4*)h->d_k2_tiles[g],      \
             (const u32*)h->d_k2_pix[g], (const uint16_t*)h->d_k2_pix16[g], h->k2_pix_stride, h->tb.dlut, pa, h->k2_tile_cap[g],      \
-            (u32)n_frames, gx, gy, h->k2_pipe_nlds, gx_magic)
+            (u32)n_frames, gx, gy, h->k2_pipe_nlds, gx_magic, (const uint4*)h->d_k2_live[g])
   std::unique_lock<std::mutex> chain_lock(h->k2_chain_mu, std::defer_lock);
   if (h->k2_chain && COND == 0) {  // one K2 at a time: wait for the one launched last (whatever its stream)
     chain_lock.lock();

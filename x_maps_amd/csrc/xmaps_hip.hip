@@ -45,6 +45,7 @@ using namespace xm;
 #include "host/xm_host.hpp"         // errors, slots, launch workers, the handle, launch macros
 #include "host/xm_launch.hpp"       // launch helpers of every kernel variant
 #include "host/xm_own_plan.hpp"     // owner-tile tables (host analysis in xm_create)
+#include "host/xm_k2_live.hpp"      // the frame quads the column tiles can ever write -> the pipelined K2's live-slot masks (standard C++ only)
 #include "host/xm_enqueue.hpp"      // path selection + the launches of one frame
 #include "host/xm_batch.hpp"        // multi-frame launches (groups)
 #include "host/xm_workers.hpp"      // redo of failed shortcuts, launch workers, single-frame entry

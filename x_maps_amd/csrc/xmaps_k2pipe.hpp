@@ -15,7 +15,10 @@
 //     (frame_proj_tiled_body, FMT = 2): same tables (k2_tiles / k2_pix), same arithmetic, same outputs;
 //   * patches that stick out of the frame load zeros for the octets outside (patch rows start on a multiple of 8 and so does
 //     the frame's height: an octet is inside or outside as a whole); a rig with a patch of more than 128 rows or more quads than
-//     the loader's registers hold keeps the one-block-per-tile kernel (k2_pipe_tile_ok, checked once in xm_create).
+//     the loader's registers hold keeps the one-block-per-tile kernel (k2_pipe_tile_ok, checked once in xm_create);
+//   * a 16-byte quad of the frame that no (row, time column) pair of the column tiles can ever store into is zero from xm_create
+//     on: its slot is not loaded either (k2_live: one bit per tile and loader slot, built once per handle on the host --
+//     host/xm_k2_live.hpp; at C-1M 59 % of the quads).  Rigs whose frame has another writer (owner tiles) get all ones.
 #pragma once
 #include "xmaps_common.hpp"
 #include "xmaps_k2.hpp"      // K2_TX / K2_TY, k2_rowmax8, the tile tables of k_build_k2_tables
@@ -26,6 +29,7 @@ namespace xm {
 // 16-byte patch loads per thread kept in registers: thread slot s = tid + j * 256 holds quad s of the patch in memory order
 // (column s / oct, row octet s % oct, oct = rows / 8), so a patch of q quads needs ceil(q / 256) of them: four cover 8192 cells
 constexpr int K2P_UN = 4;
+static_assert(K2P_UN % 2 == 0, "the live masks come as 16-byte pairs of loader registers");
 
 // Can every tile of the rig take the pipelined kernel?  (decided once in xm_create from the tile table; rows a multiple of 8 --
 // then every 8-row octet of a patch lies entirely inside or outside the frame -- and at most 128)
@@ -37,6 +41,16 @@ __host__ __device__ inline bool k2_pipe_tile_ok(const int4& rec) {
 // memory operation (s_waitcnt vmcnt(0)) -- including the next item's patch loads that are meant to stay in flight across it.
 // This one waits for the wave's LDS operations and joins the barrier; the prefetched registers are waited for where they are used.
 __device__ __forceinline__ void k2p_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// This lane's bit of a wave-uniform 64-bit lane mask {lo, hi}: the mask sits in scalar registers and becomes the branch's
+// execution mask as it is -- no vector instruction, no vector register.
+__device__ __forceinline__ bool k2p_lane_bit(u32 lo, u32 hi) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_inverse_ballot_w64(((unsigned long long)hi << 32) | (unsigned long long)lo);
+#else
+  return (lo | hi) != 0;  // (host pass: the body is only parsed)
+#endif
+}
 
 // the output frames are written once and not read again by any kernel: XM_K2P_NT = 1 marks their stores non-temporal (experiment)
 #ifndef XM_K2P_NT
@@ -95,7 +109,7 @@ __global__ __launch_bounds__(K2_TX* K2_TY) void k_frame_proj_pipe(const FrameDes
                                                                 const u32* __restrict__ k2_pix, const uint16_t* __restrict__ k2_pix16,
                                                                 int pix_stride, const uint2* __restrict__ dlut,
                                                                 K2PipeArgs a, int tile_cap, u32 n_frames, u32 grid_x, u32 grid_y,
-                                                                int n_lds, u32 gx_magic) {
+                                                                int n_lds, u32 gx_magic, const uint4* __restrict__ k2_live) {
   // (the tables are kernel parameters of their own, __restrict__: block-uniform reads of them become scalar loads -- as members
   //  of a struct they were vector loads, each with a full wait in front of the prefetch.  Pointers read from a frame descriptor
   //  are cast to the global address space: generic ones make FLAT loads / stores, which count against the LDS counter too, and
@@ -106,6 +120,7 @@ __global__ __launch_bounds__(K2_TX* K2_TY) void k_frame_proj_pipe(const FrameDes
   uint2* s_dlut = reinterpret_cast<uint2*>(k2_lds + ((tile_cap + 32 + 7) & ~7));  // [n_lds] {f32 depth bits, BGR word}
   __shared__ __attribute__((aligned(16))) uint8_t s_out[K2_TY][K2_TW * 3];
   const int tid = threadIdx.x, tx = tid & (K2_TX - 1), ty = tid / K2_TX;
+  const u32 wave = __builtin_amdgcn_readfirstlane((u32)tid >> 6);  // (uniform: the live masks below are scalar loads)
   const u32 tpf = grid_x * grid_y;
   for (int i = tid; i < n_lds; i += NT) s_dlut[i] = dlut[i];  // (n_lds covers every disparity of the rig; visible after the first barrier)
 
@@ -148,6 +163,19 @@ __global__ __launch_bounds__(K2_TX* K2_TY) void k_frame_proj_pipe(const FrameDes
   // outside the frame is not loaded: it reads as zeros) and the pixels' offsets into the patch
   constexpr int NP = CONSEC ? PPT / 2 : PPT;  // registers that hold a thread's patch offsets (CONSEC: u16 pairs)
   const auto issue = [&](const Meta& m, u32 (&poff)[NP]) {
+    // k2_live[lin][wave]: per loader register j the wave's 64 lanes, {lo, hi}: slot tid + j * 256 holds a live quad.  Block-uniform
+    // scalar loads, here and not with the tile record in meta_at: held in the item's Meta they cost <4, true, 0> four spilled
+    // scalar registers and the ESL-like step 1 - 2.6 %.  (readfirstlane is a no-op on the uniform value; it keeps the loads in
+    // front of the slots' branches instead of one dependent scalar round trip inside each)
+    uint4 live[K2P_UN / 2];
+    {
+      const uint4* lp = k2_live + (m.lin * (u32)(NT / 64) + wave) * (u32)(K2P_UN / 2);
+#pragma unroll
+      for (int q = 0; q < K2P_UN / 2; ++q) {
+        const uint4 w = lp[q];
+        live[q] = make_uint4(__builtin_amdgcn_readfirstlane(w.x), __builtin_amdgcn_readfirstlane(w.y), __builtin_amdgcn_readfirstlane(w.z), __builtin_amdgcn_readfirstlane(w.w));
+      }
+    }
     const u32 tile_y = m.tile_y, tile_x = m.tile_x;
     const int v = tile_y * K2_TY + ty;
     if constexpr (CONSEC) {  // (poff[] holds the PPT u16 offsets packed in pairs; the rest of it stays ~0)
@@ -183,7 +211,9 @@ __global__ __launch_bounds__(K2_TX* K2_TY) void k_frame_proj_pipe(const FrameDes
     for (int j = 0; j < UN; ++j) {
       const int sj = tid + j * NT, c = (int)(((float)sj + 0.5f) * inv_oct), ro = sj - __mul24(c, oct);
       const int gx = bx + c, gy = by + 8 * ro;
-      const bool has = sj < nslot && (u32)gx < (u32)a.rect_w && (u32)gy < (u32)a.rect_h;  // (rect_h % 8 == 0)
+      const uint4 lq = live[j >> 1];
+      // (rect_h % 8 == 0; a dead quad -- no pair of the column tiles ever stores into it -- reads as the zeros it holds)
+      const bool has = sj < nslot && (u32)gx < (u32)a.rect_w && (u32)gy < (u32)a.rect_h && k2p_lane_bit(j & 1 ? lq.z : lq.x, j & 1 ? lq.w : lq.y);
       K[j] = make_uint4(0, 0, 0, 0);
       if (XM_K2P_EMU_COMPACT || XM_CABL(21)) {  // (experiments, bit 21 / -DXM_K2P_EMU_COMPACT=1: the traffic of a COMPACT frame -- 41 % of the quads, contiguous per tile, 1.35 x overlap)
         const int live = (nslot * 105) >> 8, per_tile = (live * 190) >> 8;
