@@ -276,6 +276,13 @@ int xm_debug_last_disp_frame(xm_handle* h, uint16_t* out_host);
 /* tests: frames finished by the software-pipelined K2 (groups on the u16 frame) since xm_create; XM_K2_PIPE=2 in the environment
  * sends every group there, XM_K2_PIPE=0 none. */
 int xm_debug_k2_pipe_frames(xm_handle* h, uint64_t* count);
+/* tests: the group frame kernel (the pipelined K2 where it takes the group -- xm_debug_k2_pipe_frames tells --, else the
+ * one-block-per-tile kernel) on n_frames (1 .. 64) caller-supplied u16 disparity frames in host memory, each plain column-major
+ * [rect_width][rect_height] as xm_shard_finish_u16 takes them; the entry puts them into the slots' (sheared) frame layout.
+ * valid_host (nullable): 0 = frame f is not run, its outputs keep what they held.  depth_out / bgr_out: device pointers, either
+ * may be NULL; frame f writes depth_out + f*H*W and bgr_out + f*H*W*3.  Projector view only.  Synchronous; touches no slot. */
+int xm_debug_k2_group_u16(xm_handle* h, const uint16_t* frames_host, int n_frames, const uint8_t* valid_host,
+                          float* depth_out, uint8_t* bgr_out);
 int xm_debug_event_outputs(xm_handle* h, const uint16_t* x, const uint16_t* y, const void* t, const int16_t* p,
                            size_t n, int t_dtype, int mem, int16_t* xr, int16_t* yr, int16_t* ts, int16_t* disp,
                            uint8_t* mask);

@@ -17,63 +17,11 @@ import pytest
 
 import xmaps_oracle as O
 from x_maps_amd import XMapsEngine
-from x_maps_amd import synthetic as S
+from k2_frame_cases import border_tables, brute_dilate_remap, sparse_frame  # (shared with the pipelined K2's tests)
 
 pytestmark = pytest.mark.gpu
 
 KEY_IDX_SHIFT, KEY_TAG_SHIFT = 16, 44
-
-
-def brute_dilate_remap(rect: np.ndarray, pmap: np.ndarray) -> np.ndarray:
-    """49 taps per output pixel, straight from the definition."""
-    H, W = rect.shape
-    ph, pw = pmap.shape[:2]
-    out = np.zeros((ph, pw), np.float32)
-    for v in range(ph):
-        for u in range(pw):
-            mx, my = int(pmap[v, u, 0]), int(pmap[v, u, 1])
-            if not (0 <= mx < W and 0 <= my < H):
-                continue  # BORDER_CONSTANT 0
-            best = -np.inf
-            for dy in range(-3, 4):
-                for dx in range(-3, 4):
-                    yy, xx = my + dy, mx + dx
-                    if 0 <= yy < H and 0 <= xx < W:
-                        best = max(best, float(rect[yy, xx]))
-            out[v, u] = best
-    return out
-
-
-def border_tables(rect_w, rect_h, proj_w, proj_h, seed):
-    """Tables whose projector map sweeps from 6 px outside the rectified frame on one side to 6 px outside on the other,
-    with every pixel's target jittered -- so targets sit 0,1,2,3 px from each edge and beyond it."""
-    rng = np.random.default_rng(seed)
-    tb = S.make_tables(S.C_TINY)
-    vs, us = np.mgrid[0:proj_h, 0:proj_w].astype(np.float64)
-    mx = np.rint(-6 + us * (rect_w + 12) / max(proj_w - 1, 1) + rng.integers(-2, 3, us.shape))
-    my = np.rint(-6 + vs * (rect_h + 12) / max(proj_h - 1, 1) + rng.integers(-2, 3, vs.shape))
-    # pin a few targets exactly onto the corners / edges
-    mx[0, :4] = [0, 1, 2, 3]
-    my[0, :4] = [0, 0, 0, 0]
-    mx[-1, -4:] = [rect_w - 4, rect_w - 3, rect_w - 2, rect_w - 1]
-    my[-1, -4:] = rect_h - 1
-    mx[1, :3] = [-1, rect_w, 5]
-    my[1, :3] = [5, 5, rect_h]
-    tb.update({"rect_w": rect_w, "rect_h": rect_h, "proj_w": proj_w, "proj_h": proj_h,
-               "disp_proj_mapxy_i16": np.ascontiguousarray(np.stack((mx, my), -1).astype(np.int16)),
-               "proj_x_map": np.zeros((rect_h, tb["proj_x_map"].shape[1]), np.int16)})
-    return tb, rng
-
-
-def sparse_frame(rng, rect_w, rect_h, fill):
-    rect = rng.integers(1, 900, (rect_h, rect_w)).astype(np.float32)
-    rect[rng.random(rect.shape) >= fill] = 0
-    # make sure the border cells themselves carry values (they decide the edge cases)
-    rect[0, :] = rng.integers(1, 900, rect_w)
-    rect[-1, :] = rng.integers(1, 900, rect_w)
-    rect[:, 0] = rng.integers(1, 900, rect_h)
-    rect[:, -1] = rng.integers(1, 900, rect_h)
-    return rect
 
 
 CASES = [(176, 132, 64, 48, 0.05), (151, 101, 50, 37, 0.3), (97, 64, 33, 70, 0.02), (40, 23, 19, 17, 0.5),

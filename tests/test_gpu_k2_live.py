@@ -21,6 +21,7 @@ from conftest import xm_option
 import xmaps_oracle as O
 from x_maps_amd import XMapsEngine
 from x_maps_amd import synthetic as S
+from k2_frame_cases import every_pixel_frames, steep_tables as _steep_tables
 
 pytestmark = pytest.mark.gpu
 
@@ -29,26 +30,6 @@ def _ref(tb, evs):
     x, y, t, _ = S.to_soa(evs)
     r = O.process_ev_frame(tb, x.astype(np.int64), y.astype(np.int64), t)
     return r["depth"], r["bgr"]
-
-
-def _steep_tables(cfg):
-    """One frame column per 3 rows, the 64 time columns 4 frame columns apart: a frame column's live rows come in runs of 3
-    every 12 rows, so many 8-row octets hold exactly one live cell, at their row 0 or their row 7.  The camera LUT follows the
-    X-map (disparities around 30)."""
-    tb = S.make_tables(cfg)
-    rh, n_cols = cfg.rect_h, 64
-    yr, tc = np.mgrid[0:rh, 0:n_cols].astype(np.int64)
-    xmap = (S.X_OFFSET + 60 + 4 * tc + yr // 3).astype(np.int16)
-    xmap[:, 0] = 0
-    xmap[:6, :] = 0
-    xmap[rh - 5:, :] = 0
-    assert xmap.max() - S.X_OFFSET < cfg.rect_w
-    ys, xs = np.mgrid[0:cfg.cam_h, 0:cfg.cam_w].astype(np.float64)
-    rows = tb["cam_mapy_i16"].astype(np.float64)
-    tb["cam_mapx_i16"] = np.ascontiguousarray(np.rint(30.0 + 4.0 * n_cols * (xs / cfg.cam_w) + np.floor(np.clip(rows, 0, rh) / 3.0)).astype(np.int16))
-    tb["proj_x_map"] = np.ascontiguousarray(xmap)
-    tb["x_map_width"], tb["t_px_scale"] = n_cols, n_cols - 1
-    return tb
 
 
 @functools.lru_cache(maxsize=None)
@@ -174,16 +155,7 @@ def test_every_cell_a_camera_pixel_can_reach_holds_a_winner():
     xm_option("XM_K2_PIPE", "2")
     cfg, tb, _, _ = _rig("cols", 256)
     n_cols = tb["proj_x_map"].shape[1]
-    frames = []
-    for k in range(8):
-        ys, xs = np.mgrid[0:cfg.cam_h, k:cfg.cam_w:8]
-        px = xs.size
-        e = np.zeros(n_cols * px, dtype=S.EVENT_CD_DTYPE)
-        e["x"] = np.tile(xs.reshape(-1), n_cols)
-        e["y"] = np.tile(ys.reshape(-1), n_cols)
-        e["t"] = 5_000_000 + np.repeat(np.arange(n_cols, dtype=np.int64), px) * 1_000  # column c exactly: (t - t0) / span * (n_cols - 1) = c
-        e["p"] = 1
-        frames.append(e)
+    frames = every_pixel_frames(tb, cfg)
     assert n_cols * (cfg.cam_w // 8) * cfg.cam_h == len(frames[0]) and (cfg.cam_w // 8) * cfg.cam_h * 16 < 65_527
     refs = [_ref(tb, e) for e in frames]
     assert sum(int(np.count_nonzero(r[0])) for r in refs) > 0

@@ -231,6 +231,59 @@ int xm_debug_k2_pipe_frames(xm_handle* h, uint64_t* count) {
   return XM_OK;
 }
 
+// tests: the group frame kernel (launch_k2_batch<2>: the pipelined K2, or k_frame_proj_tiled_batch<2> where that one does not take
+// the group) on caller-supplied disparity frames, plain [rect_w][rect_h] column-major like xm_shard_finish_u16's.  Every frame gets
+// a device buffer of its own in the slot layout (cell (x, row) at column frame16_col: the inverse of xm_debug_last_disp_frame;
+// cells no (x, row) maps to are zero) and a zeroed scratch SlotState of its own (tag_a = 0, no host flags): no slot's state, tag
+// or frame is touched.  valid_host[f] == 0: FrameDesc.valid = 0, the frame is not run.  Frame f writes depth_out + f * H * W and
+// bgr_out + f * H * W * 3 (device pointers; either may be NULL).  Synchronous.
+int xm_debug_k2_group_u16(xm_handle* h, const uint16_t* frames_host, int n_frames, const uint8_t* valid_host, float* depth_out,
+                          uint8_t* bgr_out) {
+  if (!h || !frames_host) return fail(XM_ERR_INVALID, "NULL argument");
+  if (n_frames < 1 || n_frames > 64) return fail(XM_ERR_INVALID, "n_frames must be in [1, 64]");
+  if (h->cfg.view != XM_VIEW_PROJECTOR || h->k2_direct || !h->d_k2_tiles[1])
+    return fail(XM_ERR_INVALID, "xm_debug_k2_group_u16 needs a projector-view handle with the tiled frame kernel");
+  XM_ENTER(h);
+  const int rw = h->tb.rect_w, rh = h->tb.rect_h;
+  const size_t cells = frame16_cells(h->tb), px = (size_t)h->tb.proj_w * h->tb.proj_h;
+  hipStream_t stream = h->slots[0].stream;
+  DevMem<uint16_t> d_frames;
+  DevMem<SlotState> d_st;
+  DevMem<FrameDesc> d_descs;
+  HIP_TRY(d_frames.alloc(cells * (size_t)n_frames, 64));
+  HIP_TRY(d_st.alloc((size_t)n_frames));
+  HIP_TRY(d_descs.alloc((size_t)n_frames));
+  std::vector<uint16_t> raw(cells * (size_t)n_frames, (uint16_t)0);
+  std::vector<FrameDesc> descs((size_t)n_frames);
+  for (int f = 0; f < n_frames; ++f) {
+    const uint16_t* src = frames_host + (size_t)f * rw * rh;
+    uint16_t* dst = raw.data() + (size_t)f * cells;
+    for (int x = 0; x < rw; ++x)
+      for (int r = 0; r < rh; ++r) {
+        const int col = frame16_col(h->tb, x, r);
+        if (col < 0 || (size_t)col * rh + r >= cells) return fail(XM_ERR_INVALID, "cell (%d, %d) has no place in the sheared frame", x, r);
+        dst[(size_t)col * rh + r] = src[(size_t)x * rh + r];
+      }
+    FrameDesc& d = descs[f];
+    std::memset(&d, 0, sizeof d);
+    d.key_frame = reinterpret_cast<u64*>(d_frames.get() + (size_t)f * cells);
+    d.st = d_st.get() + f;
+    d.depth = depth_out ? depth_out + (size_t)f * px : nullptr;
+    d.bgr = bgr_out ? bgr_out + (size_t)f * px * 3 : nullptr;
+    d.valid = valid_host && !valid_host[f] ? 0u : 1u;
+  }
+  HIP_TRY(hipMemsetAsync(d_frames.get(), 0, cells * (size_t)n_frames * sizeof(uint16_t) + 64, stream));
+  HIP_TRY(hipMemsetAsync(d_st.get(), 0, sizeof(SlotState) * (size_t)n_frames, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  HIP_TRY(hipMemcpy(d_frames.get(), raw.data(), raw.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_descs.get(), descs.data(), descs.size() * sizeof(FrameDesc), hipMemcpyHostToDevice));
+  launch_k2_batch<2>(h, stream, d_descs.get(), n_frames);
+  const hipError_t launched = hipGetLastError();
+  HIP_TRY(hipStreamSynchronize(stream));  // (the buffers are released on return: the kernel has run by then either way)
+  HIP_TRY(launched);
+  return XM_OK;
+}
+
 void* xm_stream(xm_handle* h, int slot) {
   if (!h || slot < 0 || slot >= (int)h->slots.size()) return nullptr;
   return (void*)h->slots[slot].stream;

@@ -53,6 +53,7 @@ void read_create_options(xm_handle* h, CreateOpts& o) {
   }
   if (const char* e = dbg_opt("XM_K2_CHAIN")) h->k2_chain = e[0] != '0';
   if (const char* e = dbg_opt("XM_K2_PER_CU")) h->k2_per_cu_max = std::max(1, atoi(e));
+  if (const char* e = dbg_opt("XM_K2_PIPE_BLOCKS")) h->k2_pipe_blocks = std::max(0, atoi(e));
   if (const char* e = dbg_opt("XM_COLS_LDS_PAD")) h->cols_lds_pad = std::max(0, std::min(64 * 1024, atoi(e)));
   if (const char* e = dbg_opt("XM_K2_LIVE")) {
     h->k2_live = e[0] != '0';

@@ -187,6 +187,7 @@ struct xm_handle {
   std::mutex k2_chain_mu;
   unsigned k2_chain_n = 0;
   bool k2_pipe_force = false;   // XM_K2_PIPE=2 (tests): also for groups too small for the pipeline to matter
+  int k2_pipe_blocks = 0;       // "XM_K2_PIPE_BLOCKS" (tests): at most this many persistent blocks, so that each walks several items; 0 = no cap
   bool k2_pipe = true, k2_pipe_rig_ok = false;  // (rig_ok: every tile's patch fits the pipelined loader, rect_h % 8 == 0)
   DevMem<ulonglong2> d_zero16;  // 16 zero bytes: what K2 reads instead of a clean key-frame line
   DevMem<SlotState> d_states;  // n_slots + 1 (last = aux state for stage / shard calls)

@@ -262,6 +262,7 @@ bool launch_k2_pipe(xm_handle* h, hipStream_t stream, const FrameDesc* d_descs, 
   unsigned blocks = (unsigned)h->n_cus * per_cu / 8 * 8;
   if (total < 3ull * blocks && !h->k2_pipe_force) return false;  // too few items per block for the pipeline to matter: one block per tile
   blocks = (unsigned)std::min<u64>(blocks, std::max<u64>(total, 1));
+  if (h->k2_pipe_blocks > 0) blocks = std::min(blocks, (unsigned)h->k2_pipe_blocks);  // (tests: any grid is legal -- items are (f, b) with stride gridDim.x)
   // divmod(tile, gx) by a multiply in the kernel: exact while tile * gx < 2^32
   const u32 gx_magic = gx > 1 && (u64)gx * gy * gx < (1ull << 32) ? (u32)(((1ull << 32) + gx - 1) / gx) : 0u;
   const bool cs = (h->k2_consec < 0 ? g >= 2 : h->k2_consec != 0) && h->d_k2_pix16[g];  // default: consecutive pixels on the 64 x 16 tiles

@@ -364,6 +364,19 @@ class XMapsEngine:
         N.check(self._lib.xm_debug_last_disp_frame(self._h, out.ctypes.data_as(C.POINTER(C.c_uint16))))
         return out
 
+    def debug_k2_group_u16(self, frames, valid=None, depth_ptr=None, bgr_ptr=None):
+        """tests: the group frame kernel on caller-supplied disparity frames, u16 [n][rect_h][rect_w] (the layout
+        debug_last_disp_frame returns).  valid: per frame, 0 = not run.  depth_ptr / bgr_ptr: device memory for n frames (either
+        may be None); frame f goes to + f*H*W floats / + f*H*W*3 bytes.  Synchronous; touches no slot."""
+        fr = np.asarray(frames)
+        if fr.ndim != 3 or fr.shape[1:] != (self.rect_h, self.rect_w) or fr.dtype != np.uint16:
+            raise ValueError(f"frames must be uint16 [n][{self.rect_h}][{self.rect_w}]")
+        cm = np.ascontiguousarray(fr.transpose(0, 2, 1))  # column-major [col][row], as xm_shard_finish_u16 takes a frame
+        v = None if valid is None else np.ascontiguousarray(valid, dtype=np.uint8)
+        if v is not None and v.shape != (len(cm),):
+            raise ValueError("one valid flag per frame")
+        N.check(self._lib.xm_debug_k2_group_u16(self._h, _ptr(cm), len(cm), _ptr(v), _ptr(depth_ptr), _ptr(bgr_ptr)))
+
     def debug_event_outputs(self, x, y, t, p=None):
         x, y = _coords_u16(x, "x"), _coords_u16(y, "y")
         t, tdt = _time_col(t)
