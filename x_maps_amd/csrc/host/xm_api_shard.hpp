@@ -2,55 +2,39 @@
 // (part of libxmaps_hip.so's host side: included by ../xmaps_hip.hip, one translation unit; see that file for the order)
 #pragma once
 
-extern "C" {
+namespace {
 
-// ---- shards -----------------------------------------------------------------------------------------------
-int xm_shard_minmax(xm_handle* h, const void* t, const int16_t* p, size_t n, int t_dtype, void* minmax_out_host) {
-  if (!h || !minmax_out_host || (n && !t)) return fail(XM_ERR_INVALID, "NULL argument");
-  XM_ENTER(h);
-  Slot& s = h->slots[0];
-  int rc;
-  if ((rc = rearm_aux(h, s.stream, nullptr, 0))) return rc;
-  EventsView ev;
-  ev.t = n ? t : (const void*)h->d_lut; ev.p = p; ev.n = n; ev.t_dtype = t_dtype; ev.use_p = p != nullptr;
-  ev.x = (const uint16_t*)h->d_lut.get(); ev.y = ev.x;
-  launch_minmax(ev, h->aux_st, 2, s.stream);
-  HIP_TRY(hipGetLastError());
-  SlotState hs;
-  HIP_TRY(hipMemcpyAsync(&hs, h->aux_st, sizeof hs, hipMemcpyDeviceToHost, s.stream));
-  HIP_TRY(hipStreamSynchronize(s.stream));
-  switch (t_dtype) {
-    case XM_T_INT64: host_minmax_out<long long>(hs, minmax_out_host); break;
-    case XM_T_FLOAT32: host_minmax_out<float>(hs, minmax_out_host); break;
-    case XM_T_FLOAT64: host_minmax_out<double>(hs, minmax_out_host); break;
-    default: return fail(XM_ERR_INVALID, "unknown t_dtype");
-  }
-  return XM_OK;
-}
-
-int xm_shard_minmax_device(xm_handle* h, const void* t, const int16_t* p, size_t n, int t_dtype, void* mm_dev) {
-  if (!h || !mm_dev || (n && !t)) return fail(XM_ERR_INVALID, "NULL argument");
+// both xm_shard_minmax*: the shard's extrema to the host (synchronises), or as {tmin, -tmax} into device memory
+int shard_minmax(xm_handle* h, const void* t, const int16_t* p, size_t n, int t_dtype, void* out_host, void* out_dev) {
+  if (!h || !(out_host || out_dev) || (n && !t)) return fail(XM_ERR_INVALID, "NULL argument");
   if (t_dtype != XM_T_INT64 && t_dtype != XM_T_FLOAT32 && t_dtype != XM_T_FLOAT64) return fail(XM_ERR_INVALID, "unknown t_dtype");
   XM_ENTER(h);
-  Slot& s = h->slots[0];
+  hipStream_t st = h->slots[0].stream;
   int rc;
-  if ((rc = rearm_aux(h, s.stream, nullptr, 0))) return rc;
+  if ((rc = rearm_aux(h, st, nullptr, 0))) return rc;
   EventsView ev;
   ev.t = n ? t : (const void*)h->d_lut; ev.p = p; ev.n = n; ev.t_dtype = t_dtype; ev.use_p = p != nullptr;
   ev.x = (const uint16_t*)h->d_lut.get(); ev.y = ev.x;
-  launch_minmax(ev, h->aux_st, 2, s.stream);
-  switch (t_dtype) {
-    case XM_T_INT64: hipLaunchKernelGGL(k_minmax_export<long long>, dim3(1), dim3(64), 0, s.stream, h->aux_st, 2u, mm_dev); break;
-    case XM_T_FLOAT32: hipLaunchKernelGGL(k_minmax_export<float>, dim3(1), dim3(64), 0, s.stream, h->aux_st, 2u, mm_dev); break;
-    default: hipLaunchKernelGGL(k_minmax_export<double>, dim3(1), dim3(64), 0, s.stream, h->aux_st, 2u, mm_dev);
+  launch_minmax(ev, h->aux_st, 2, st);
+  SlotState hs;
+  if (out_host) {
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&hs, h->aux_st, sizeof hs, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
   }
+  with_event_types(ev, [&](auto ty) {
+    using T = typename decltype(ty)::T;
+    if (out_host) host_minmax_out<T>(hs, out_host);
+    else hipLaunchKernelGGL(k_minmax_export<T>, dim3(1), dim3(64), 0, st, h->aux_st, 2u, out_dev);
+  });
   HIP_TRY(hipGetLastError());
   return XM_OK;
 }
 
-int xm_shard_scatter_device(xm_handle* h, const uint16_t* x, const uint16_t* y, const void* t, const int16_t* p, size_t n,
-                            int t_dtype, uint64_t idx_offset, const void* frame_mm_dev, uint32_t tag, uint64_t* key_frame) {
-  if (!h || !key_frame || !frame_mm_dev) return fail(XM_ERR_INVALID, "NULL argument");
+// both xm_shard_scatter*: the frame's extrema from the host (mm_host) or read on the device (mm_dev)
+int shard_scatter(xm_handle* h, const uint16_t* x, const uint16_t* y, const void* t, const int16_t* p, size_t n, int t_dtype,
+                  uint64_t idx_offset, const void* mm_host, const void* mm_dev, uint32_t tag, uint64_t* key_frame) {
+  if (!h || !key_frame || !(mm_host || mm_dev)) return fail(XM_ERR_INVALID, "NULL argument");
   if (tag == 0 || tag > KEY_MAX_TAG) return fail(XM_ERR_INVALID, "tag must be in [1, 2^19)");
   XM_ENTER(h);
   if (n == 0) return XM_OK;
@@ -59,43 +43,43 @@ int xm_shard_scatter_device(xm_handle* h, const uint16_t* x, const uint16_t* y, 
   ev.x = x; ev.y = y; ev.t = t; ev.p = p; ev.n = n; ev.t_dtype = t_dtype; ev.use_p = p != nullptr;
   int rc = check_events(ev);
   if (rc) return rc;
-  if ((rc = launch_scatter(h, ev, h->aux_st, tag, idx_offset, 0, 0, (u64*)key_frame, nullptr, h->slots[0].stream, false,
-                           frame_mm_dev)))
-    return rc;
+  u64 lo = 0, hi = 0;
+  if (mm_host)
+    with_event_types(ev, [&](auto ty) {
+      using T = typename decltype(ty)::T;
+      lo = TimeCodec<T>::enc(((const T*)mm_host)[0]);
+      hi = TimeCodec<T>::enc(((const T*)mm_host)[1]);
+    });
+  if ((rc = launch_scatter(h, ev, h->aux_st, tag, idx_offset, lo, hi, (u64*)key_frame, nullptr, h->slots[0].stream, false, mm_dev))) return rc;
   HIP_TRY(hipGetLastError());
   return XM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- shards -----------------------------------------------------------------------------------------------
+int xm_shard_minmax(xm_handle* h, const void* t, const int16_t* p, size_t n, int t_dtype, void* minmax_out_host) {
+  return shard_minmax(h, t, p, n, t_dtype, minmax_out_host, nullptr);
+}
+int xm_shard_minmax_device(xm_handle* h, const void* t, const int16_t* p, size_t n, int t_dtype, void* mm_dev) {
+  return shard_minmax(h, t, p, n, t_dtype, nullptr, mm_dev);
+}
+
+int xm_shard_scatter(xm_handle* h, const uint16_t* x, const uint16_t* y, const void* t, const int16_t* p, size_t n,
+                     int t_dtype, uint64_t idx_offset, const void* frame_minmax_host, uint32_t tag, uint64_t* key_frame) {
+  return shard_scatter(h, x, y, t, p, n, t_dtype, idx_offset, frame_minmax_host, nullptr, tag, key_frame);
+}
+int xm_shard_scatter_device(xm_handle* h, const uint16_t* x, const uint16_t* y, const void* t, const int16_t* p, size_t n,
+                            int t_dtype, uint64_t idx_offset, const void* frame_mm_dev, uint32_t tag, uint64_t* key_frame) {
+  return shard_scatter(h, x, y, t, p, n, t_dtype, idx_offset, nullptr, frame_mm_dev, tag, key_frame);
 }
 
 int xm_shard_clear(xm_handle* h, uint64_t* key_frame) {
   if (!h || !key_frame) return fail(XM_ERR_INVALID, "NULL argument");
   XM_ENTER(h);
   HIP_TRY(hipMemsetAsync(key_frame, 0, h->key_cells * sizeof(u64), h->slots[0].stream));
-  return XM_OK;
-}
-
-int xm_shard_scatter(xm_handle* h, const uint16_t* x, const uint16_t* y, const void* t, const int16_t* p, size_t n,
-                     int t_dtype, uint64_t idx_offset, const void* frame_minmax_host, uint32_t tag, uint64_t* key_frame) {
-  if (!h || !key_frame || !frame_minmax_host) return fail(XM_ERR_INVALID, "NULL argument");
-  if (tag == 0 || tag > KEY_MAX_TAG) return fail(XM_ERR_INVALID, "tag must be in [1, 2^19)");
-  XM_ENTER(h);
-  if (n == 0) return XM_OK;
-  if (idx_offset + n >= XM_KEY_MAX_EVENTS) return fail(XM_ERR_TOO_MANY, "global event index exceeds 2^%d", XM_KEY_IDX_BITS);
-  EventsView ev;
-  ev.x = x; ev.y = y; ev.t = t; ev.p = p; ev.n = n; ev.t_dtype = t_dtype; ev.use_p = p != nullptr;
-  int rc = check_events(ev);
-  if (rc) return rc;
-  u64 lo, hi;
-  switch (t_dtype) {
-    case XM_T_INT64: lo = TimeCodec<long long>::enc(((const long long*)frame_minmax_host)[0]);
-                     hi = TimeCodec<long long>::enc(((const long long*)frame_minmax_host)[1]); break;
-    case XM_T_FLOAT32: lo = TimeCodec<float>::enc(((const float*)frame_minmax_host)[0]);
-                       hi = TimeCodec<float>::enc(((const float*)frame_minmax_host)[1]); break;
-    case XM_T_FLOAT64: lo = TimeCodec<double>::enc(((const double*)frame_minmax_host)[0]);
-                       hi = TimeCodec<double>::enc(((const double*)frame_minmax_host)[1]); break;
-    default: return fail(XM_ERR_INVALID, "unknown t_dtype");
-  }
-  if ((rc = launch_scatter(h, ev, h->aux_st, tag, idx_offset, lo, hi, (u64*)key_frame, nullptr, h->slots[0].stream))) return rc;
-  HIP_TRY(hipGetLastError());
   return XM_OK;
 }
 

@@ -6,11 +6,9 @@
 //                                                         (MPI_Bcast, a file, torch.distributed: x_maps_amd.sharded.ShardComm)
 //   every rank:  xm_shard_comm_create(h, id, rank, world, n_frame_events, &c)     -- collective (ncclCommInitRank on h's device)
 //   per frame:   xm_shard_comm_frame(c, x, y, t, n_own, depth, bgr)               -- ONE call, everything on h's stream, asynchronous:
-//                  pack -> ncclAllGather(headers + last events) -> prepare + boundary pass + column-tile K1
-//                       -> ncclAllReduce(SUM, the u16 frame as int32 pairs) -> frame kernel              (the "columns" merge)
-//                xm_shard_comm_frame_keys(c, x, y, t, p, n_own, first_index, depth, bgr)                  -- the packed keys:
-//                  extrema -> ncclAllReduce(MIN) -> clear + scatter with global indices -> ncclAllReduce(MAX, uint64) -> frame kernel
-//                (any rig, any event order, polarity column; also the redo of frames the columns merge flagged)
+//                the "columns" merge (xm_shard_peers.hpp: shard_exchange_columns, the rank reaching its peers by RCCL alone)
+//                xm_shard_comm_frame_keys(c, x, y, t, p, n_own, first_index, depth, bgr)  -- the packed keys (shard_exchange_keys):
+//                any rig, any event order, polarity column; also the redo of frames the columns merge flagged
 //   now and then: xm_shard_comm_failed(c, &failed)    -- collective + synchronises: did ANY rank flag a columns frame?
 // What a host thread pays per frame is the enqueue of ~8 launches (~15 us) instead of five Python calls and two torch.distributed
 // collectives (~64 us): the frame loop is GPU-bound again, and a C / C++ host (one process per GPU) needs no Python at all.
@@ -19,8 +17,8 @@
 struct xm_shard_comm {
   xm_handle* h = nullptr;
   RcclApi rccl;
-  void* comm = nullptr;
-  int rank = 0, world = 1;
+  ShardPeers peers;                // rccl, the communicator, the rank
+  int world = 1;
   uint64_t n_frame = 0;
   bool cols = false;               // the rig / density takes the column tiles
   size_t cap = 0, send_bytes = 0, reduce_u32 = 0, frame_bytes = 0;
@@ -51,7 +49,7 @@ void xm_shard_comm_destroy(xm_shard_comm* c) {
     (void)hipSetDevice(c->h->cfg.device);
     (void)xm_sync(c->h);
   }
-  if (c->comm && c->rccl.CommDestroy) (void)c->rccl.CommDestroy(c->comm);
+  if (c->peers.comm && c->rccl.CommDestroy) (void)c->rccl.CommDestroy(c->peers.comm);
   delete c;
 }
 
@@ -63,7 +61,8 @@ int xm_shard_comm_create(xm_handle* h, const void* id, int rank, int world, uint
   Owned<xm_shard_comm, xm_shard_comm_destroy> c(new (std::nothrow) xm_shard_comm());
   if (!c) return fail(XM_ERR_NOMEM, "out of host memory");
   c->h = h;
-  c->rank = rank;
+  c->peers.rccl = &c->rccl;
+  c->peers.rank = rank;
   c->world = world;
   c->n_frame = n_frame_events;
   c->rccl = load_rccl();
@@ -93,9 +92,9 @@ int xm_shard_comm_create(xm_handle* h, const void* id, int rank, int world, uint
   }
   RcclApi::UniqueId uid;
   memcpy(uid.bytes, id, sizeof uid.bytes);
-  const int ne = c->rccl.CommInitRank(&c->comm, world, uid, rank);  // (collective: every rank of the id is in here now)
+  const int ne = c->rccl.CommInitRank(&c->peers.comm, world, uid, rank);  // (collective: every rank of the id is in here now)
   if (ne) {
-    c->comm = nullptr;
+    c->peers.comm = nullptr;
     (void)fail(XM_ERR_HIP, "ncclCommInitRank(rank %d of %d) failed: %s", rank, world, c->rccl.err(ne));
     return bail(XM_ERR_HIP);
   }
@@ -115,39 +114,17 @@ int xm_shard_comm_info(xm_shard_comm* c, int* takes_columns, size_t* cap_events,
 int xm_shard_comm_frame(xm_shard_comm* c, uint16_t* x, uint16_t* y, int64_t* t, size_t n_own, float* depth_out, uint8_t* bgr_out) {
   if (!c) return fail(XM_ERR_INVALID, "NULL argument");
   if (!c->cols) return fail(XM_ERR_INVALID, "this rig / frame density does not take the column tiles: xm_shard_comm_frame_keys");
-  xm_handle* h = c->h;
-  hipStream_t st = h->slots[0].stream;
-  int rc, e;
-  if ((rc = xm_shard_cols_pack(h, x, y, t, n_own, c->send, c->cap))) return rc;
-  if ((e = c->rccl.AllGather(c->send, c->gathered, c->send_bytes, RcclApi::Uint8, c->comm, st)))
-    return fail(XM_ERR_HIP, "ncclAllGather(headers + last events) failed: %s", c->rccl.err(e));
-  if ((rc = xm_shard_cols_scatter(h, x, y, t, n_own, c->n_frame, c->gathered, c->send_bytes, c->rank, c->world, c->cap, c->frame16))) return rc;
-  if ((e = c->rccl.AllReduce(c->frame16, c->frame16, c->reduce_u32, RcclApi::Int32, RcclApi::Sum, c->comm, st)))
-    return fail(XM_ERR_HIP, "ncclAllReduce(SUM, u16 frame) failed: %s", c->rccl.err(e));
-  if (depth_out || bgr_out)
-    if ((rc = xm_shard_finish_u16(h, c->frame16, depth_out, bgr_out))) return rc;
-  return XM_OK;
+  const ShardColsBufs bufs{c->cap, c->send_bytes, c->reduce_u32, c->send, c->gathered, c->frame16};
+  return shard_exchange_columns(c->peers, c->h, x, y, t, n_own, c->n_frame, c->world, bufs, depth_out, bgr_out, XM_OK);
 }
 
 int xm_shard_comm_frame_keys(xm_shard_comm* c, const uint16_t* x, const uint16_t* y, const void* t, const int16_t* p, size_t n_own,
                              int t_dtype, uint64_t first_index, float* depth_out, uint8_t* bgr_out) {
   if (!c) return fail(XM_ERR_INVALID, "NULL argument");
-  xm_handle* h = c->h;
-  XM_ENTER(h);
-  hipStream_t st = h->slots[0].stream;
-  if (!c->key) HIP_TRY(c->key.alloc(h->key_cells));
+  XM_ENTER(c->h);
+  if (!c->key) HIP_TRY(c->key.alloc(c->h->key_cells));
   c->tag = c->tag >= 1000 ? 1 : c->tag + 1;  // (the key frame is cleared every frame: any tag in [1, 2^19) would do)
-  int rc, e;
-  if ((rc = xm_shard_minmax_device(h, t, p, n_own, t_dtype, c->mm))) return rc;
-  if ((e = c->rccl.AllReduce(c->mm, c->mm, 2, t_dtype == XM_T_INT64 ? RcclApi::Int64 : RcclApi::Float64, RcclApi::Min, c->comm, st)))
-    return fail(XM_ERR_HIP, "ncclAllReduce(MIN, extrema) failed: %s", c->rccl.err(e));
-  if ((rc = xm_shard_clear(h, c->key))) return rc;
-  if ((rc = xm_shard_scatter_device(h, x, y, t, p, n_own, t_dtype, first_index, c->mm, c->tag, c->key))) return rc;
-  if ((e = c->rccl.AllReduce(c->key, c->key, h->key_cells, RcclApi::Uint64, RcclApi::Max, c->comm, st)))
-    return fail(XM_ERR_HIP, "ncclAllReduce(MAX, key frame) failed: %s", c->rccl.err(e));
-  if (depth_out || bgr_out)
-    if ((rc = xm_shard_finish(h, c->key, c->tag, depth_out, bgr_out))) return rc;
-  return XM_OK;
+  return shard_exchange_keys(c->peers, c->h, x, y, t, p, n_own, t_dtype, first_index, c->mm, c->key, c->tag, depth_out, bgr_out, XM_OK);
 }
 
 // did ANY rank flag a columns frame since the last call?  Collective (every rank calls it at the same point of its frame
@@ -159,8 +136,7 @@ int xm_shard_comm_failed(xm_shard_comm* c, int* failed) {
   if ((rc = xm_shard_cols_failed(h, &mine))) return rc;
   hipStream_t st = h->slots[0].stream;
   HIP_TRY(hipMemcpyAsync(c->flag, &mine, sizeof mine, hipMemcpyHostToDevice, st));
-  const int e = c->rccl.AllReduce(c->flag, c->flag, 1, RcclApi::Int32, RcclApi::Max, c->comm, st);
-  if (e) return fail(XM_ERR_HIP, "ncclAllReduce(MAX, verdicts) failed: %s", c->rccl.err(e));
+  if ((rc = c->peers.all_reduce(c->flag, 1, RcclApi::Int32, RcclApi::Max, st))) return rc;
   int any = 0;
   HIP_TRY(hipMemcpyAsync(&any, c->flag, sizeof any, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));

@@ -151,10 +151,12 @@ int fetch_stats(xm_handle* h, Slot& s, int t_dtype, xm_frame_stats* out) {
   return XM_OK;
 }
 
-int stage_in(DevBuf& b, const void* host, size_t bytes, hipStream_t st) {
-  int rc = b.reserve(bytes ? bytes : 16);
+// (`head` bytes of room in front of the copy, `tail` behind it: the data stand at b.p + head)
+int stage_in(DevBuf& b, const void* host, size_t bytes, hipStream_t st, size_t head = 0, size_t tail = 0) {
+  const size_t room = head + bytes + tail;
+  int rc = b.reserve(room ? room : 16);
   if (rc) return rc;
-  if (bytes) HIP_TRY(hipMemcpyAsync(b.p, host, bytes, hipMemcpyHostToDevice, st));
+  if (bytes) HIP_TRY(hipMemcpyAsync((char*)b.p + head, host, bytes, hipMemcpyHostToDevice, st));
   return XM_OK;
 }
 

@@ -41,6 +41,7 @@ using namespace xm;
 
 // The host side is one translation unit, split by concern (each file closes the namespaces / linkage blocks it opens):
 #include "host/xm_queue.hpp"        // the host threads' job queues and first-error latches (standard C++ only)
+#include "host/xm_agree.hpp"        // the agreement among a sharded handle's device threads (standard C++ only)
 #include "host/xm_res.hpp"          // owners of device / pinned memory, streams and events (RAII)
 #include "host/xm_host.hpp"         // errors, slots, launch workers, the handle, launch macros
 #include "host/xm_launch.hpp"       // launch helpers of every kernel variant
@@ -54,8 +55,9 @@ using namespace xm;
 #include "host/xm_api_graph.hpp"    // hipGraph batches
 #include "host/xm_api_stage.hpp"    // debug + stage API
 #include "host/xm_api_shard.hpp"    // shards (multi-GPU)
-#include "host/xm_api_sharded.hpp"  // one frame over several GPUs of one process (RCCL communicators owned by the handle)
-#include "host/xm_api_shardcomm.hpp"  // one rank of a frame sharded over several processes: the library drives RCCL itself
+#include "host/xm_shard_peers.hpp"  // how a rank reaches its peers (RCCL at run time, agreements, virtual ranks); the two shard exchanges, once
+#include "host/xm_api_sharded.hpp"  // one frame over several GPUs of one process: the devices, their threads, the frame's three steps
+#include "host/xm_api_shardcomm.hpp"  // one rank of a frame sharded over several processes: argument checks + the same exchanges
 #include "host/xm_api_filters.hpp"  // frame event filters, pause detection
 #include "host/xm_api_activity.hpp" // the activity filter alone; its device state (shared with the ingest)
 #include "host/xm_api_evt3.hpp"     // EVT 3.0 / 2.0 decoder on the device
