@@ -703,6 +703,55 @@ int xm_surface_set_cloud_tables(xm_handle* h, const float* mapx_f32, const float
 int xm_process_time_surfaces(xm_handle* h, const void* surfaces, int dtype, int n_surfaces, int mem, float* depth_out,
                              float* cloud_out, xm_surface_stats* stats_out);
 
+/* ---- ESL-init: the baseline of the reference's evaluation table, on the device ------------------------------------------------
+ * What python/eval/compute_depth_esl.py:204-226 computes up to depth_init (the optimisation behind it and MC3D stay out of scope),
+ * for a GROUP of camera time surfaces in one device call.  Per surface:
+ *   1. lo / hi over the non-zero pixels, v' = ((double)v - lo) / (hi - lo), negatives to 0 -- widened to float64 first, exactly
+ *      as xm_process_time_surfaces does (golden G7's convention);
+ *   2. cam_rect[r][c] = v'[my][mx], (mx, my) = cam_to_rect_map[r][c], 0 where the entry lies outside the camera (nearest remap,
+ *      constant border 0);
+ *   3. disparity_init (:72-85): for every rectified pixel with cam_rect > 0 the window proj_rect[r][c + min_disp : c + max_disp],
+ *      clipped at the row's end; candidates = its non-zero entries; with MORE THAN ONE candidate the disparity is (column of the
+ *      FIRST minimum of ((double)p - e)^2, float64, no contraction) - c, otherwise 0;
+ *   4. disp_cam[y][x] = disparity[ry][rx], (rx, ry) = rect_to_cam_map[y][x], 0 outside the rectified frame;
+ *   5. depth = (float)(p1_03 / (double)disp_cam), 0 where the disparity is 0 (never inf).
+ * The fused kernel searches only the rectified pixels step 4 references and materialises no rectified image; results equal the
+ * staged composition bit for bit (golden G11 pins step 3 against the reference's own code).  No kernel has atomics or waits for
+ * another block.  UNPINNED: the float -> int16 rounding of the two maps is the table builder's (x_maps_amd/esl_init.py, np.rint
+ * like every other map here), not checked against a cv2.remap(INTER_NEAREST) run.
+ * Defined, not errors: an all-zero surface and one with hi == lo search nothing -- zero maps, n_searched 0, visible in the
+ * statistics.  NaN / +-inf surfaces are out of contract; they neither fault nor index outside a table.
+ * No xm_handle is involved: like xm_build_x_map / xm_eval_stats these take a device ordinal.  An object serves one thread at a time. */
+typedef struct xm_esl_init xm_esl_init;
+typedef struct xm_esl_init_config {
+  uint32_t struct_size; /* sizeof(xm_esl_init_config) */
+  int32_t cam_width, cam_height;
+  int32_t rect_width, rect_height; /* the reference: 3 x the projector */
+  int32_t min_disp, max_disp;      /* 0, 0 = the reference's 5, 900; invalid: min_disp < 0, max_disp <= min_disp, max_disp > 65535 */
+  int32_t reserved;
+  double p1_03;                    /* P1[0, 3] of the rectification (either sign; 0 is allowed and gives zero depth) */
+  const int16_t* cam_to_rect_map;  /* host, [rect_height][rect_width][2] (x, y): rectified pixel -> camera pixel   */
+  const int16_t* rect_to_cam_map;  /* host, [cam_height][cam_width][2]  (x, y): camera pixel -> rectified pixel    */
+  const float* proj_rect;          /* host, [rect_height][rect_width]: the rectified projector time surface, 0 = no data */
+} xm_esl_init_config;              /* the three tables are copied to the device; the caller keeps ownership */
+typedef struct xm_esl_init_stats {
+  uint64_t n_nonzero;  /* pixels != 0                                                                        */
+  uint64_t n_searched; /* camera pixels whose rectified pixel holds v' > 0 (their windows were walked)       */
+  uint64_t n_matched;  /* ... of which the disparity is non-zero                                             */
+  double lo, hi;       /* extrema of the non-zero pixels (0, 0 for an all-zero surface)                      */
+} xm_esl_init_stats;
+int xm_esl_init_create(int device, const xm_esl_init_config* cfg, xm_esl_init** out);
+void xm_esl_init_destroy(xm_esl_init* e);
+/* surfaces: [n_surfaces][cam_height][cam_width], XM_T_FLOAT32 or XM_T_FLOAT64.  depth_out: f32, the same shape.  disp_cam_out
+ * (may be NULL): u16, the same shape.  stats_out (may be NULL): xm_esl_init_stats[n_surfaces].  mem == XM_MEM_HOST: every pointer
+ * is host memory; XM_MEM_DEVICE: every pointer is device memory of the object's device.  Synchronous in both: the results are
+ * there when the call returns.  Scratch is allocated by the first call and grown when a larger group arrives. */
+int xm_esl_init_time_surfaces(xm_esl_init* e, const void* surfaces, int dtype, int n_surfaces, int mem, float* depth_out,
+                              uint16_t* disp_cam_out, xm_esl_init_stats* stats_out);
+/* Step 3 alone, on a caller-supplied rectified camera image (host, f64 [rect_height][rect_width]) against the object's proj_rect:
+ * the reference's disparity_init as a function -> u16 [rect_height][rect_width] (host).  Synchronous. */
+int xm_esl_init_stage_disparity(xm_esl_init* e, const double* cam_rect_host, uint16_t* disparity_rect_out);
+
 /* ---- pinned host memory for XM_MEM_HOST_PINNED ------------------------------------------------------------- */
 int xm_host_alloc(xm_handle* h, size_t bytes, void** out);
 int xm_host_free(xm_handle* h, void* p);

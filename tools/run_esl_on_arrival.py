@@ -16,8 +16,10 @@ Part B -- the accuracy row (eval/x-map-eval.sh:24-72 -> python/eval/compute_dept
 python/eval/create_evaluation_table.py:84-180): every `<scans>/scans_np/*.npy` time surface -> X-maps depth in camera view on
 the evaluation's tables (from_ESL_yaml, rect = 3 x projector, scan downwards) -> `<scans>/x_maps/depth_init/scansNNN.npy`
 (+ point clouds as PLY with --point-clouds), then fill rate / RMSE against `<scans>/esl/depth_optim_filtered/*.npy` -- the
-table's ground truth, which the reference's ESL baseline writes (out of scope here: without it the depth maps are written and
-the row is reported as not computable) -- next to the published Book-Duck cell, FR 0.91 / RMSE 0.31 cm.
+table's ground truth, which the reference's ESL optimisation writes (out of scope here: without it the depth maps are written and
+the row is reported as not computable) -- next to the published Book-Duck cell, FR 0.91 / RMSE 0.31 cm.  With --esl-init the
+same scans also go through the ESL-init baseline on the device (x_maps_amd/esl_init.py) -> `<scans>/esl/depth_init/scansNNN.npy`
+and the table's "ESL (init)" row is printed beside the X-maps one.
 
 Tables come from the cv2-free builder (x_maps_amd/calibration.py: rectifying rotations pinned to OpenCV's on this calibration,
 map rounding unpinned): a difference from the published numbers on the real data is therefore a finding about that builder or
@@ -170,6 +172,43 @@ def depth_from_scans(object_dir, eval_calib, proj_w, proj_h, num_scans=0, start_
             "reference_published_ms_per_frame": PUBLISHED["ms_per_frame"], "depth_dir": depth_dir}
 
 
+def esl_init_from_scans(object_dir, eval_calib, proj_w, proj_h, num_scans=0, start_scan=0, device=0, tables=None, group=8):
+    """Part B for the baseline: compute_depth_esl.py:179-226 up to depth_init.  Every scan of <scans>/scans_np through
+    x_maps_amd.esl_init in groups of `group` -> <scans>/esl/depth_init/scansNNN.npy (an all-zero scan is skipped, :205).  -> report"""
+    from x_maps_amd import calibration as C
+    from x_maps_amd.esl_init import EslInit, build_esl_init_tables
+    names = sorted(glob.glob(os.path.join(object_dir, "scans_np", "*.npy")))
+    if not names:
+        return {"error": f"no camera files found in {os.path.join(object_dir, 'scans_np')}"}
+    depth_dir = os.path.join(object_dir, "esl", "depth_init")
+    os.makedirs(depth_dir, exist_ok=True)
+    t0 = time.perf_counter()
+    if tables is None:
+        tables = build_esl_init_tables(C.CamProjCalibrationParams.from_ESL_yaml(eval_calib, 640, 480, proj_w, proj_h))
+    last = len(names) if not num_scans else min(len(names), start_scan + num_scans)
+    per, skipped, filled = [], 0, []
+    with EslInit(tables, device=device) as esl:
+        t_setup = time.perf_counter() - t0
+        for g0 in range(start_scan, last, max(1, group)):
+            idx = range(g0, min(last, g0 + max(1, group)))
+            surfs = [np.load(names[i]) for i in idx]
+            c0 = time.perf_counter()
+            out = esl.depths_from_time_surfaces(surfs)
+            dt = (time.perf_counter() - c0) / len(idx)
+            for i, (depth, _, st) in zip(idx, out):
+                if st.n_nonzero == 0:
+                    skipped += 1
+                    continue
+                per.append(dt)
+                np.save(os.path.join(depth_dir, "scans" + str(i).zfill(3) + ".npy"), depth)
+                filled.append(float((depth > 0).mean()))
+    return {"scans_found": len(names), "scans_processed": len(per), "scans_empty": skipped, "setup_seconds": round(t_setup, 3),
+            "ms_per_scan_depth_init": round(float(np.mean(per)) * 1e3, 4) if per else None,
+            "mean_fraction_of_pixels_with_depth": round(float(np.mean(filled)), 4) if filled else None,
+            "paper_esl_init_ms_rtx4090": 18.99, "depth_dir": depth_dir,
+            "unpinned": "the int16 rounding of the two remap tables (np.rint) has not been compared with a cv2.remap run"}
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--raw", help="Prophesee RAW recording (EVT 3.0 / 2.0), e.g. /ESL_data/static/seq1/data.raw")
@@ -192,6 +231,8 @@ def main(argv=None):
     ap.add_argument("--surfaces-on-device", action="store_true",
                     help="part B: the scans go through the time-surface entry in groups (one device call per group)")
     ap.add_argument("--surface-group", type=int, default=8, help="scans per group with --surfaces-on-device")
+    ap.add_argument("--esl-init", action="store_true",
+                    help="part B: also write <scans>/esl/depth_init/scansNNN.npy (the ESL-init baseline on the device) and print its row")
     ap.add_argument("--min-depth", type=float, default=20)
     ap.add_argument("--max-depth", type=float, default=500, help="eval/x-map-eval.sh:72 passes 500 (the table script's own default is 120)")
     ap.add_argument("--save-frames", type=int, default=0, help="part A: keep the first N BGR frames as frame_NNN.npy beside --out")
@@ -226,6 +267,12 @@ def main(argv=None):
             row = x_maps_table_row(a.scans, a.min_depth, a.max_depth, device=a.device)
             row["published_cell_seq1"] = "{fill_rate} & {rmse_cm}".format(**PUBLISHED["seq1_book_duck"])
             report["table_1_row_x_maps"] = row
+        if a.esl_init:
+            report["esl_init_from_scans"] = esl_init_from_scans(a.scans, a.eval_calib, a.projector_width, a.projector_height,
+                                                                a.num_scans, a.start_scan, a.device, group=a.surface_group)
+            if "error" not in report["esl_init_from_scans"]:
+                from x_maps_amd.eval_table import esl_init_table_row
+                report["table_1_row_esl_init"] = esl_init_table_row(a.scans, a.min_depth, a.max_depth, device=a.device)
     txt = json.dumps(report, indent=1)
     print(txt)
     if a.out:

@@ -135,6 +135,18 @@ class xm_surface_stats(C.Structure):
                 ("lo", C.c_double), ("hi", C.c_double), ("t_min", C.c_double), ("t_max", C.c_double)]
 
 
+class xm_esl_init_config(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("cam_width", C.c_int32), ("cam_height", C.c_int32),
+                ("rect_width", C.c_int32), ("rect_height", C.c_int32), ("min_disp", C.c_int32), ("max_disp", C.c_int32),
+                ("reserved", C.c_int32), ("p1_03", C.c_double),
+                ("cam_to_rect_map", C.c_void_p), ("rect_to_cam_map", C.c_void_p), ("proj_rect", C.c_void_p)]
+
+
+class xm_esl_init_stats(C.Structure):
+    _fields_ = [("n_nonzero", C.c_uint64), ("n_searched", C.c_uint64), ("n_matched", C.c_uint64),
+                ("lo", C.c_double), ("hi", C.c_double)]
+
+
 # every symbol include/xmaps.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -239,6 +251,10 @@ SYMBOLS = {
     "xm_build_x_map": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "xm_surface_set_cloud_tables": (C.c_int, [_P, _P, _P, _P]),
     "xm_process_time_surfaces": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "xm_esl_init_create": (C.c_int, [C.c_int, C.POINTER(xm_esl_init_config), C.POINTER(_P)]),
+    "xm_esl_init_destroy": (None, [_P]),
+    "xm_esl_init_time_surfaces": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "xm_esl_init_stage_disparity": (C.c_int, [_P, _P, _P]),
     "xm_stream": (_P, [_P, C.c_int]),
     "xm_host_alloc": (C.c_int, [_P, C.c_size_t, C.POINTER(_P)]),
     "xm_host_free": (C.c_int, [_P, _P]),

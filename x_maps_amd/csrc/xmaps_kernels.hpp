@@ -32,3 +32,4 @@
 #include "xmaps_filters.hpp"    // frame event filters, pause detection
 #include "xmaps_eval.hpp"       // evaluation metrics
 #include "xmaps_slots.hpp"      // slot reset, redo preparation
+#include "xmaps_eslinit.hpp"    // the ESL-init baseline: disparity search per rectified / per camera pixel (brings xmaps_surface.hpp)

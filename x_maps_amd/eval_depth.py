@@ -13,8 +13,10 @@ depth maps and point clouds out, nothing on the host in between, no atomics; cam
 before normalising it (the reference normalises a float32 file in float32: the last bit of t can differ; golden G7 pins
 this build's choice), and both give the same depth maps and clouds bit for bit.
 
-Out of scope: file handling, the ESL and MC3D baselines and the ground truth they produce, a projector-view
-surface path.  (The metrics of eval/ are in eval_metrics.py.)
+The baseline of the same evaluation, ESL-init (compute_depth_esl.py up to depth_init), takes the same surfaces: esl_init.py.
+
+Out of scope: file handling, ESL's optimisation (which produces the table's ground truth) and the MC3D baseline, a
+projector-view surface path.  (The metrics of eval/ are in eval_metrics.py.)
 """
 from __future__ import annotations
 

@@ -1,11 +1,12 @@
-"""The X-maps row of the reference's Table 1, from files on disk (python/eval/create_evaluation_table.py:57-62,84-180 and the
-ground-truth combination it borrows from python/eval/esl_utilities.py:153-175), for one sequence directory laid out as the
+"""The X-maps row and the "ESL (init)" row of the reference's Table 1, from files on disk
+(python/eval/create_evaluation_table.py:57-62,84-180 and the ground-truth combination it borrows from python/eval/esl_utilities.py:153-175), for one sequence directory laid out as the
 reference's evaluation leaves it:
 
     <seq>/scans_np/*.npy                   camera time surfaces (input of compute_depth_x_maps.py)
     <seq>/x_maps/depth_init/scansNNN.npy   X-maps depth per scan        (written by x_maps_amd / tools/run_esl_on_arrival.py)
+    <seq>/esl/depth_init/scansNNN.npy      ESL-init depth per scan      (x_maps_amd.esl_init / tools/run_esl_on_arrival.py --esl-init)
     <seq>/esl/depth_optim_filtered/*.npy   ESL's optimised depth = the table's ground truth (written by the reference's
-                                           compute_depth_esl.py -- a competitor algorithm, out of scope here: when the directory
+                                           compute_depth_esl.py's optimisation -- out of scope here: when the directory
                                            is absent the row cannot be computed and the caller says so)
 
 The metrics themselves run on the GPU (x_maps_amd.eval_metrics, pinned by golden G8); what is restated here is the file-level
@@ -63,19 +64,20 @@ def load_and_filter(filename, gt, min_depth, max_depth):
     return r
 
 
-def x_maps_table_row(seq_dir: str, min_depth: float = 20, max_depth: float = 120, device: int = 0) -> dict:
-    """Mean fill rate / RMSE of <seq>/x_maps/depth_init against <seq>/esl/depth_optim_filtered, scan by scan
-    (create_evaluation_table.py:121-160; its defaults are min 20 / max 120, eval/x-map-eval.sh:72 passes -max_depth 500)."""
+def depth_table_row(seq_dir: str, est_subdir, files_key: str, min_depth: float = 20, max_depth: float = 120, device: int = 0) -> dict:
+    """One row of the table: mean fill rate / RMSE of <seq>/<est_subdir>/*.npy against <seq>/esl/depth_optim_filtered, scan by
+    scan (create_evaluation_table.py:121-180 runs the same lines for every method).  est_subdir: path components below <seq>;
+    files_key: the name under which an error result reports how many estimate files were found."""
     gt_files = sorted(glob.glob(os.path.join(seq_dir, "esl", "depth_optim_filtered", "*.npy")))
-    xm_files = sorted(glob.glob(os.path.join(seq_dir, "x_maps", "depth_init", "*.npy")))
+    est_files = sorted(glob.glob(os.path.join(seq_dir, *est_subdir, "*.npy")))
     if not gt_files:
         return {"error": f"no ground truth under {os.path.join(seq_dir, 'esl', 'depth_optim_filtered')} (the reference's "
-                         f"compute_depth_esl.py writes it; that baseline is out of scope here)", "x_maps_files": len(xm_files)}
-    if len(gt_files) != len(xm_files):
-        return {"error": "frames are missing", "gt_files": len(gt_files), "x_maps_files": len(xm_files)}
+                         f"compute_depth_esl.py writes it; that baseline is out of scope here)", files_key: len(est_files)}
+    if len(gt_files) != len(est_files):
+        return {"error": "frames are missing", "gt_files": len(gt_files), files_key: len(est_files)}
     gt_combined, _, avg_depth = combine_depth_maps(gt_files, min_depth, max_depth)
     rows = []
-    for g, x in zip(gt_files, xm_files):
+    for g, x in zip(gt_files, est_files):
         gt = load_and_filter(g, gt_combined, min_depth, max_depth)
         est = load_and_filter(x, gt_combined, min_depth, max_depth)
         s = evaluation_stats(est, gt, device=device)
@@ -83,3 +85,15 @@ def x_maps_table_row(seq_dir: str, min_depth: float = 20, max_depth: float = 120
     fr, rmse = np.mean(np.array(rows, np.float64), axis=0)
     return {"scans": len(rows), "mean_depth": round(avg_depth, 3), "fill_rate": float(fr), "rmse": float(rmse),
             "table_cell": f"{round(float(fr), 2)} & {round(float(rmse), 2)}"}
+
+
+def x_maps_table_row(seq_dir: str, min_depth: float = 20, max_depth: float = 120, device: int = 0) -> dict:
+    """Mean fill rate / RMSE of <seq>/x_maps/depth_init against <seq>/esl/depth_optim_filtered, scan by scan
+    (create_evaluation_table.py:121-160; its defaults are min 20 / max 120, eval/x-map-eval.sh:72 passes -max_depth 500)."""
+    return depth_table_row(seq_dir, ("x_maps", "depth_init"), "x_maps_files", min_depth, max_depth, device)
+
+
+def esl_init_table_row(seq_dir: str, min_depth: float = 20, max_depth: float = 120, device: int = 0) -> dict:
+    """The "ESL (init)" row (create_evaluation_table.py:143-180): <seq>/esl/depth_init -- what x_maps_amd.esl_init /
+    tools/run_esl_on_arrival.py --esl-init write -- against the same ground truth."""
+    return depth_table_row(seq_dir, ("esl", "depth_init"), "esl_init_files", min_depth, max_depth, device)
