@@ -142,10 +142,7 @@ int xm_sync(xm_handle* h) {
     int rcw = wait_stream(gs);
     if (rcw) return rcw;
   }
-  for (Slot& s : h->slots) {  // every stream is idle: nothing left to order against
-    s.pending_batch_ev = nullptr;
-    s.eager_dirty = false;
-  }
+  for (Slot& s : h->slots) s.order.forget();  // every stream is idle: nothing left to order against
   if (h->try_sorted) {  // frames whose shortcut failed are redone now, then waited for
     for (Slot& s : h->slots) {
       bool redone = false;
@@ -209,11 +206,7 @@ int xm_debug_last_disp_frame(xm_handle* h, uint16_t* out_host) {
   XM_ENTER(h);
   Slot& s = h->slots[h->last_slot];
   if (!s.frame16) return fail(XM_ERR_INVALID, "this handle has no column-tile frames");
-  if (s.pending_batch_ev) {
-    HIP_TRY(hipEventSynchronize(s.pending_batch_ev));
-    s.pending_batch_ev = nullptr;
-  }
-  HIP_TRY(hipStreamSynchronize(s.stream));
+  if (int rc = s.order.host_wait()) return rc;
   const size_t cells = frame16_cells(h->tb);
   std::vector<uint16_t> raw(cells);
   HIP_TRY(hipMemcpy(raw.data(), s.frame16, cells * sizeof(uint16_t), hipMemcpyDeviceToHost));
@@ -318,12 +311,8 @@ int xm_last_frame_stats(xm_handle* h, xm_frame_stats* stats) {
   if (!h || !stats) return fail(XM_ERR_INVALID, "NULL argument");
   XM_ENTER(h);
   Slot& s = h->slots[h->last_slot];
-  if (s.pending_batch_ev) {  // the slot's last frame ran inside a multi-frame launch / graph replay on another stream
-    HIP_TRY(hipEventSynchronize(s.pending_batch_ev));
-    s.pending_batch_ev = nullptr;
-  }
-  HIP_TRY(hipStreamSynchronize(s.stream));
-  return fetch_stats(h, s, s.last_t_dtype, stats);
+  if (int rc = s.order.host_wait()) return rc;  // (its last frame may have run inside a group / a graph replay on another stream)
+  return fetch_stats(h, s, s.last.t_dtype, stats);
 }
 
 int xm_profile_event_overhead(xm_handle* h, int reps, float* ms_out) {
@@ -345,8 +334,7 @@ int xm_profile_event_overhead(xm_handle* h, int reps, float* ms_out) {
 }
 
 // ---- a group of frames in one set of multi-frame launches ---------------------------------------------------
-static int submit_group(xm_handle* h, const std::vector<EventsView>& evs, const std::vector<float*>& dep, const std::vector<uint8_t*>& bg,
-                        float* gpu_ms, hipEvent_t* done_out = nullptr);
+static int submit_group(xm_handle* h, const BatchViews& v, float* gpu_ms, hipEvent_t* done_out = nullptr);
 
 static int process_batch_impl(xm_handle* h, const uint16_t* x, const uint16_t* y, const void* t, const int16_t* p, int t_dtype,
                               const uint64_t* offsets_host, int n_frames, float* depth_out, uint8_t* bgr_out, float* gpu_ms,
@@ -355,35 +343,14 @@ static int process_batch_impl(xm_handle* h, const uint16_t* x, const uint16_t* y
   const int ns = (int)h->slots.size();
   if (n_frames > ns) return fail(XM_ERR_INVALID, "a batch of %d frames needs n_slots >= %d (handle has %d)", n_frames, n_frames, ns);
   XM_ENTER(h);
-  const size_t px = (size_t)h->out_w * h->out_h;
-  const size_t tsz = t_size(t_dtype);
-  std::vector<EventsView> evs(n_frames);
-  std::vector<float*> dep(n_frames);
-  std::vector<uint8_t*> bg(n_frames);
-  for (int f = 0; f < n_frames; ++f) {
-    const u64 a = offsets_host[f], b = offsets_host[f + 1];
-    if (b < a) return fail(XM_ERR_INVALID, "offsets must be non-decreasing");
-    EventsView& ev = evs[f];
-    if (aos) {  // Metavision EventCD records (16 bytes each), every event used
-      ev.aos = (const char*)aos + a * 16;
-      ev.t_dtype = XM_T_INT64;
-    } else {
-      ev.x = x + a; ev.y = y + a; ev.t = (const char*)t + a * tsz; ev.p = p ? p + a : nullptr;
-      ev.t_dtype = t_dtype; ev.use_p = p != nullptr;
-    }
-    ev.n = (size_t)(b - a);
-    int rc = check_events(ev);
-    if (rc) return rc;
-    dep[f] = depth_out ? depth_out + f * px : nullptr;
-    bg[f] = bgr_out ? bgr_out + f * px * 3 : nullptr;
-  }
-  return submit_group(h, evs, dep, bg, gpu_ms);
+  BatchViews v;
+  if (int rc = batch_views(h, x, y, t, p, t_dtype, aos, offsets_host, n_frames, depth_out, bgr_out, v)) return rc;
+  return submit_group(h, v, gpu_ms);
 }
 
-// frames evs[f] -> outputs dep[f] / bg[f] (device pointers) as ONE group on the next n slots: one set of multi-frame launches
-static int submit_group(xm_handle* h, const std::vector<EventsView>& evs, const std::vector<float*>& dep, const std::vector<uint8_t*>& bg,
-                        float* gpu_ms, hipEvent_t* done_out) {
-  const int n_frames = (int)evs.size(), ns = (int)h->slots.size();
+// frames v.evs[f] -> outputs v.dep[f] / v.bg[f] (device pointers) as ONE group on the next n slots: one set of multi-frame launches
+static int submit_group(xm_handle* h, const BatchViews& v, float* gpu_ms, hipEvent_t* done_out) {
+  const int n_frames = (int)v.evs.size(), ns = (int)h->slots.size();
   std::vector<int> idx(n_frames);
   for (int f = 0; f < n_frames; ++f) {
     idx[f] = (h->next_slot + f) % ns;
@@ -402,7 +369,7 @@ static int submit_group(xm_handle* h, const std::vector<EventsView>& evs, const 
   FrameDesc* hd = h->h_descs + (size_t)k * ns;
   FrameDesc* dd = h->d_descs + (size_t)k * ns;
   int kinds[2] = {-1, -1};  // (stay -1 when the group fell back to frame-by-frame launches: nothing was attached then)
-  int rc = enqueue_batch(h, idx.data(), evs.data(), dep.data(), bg.data(), n_frames, stream, hd, dd, true, true,
+  int rc = enqueue_batch(h, idx.data(), v.evs.data(), v.dep.data(), v.bg.data(), n_frames, stream, hd, dd, true, true,
                          gpu_ms ? h->prof_ev : nullptr, kinds);
   if (rc) return rc;
   HIP_TRY(hipEventRecord(h->desc_ev[k], stream));
@@ -412,19 +379,9 @@ static int submit_group(xm_handle* h, const std::vector<EventsView>& evs, const 
   if (done_out) *done_out = done;
   for (int f = 0; f < n_frames; ++f) {
     Slot& s = h->slots[idx[f]];
-    s.pending_batch_ev = done;
-    s.pending_batch_stream = stream;
-    if (s.h_flags) {  // slot gate + try-sorted verdict, read when the slot comes round again or in xm_sync
-      s.prev.valid = true;
-      s.prev.check = h->try_sorted && s.last_sorted;
-      s.prev.ev = evs[f];
-      s.prev.depth = dep[f];
-      s.prev.bgr = bg[f];
-      s.prev.host_depth = nullptr;
-      s.prev.host_bgr = nullptr;
-      s.prev.tag = s.host_tag;
-      s.prev.stream = stream;
-    }
+    s.order.note_group(done, stream);
+    if (s.h_flags)  // slot gate + try-sorted verdict, read when the slot comes round again or in xm_sync
+      s.prev.set(v.evs[f], v.dep[f], v.bg[f], nullptr, nullptr, s.last.host_tag, stream, h->try_sorted && s.last.sorted);
   }
   if (gpu_ms) {  // profile mode: durations of the group's dispatches (the events were attached to the dispatch packets)
     HIP_TRY(hipStreamSynchronize(stream));
@@ -444,17 +401,16 @@ static int submit_group(xm_handle* h, const std::vector<EventsView>& evs, const 
 int flush_pending(xm_handle* h) {
   if (h->pending.empty()) return XM_OK;
   const size_t n = h->pending.size();
-  std::vector<EventsView> evs(n);
-  std::vector<float*> dep(n);
-  std::vector<uint8_t*> bg(n);
-  for (size_t i = 0; i < n; ++i) {
-    evs[i] = h->pending[i].ev;
-    dep[i] = h->pending[i].depth;
-    bg[i] = h->pending[i].bgr;
+  BatchViews v;
+  v.evs.reserve(n), v.dep.reserve(n), v.bg.reserve(n);
+  for (const xm_handle::Deferred& d : h->pending) {
+    v.evs.push_back(d.ev);
+    v.dep.push_back(d.depth);
+    v.bg.push_back(d.bgr);
   }
   h->pending.clear();  // (first: submit_group's callees pass through XM_ENTER-free paths only, but keep re-entry harmless)
   hipEvent_t done = nullptr;
-  int rc = submit_group(h, evs, dep, bg, nullptr, &done);
+  int rc = submit_group(h, v, nullptr, &done);
   if (rc) return rc;
   h->ab_inflight[h->ab_groups & 3] = done;
   h->ab_groups += 1;
@@ -481,6 +437,5 @@ int xm_profile_batch(xm_handle* h, const uint16_t* x, const uint16_t* y, const v
   if (!gpu_ms) return fail(XM_ERR_INVALID, "NULL argument");
   return process_batch_impl(h, x, y, t, p, t_dtype, offsets_host, n_frames, depth_out, bgr_out, gpu_ms);
 }
-
 
 }  // extern "C"

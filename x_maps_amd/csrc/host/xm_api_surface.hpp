@@ -100,7 +100,7 @@ int xm_process_time_surfaces(xm_handle* h, const void* surfaces, int dtype, int 
     XM_LAUNCH(k_surf_cloud, dim3(grid_for(n_seg, BLOCK / 64), (unsigned)n), dim3(BLOCK), 0, stream, (const uint16_t*)code,
               (const u32*)seg_off, tb.cam_w, tb.cam_h, tiles_x, (const float*)sc.mapx.get(), (const float*)sc.mapy.get(), sc.q, d_cloud);
   HIP_TRY(hipGetLastError());
-  s.eager_dirty = true;
+  s.order.note_eager();
 
   if (!host) {
     if (stats_out) HIP_TRY(hipMemcpyAsync(stats_out, d_stats, n * sizeof(SurfStats), hipMemcpyDeviceToDevice, stream));

@@ -1,4 +1,5 @@
-// xm_batch.hpp -- multi-frame launches: one K0 / K1 / K2 launch each for a group of frames (enqueue_batch), frame statistics, host staging
+// xm_batch.hpp -- multi-frame launches: a batch's offsets as one view per frame (batch_views), one K0 / K1 / K2 launch each for a
+// group of frames (enqueue_batch), frame statistics, host staging
 // (part of libxmaps_hip.so's host side: included by ../xmaps_hip.hip, one translation unit; see that file for the order)
 #pragma once
 
@@ -50,6 +51,38 @@ int launch_group(xm_handle* h, const FrameGroup& g, const FramePath& p, hipStrea
   return XM_OK;
 }
 
+// A batch as the API takes it -- columns (or EventCD records, 16 bytes each, every event used) cut into frames by offsets_host[0 ..
+// n_frames], outputs packed frame after frame -- as one EventsView and one pair of output pointers per frame, each checked
+struct BatchViews {
+  std::vector<EventsView> evs;
+  std::vector<float*> dep;
+  std::vector<uint8_t*> bg;
+};
+int batch_views(const xm_handle* h, const uint16_t* x, const uint16_t* y, const void* t, const int16_t* p, int t_dtype, const void* aos,
+                const uint64_t* offsets_host, int n_frames, float* depth_out, uint8_t* bgr_out, BatchViews& v) {
+  const size_t px = (size_t)h->out_w * h->out_h, tsz = t_size(t_dtype);
+  v.evs.assign(n_frames, EventsView{});
+  v.dep.assign(n_frames, nullptr);
+  v.bg.assign(n_frames, nullptr);
+  for (int f = 0; f < n_frames; ++f) {
+    const u64 a = offsets_host[f], b = offsets_host[f + 1];
+    if (b < a) return fail(XM_ERR_INVALID, "offsets must be non-decreasing");
+    EventsView& ev = v.evs[f];
+    if (aos) {
+      ev.aos = (const char*)aos + a * 16;
+      ev.t_dtype = XM_T_INT64;
+    } else {
+      ev.x = x + a; ev.y = y + a; ev.t = (const char*)t + a * tsz; ev.p = p ? p + a : nullptr;
+      ev.t_dtype = t_dtype; ev.use_p = p != nullptr;
+    }
+    ev.n = (size_t)(b - a);
+    if (int rc = check_events(ev)) return rc;
+    if (depth_out) v.dep[f] = depth_out + f * px;
+    if (bgr_out) v.bg[f] = bgr_out + f * px * 3;
+  }
+  return XM_OK;
+}
+
 // Enqueue one group: frame f = evs[f] on slot slot_idx[f], outputs depth[f] / bgr[f] (device pointers), everything on `stream`.
 // d_descs / h_descs: where the group's descriptors live (the caller owns their lifetime).  `upload`: copy them now
 // (eager) -- false when the caller uploads once (graph capture).
@@ -58,37 +91,26 @@ int enqueue_batch(xm_handle* h, const int* slot_idx, const EventsView* evs, floa
                   const Event* prof = nullptr, int* kinds = nullptr, FrameDesc* h_descs_redo = nullptr,
                   FrameDesc* d_descs_redo = nullptr) {
   const FramePath p = frame_path(h, evs, n_frames, allow_sorted, true, d_descs_redo != nullptr);
-  for (int f = 0; f < n_frames; ++f) {  // order the group after whatever its slots did last on other streams
-    Slot& s = h->slots[slot_idx[f]];
-    if (s.pending_batch_ev) {
-      if (s.pending_batch_stream != stream && !h->capturing) HIP_TRY(hipStreamWaitEvent(stream, s.pending_batch_ev, 0));
-      s.pending_batch_ev = nullptr;
-    }
-    if (s.eager_dirty && !h->capturing) {
-      if (s.stream != stream) {
-        HIP_TRY(hipEventRecord(h->join_ev[slot_idx[f]], s.stream));
-        HIP_TRY(hipStreamWaitEvent(stream, h->join_ev[slot_idx[f]], 0));
-      }
-      s.eager_dirty = false;
-    }
-  }
+  for (int f = 0; f < n_frames; ++f)  // order the group after whatever its slots did last on other streams
+    if (int rc = h->slots[slot_idx[f]].order.before(stream, h->capturing)) return rc;
   if (p.per_frame) {  // untiled K2: frame by frame, still on the group's stream
     for (int f = 0; f < n_frames; ++f) {
-      int rc = enqueue_frame(h, h->slots[slot_idx[f]], evs[f], depth[f], bgr[f], nullptr, allow_sorted, stream);
+      Slot& s = h->slots[slot_idx[f]];
+      int rc = enqueue_frame(h, s, evs[f], depth[f], bgr[f], nullptr, allow_sorted, stream);
       if (rc) return rc;
-      h->slots[slot_idx[f]].api_tag = h->slots[slot_idx[f]].host_tag;
+      s.last.api_tag = s.last.host_tag;
     }
     return XM_OK;
   }
   key32_pause_tick(h, n_frames);
   for (int f = 0; f < n_frames; ++f) {
     Slot& s = h->slots[slot_idx[f]];
-    if (s.host_tag >= KEY_MAX_TAG && !h->capturing) {
+    if (s.last.host_tag >= KEY_MAX_TAG && !h->capturing) {
       int rc = reset_slot(h, s, stream);
       if (rc) return rc;
     }
     if (p.key32) {
-      int rc = key32_prepare(h, s, s.host_tag + 1, stream);
+      int rc = key32_prepare(h, s, s.last.host_tag + 1, stream);
       if (rc) return rc;
     }
     FrameDesc& d = h_descs[f];
@@ -133,16 +155,16 @@ void decode_minmax(const SlotState& hs, u32 parity, double& lo, double& hi, bool
 int fetch_stats(xm_handle* h, Slot& s, int t_dtype, xm_frame_stats* out) {
   SlotState hs;
   HIP_TRY(hipMemcpy(&hs, s.st, sizeof hs, hipMemcpyDeviceToHost));
-  const u32 parity = s.host_tag & 1;
+  const u32 parity = s.last.host_tag & 1;
   memset(out, 0, sizeof *out);
-  out->n_events = s.last_n;
+  out->n_events = s.last.n;
   for (int i = 0; i < CNT_SLOTS; ++i) {
     out->n_used += hs.cnt[parity][i][CNT_USED];
     out->n_inliers += hs.cnt[parity][i][CNT_INLIER];
     out->n_index_errors += hs.cnt[parity][i][CNT_OOB];
     out->n_unsorted += hs.cnt[parity][i][CNT_UNSORTED];
   }
-  if (s.last_sorted) out->n_used = s.last_n;  // no polarity column on the time-sorted path; K0 (which counts) did not run
+  if (s.last.sorted) out->n_used = s.last.n;  // no polarity column on the time-sorted path; K0 (which counts) did not run
   bool any;
   if (t_dtype == XM_T_FLOAT32) decode_minmax<float>(hs, parity, out->t_min, out->t_max, any);
   else if (t_dtype == XM_T_FLOAT64) decode_minmax<double>(hs, parity, out->t_min, out->t_max, any);

@@ -402,6 +402,7 @@ int create_batch_rings(xm_handle* h) {
   HIP_TRY(h->fork_ev.create());
   h->join_ev.resize(n_slots);
   for (Event& e : h->join_ev) HIP_TRY(e.create());
+  for (int i = 0; i < n_slots; ++i) h->slots[i].order.bind(h->slots[i].stream.get(), h->join_ev[i].get());
   for (int i = 0; i < n_slots; ++i) HIP_TRY(hipStreamSynchronize(h->slots[i].stream));
   for (int i = 0; i < n_slots; ++i) {
     bool seen = false;

@@ -270,14 +270,14 @@ void key32_pause_tick(xm_handle* h, int frames) {
 // frame `ev` was enqueued on slot s along path p: what the slot's redo and statistics read later, and the path counters.  A group
 // hands its tags to the API at once (api_tag); a lone frame's caller does that itself.
 void note_enqueued(xm_handle* h, Slot& s, const EventsView& ev, const FramePath& p, bool group) {
-  s.host_tag += 1;
-  if (group) s.api_tag = s.host_tag;
-  s.any_frame = true;
-  s.last_n = ev.n;
-  s.last_sorted = p.sorted || p.cols_w != 0;  // (no K0 either on a captured group's column tiles; a lone frame's are sorted)
-  s.last_key32 = p.key32 || p.cols_w;
-  s.last_cols = p.cols_w != 0;
-  s.last_t_dtype = ev.aos ? XM_T_INT64 : ev.t_dtype;
+  Slot::Last& l = s.last;
+  l.host_tag += 1;
+  if (group) l.api_tag = l.host_tag;
+  l.n = ev.n;
+  l.sorted = p.sorted || p.cols_w != 0;  // (no K0 either on a captured group's column tiles; a lone frame's are sorted)
+  l.key32 = p.key32 || p.cols_w;
+  l.cols = p.cols_w != 0;
+  l.t_dtype = ev.aos ? XM_T_INT64 : ev.t_dtype;
   h->path_counts[p.counter()].fetch_add(1, std::memory_order_relaxed);
   if (p.key32 || p.cols_w) key32_note(h, false);
 }
@@ -288,11 +288,10 @@ int enqueue_frame(xm_handle* h, Slot& s, const EventsView& ev, float* depth, uin
   const FramePath p = frame_path(h, &ev, 1, allow_sorted);
   key32_pause_tick(h, 1);
   hipStream_t stream = stream_override ? stream_override : s.stream;
-  if (s.pending_batch_ev) {  // the slot's previous frame ran inside a multi-frame launch, maybe on another stream
-    if (s.pending_batch_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, s.pending_batch_ev, 0));
-    s.pending_batch_ev = nullptr;
-  }
-  if (s.host_tag >= KEY_MAX_TAG) {  // tag field about to wrap: clear the frame once per 2^19 frames
+  // the slot's previous frame may have run inside a group or a replay on another stream (the own stream's eager work: a group's
+  // stream was ordered behind it by enqueue_batch, the own stream needs no order with itself)
+  if (int rc = s.order.before_group_only(stream)) return rc;
+  if (s.last.host_tag >= KEY_MAX_TAG) {  // tag field about to wrap: clear the frame once per 2^19 frames
     int rc = reset_slot(h, s, stream);
     if (rc) return rc;
   }
@@ -312,7 +311,7 @@ int enqueue_frame(xm_handle* h, Slot& s, const EventsView& ev, float* depth, uin
       if (!(skip & 1) && p.cols_w) launch_cols_bounds<E::AOS>(h, fr, p.cols_w, 0, stream);  // K0b takes K0's place (and its profile events)
     }
     if (p.key32) {
-      const int rc_k = key32_prepare(h, s, s.host_tag + 1, stream);
+      const int rc_k = key32_prepare(h, s, s.last.host_tag + 1, stream);
       if (rc_k) return rc_k;
     }
     ps.at(1);
@@ -327,9 +326,8 @@ int enqueue_frame(xm_handle* h, Slot& s, const EventsView& ev, float* depth, uin
   if (!(skip & 4)) launch_frame_kernel(h, fr, p.kmode(), stream);
   HIP_TRY(hipGetLastError());
   note_enqueued(h, s, ev, p, false);
-  if (!stream_override) s.eager_dirty = true;
+  if (!stream_override) s.order.note_eager();
   return XM_OK;
 }
-
 
 }  // namespace

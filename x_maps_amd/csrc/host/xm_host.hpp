@@ -1,4 +1,5 @@
-// xm_host.hpp -- error reporting, device scratch, slots, launch workers, the handle, launch / profile macros
+// xm_host.hpp -- error reporting, device scratch, slots (their last-frame record, their redo record; their ordering record is
+// xm_slot_order.hpp's, instantiated with HIP here), launch workers, the handle, launch / profile macros
 // (part of libxmaps_hip.so's host side: included by ../xmaps_hip.hip, one translation unit; see that file for the order)
 #pragma once
 
@@ -65,10 +66,31 @@ struct EventsView {
   bool use_p = false;
 };
 
+struct HipOrderOps {  // SlotOrder's calls on the HIP runtime
+  static int rc(hipError_t e, const char* call) { return e == hipSuccess ? XM_OK : fail(XM_ERR_HIP, "%s failed: %s", call, hipGetErrorString(e)); }
+  static hipEvent_t ev(void* e) { return static_cast<hipEvent_t>(e); }
+  static hipStream_t st(void* s) { return static_cast<hipStream_t>(s); }
+  static int record(void* e, void* s) { return rc(hipEventRecord(ev(e), st(s)), "hipEventRecord"); }
+  static int wait(void* s, void* e) { return rc(hipStreamWaitEvent(st(s), ev(e), 0), "hipStreamWaitEvent"); }
+  static int sync_event(void* e) { return rc(hipEventSynchronize(ev(e)), "hipEventSynchronize"); }
+  static int sync_stream(void* s) { return rc(hipStreamSynchronize(st(s)), "hipStreamSynchronize"); }
+};
+
 struct Slot {
   Stream stream;      // its own, or borrowed from an earlier slot (slots beyond the hardware-queue count share streams)
   int worker = -1;    // launch worker of this slot's stream (-1: none)
-  u32 api_tag = 0;    // tag of the slot's last frame as the API thread counts them (== host_tag once the workers are idle)
+  SlotOrder<HipOrderOps> order;  // where the slot's last work ran: every use of its buffers on a stream goes through this first
+  // What the slot's last frame was: written by note_enqueued, reset_slot and a graph replay; xm_graph_create copies it out and
+  // back around its capture, whose launches run nothing
+  struct Last {
+    u32 host_tag = 0;  // mirrors st->tag_a after the enqueued work has run
+    u32 api_tag = 0;   // the same tag as the API thread counts them (== host_tag once the workers are idle)
+    bool sorted = false;
+    bool key32 = false;  // it took a compact path (key32 or column tiles): a failure counts against it
+    bool cols = false;   // ... the column tiles (K0b was launched in K0's place)
+    uint64_t n = 0;
+    int t_dtype = XM_T_INT64;  // how xm_last_frame_stats decodes t_min / t_max
+  } last;
   // XM_FLAG_TRY_SORTED: pinned host words the kernels report to ([0] tag of the last frame whose shortcut failed, [1] tag of
   // the last frame whose K2 has started) and what is needed to redo the slot's last asynchronous frame on the general path
   PinnedMem<u32> h_flags;
@@ -82,25 +104,19 @@ struct Slot {
     uint8_t* host_bgr = nullptr;
     u32 tag = 0;
     hipStream_t stream = nullptr;  // the stream the frame's launches went to (the group's stream for xm_process_batch)
+    void set(const EventsView& ev_, float* depth_, uint8_t* bgr_, float* host_depth_, uint8_t* host_bgr_, u32 tag_,
+             hipStream_t stream_, bool check_) {
+      valid = true, ev = ev_, depth = depth_, bgr = bgr_, host_depth = host_depth_, host_bgr = host_bgr_;
+      tag = tag_, stream = stream_, check = check_;
+    }
   } prev;
   DevMem<u64> key_frame;
   DevMem<u32> key32;               // compact key frame of the verified-sorted projector-view path (see key32_tag)
   u32 key32_valid_from = 0;        // tag of the frame before which key32 was last cleared: every key in it has a tag in
                                    // [valid_from, valid_from + 15), so the 4-bit tag field is unambiguous
-  bool last_key32 = false;         // the slot's last frame took a compact path (key32 or column tiles): a failure counts against it
-  bool last_cols = false;          // ... the column tiles (K0b was launched in K0's place)
   DevMem<uint16_t> frame16;        // plain u16 disparity frame of the column-tile path (xmaps_k1cols.hpp): rewritten by every frame
   DevMem<unsigned char> dirty;     // projector view: one flag byte per 128-byte line of key_frame
   SlotState* st = nullptr;  // device: a view into xm_handle::d_states
-  u32 host_tag = 0;         // mirrors st->tag_a after the enqueued work has run
-  bool any_frame = false;
-  bool last_sorted = false;
-  uint64_t last_n = 0;
-  int last_t_dtype = XM_T_INT64;  // how xm_last_frame_stats decodes t_min / t_max
-  // the slot's last frame ran inside a multi-frame launch on ANOTHER stream: work on the slot's own stream waits for this
-  hipEvent_t pending_batch_ev = nullptr;  // view: an event of xm_handle::batch_ev / graph_ev
-  hipStream_t pending_batch_stream = nullptr;
-  bool eager_dirty = false;  // eager work was enqueued on the slot's own stream since the last synchronisation point
   // staging for XM_MEM_HOST calls
   DevBuf ev_x, ev_y, ev_t, ev_p, ev_aos, out_depth, out_bgr, dbg[5];
 };
@@ -333,14 +349,13 @@ int reset_slot(xm_handle* h, Slot& s, hipStream_t stream = nullptr) {
   HIP_TRY(hipGetLastError());
   if (s.key32) HIP_TRY(hipMemsetAsync(s.key32, 0, h->key_cells * sizeof(u32), stream));
   s.key32_valid_from = 0;
-  s.host_tag = 0;
-  s.api_tag = 0;
+  s.last.host_tag = 0;
+  s.last.api_tag = 0;
   if (s.h_flags) {  // tags start over: forget the verdicts of the old numbering (no frame of this slot is pending here)
     HIP_TRY(hipStreamSynchronize(stream));
     s.h_flags[0] = s.h_flags[1] = 0;
   }
   return XM_OK;
 }
-
 
 }  // namespace

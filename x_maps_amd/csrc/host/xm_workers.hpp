@@ -1,4 +1,5 @@
-// xm_workers.hpp -- slot rotation, the verified-shortcut verdict and redo (resolve_prev), launch workers, the single-frame entry (process_common)
+// xm_workers.hpp -- slot rotation, launch workers, a frame from the API thread or posted to a worker (run_frame, post_frame), the
+// verified-shortcut verdict and redo (resolve_prev), the single-frame entry (process_common)
 // (part of libxmaps_hip.so's host side: included by ../xmaps_hip.hip, one translation unit; see that file for the order)
 #pragma once
 
@@ -47,6 +48,28 @@ int drain_workers(xm_handle* h, int only = -1) {
     if (!(h)->pending.empty() && (rc_enter_ = flush_pending(h))) return rc_enter_;  \
   } while (0)
 
+// One frame on the slot's own stream from the API thread: its launches, the API's tag, and -- a host-memory call -- the copies of
+// the outputs to where the caller wants them.  redo_frame: the same frame again on the general path (its shortcut did not hold).
+int run_frame(xm_handle* h, Slot& s, const EventsView& ev, float* depth, uint8_t* bgr, float* host_depth, uint8_t* host_bgr,
+              const Event* prof = nullptr, bool allow_sorted = true) {
+  if (int rc = enqueue_frame(h, s, ev, depth, bgr, prof, allow_sorted)) return rc;
+  s.last.api_tag = s.last.host_tag;
+  const size_t px = (size_t)h->out_w * h->out_h;
+  if (host_depth) HIP_TRY(hipMemcpyAsync(host_depth, depth, px * 4, hipMemcpyDeviceToHost, s.stream));
+  if (host_bgr) HIP_TRY(hipMemcpyAsync(host_bgr, bgr, px * 3, hipMemcpyDeviceToHost, s.stream));
+  return XM_OK;
+}
+int redo_frame(xm_handle* h, Slot& s, const EventsView& ev, float* depth, uint8_t* bgr, float* host_depth, uint8_t* host_bgr) {
+  return run_frame(h, s, ev, depth, bgr, host_depth, host_bgr, nullptr, false);
+}
+
+// the frame's launches are the job of the slot's worker: the API counts its tag at once (with the wrap enqueue_frame will make)
+void post_frame(xm_handle* h, Slot& s, const EventsView& ev, float* depth, uint8_t* bgr, bool allow_sorted) {
+  const Job j{Job::FRAME, (int)(&s - h->slots.data()), ev, depth, bgr, allow_sorted};
+  s.last.api_tag = s.last.api_tag >= KEY_MAX_TAG ? 1 : s.last.api_tag + 1;
+  h->workers[s.worker]->q.post(j);
+}
+
 // XM_FLAG_TRY_SORTED: did the (t[0], t[n-1]) shortcut hold for the slot's last asynchronous frame?  The kernels answer in
 // pinned host memory (no API call when the frame has finished, which it has when a slot comes round again); a frame that
 // failed is redone here on the general path, into the same output buffers, before anything else happens on the slot.
@@ -84,27 +107,15 @@ int resolve_prev(xm_handle* h, Slot& s, bool* redone = nullptr) {
   }
   if (!s.prev.check || __atomic_load_n(&s.h_flags[0], __ATOMIC_ACQUIRE) != tag) return XM_OK;
   h->sorted_fallbacks += 1;
-  if (s.last_key32) key32_note(h, true);
-  if (s.worker >= 0 && !s.prev.host_depth && !s.prev.host_bgr) {  // the redo goes the way the frame went
-    Job j;
-    j.slot = (int)(&s - h->slots.data());
-    j.ev = s.prev.ev;
-    j.depth = s.prev.depth;
-    j.bgr = s.prev.bgr;
-    j.allow_sorted = false;
-    s.api_tag = s.api_tag >= KEY_MAX_TAG ? 1 : s.api_tag + 1;
-    h->workers[s.worker]->q.post(j);
-    if (redone) *redone = true;
-    return XM_OK;
+  if (s.last.key32) key32_note(h, true);
+  const Slot::Prev& pv = s.prev;
+  if (s.worker >= 0 && !pv.host_depth && !pv.host_bgr) {  // the redo goes the way the frame went
+    post_frame(h, s, pv.ev, pv.depth, pv.bgr, false);
+  } else {
+    int rc = s.worker >= 0 ? drain_workers(h, s.worker) : XM_OK;
+    if (rc) return rc;
+    if ((rc = redo_frame(h, s, pv.ev, pv.depth, pv.bgr, pv.host_depth, pv.host_bgr))) return rc;
   }
-  int rc = s.worker >= 0 ? drain_workers(h, s.worker) : XM_OK;
-  if (rc) return rc;
-  rc = enqueue_frame(h, s, s.prev.ev, s.prev.depth, s.prev.bgr, nullptr, false);
-  if (rc) return rc;
-  s.api_tag = s.host_tag;
-  const size_t px = (size_t)h->out_w * h->out_h;
-  if (s.prev.host_depth) HIP_TRY(hipMemcpyAsync(s.prev.host_depth, s.prev.depth, px * 4, hipMemcpyDeviceToHost, s.stream));
-  if (s.prev.host_bgr) HIP_TRY(hipMemcpyAsync(s.prev.host_bgr, s.prev.bgr, px * 3, hipMemcpyDeviceToHost, s.stream));
   if (redone) *redone = true;
   return XM_OK;
 }
@@ -142,24 +153,8 @@ int process_common(xm_handle* h, EventsView ev, int mem, float* depth_out, uint8
   if ((rc = resolve_prev(h, s))) return rc;
   if (s.worker >= 0 && mem == XM_MEM_DEVICE && !profile && !h->capturing) {
     // asynchronous device-pointer frame: the launches are the worker's job
-    Job j;
-    j.slot = (int)(&s - h->slots.data());
-    j.ev = ev;
-    j.depth = depth_out;
-    j.bgr = bgr_out;
-    s.api_tag = s.api_tag >= KEY_MAX_TAG ? 1 : s.api_tag + 1;
-    h->workers[s.worker]->q.post(j);
-    if (s.h_flags) {
-      s.prev.valid = true;
-      s.prev.check = h->try_sorted && sorted_path(h, ev);
-      s.prev.ev = ev;
-      s.prev.depth = depth_out;
-      s.prev.bgr = bgr_out;
-      s.prev.host_depth = nullptr;
-      s.prev.host_bgr = nullptr;
-      s.prev.tag = s.api_tag;
-      s.prev.stream = s.stream;
-    }
+    post_frame(h, s, ev, depth_out, bgr_out, true);
+    if (s.h_flags) s.prev.set(ev, depth_out, bgr_out, nullptr, nullptr, s.last.api_tag, s.stream, h->try_sorted && sorted_path(h, ev));
     return XM_OK;
   }
   if (s.worker >= 0 && (rc = drain_workers(h, s.worker))) return rc;  // this call uses the slot's stream itself
@@ -194,31 +189,21 @@ int process_common(xm_handle* h, EventsView ev, int mem, float* depth_out, uint8
   } else if (mem != XM_MEM_DEVICE) {
     return fail(XM_ERR_INVALID, "mem must be XM_MEM_HOST, XM_MEM_HOST_PINNED or XM_MEM_DEVICE");
   }
-  if ((rc = enqueue_frame(h, s, ev, d_depth, d_bgr, profile ? h->prof_ev : nullptr))) return rc;
-  s.api_tag = s.host_tag;
-  if (host_in) {
-    if (depth_out) HIP_TRY(hipMemcpyAsync(depth_out, d_depth, px * 4, hipMemcpyDeviceToHost, s.stream));
-    if (bgr_out) HIP_TRY(hipMemcpyAsync(bgr_out, d_bgr, px * 3, hipMemcpyDeviceToHost, s.stream));
-  }
+  float* const host_depth = host_in ? depth_out : nullptr;  // (d_depth / d_bgr are NULL where these are)
+  uint8_t* const host_bgr = host_in ? bgr_out : nullptr;
+  if ((rc = run_frame(h, s, ev, d_depth, d_bgr, host_depth, host_bgr, profile ? h->prof_ev : nullptr))) return rc;
   if (s.h_flags && !h->capturing && mem != XM_MEM_HOST && !profile) {
     // asynchronous call: the slot is not reused before this frame has reached K2 (keeps the host from running queues
     // deep ahead of the GPU, which made the frame rate uneven), and a try-sorted verdict is read then
-    s.prev.valid = true;
-    s.prev.check = h->try_sorted && s.last_sorted;
-    s.prev.ev = ev;  // device pointers (the slot's staging buffers for pinned host input)
-    s.prev.depth = d_depth;
-    s.prev.bgr = d_bgr;
-    s.prev.host_depth = host_in ? depth_out : nullptr;
-    s.prev.host_bgr = host_in ? bgr_out : nullptr;
-    s.prev.tag = s.host_tag;
-    s.prev.stream = s.stream;
+    // (ev: device pointers -- the slot's staging buffers for pinned host input)
+    s.prev.set(ev, d_depth, d_bgr, host_depth, host_bgr, s.last.host_tag, s.stream, h->try_sorted && s.last.sorted);
   }
   if (mem == XM_MEM_HOST || profile) {
-    HIP_TRY(hipStreamSynchronize(s.stream));
+    if ((rc = s.order.host_wait())) return rc;
     xm_frame_stats st;
     if ((rc = fetch_stats(h, s, ev.aos ? XM_T_INT64 : ev.t_dtype, &st))) return rc;
     if (profile) {
-      const int first = s.last_sorted && !s.last_cols ? 1 : 0;  // K0 is not launched on the time-sorted path (column tiles: K0b in its place)
+      const int first = s.last.sorted && !s.last.cols ? 1 : 0;  // K0 is not launched on the time-sorted path (column tiles: K0b in its place)
 #ifdef XM_ABLATE  // experiment builds may skip kernels (XM_SKIP_MASK): their events were never recorded
       for (int i = first; i < 3; ++i)
         if (hipEventElapsedTime(&st.gpu_ms[i], h->prof_ev[2 * i], h->prof_ev[2 * i + 1]) != hipSuccess) (void)hipGetLastError();
@@ -228,17 +213,12 @@ int process_common(xm_handle* h, EventsView ev, int mem, float* depth_out, uint8
       HIP_TRY(hipEventElapsedTime(&st.gpu_ms[3], h->prof_ev[2 * first], h->prof_ev[5]));  // start of first .. end of K2
 #endif
     }
-    if (st.n_unsorted && s.last_sorted) {
+    if (st.n_unsorted && s.last.sorted) {
       // the time-sorted declaration did not hold for this frame: redo it on the general path (K0 -> K1 -> K2)
       h->sorted_fallbacks += 1;
-      if (s.last_key32) key32_note(h, true);
-      if ((rc = enqueue_frame(h, s, ev, d_depth, d_bgr, nullptr, false))) return rc;
-      s.api_tag = s.host_tag;
-      if (mem == XM_MEM_HOST) {
-        if (depth_out) HIP_TRY(hipMemcpyAsync(depth_out, d_depth, px * 4, hipMemcpyDeviceToHost, s.stream));
-        if (bgr_out) HIP_TRY(hipMemcpyAsync(bgr_out, d_bgr, px * 3, hipMemcpyDeviceToHost, s.stream));
-      }
-      HIP_TRY(hipStreamSynchronize(s.stream));
+      if (s.last.key32) key32_note(h, true);
+      if ((rc = redo_frame(h, s, ev, d_depth, d_bgr, host_depth, host_bgr))) return rc;
+      if ((rc = s.order.host_wait())) return rc;
       const uint64_t flagged = st.n_unsorted;
       if ((rc = fetch_stats(h, s, ev.aos ? XM_T_INT64 : ev.t_dtype, &st))) return rc;
       st.n_unsorted = flagged;
@@ -284,6 +264,5 @@ void host_minmax_out(const SlotState& hs, void* out) {
   o[0] = TimeCodec<T>::dec(a);
   o[1] = TimeCodec<T>::dec(b);
 }
-
 
 }  // namespace

@@ -43,6 +43,7 @@ using namespace xm;
 #include "host/xm_queue.hpp"        // the host threads' job queues and first-error latches (standard C++ only)
 #include "host/xm_agree.hpp"        // the agreement among a sharded handle's device threads (standard C++ only)
 #include "host/xm_res.hpp"          // owners of device / pinned memory, streams and events (RAII)
+#include "host/xm_slot_order.hpp"   // where a slot's last work ran; the only code that orders a stream or the host behind it (standard C++ only)
 #include "host/xm_host.hpp"         // errors, slots, launch workers, the handle, launch macros
 #include "host/xm_launch.hpp"       // launch helpers of every kernel variant
 #include "host/xm_own_plan.hpp"     // owner-tile tables (host analysis in xm_create)
