@@ -6,6 +6,8 @@ semantics restated in tests/test_gpu_a4_bruteforce.py), border-heavy tables and 
 * expected(tb, rect): depth and BGR of a rectified disparity frame through the oracle's A5 - A7;
 * border_tables / sparse_frame (the a4 test's), pipe_tables: the same projector map on a rig that takes neither column nor
   owner tiles, with a chosen largest disparity (the pipelined kernel's LDS copy of the per-disparity table holds that many + 1);
+* classify_tiles / tiled_loader_paths: k_build_k2_tables restated -- which patch loader of the tiled K2 each tile of a rig takes --
+  and TILED_PATH_CASES, the shapes of tests/test_gpu_k2_tiled_paths.py that between them reach every one;
 * table_tables / table_frames: the 256 x 256 identity rig and the frames that between them sample every disparity 0 .. 65535;
 * steep_tables, every_pixel_frames, writable_cells: the column rigs' frames that put an event on every camera pixel in every time
   column, and the cells the ORACLE writes over them (never derived from host/xm_k2_live.hpp).
@@ -92,6 +94,70 @@ def sparse_frame(rng, rect_w, rect_h, fill):
     rect[:, 0] = rng.integers(1, 900, rect_h)
     rect[:, -1] = rng.integers(1, 900, rect_h)
     return rect
+
+
+# ---- which loader of the tiled K2 a tile takes ----------------------------------------------------------------------------------
+K2_TX, K2_TY, K2_TILE_MAX = 16, 16, 10240  # xmaps_k2.hpp: a block is 16 x 16 threads, a patch at most 10240 cells of LDS
+
+
+def classify_tiles(tb, ppt):
+    """k_build_k2_tables restated: per tile of 16 * ppt x 16 projector pixels (row-major list of dicts) its `kind` -- 'empty' (no
+    pixel maps into the frame), 'too_large' (the patch does not fit in LDS: the kernel reads the frame per pixel), 'interior'
+    (the patch lies inside the frame) or 'border' --, the patch's `cols` and `rows_p`, and the 16-byte loads per thread that
+    carry it: `loads64` of two 64-bit keys, `loads16` of eight u16 disparities."""
+    pmap = tb["disp_proj_mapxy_i16"].astype(np.int64)
+    rect_w, rect_h, tw = tb["rect_w"], tb["rect_h"], K2_TX * ppt
+    out = []
+    for v0 in range(0, pmap.shape[0], K2_TY):
+        for u0 in range(0, pmap.shape[1], tw):
+            mx, my = pmap[v0:v0 + K2_TY, u0:u0 + tw, 0], pmap[v0:v0 + K2_TY, u0:u0 + tw, 1]
+            valid = (mx >= 0) & (mx < rect_w) & (my >= 0) & (my < rect_h)
+            if not valid.any():
+                out.append({"kind": "empty", "cols": 0, "rows_p": 0, "loads64": 0, "loads16": 0})
+                continue
+            bx, by = int(mx[valid].min()) - 3, (int(my[valid].min()) - 3) & ~7  # (3 cells of dilate margin; rows start on a multiple of 8)
+            cols = int(mx[valid].max()) + 3 - bx + 1
+            rows_p = (int(my[valid].max()) + 3 - by + 1 + 7) & ~7
+            if cols * rows_p > K2_TILE_MAX:
+                kind = "too_large"
+            elif bx >= 0 and by >= 0 and bx + cols <= rect_w and by + rows_p <= rect_h:
+                kind = "interior"
+            else:
+                kind = "border"
+            nt = K2_TX * K2_TY
+            out.append({"kind": kind, "cols": cols, "rows_p": rows_p, "loads64": -(-(cols * rows_p // 2) // nt),
+                        "loads16": -(-(cols * rows_p // 8) // nt)})
+    return out
+
+
+def tiled_loader_paths(tb, ppt):
+    """The patch loaders of frame_proj_tiled_body (xmaps_k2.hpp) that the rig's tiles take at `ppt` pixels per thread, as names:
+    'too_large' (both formats read the frame per pixel), 'border' (both: cell by cell, or the clamped 64-bit pairs), and for
+    interior patches 'u16_oct_gt8' / 'u16_oct_le8' (rect_h % 8 == 0: 16-byte loads, patches of more / at most 64 rows),
+    'u16_quad' (rect_h % 8 == 4: 8-byte loads) and 'key64_un2' / '_un3' / '_un4' / '_un8' (rect_h even: the unroll the 16-byte
+    loads per thread select)."""
+    rect_h, names = tb["rect_h"], set()
+    for t in classify_tiles(tb, ppt):
+        if t["kind"] != "interior":
+            names.add(t["kind"])
+            continue
+        if rect_h % 8 == 0:
+            names.add("u16_oct_gt8" if t["rows_p"] > 64 else "u16_oct_le8")
+        elif rect_h % 4 == 0:
+            names.add("u16_quad")
+        if rect_h % 2 == 0:
+            names.add("key64_un%d" % (t["loads64"] if t["loads64"] in (3, 4) else 2 if t["loads64"] <= 2 else 8))
+    return names
+
+
+# (rect_w, rect_h, proj_w, proj_h) of tests/test_gpu_k2_tiled_paths.py, tables from border_tables(..., seed=rect_w): interior patches
+# of 96 and 104 rows; one tile whose patch exceeds LDS; interior patches of 24 and 32 rows in 2, 3 and 4 loads per thread; interior
+# tiles of a frame whose height is 4 mod 8
+TILED_PATH_CASES = [(128, 256, 128, 48), (120, 104, 8, 8), (256, 64, 256, 128), (320, 64, 256, 128), (176, 132, 128, 48)]
+# what they have to reach between them, per pixels-per-thread setting: every u16 loader at both, the 64-bit loader's four unroll
+# variants between the two (the 24- and 32-row patches are 2 loads per thread for 16-pixel tiles, 3 and 4 for 32-pixel ones)
+TILED_PATHS_WANTED = {1: {"too_large", "border", "u16_oct_gt8", "u16_oct_le8", "u16_quad", "key64_un2", "key64_un8"},
+                      2: {"too_large", "border", "u16_oct_gt8", "u16_oct_le8", "u16_quad", "key64_un3", "key64_un4", "key64_un8"}}
 
 
 # ---- rigs for arbitrary frames through the group frame kernel -----------------------------------------------------------------

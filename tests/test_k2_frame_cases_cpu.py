@@ -1,7 +1,8 @@
 """CPU: what the GPU tests of the pipelined K2 on arbitrary frames (tests/test_gpu_k2pipe_frames.py) rest on, pinned without a GPU
 (tests/k2_frame_cases.py): the vectorised A4 reference equals the 49-tap loops on every border case those tests use; the frames
 of the whole-table test sample every disparity 0 .. 65535; the chosen P03 / z_near / z_far put the clamp's and the u8's edges on
-integer disparities that the value-range frames hold; the cells the oracle writes on the column rigs are a proper part of the frame."""
+integer disparities that the value-range frames hold; the cells the oracle writes on the column rigs are a proper part of the frame;
+the tile classifier of tests/test_gpu_k2_tiled_paths.py gives what was worked out by hand, and that test's shapes reach every loader."""
 import numpy as np
 import pytest
 
@@ -69,6 +70,58 @@ def test_the_clamp_edges_fall_on_integer_disparities_the_value_frames_hold():
             if case[2] * case[3] >= 256:
                 assert {0, 1, 252, 255} <= set(int(v) for v in u8s), (case, u8s)
             assert len(got) > 1
+
+
+def _map_tables(mx, my, rect_w, rect_h):
+    return {"disp_proj_mapxy_i16": np.stack((mx, my), -1).astype(np.int16), "rect_w": rect_w, "rect_h": rect_h}
+
+
+def test_the_tile_classifier_on_maps_worked_out_by_hand():
+    """a 48 x 32 projector shifted by (8, 8) into a 64 x 48 frame: a 16-pixel tile's targets span 16 cells, + 3 of margin either
+    side = 22 columns; rows 8 .. 23 - 3 start at 5 -> 0, end at 26 -> 32 rows"""
+    vs, us = np.mgrid[0:32, 0:48]
+    tb = _map_tables(us + 8, vs + 8, 64, 48)
+    t1 = K.classify_tiles(tb, 1)
+    assert len(t1) == 3 * 2
+    assert t1[0] == {"kind": "interior", "cols": 22, "rows_p": 32, "loads64": 2, "loads16": 1}  # 352 pairs, 88 octets on 256 threads
+    assert t1[3] == t1[0]  # rows 24 .. 39: 21 -> 16 .. 42 -> 48, the frame's last row
+    t2 = K.classify_tiles(tb, 2)
+    assert len(t2) == 2 * 2
+    assert t2[0] == {"kind": "interior", "cols": 38, "rows_p": 32, "loads64": 3, "loads16": 1}  # 608 pairs
+    assert t2[1]["cols"] == 22  # the projector's last 16 columns alone
+    assert K.tiled_loader_paths(tb, 1) == {"u16_oct_le8", "key64_un2"} and K.tiled_loader_paths(tb, 2) == {"u16_oct_le8", "key64_un2", "key64_un3"}
+    # one frame row less: the lower tiles' patches stick out; the upper ones no longer take the 16-byte u16 loads (47 % 4 != 0)
+    low = K.classify_tiles(_map_tables(us + 8, vs + 8, 64, 47), 1)
+    assert [t["kind"] for t in low] == ["interior"] * 3 + ["border"] * 3
+    assert K.tiled_loader_paths(_map_tables(us + 8, vs + 8, 64, 47), 1) == {"border"}
+    assert K.tiled_loader_paths(_map_tables(us + 8, vs + 8, 64, 52), 1) == {"u16_quad", "key64_un2"}
+    # targets 8 cells apart: 15 * 8 + 7 = 127 columns; rows 128 .. 248 -> 120 .. 251 = 132 -> 136 rows: > 10240 cells, also where
+    # the patch sticks out of the frame (the first tile).  A tile whose targets all lie outside is empty
+    mx, my = us * 8, vs * 8
+    mx[:16, 16:32] = -1
+    wild = K.classify_tiles(_map_tables(mx, my, 512, 512), 1)
+    assert [t["kind"] for t in wild] == ["too_large", "empty"] + ["too_large"] * 4
+    assert wild[5] == {"kind": "too_large", "cols": 127, "rows_p": 136, "loads64": 34, "loads16": 9}
+    assert wild[1] == {"kind": "empty", "cols": 0, "rows_p": 0, "loads64": 0, "loads16": 0}
+
+
+@pytest.mark.parametrize("ppt", [1, 2])
+def test_every_window_lies_inside_its_tiles_patch_and_the_path_cases_reach_every_loader(ppt):
+    """what the classifier claims of tests/test_gpu_k2_tiled_paths.py's shapes, and that its patches hold what k_build_k2_tables'
+    do: the 7 x 7 window of every target inside the frame, rows from a multiple of 8 in whole octets"""
+    reached = set()
+    for case in K.TILED_PATH_CASES:
+        tb, _ = K.border_tables(*case, seed=case[0])
+        tiles = K.classify_tiles(tb, ppt)
+        assert len(tiles) == -(-case[2] // (16 * ppt)) * -(-case[3] // 16)
+        for t in tiles:
+            assert t["rows_p"] % 8 == 0 and (t["kind"] == "too_large") == (t["cols"] * t["rows_p"] > K.K2_TILE_MAX)
+            if t["kind"] == "interior":
+                assert t["cols"] >= 7 and t["rows_p"] >= 8 and t["cols"] <= case[0] and t["rows_p"] <= case[1]
+                assert (t["loads64"] - 1) * 256 < t["cols"] * t["rows_p"] // 2 <= t["loads64"] * 256
+                assert (t["loads16"] - 1) * 256 < t["cols"] * t["rows_p"] // 8 <= t["loads16"] * 256
+        reached |= K.tiled_loader_paths(tb, ppt)
+    assert K.TILED_PATHS_WANTED[ppt] <= reached, K.TILED_PATHS_WANTED[ppt] - reached
 
 
 @pytest.mark.parametrize("kind,proj_w", [("cols", 256), ("cols", 250), ("steep", 256), ("tall", 256)])

@@ -256,6 +256,35 @@ __device__ __forceinline__ uint4 k2_rowmax8(const uint4 a, const uint4 b) {
   return w;
 }
 
+// ---- Pieces of a K2 block written once.  Only those whose extraction left every kernel's assembly byte for byte as it was are
+// here; the stages that did not (row maxima, 7-tap sample, output writer, the patch loaders) stay spelled out at their sites:
+// profiles/k2_stages_identity.md has the table.
+
+// (i / n, i % n) without the integer divide: the quotient through inv_n ~ 1 / n in float (approximate is enough: the +-1 fix-ups
+// absorb it).  MUL24: q * n by the full-rate 24-bit multiply.  (By value: through references such a helper moved assembly)
+struct K2DivMod {
+  int q, r;
+};
+template <bool MUL24 = false>
+__device__ __forceinline__ K2DivMod k2_divmod(int i, int n, float inv_n) {
+  int q = (int)((float)i * inv_n), r = i - (MUL24 ? __mul24(q, n) : q * n);
+  if (r < 0) { q -= 1; r += n; }
+  if (r >= n) { q += 1; r -= n; }
+  return {q, r};
+}
+
+// Re-arm the next frame's counters (threads tid < CNT_SLOTS of the frame's first tile) and publish the tag: frame_proj_tiled_body
+// and k_frame_proj_pipe (xmaps_k2pipe.hpp).  State: SlotState*, or the pipelined kernel's pointer into the global address space
+template <typename State>
+__device__ __forceinline__ void k2_rearm_counters(State st, u32 tag, int tid) {
+  auto* c = st->cnt[(tag & 1) ^ 1][tid];
+  c[0] = c[1] = c[2] = c[3] = 0;
+  if (tid == 0) {
+    st->tag_b = tag;  // time-sorted mode: K1 derived the tag from tag_b without touching it
+    if (u32* hf = st->host_flags) host_flag_store(hf + 1, tag);
+  }
+}
+
 // blk_lin / grid_x / grid_y = linear block index inside the frame's tile grid and that grid's shape
 // FMT: what `keys` points at -- 0: the 64-bit packed-key frame; 1: the compact 32-bit key frame of the verified-sorted path
 // (see key32_tag); 2: a plain u16 disparity frame, no tags (sharded frames after reduce-scatter + all-gather, xm_shard_finish_u16)
@@ -297,14 +326,8 @@ __device__ __forceinline__ void frame_proj_tiled_body(const u64* __restrict__ ke
     pix_i[j] = __umul24((u32)v, (u32)tb.proj_w) + (u32)u;  // (24-bit multiplies are full rate, v_mul_lo_u32 a quarter)
     poff[j] = in_img[j] ? k2_pix[pix_i[j]] : ~0u;
   }
-  // generic path only; the tiled path tests poff where it needs it (after the patch loads are out: testing it here put a
-  // full wait for this load in front of them)
-  int x0 = 0, x1 = -1;
-  if (rec.z < 0) {  // patch too large for LDS (wild map): generic path needs the map entries themselves
-    x1 = 0;         // "some pixel maps into the frame": take the branch below, which falls through to the global reads
-  } else if (rec.z > 0) {
-    x1 = 0;
-  }
+  // (poff is tested where it is needed, after the patch loads are out: testing it here put a full wait for this load in
+  // front of them)
   float d[K2_PPT];  // generic path (a patch too large for LDS)
   u32 di[K2_PPT];   // tiled path: the integer disparity itself (no int -> float -> int round trip: conversions are quarter rate)
 #pragma unroll
@@ -312,7 +335,7 @@ __device__ __forceinline__ void frame_proj_tiled_body(const u64* __restrict__ ke
     d[j] = 0.0f;
     di[j] = 0;
   }
-  if (x1 >= x0) {  // at least one pixel of the tile maps into the frame
+  if (rec.z != 0) {  // at least one pixel of the tile maps into the frame (rec.z < 0: into a patch too large for LDS)
     const int bx = rec.x, by = rec.y;                    // patch origin (rows start on an even row: 16-byte aligned pairs)
     const int cols = rec.z, rows_p = rec.w;              // column stride in LDS: 16-byte aligned runs
     if (cols > 0) {
@@ -365,15 +388,13 @@ __device__ __forceinline__ void frame_proj_tiled_body(const u64* __restrict__ ke
               }
             }
           } else {
-          const float inv_o = __builtin_amdgcn_rcpf((float)oct);  // (approximate: the +-1 fix-ups below absorb it)
+          const float inv_o = __builtin_amdgcn_rcpf((float)oct);  // (approximate: k2_divmod's +-1 fix-ups absorb it)
           for (int i0 = tid; i0 < total; i0 += 2 * NT) {
             uint4 k[2];
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-              const int i = min(i0 + j * NT, total - 1);
-              int c = (int)((float)i * inv_o), ro = i - __mul24(c, oct);
-              if (ro < 0) { c -= 1; ro += oct; }
-              if (ro >= oct) { c += 1; ro -= oct; }
+              const K2DivMod at = k2_divmod<true>(min(i0 + j * NT, total - 1), oct, inv_o);
+              const int c = at.q, ro = at.r;
               k[j] = *reinterpret_cast<const uint4*>(d16 + __umul24((u32)(bx + c + tb.shear_bias + (((g0 + ro) * tb.shear_m) >> 12)), (u32)tb.rect_h) +
                                                      (u32)(by + 8 * ro));
             }
@@ -389,10 +410,8 @@ __device__ __forceinline__ void frame_proj_tiled_body(const u64* __restrict__ ke
             uint2 k[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-              const int i = min(i0 + j * NT, total - 1);
-              int c = (int)((float)i * inv_q), rq = i - __mul24(c, quarter);
-              if (rq < 0) { c -= 1; rq += quarter; }
-              if (rq >= quarter) { c += 1; rq -= quarter; }
+              const K2DivMod at = k2_divmod<true>(min(i0 + j * NT, total - 1), quarter, inv_q);
+              const int c = at.q, rq = at.r;
               k[j] = *reinterpret_cast<const uint2*>(d16 + __umul24((u32)frame16_col(tb, bx + c, by + 4 * rq), (u32)tb.rect_h) + (u32)(by + 4 * rq));
             }
 #pragma unroll
@@ -544,11 +563,8 @@ __device__ __forceinline__ void frame_proj_tiled_body(const u64* __restrict__ ke
           bool inside[UN];
 #pragma unroll
           for (int j = 0; j < UN; ++j) {
-            const int i = min(i0 + j * NT, total - 1);
-            int c = (int)((float)i * inv_rows), r = i - c * rows_p;
-            if (r < 0) { c -= 1; r += rows_p; }
-            if (r >= rows_p) { c += 1; r -= rows_p; }
-            const int gx = bx + c, gy = by + r;
+            const K2DivMod at = k2_divmod(min(i0 + j * NT, total - 1), rows_p, inv_rows);
+            const int gx = bx + at.q, gy = by + at.r;
             inside[j] = gx >= 0 && gx < tb.rect_w && gy >= 0 && gy < tb.rect_h;
             const int cx = min(max(gx, 0), tb.rect_w - 1), cy = min(max(gy, 0), tb.rect_h - 1);
             k[j] = keys[(u32)cx * (u32)tb.rect_h + (u32)cy];
@@ -635,14 +651,7 @@ __device__ __forceinline__ void frame_proj_tiled_body(const u64* __restrict__ ke
     o[q].depth = __uint_as_float(e.x);
     o[q].bgr = e.y;
   }
-  if (!tag_override && lin_tile == 0 && tid < CNT_SLOTS) {  // re-arm the next frame's counters
-    u32* c = st->cnt[(tag & 1) ^ 1][tid];
-    c[0] = c[1] = c[2] = c[3] = 0;
-    if (tid == 0) {
-      st->tag_b = tag;  // time-sorted mode: K1 derived the tag from tag_b without touching it
-      if (u32* hf = st->host_flags) host_flag_store(hf + 1, tag);
-    }
-  }
+  if (!tag_override && lin_tile == 0 && tid < CNT_SLOTS) k2_rearm_counters(st, tag, tid);
   if (depth) {
 #pragma unroll
     for (int q = 0; q < K2_PPT; ++q)

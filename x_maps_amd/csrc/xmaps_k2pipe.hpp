@@ -12,7 +12,12 @@
 //     (k_build_dlut) is copied into LDS once per block (its first n_lds entries; larger disparities -- rare -- read the global
 //     table, behind a branch), so no wait of the iteration has to drain the prefetch;
 //   * the tile's patch is written to LDS, reduced (7-tap maxima along the rows, in place) and sampled exactly as before
-//     (frame_proj_tiled_body, FMT = 2): same tables (k2_tiles / k2_pix), same arithmetic, same outputs;
+//     (frame_proj_tiled_body, FMT = 2): same tables (k2_tiles / k2_pix), same arithmetic, same outputs.  Of the stages the two
+//     kernels have in common only the counter re-arm is one text (k2_rearm_counters, xmaps_k2.hpp).  The row-maxima pass, the
+//     7-tap sample and the strided output writer (the non-CONSEC branch) are COPIES of frame_proj_tiled_body's with this
+//     kernel's barrier and address-space casts: as shared functions they changed this kernel's assembly
+//     (profiles/k2_stages_identity.md), so a fix to one has to be made in the other (tests/test_k2_stage_copies_cpu.py
+//     compares the texts of the first two);
 //   * patches that stick out of the frame load zeros for the octets outside (patch rows start on a multiple of 8 and so does
 //     the frame's height: an octet is inside or outside as a whole); a rig with a patch of more than 128 rows or more quads than
 //     the loader's registers hold keeps the one-block-per-tile kernel (k2_pipe_tile_ok, checked once in xm_create);
@@ -21,7 +26,7 @@
 //     host/xm_k2_live.hpp; at C-1M 59 % of the quads).  Rigs whose frame has another writer (owner tiles) get all ones.
 #pragma once
 #include "xmaps_common.hpp"
-#include "xmaps_k2.hpp"      // K2_TX / K2_TY, k2_rowmax8, the tile tables of k_build_k2_tables
+#include "xmaps_k2.hpp"      // K2_TX / K2_TY, k2_rowmax8, k2_rearm_counters, the tile tables of k_build_k2_tables
 #include "xmaps_k1cols.hpp"  // XM_CABL (experiment switches), the u16 frame these kernels read
 
 namespace xm {
@@ -319,15 +324,9 @@ __global__ __launch_bounds__(K2_TX* K2_TY) void k_frame_proj_pipe(const FrameDes
       XM_K2P_GLOBAL uint8_t* bgr = (XM_K2P_GLOBAL uint8_t*)d.bgr;
       const u32 tile_y = m0.tile_y, tile_x = m0.tile_x;
       const int v = tile_y * K2_TY + ty;
-      if (m0.lin == 0 && tid < CNT_SLOTS) {  // re-arm the frame's next counters (as frame_proj_tiled_body)
+      if (m0.lin == 0 && tid < CNT_SLOTS) {  // re-arm the frame's next counters
         XM_K2P_GLOBAL SlotState* st = (XM_K2P_GLOBAL SlotState*)d.st;
-        const u32 tag = st->tag_a;
-        XM_K2P_GLOBAL u32* c = st->cnt[(tag & 1) ^ 1][tid];
-        c[0] = c[1] = c[2] = c[3] = 0;
-        if (tid == 0) {
-          st->tag_b = tag;
-          if (u32* hf = st->host_flags) host_flag_store(hf + 1, tag);
-        }
+        k2_rearm_counters(st, st->tag_a, tid);
       }
       if constexpr (CONSEC) {
         const int u0 = tile_x * K2_TW + tx * PPT;
