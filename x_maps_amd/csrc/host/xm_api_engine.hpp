@@ -19,21 +19,23 @@ int xm_create(const xm_config* cfg, xm_handle** out) {
   h->cfg = *cfg;
   h->cfg.n_slots = cfg->n_slots > 0 ? cfg->n_slots : 1;
   h->cfg.xmap_height = cfg->xmap_height > 0 ? cfg->xmap_height : cfg->rect_height;
-  h->time_sorted = (cfg->flags & XM_FLAG_TIME_SORTED) != 0;
+  RigPlan& plan = h->plan_in_create();
+  plan.modes.time_sorted = (cfg->flags & XM_FLAG_TIME_SORTED) != 0;
   // default: the verified (t[0], t[n-1]) shortcut with automatic redo (exact for any event order); XM_FLAG_GENERAL forces the
   // extrema pass on every frame
-  h->try_sorted = !h->time_sorted && !(cfg->flags & XM_FLAG_GENERAL);
+  plan.modes.try_sorted = !plan.modes.time_sorted && !(cfg->flags & XM_FLAG_GENERAL);
   if ((cfg->flags & XM_FLAG_ADAPTIVE_BATCH) && h->cfg.n_slots >= 8) h->ab_max = std::min(h->cfg.n_slots / 4, 32);  // (four groups' worth of slots)
 
   CreateOpts o;
-  read_create_options(h.get(), o);
+  read_create_options(plan, o);
   int rc;
   if ((rc = upload_tables(h.get()))) return rc;
   if ((rc = build_k2_tables(h.get(), o))) return rc;
   if ((rc = classify_rig(h.get(), o))) return rc;
-  size_k1_windows(h.get(), o);
-  if ((rc = build_k2_live(h.get(), o))) return rc;
-  if ((rc = create_slots(h.get(), o))) return rc;
+  apply_k1_windows(plan, o);
+  const RigPlan& done = h->plan();  // the plan is finished: read-only from here on
+  if ((rc = build_k2_live(h.get(), done, o))) return rc;
+  if ((rc = create_slots(h.get(), done, o))) return rc;
   if ((rc = create_batch_rings(h.get()))) return rc;
   start_workers(h.get(), o);
   *out = h.release();
@@ -67,9 +69,10 @@ int xm_path_counts(xm_handle* h, uint64_t counts[4]) {
 int xm_cols_info(xm_handle* h, int32_t info[12]) {
   if (!h || !info) return fail(XM_ERR_INVALID, "NULL argument");
   for (int i = 0; i < 12; ++i) info[i] = 0;
-  info[0] = !h->cols_ok ? 0 : h->own_mode ? 2 : 1;
-  if (h->cols_ok && h->own_mode) {
-    const xm_handle::OwnSet& os = h->own[0];  // (the plan frames take by default; [10], [11]: width and halo of the one for denser frames)
+  const RigPlan& p = h->plan();
+  info[0] = !p.cols.ok ? 0 : p.cols.own_mode ? 2 : 1;
+  if (p.cols.ok && p.cols.own_mode) {
+    const RigPlan::Own& os = p.own[0];  // (the plan frames take by default; [10], [11]: width and halo of the one for denser frames)
     info[1] = os.w;
     info[2] = os.halo;
     info[3] = os.nxs_max;
@@ -79,10 +82,10 @@ int xm_cols_info(xm_handle* h, int32_t info[12]) {
     info[7] = os.hr;
     info[8] = os.extras;
     info[9] = os.extra_max;
-    for (int i = 1; i < xm_handle::OWN_PLANS; ++i)  // (the narrowest plan: the one the densest frames take)
-      if (h->own[i].ok) {
-        info[10] = h->own[i].w;
-        info[11] = h->own[i].halo;
+    for (int i = 1; i < OWN_PLANS; ++i)  // (the narrowest plan: the one the densest frames take)
+      if (p.own[i].ok) {
+        info[10] = p.own[i].w;
+        info[11] = p.own[i].halo;
       }
   }
   return XM_OK;
@@ -96,8 +99,7 @@ int xm_own_plan_info(const xm_config* cfg, int32_t info[12]) {
     return fail(XM_ERR_INVALID, "bad tables");
   for (int i = 0; i < 12; ++i) info[i] = 0;
   const int xmap_h = cfg->xmap_height > 0 ? cfg->xmap_height : cfg->rect_height;
-  int xr_min = 32767;
-  for (size_t i = 0; i < (size_t)cfg->cam_width * cfg->cam_height; ++i) xr_min = std::min<int>(xr_min, cfg->cam_mapx_i16[i]);
+  const int xr_min = table_extrema(cfg->cam_mapx_i16, (size_t)cfg->cam_width * cfg->cam_height, cfg->proj_x_map, 0).xr_min;
   OwnPlan pls[OWN_PLANS];
   own_plans(cfg, xmap_h, xr_min, pls);
   const OwnPlan& pl = pls[0];  // (the plan frames take by default)
@@ -143,7 +145,7 @@ int xm_sync(xm_handle* h) {
     if (rcw) return rcw;
   }
   for (Slot& s : h->slots) s.order.forget();  // every stream is idle: nothing left to order against
-  if (h->try_sorted) {  // frames whose shortcut failed are redone now, then waited for
+  if (h->plan().modes.try_sorted) {  // frames whose shortcut failed are redone now, then waited for
     for (Slot& s : h->slots) {
       bool redone = false;
       int rc = resolve_prev(h, s, &redone);
@@ -154,7 +156,7 @@ int xm_sync(xm_handle* h) {
       }
     }
   }
-  if (h->time_sorted) {  // any asynchronously processed frame that was not sorted after all?
+  if (h->plan().modes.time_sorted) {  // any asynchronously processed frame that was not sorted after all?
     u32 bad = 0;
     // one copy of all slot states (3 KB each) instead of one synchronous 4-byte copy per slot (60 slots: 0.9 ms)
     std::vector<SlotState> hs(h->slots.size());
@@ -234,7 +236,7 @@ int xm_debug_k2_group_u16(xm_handle* h, const uint16_t* frames_host, int n_frame
                           uint8_t* bgr_out) {
   if (!h || !frames_host) return fail(XM_ERR_INVALID, "NULL argument");
   if (n_frames < 1 || n_frames > 64) return fail(XM_ERR_INVALID, "n_frames must be in [1, 64]");
-  if (h->cfg.view != XM_VIEW_PROJECTOR || h->k2_direct || !h->d_k2_tiles[1])
+  if (!h->plan().dims.projector || h->plan().modes.k2_direct || !h->plan().k2.has_tables)
     return fail(XM_ERR_INVALID, "xm_debug_k2_group_u16 needs a projector-view handle with the tiled frame kernel");
   XM_ENTER(h);
   const int rw = h->tb.rect_w, rh = h->tb.rect_h;
@@ -344,7 +346,7 @@ static int process_batch_impl(xm_handle* h, const uint16_t* x, const uint16_t* y
   if (n_frames > ns) return fail(XM_ERR_INVALID, "a batch of %d frames needs n_slots >= %d (handle has %d)", n_frames, n_frames, ns);
   XM_ENTER(h);
   BatchViews v;
-  if (int rc = batch_views(h, x, y, t, p, t_dtype, aos, offsets_host, n_frames, depth_out, bgr_out, v)) return rc;
+  if (int rc = batch_views(h->plan(), x, y, t, p, t_dtype, aos, offsets_host, n_frames, depth_out, bgr_out, v)) return rc;
   return submit_group(h, v, gpu_ms);
 }
 
@@ -381,7 +383,7 @@ static int submit_group(xm_handle* h, const BatchViews& v, float* gpu_ms, hipEve
     Slot& s = h->slots[idx[f]];
     s.order.note_group(done, stream);
     if (s.h_flags)  // slot gate + try-sorted verdict, read when the slot comes round again or in xm_sync
-      s.prev.set(v.evs[f], v.dep[f], v.bg[f], nullptr, nullptr, s.last.host_tag, stream, h->try_sorted && s.last.sorted);
+      s.prev.set(v.evs[f], v.dep[f], v.bg[f], nullptr, nullptr, s.last.host_tag, stream, h->plan().modes.try_sorted && s.last.sorted);
   }
   if (gpu_ms) {  // profile mode: durations of the group's dispatches (the events were attached to the dispatch packets)
     HIP_TRY(hipStreamSynchronize(stream));

@@ -67,7 +67,7 @@ int xm_graph_create(xm_handle* h, const uint16_t* x, const uint16_t* y, const vo
   const int ns = (int)h->slots.size();
   if ((u64)n_frames / ns + 1 >= KEY_MAX_TAG) return fail(XM_ERR_INVALID, "too many frames per graph");
   BatchViews v;  // (offsets that decrease, frames too large: refused before anything is captured)
-  if (int rc = batch_views(h, x, y, t, p, t_dtype, nullptr, offsets_host, n_frames, depth_out, bgr_out, v)) return rc;
+  if (int rc = batch_views(h->plan(), x, y, t, p, t_dtype, nullptr, offsets_host, n_frames, depth_out, bgr_out, v)) return rc;
   for (Slot& s : h->slots) HIP_TRY(hipStreamSynchronize(s.stream));
   for (Slot& s : h->slots) s.order.forget();  // idle: nothing to order the capture against
   Owned<xm_graph, xm_graph_destroy> g(new (std::nothrow) xm_graph());
@@ -104,7 +104,7 @@ int xm_graph_launch(xm_graph* g) {
   XM_ENTER(h);
   const int ns = (int)h->slots.size();
   hipStream_t origin = h->gstreams[0];
-  if (h->try_sorted)
+  if (h->plan().modes.try_sorted)
     for (Slot& s : h->slots) {  // settle pending try-sorted verdicts before the replay advances the slots' tags
       int rc = resolve_prev(h, s);
       if (rc) return rc;
@@ -116,7 +116,7 @@ int xm_graph_launch(xm_graph* g) {
   for (int i = 0; i < ns; ++i) {  // tag wrap per slot
     Slot& s = h->slots[i];
     if ((u64)s.last.host_tag + g->frames_on_slot[i] >= KEY_MAX_TAG) {
-      hipLaunchKernelGGL(k_reset_slot, dim3(1024), dim3(BLOCK), 0, origin, s.st, s.key_frame, (u64)h->key_cells, s.dirty);
+      hipLaunchKernelGGL(k_reset_slot, dim3(1024), dim3(BLOCK), 0, origin, s.st, s.key_frame, (u64)h->plan().dims.key_cells, s.dirty);
       HIP_TRY(hipGetLastError());
       s.last.host_tag = 0;
       s.last.api_tag = 0;

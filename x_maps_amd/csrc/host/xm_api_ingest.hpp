@@ -276,8 +276,8 @@ static int ingest_frame_filter_alloc(xm_ingest* g) {
   const IngestFixed& fx = g->fx;
   const xm_handle* h = fx.h;
   ff.cells_xy = (u32)h->tb.cam_w * (u32)h->tb.cam_h;
-  ff.yt_w = h->lut_xr_max + 1;
-  ff.yt_wrap = h->cols_xr_min < 0;
+  ff.yt_w = h->plan().cols.xr_max + 1;
+  ff.yt_wrap = h->plan().cols.xr_min < 0;
   const u64 cells_yt = ff.yt_w > 0 ? (u64)ff.yt_w * (u64)h->tb.cam_h : 0;
   ff.yt_ok = cells_yt > 0 && cells_yt <= ING_YT_MAX_CELLS;
   ff.cells_yt = ff.yt_ok ? (u32)cells_yt : 0u;

@@ -79,7 +79,7 @@ int xm_shard_scatter_device(xm_handle* h, const uint16_t* x, const uint16_t* y, 
 int xm_shard_clear(xm_handle* h, uint64_t* key_frame) {
   if (!h || !key_frame) return fail(XM_ERR_INVALID, "NULL argument");
   XM_ENTER(h);
-  HIP_TRY(hipMemsetAsync(key_frame, 0, h->key_cells * sizeof(u64), h->slots[0].stream));
+  HIP_TRY(hipMemsetAsync(key_frame, 0, h->plan().dims.key_cells * sizeof(u64), h->slots[0].stream));
   return XM_OK;
 }
 
@@ -109,7 +109,7 @@ int xm_shard_decode_u16(xm_handle* h, const uint64_t* key_cells, size_t n_cells,
 // only; the caller's depth / BGR buffers keep what they held everywhere else (zero them first, MAX-reduce them over the ranks).
 int xm_shard_finish_u16_band(xm_handle* h, const uint16_t* disp_frame, int col_lo, int col_hi, float* depth_out, uint8_t* bgr_out) {
   if (!h || !disp_frame) return fail(XM_ERR_INVALID, "NULL argument");
-  if (h->cfg.view != XM_VIEW_PROJECTOR || h->k2_direct) return fail(XM_ERR_INVALID, "the band-sharded finish is the tiled projector-view frame kernel");
+  if (h->cfg.view != XM_VIEW_PROJECTOR || h->plan().modes.k2_direct) return fail(XM_ERR_INVALID, "the band-sharded finish is the tiled projector-view frame kernel");
   if (col_lo < 0 || col_hi <= col_lo) return fail(XM_ERR_INVALID, "empty column band");
   XM_ENTER(h);
   launch_k2<2>(h, h->slots[0].stream, reinterpret_cast<const u64*>(disp_frame), h->aux_st, 1u, nullptr, depth_out, bgr_out, true, col_lo, col_hi);
@@ -121,7 +121,7 @@ int xm_shard_finish_u16_band(xm_handle* h, const uint16_t* disp_frame, int col_l
 // a tile reads the frame wherever its map points: no band can be cut for it).  The halo a band-sharded rank needs on either side.
 int xm_k2_patch_cols_max(xm_handle* h, int* cols_out) {
   if (!h || !cols_out) return fail(XM_ERR_INVALID, "NULL argument");
-  *cols_out = h->k2_patch_cols_max;
+  *cols_out = h->plan().k2.patch_cols_max;
   return XM_OK;
 }
 
@@ -130,7 +130,7 @@ int xm_shard_finish_u16(xm_handle* h, const uint16_t* disp_frame, float* depth_o
   XM_ENTER(h);
   hipStream_t stream = h->slots[0].stream;
   if (h->cfg.view == XM_VIEW_PROJECTOR) {
-    if (h->k2_direct) return fail(XM_ERR_INVALID, "xm_shard_finish_u16 needs the tiled frame kernel (XM_K2_DIRECT is set)");
+    if (h->plan().modes.k2_direct) return fail(XM_ERR_INVALID, "xm_shard_finish_u16 needs the tiled frame kernel (XM_K2_DIRECT is set)");
     launch_k2<2>(h, stream, reinterpret_cast<const u64*>(disp_frame), h->aux_st, 1u, nullptr, depth_out, bgr_out, true);
   } else {
     const u64 px = (u64)h->tb.cam_w * h->tb.cam_h;
@@ -144,8 +144,8 @@ int xm_shard_finish_u16(xm_handle* h, const uint16_t* disp_frame, float* depth_o
 // ---- shards on the column tiles: every time column processed by one rank, u16 frames merged by SUM (xmaps_k1cols.hpp) ----
 int xm_shard_cols_info(xm_handle* h, uint64_t n_frame_events, size_t* frame_bytes, size_t* reduce_u32, size_t* send_bytes, size_t* cap_events) {
   if (!h) return fail(XM_ERR_INVALID, "NULL handle");
-  const int W = h->own_mode ? 0 : cols_width(h, n_frame_events);
-  if (!h->cols_ok || h->own_mode || W == 0 || h->cfg.view != XM_VIEW_PROJECTOR || h->k2_direct)
+  const int W = h->plan().cols.own_mode ? 0 : cols_width(h->plan(), n_frame_events);
+  if (!h->plan().cols.ok || h->plan().cols.own_mode || W == 0 || h->cfg.view != XM_VIEW_PROJECTOR || h->plan().modes.k2_direct)
     return fail(XM_ERR_INVALID, "this rig / frame density does not take the column tiles (injective X-map, projector view, >= 1024 events per tile)");
   const size_t cells = frame16_cells(h->tb);
   // room for the events of four mean time columns (a shard's last column), a multiple of 8
@@ -173,8 +173,8 @@ int xm_shard_cols_scatter(xm_handle* h, uint16_t* x, uint16_t* y, int64_t* t, si
   if (world < 1 || rank < 0 || rank >= world) return fail(XM_ERR_INVALID, "bad rank / world");
   if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)t) & 15) return fail(XM_ERR_INVALID, "x / y / t must be 16-byte aligned");
   XM_ENTER(h);
-  const int W = cols_width(h, n_frame_events);
-  if (!h->cols_ok || h->own_mode || W == 0) return fail(XM_ERR_INVALID, "this rig / frame density does not take the column tiles");
+  const int W = cols_width(h->plan(), n_frame_events);
+  if (!h->plan().cols.ok || h->plan().cols.own_mode || W == 0) return fail(XM_ERR_INVALID, "this rig / frame density does not take the column tiles");
   if (!h->d_shard_n) HIP_TRY(h->d_shard_n.alloc(8, sizeof(FrameDesc)));
   hipStream_t s = h->slots[0].stream;
   long long* mm = reinterpret_cast<long long*>(h->d_shard_n.get());  // {tmin, -tmax} of the frame
@@ -182,7 +182,7 @@ int xm_shard_cols_scatter(xm_handle* h, uint16_t* x, uint16_t* y, int64_t* t, si
   hipLaunchKernelGGL(k_shard_cols_prepare, dim3(1), dim3(256), 0, s, x, y, (long long*)t, (u64)n, (const unsigned char*)gathered_dev,
                      (u64)send_bytes, rank, world, h->tb, (u64)cap_events, mm, frame16, h->aux_st, desc);
   const FrameGroup piece{desc, 1, n_frame_events, n_frame_events, true};  // (the piece starts 8-aligned: 16-byte event loads)
-  launch_cols_bounds<false>(h, piece, W, h->cols_flags | COLS_F_EXT_EXTREMA, s);
+  launch_cols_bounds<false>(h, piece, W, h->plan().cols.flags | COLS_F_EXT_EXTREMA, s);
   // (measurement: HIP events tied to THIS dispatch -- xm_shard_cols_last_k1_ms -- beside the three-launch bracket a caller can take itself)
   const ProfSlots ps{dbg_opt("XM_SHARD_PROFILE") ? h->prof_ev + 2 : nullptr};
   ps.at(0);

@@ -107,7 +107,7 @@ int xm_shard_comm_info(xm_shard_comm* c, int* takes_columns, size_t* cap_events,
   if (takes_columns) *takes_columns = c->cols ? 1 : 0;
   if (cap_events) *cap_events = c->cap;
   if (send_bytes) *send_bytes = c->send_bytes;
-  if (frame_bytes) *frame_bytes = c->cols ? c->reduce_u32 * 4 : (size_t)c->h->key_cells * 8;
+  if (frame_bytes) *frame_bytes = c->cols ? c->reduce_u32 * 4 : (size_t)c->h->plan().dims.key_cells * 8;
   return XM_OK;
 }
 
@@ -122,7 +122,7 @@ int xm_shard_comm_frame_keys(xm_shard_comm* c, const uint16_t* x, const uint16_t
                              int t_dtype, uint64_t first_index, float* depth_out, uint8_t* bgr_out) {
   if (!c) return fail(XM_ERR_INVALID, "NULL argument");
   XM_ENTER(c->h);
-  if (!c->key) HIP_TRY(c->key.alloc(c->h->key_cells));
+  if (!c->key) HIP_TRY(c->key.alloc(c->h->plan().dims.key_cells));
   c->tag = c->tag >= 1000 ? 1 : c->tag + 1;  // (the key frame is cleared every frame: any tag in [1, 2^19) would do)
   return shard_exchange_keys(c->peers, c->h, x, y, t, p, n_own, t_dtype, first_index, c->mm, c->key, c->tag, depth_out, bgr_out, XM_OK);
 }

@@ -71,7 +71,7 @@ int sharded_frame_on(xm_sharded* s, int g) {
   HIP_TRY(hipSetDevice(d.id));
   hipStream_t st = (hipStream_t)xm_stream(d.h, 0);
   const size_t a = (size_t)(((unsigned __int128)g * s->n) / (unsigned)W), b = (size_t)(((unsigned __int128)(g + 1) * s->n) / (unsigned)W);
-  const size_t m = b - a, tsz = t_size(s->t_dtype), px = (size_t)d.h->out_w * d.h->out_h;
+  const size_t m = b - a, tsz = t_size(s->t_dtype), px = (size_t)d.h->plan().dims.out_w * d.h->plan().dims.out_h;
   // 1. the shard and what the exchange needs.  The columns exchange wants cap + 8 events of headroom in front of the shard (the
   // predecessor's last column is copied there on the device) and 8 behind it.
   const size_t head = cols ? s->cols.cap + 8 : 0, tail = cols ? 8 : 0;
@@ -212,7 +212,7 @@ int xm_create_sharded(const int* dev_ids, int n_dev, const xm_config* cfg, xm_sh
     c.device = d.id;
     if ((rc = xm_create(&c, &d.h))) break;
     hipError_t e = hipSetDevice(d.id);
-    if (e == hipSuccess) e = d.key.alloc(d.h->key_cells);
+    if (e == hipSuccess) e = d.key.alloc(d.h->plan().dims.key_cells);
     if (e == hipSuccess) e = d.mm.alloc(2);
     for (Event& ev : d.ev)
       if (e == hipSuccess) e = ev.create(hipEventDefault);
@@ -309,7 +309,7 @@ int xm_sharded_info(xm_sharded* s, int* n_dev, int* uses_rccl, uint64_t* key_fra
   if (!s) return fail(XM_ERR_INVALID, "NULL argument");
   if (n_dev) *n_dev = (int)s->devs.size();
   if (uses_rccl) *uses_rccl = s->use_rccl ? 1 : 0;
-  if (key_frame_bytes) *key_frame_bytes = (uint64_t)s->devs[0]->h->key_cells * 8;
+  if (key_frame_bytes) *key_frame_bytes = (uint64_t)s->devs[0]->h->plan().dims.key_cells * 8;
   return XM_OK;
 }
 

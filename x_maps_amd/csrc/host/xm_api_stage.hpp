@@ -209,7 +209,7 @@ int xm_stage_disp_map_camera_view(xm_handle* h, const uint16_t* x, const uint16_
 
 int xm_stage_remap_rectified_disp_map_to_proj(xm_handle* h, const float* rect_disp, float* proj_disp) {
   if (!h || !rect_disp || !proj_disp) return fail(XM_ERR_INVALID, "NULL argument");
-  if (!h->d_pmap) return fail(XM_ERR_INVALID, "handle was created without disp_proj_mapxy_i16");
+  if (!h->plan().dims.has_pmap) return fail(XM_ERR_INVALID, "handle was created without disp_proj_mapxy_i16");
   XM_ENTER(h);
   Slot& s = h->slots[0];
   const size_t cells = (size_t)h->tb.rect_w * h->tb.rect_h, px = (size_t)h->tb.proj_w * h->tb.proj_h;

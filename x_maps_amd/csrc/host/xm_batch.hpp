@@ -18,7 +18,7 @@ int launch_group(xm_handle* h, const FrameGroup& g, const FramePath& p, hipStrea
       ps.at(0);
       launch_cols_bounds<AOS>(h, g, p.cols_w, 0, stream);
       ps.at(1);
-      int rc = launch_tiles_k1<AOS>(h, g, p.cols_w, p.dev_redo ? COLS_F_DEVICE_REDO : 0, (size_t)h->cols_lds_pad, stream);
+      int rc = launch_tiles_k1<AOS>(h, g, p.cols_w, p.dev_redo ? COLS_F_DEVICE_REDO : 0, (size_t)h->plan().cols.lds_pad, stream);
       if (rc) return rc;
       ps.at(2);
       if (!p.dev_redo) {
@@ -58,9 +58,9 @@ struct BatchViews {
   std::vector<float*> dep;
   std::vector<uint8_t*> bg;
 };
-int batch_views(const xm_handle* h, const uint16_t* x, const uint16_t* y, const void* t, const int16_t* p, int t_dtype, const void* aos,
+int batch_views(const RigPlan& pl, const uint16_t* x, const uint16_t* y, const void* t, const int16_t* p, int t_dtype, const void* aos,
                 const uint64_t* offsets_host, int n_frames, float* depth_out, uint8_t* bgr_out, BatchViews& v) {
-  const size_t px = (size_t)h->out_w * h->out_h, tsz = t_size(t_dtype);
+  const size_t px = (size_t)pl.dims.out_w * pl.dims.out_h, tsz = t_size(t_dtype);
   v.evs.assign(n_frames, EventsView{});
   v.dep.assign(n_frames, nullptr);
   v.bg.assign(n_frames, nullptr);
@@ -90,7 +90,7 @@ int enqueue_batch(xm_handle* h, const int* slot_idx, const EventsView* evs, floa
                   int n_frames, hipStream_t stream, FrameDesc* h_descs, FrameDesc* d_descs, bool upload, bool allow_sorted,
                   const Event* prof = nullptr, int* kinds = nullptr, FrameDesc* h_descs_redo = nullptr,
                   FrameDesc* d_descs_redo = nullptr) {
-  const FramePath p = frame_path(h, evs, n_frames, allow_sorted, true, d_descs_redo != nullptr);
+  const FramePath p = frame_path(h->plan(), path_now(h), evs, n_frames, allow_sorted, true, d_descs_redo != nullptr);
   for (int f = 0; f < n_frames; ++f)  // order the group after whatever its slots did last on other streams
     if (int rc = h->slots[slot_idx[f]].order.before(stream, h->capturing)) return rc;
   if (p.per_frame) {  // untiled K2: frame by frame, still on the group's stream
@@ -106,11 +106,11 @@ int enqueue_batch(xm_handle* h, const int* slot_idx, const EventsView* evs, floa
   for (int f = 0; f < n_frames; ++f) {
     Slot& s = h->slots[slot_idx[f]];
     if (s.last.host_tag >= KEY_MAX_TAG && !h->capturing) {
-      int rc = reset_slot(h, s, stream);
+      int rc = reset_slot(h->plan(), s, stream);
       if (rc) return rc;
     }
     if (p.key32) {
-      int rc = key32_prepare(h, s, s.last.host_tag + 1, stream);
+      int rc = key32_prepare(h->plan(), s, s.last.host_tag + 1, stream);
       if (rc) return rc;
     }
     FrameDesc& d = h_descs[f];

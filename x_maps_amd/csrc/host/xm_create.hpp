@@ -1,4 +1,6 @@
-// xm_create.hpp -- the stages of xm_create, in the order it calls them.  Every stage returns an xm_* code; a failure leaves the
+// xm_create.hpp -- the stages of xm_create, in the order it calls them.  The stages up to apply_k1_windows fill the rig plan
+// (RigPlan, xm_plan.hpp) through xm_handle::plan_in_create() -- the only code that writes it; from build_k2_live on a stage is
+// handed the finished plan as a const RigPlan&, like everything outside this file.  Every stage returns an xm_* code; a failure leaves the
 // half-built handle to xm_destroy (xm_create holds it in an Owned<>).  The order of the HIP calls on the device, every
 // hipDeviceSynchronize among them, is part of the contract: the stages' default-stream work must not be reordered.
 // (part of libxmaps_hip.so's host side: included by ../xmaps_hip.hip, one translation unit; see that file for the order)
@@ -6,7 +8,7 @@
 
 namespace {
 
-// the switches that have no field of their own in the handle: read once (read_create_options), used by one stage each
+// the switches that have no field of their own in the plan: read once (read_create_options), used by one stage each
 struct CreateOpts {
   const char* k2_pipe_ppt = nullptr;  // "XM_K2_PIPE_PPT" (experiments / tests): 2 / 4
   const char* key32 = nullptr;        // "XM_KEY32": 0 = no compact key frame
@@ -42,30 +44,30 @@ int validate_config(const xm_config* cfg) {
 // Every switch xm_create reads (xm_debug_option sets them; see dbg_opt), in one place, and for every rig ("XM_K2_PPT" and
 // "XM_K2_PIPE_PPT" used to be read only when the rig has a projector map: only K2's projector path looks at what they set).
 // (own_setup reads the owner tiles' own: "XM_OWN_W", "XM_OWN_GROUPED", "XM_OWN_EPT".)
-void read_create_options(xm_handle* h, CreateOpts& o) {
-  if (const char* e = dbg_opt("XM_K2_PPT")) h->k2_force_ppt = atoi(e);
+void read_create_options(RigPlan& p, CreateOpts& o) {
+  if (const char* e = dbg_opt("XM_K2_PPT")) p.k2.force_ppt = atoi(e);
   o.k2_pipe_ppt = dbg_opt("XM_K2_PIPE_PPT");
   o.key32 = dbg_opt("XM_KEY32");
   if (const char* e = dbg_opt("XM_K2_NLDS_MAX")) o.k2_nlds_max = std::max(1, std::min(4096, atoi(e)));
   if (const char* e = dbg_opt("XM_K2_PIPE")) {
-    h->k2_pipe = e[0] != '0';
-    h->k2_pipe_force = e[0] == '2';
+    p.k2pipe.on = e[0] != '0';
+    p.k2pipe.force = e[0] == '2';
   }
-  if (const char* e = dbg_opt("XM_K2_CHAIN")) h->k2_chain = e[0] != '0';
-  if (const char* e = dbg_opt("XM_K2_PER_CU")) h->k2_per_cu_max = std::max(1, atoi(e));
-  if (const char* e = dbg_opt("XM_K2_PIPE_BLOCKS")) h->k2_pipe_blocks = std::max(0, atoi(e));
-  if (const char* e = dbg_opt("XM_COLS_LDS_PAD")) h->cols_lds_pad = std::max(0, std::min(64 * 1024, atoi(e)));
+  if (const char* e = dbg_opt("XM_K2_CHAIN")) p.k2pipe.chain = e[0] != '0';
+  if (const char* e = dbg_opt("XM_K2_PER_CU")) p.k2pipe.per_cu_max = std::max(1, atoi(e));
+  if (const char* e = dbg_opt("XM_K2_PIPE_BLOCKS")) p.k2pipe.blocks_cap = std::max(0, atoi(e));
+  if (const char* e = dbg_opt("XM_COLS_LDS_PAD")) p.cols.lds_pad = std::max(0, std::min(64 * 1024, atoi(e)));
   if (const char* e = dbg_opt("XM_K2_LIVE")) {
-    h->k2_live = e[0] != '0';
-    h->k2_live_report = e[0] == '2';
+    p.k2pipe.live = e[0] != '0';
+    p.k2pipe.live_report = e[0] == '2';
   }
-  if (const char* e = dbg_opt("XM_K2_CONSEC")) h->k2_consec = e[0] != '0' ? 1 : 0;  // experiments / tests: the strided pixel assignment
+  if (const char* e = dbg_opt("XM_K2_CONSEC")) p.k2pipe.consec = e[0] != '0' ? 1 : 0;  // experiments / tests: the strided pixel assignment
   o.cols = dbg_opt("XM_COLS");
   const char* e1 = dbg_opt("XM_K1_DIRECT");
   const char* e2 = dbg_opt("XM_K2_DIRECT");
-  h->k1_direct = e1 && e1[0] == '1';
-  h->k2_direct = e2 && e2[0] == '1';
-  if (const char* e3 = dbg_opt("XM_K2_FLAGS")) h->k2_flags = e3[0] == '1';
+  p.modes.k1_direct = e1 && e1[0] == '1';
+  p.modes.k2_direct = e2 && e2[0] == '1';
+  if (const char* e3 = dbg_opt("XM_K2_FLAGS")) p.modes.k2_flags = e3[0] == '1';
   if (const char* e = dbg_opt("XM_K1_WX")) o.k1_wx = std::max(2, std::min(64, atoi(e)));
 #ifdef XM_ABLATE
   o.ablate = dbg_opt("XM_ABLATE");
@@ -104,6 +106,7 @@ int upload_tables(xm_handle* h) {
     for (size_t i = 0; i < ppx; ++i)
       pm[i] = ((u32)(uint16_t)cfg->disp_proj_mapxy_i16[2 * i + 1] << 16) | (u32)(uint16_t)cfg->disp_proj_mapxy_i16[2 * i];
     HIP_TRY(h->d_pmap.alloc(ppx));
+    h->plan_in_create().dims.has_pmap = true;
     HIP_TRY(hipMemcpy(h->d_pmap, pm.data(), ppx * 4, hipMemcpyHostToDevice));
   }
   HIP_TRY(h->d_zero16.alloc(256 / sizeof(ulonglong2)));
@@ -118,13 +121,17 @@ int upload_tables(xm_handle* h) {
   tb.rect_w = cfg->rect_width; tb.rect_h = cfg->rect_height; tb.xmap_w = cfg->xmap_width; tb.xmap_h = xmap_h;
   tb.x_offset = cfg->x_offset; tb.t_px_scale = cfg->xmap_width - 1;
   tb.p03 = cfg->p03; tb.z_near = cfg->z_near; tb.z_far = cfg->z_far;
+  RigPlan::Dims& d = h->plan_in_create().dims;  // the same dimensions for the rules
+  d.cam_w = tb.cam_w; d.cam_h = tb.cam_h; d.proj_w = tb.proj_w; d.proj_h = tb.proj_h; d.rect_w = tb.rect_w; d.rect_h = tb.rect_h;
+  d.xmap_w = tb.xmap_w; d.xmap_h = tb.xmap_h; d.x_offset = tb.x_offset; d.projector = cfg->view == XM_VIEW_PROJECTOR;
   return XM_OK;
 }
 
 // K2's static per-tile patch rectangles and per-pixel offsets, for each of its geometries, and which one the pipelined kernel takes
 int build_k2_tables(xm_handle* h, CreateOpts& o) {
   const xm_config* cfg = &h->cfg;
-  if (!h->d_pmap) return XM_OK;
+  RigPlan& p = h->plan_in_create();
+  if (!p.dims.has_pmap) return XM_OK;
   double mean_cells2 = 0.0;
   bool pipe_ok_g[3] = {false, false, false};
   for (int g = 0; g < 3; ++g) {
@@ -132,6 +139,7 @@ int build_k2_tables(xm_handle* h, CreateOpts& o) {
     const unsigned tiles_x = grid_for(cfg->proj_width, K2_TX * ppt), tiles_y = grid_for(cfg->proj_height, K2_TY);
     HIP_TRY(h->d_k2_tiles[g].alloc((size_t)tiles_x * tiles_y));
     HIP_TRY(h->d_k2_pix[g].alloc((size_t)cfg->proj_width * cfg->proj_height));
+    if (g == 1) p.k2.has_tables = true;
     int4* const d_tiles = h->d_k2_tiles[g].get();
     u32* const d_pix = h->d_k2_pix[g].get();
     if (g == 0) hipLaunchKernelGGL(k_build_k2_tables<1>, dim3(tiles_x, tiles_y), dim3(K2_TX * K2_TY), 0, 0, h->tb, d_tiles, d_pix);
@@ -139,11 +147,12 @@ int build_k2_tables(xm_handle* h, CreateOpts& o) {
     else hipLaunchKernelGGL(k_build_k2_tables<4>, dim3(tiles_x, tiles_y), dim3(K2_TX * K2_TY), 0, 0, h->tb, d_tiles, d_pix);
     HIP_TRY(hipGetLastError());
     if (g > 0) {  // the pipelined kernel's u16 copy
-      h->k2_pix_stride = (cfg->proj_width + 7) & ~7;
-      const size_t n16 = (size_t)h->k2_pix_stride * cfg->proj_height;
+      p.k2pipe.pix_stride = (cfg->proj_width + 7) & ~7;
+      const size_t n16 = (size_t)p.k2pipe.pix_stride * cfg->proj_height;
       HIP_TRY(h->d_k2_pix16[g].alloc(n16, 16));
+      p.k2pipe.has_pix16[g] = true;
       hipLaunchKernelGGL(k_k2_pix_to_u16, dim3(grid_for(n16, BLOCK)), dim3(BLOCK), 0, 0, d_pix, h->d_k2_pix16[g].get(), cfg->proj_width,
-                         cfg->proj_height, h->k2_pix_stride);
+                         cfg->proj_height, p.k2pipe.pix_stride);
       HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipDeviceSynchronize());
@@ -160,9 +169,9 @@ int build_k2_tables(xm_handle* h, CreateOpts& o) {
       pipe_ok = pipe_ok && k2_pipe_tile_ok(r);
     }
     if (g < 2)
-      for (const int4& r : tiles) h->k2_patch_cols_max = r.z < 0 || h->k2_patch_cols_max < 0 ? -1 : std::max(h->k2_patch_cols_max, r.z);
+      for (const int4& r : tiles) p.k2.patch_cols_max = r.z < 0 || p.k2.patch_cols_max < 0 ? -1 : std::max(p.k2.patch_cols_max, r.z);
     if (g == 1) {
-      h->k2_pipe_rig_ok = pipe_ok;
+      p.k2pipe.rig_ok = pipe_ok;
       mean_cells2 = cells / (double)std::max<size_t>(tiles.size(), 1);
     }
     pipe_ok_g[g] = pipe_ok;
@@ -174,9 +183,9 @@ int build_k2_tables(xm_handle* h, CreateOpts& o) {
     if (g == 2) {
       const bool small = mean_cells2 < 2.0 * (2 * K2_TX * K2_TY);
       const int want = o.k2_pipe_ppt ? atoi(o.k2_pipe_ppt) : small ? 4 : 2;
-      h->k2_pipe_g = h->k2_pipe_rig_ok && want >= 4 && pipe_ok_g[2] ? 2 : 1;
+      p.k2pipe.g = p.k2pipe.rig_ok && want >= 4 && pipe_ok_g[2] ? 2 : 1;
     }
-    h->k2_tile_cap[g] = std::min((cap + 7) & ~7, (int)K2_TILE_MAX);
+    p.k2.tile_cap[g] = std::min((cap + 7) & ~7, (int)K2_TILE_MAX);
   }
   h->tb.k2_tiles1 = h->d_k2_tiles[0].get();
   h->tb.k2_pix1 = h->d_k2_pix[0].get();
@@ -185,43 +194,28 @@ int build_k2_tables(xm_handle* h, CreateOpts& o) {
   return XM_OK;
 }
 
-// What the rig's tables allow: the compact (32-bit) key frame, the pipelined K2's LDS table, column tiles or owner tiles.
+// What the rig's tables allow: the compact (32-bit) key frame, the pipelined K2's LDS table, column tiles or owner tiles.  The
+// arithmetic on the tables' extrema is classify_tables' (xm_plan.hpp); here: the switches, the device, and the one question only
+// the device answers (k_cols_check: is cell(row, column) injective, does every live pair land inside the frame).
 int classify_rig(xm_handle* h, const CreateOpts& o) {
   const xm_config* cfg = &h->cfg;
+  RigPlan& p = h->plan_in_create();
   const int xmap_h = cfg->xmap_height;
   const size_t cam_px = (size_t)cfg->cam_width * cfg->cam_height, xm_cells = (size_t)xmap_h * cfg->xmap_width;
-  int xr_min = 32767, xr_max = -32768, xp_min = 32767, xp_max = -32768;
-  for (size_t i = 0; i < cam_px; ++i) {
-    xr_min = std::min<int>(xr_min, cfg->cam_mapx_i16[i]);
-    xr_max = std::max<int>(xr_max, cfg->cam_mapx_i16[i]);
-  }
-  for (size_t i = 0; i < xm_cells; ++i) {
-    xp_min = std::min<int>(xp_min, cfg->proj_x_map[i]);
-    xp_max = std::max<int>(xp_max, cfg->proj_x_map[i]);
-  }
-  {  // does the rig qualify for the compact (32-bit) key frame?  (see key32_tag in xmaps_common.hpp)
-    // (largest disparity: the projector's largest x, never taken below 0, against the LUT's smallest)
-    const long max_disp = std::max<long>((long)std::max(xp_max, 0) - xr_min - cfg->x_offset, (long)0 - xr_min - cfg->x_offset);
-    // (camera view: (event index + 1) << 12 | disparity on the camera frame -- only the disparity range matters)
-    h->key32_ok = (cfg->view != XM_VIEW_PROJECTOR || (cfg->rect_height & 3) == 0) && max_disp < (1l << KEY32_DISP_BITS) &&
-                  !(o.key32 && o.key32[0] == '0');
-    // the pipelined K2 keeps the per-disparity table in LDS: every disparity an event of this rig can have (<= 4096 entries, 32 KB)
-    // (at most 2048 entries = 16 KB: with the patch and the staging rows a block then stays under 27 KB of LDS, six blocks per CU;
-    //  a larger disparity -- the reference's ESL calibration allows 3808 through LUT entries far outside the frame, no rendered
-    //  frame comes near -- reads the global table)
-    h->k2_pipe_nlds = (int)std::max<long>(1, std::min<long>(std::min<long>(max_disp + 1, 65536), o.k2_nlds_max));
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, cfg->device) == hipSuccess && prop.multiProcessorCount > 0) h->n_cus = prop.multiProcessorCount;
-  }
+  const bool projector = p.dims.projector;
+  const TableExtrema ex = table_extrema(cfg->cam_mapx_i16, cam_px, cfg->proj_x_map, xm_cells);
+  const RigClass rc = classify_tables(ex, cfg->x_offset, projector, cfg->rect_height, o.k2_nlds_max);
+  p.compact.key32_ok = rc.key32_ok && !(o.key32 && o.key32[0] == '0');
+  p.k2pipe.nlds = rc.k2_pipe_nlds;
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, cfg->device) == hipSuccess && prop.multiProcessorCount > 0) p.dims.n_cus = prop.multiProcessorCount;
   // does the rig qualify for the column-tile K1?  (xmaps_k1cols.hpp)
   const char* ec = o.cols;
-  // the reference's int16 wrap-around in disp = xp - xr - x_offset (xmd:27) must never trigger on this rig: then
-  // disp >= 0 <=> xp - x_offset >= xr, which is what makes "dead" X-map cells recognisable
-  const bool no_wrap = (long)xp_max - xr_min - cfg->x_offset <= 32767 && (long)xp_min - xr_max - cfg->x_offset >= -32768;
-  h->cols_xr_min = xr_min;
-  h->lut_xr_max = xr_max;
+  const int xr_min = ex.xr_min;
+  p.cols.xr_min = xr_min;
+  p.cols.xr_max = ex.xr_max;
   bool injective = false;
-  if (cfg->view == XM_VIEW_PROJECTOR && no_wrap && cfg->rect_width <= 65536) {
+  if (projector && rc.no_wrap && cfg->rect_width <= 65536) {
     DevMem<u32> d_dup;
     HIP_TRY(d_dup.alloc(2));
     HIP_TRY(hipMemset(d_dup, 0, 2 * sizeof(u32)));
@@ -232,82 +226,57 @@ int classify_rig(xm_handle* h, const CreateOpts& o) {
     HIP_TRY(hipMemcpy(dup, d_dup, sizeof dup, hipMemcpyDeviceToHost));
     injective = dup[0] == 0;  // every frame cell has at most one (row, time column) that can write it
     // every live pair has its cell inside the frame and every row an event can land in was looked at: no per-event cell test
-    if (dup[1] == 0 && cfg->rect_height >= xmap_h - 1) h->cols_flags |= COLS_F_ALL_IN_FRAME;
+    if (dup[1] == 0 && cfg->rect_height >= xmap_h - 1) p.cols.flags |= COLS_F_ALL_IN_FRAME;
   }
-  h->cols_ok = injective && h->d_pmap && !(ec && ec[0] == '0');
-  h->cols_single = ec && ec[0] == '2';
-  if (!injective && cfg->view == XM_VIEW_PROJECTOR && no_wrap && h->d_pmap && !(ec && ec[0] == '0')) {
+  p.cols.ok = injective && p.dims.has_pmap && !(ec && ec[0] == '0');
+  p.cols.single = ec && ec[0] == '2';
+  if (!injective && projector && rc.no_wrap && p.dims.has_pmap && !(ec && ec[0] == '0')) {
     // the reference's own calibration: several time columns per frame cell -> owner tiles (xmaps_k1own.hpp)
-    h->cols_flags = 0;
-    if (int rc = own_setup(h, cfg, xr_min)) return rc;
-    h->cols_ok = h->own_mode;
+    p.cols.flags = 0;
+    if (int rc_o = own_setup(h, p, cfg, xr_min)) return rc_o;
+    p.cols.ok = p.cols.own_mode;
     // single-frame calls take the owner tiles too unless XM_COLS=1 says groups only (measured on ESL-like frames, four frames in
     // flight: 12.05 us per frame against 13.6 with the one-thread-per-event kernel and its 150 k divergent atomics)
-    if (h->own_mode && !(ec && ec[0] == '1')) h->cols_single = true;
+    if (p.cols.own_mode && !(ec && ec[0] == '1')) p.cols.single = true;
   }
   // the compact key frame orders the writers of a cell by TILE only: two time columns of one tile that share a cell would be
   // ordered by their disparity bits -- it needs the same property (the 64-bit keys carry the full event index and do not)
-  if (cfg->view == XM_VIEW_PROJECTOR) h->key32_ok = h->key32_ok && injective;
-  if (cfg->view == XM_VIEW_PROJECTOR) {
-    h->key_cells = (size_t)cfg->rect_width * cfg->rect_height;
-    h->out_w = cfg->proj_width;
-    h->out_h = cfg->proj_height;
+  if (projector) p.compact.key32_ok = p.compact.key32_ok && injective;
+  if (projector) {
+    p.dims.key_cells = (size_t)cfg->rect_width * cfg->rect_height;
+    p.dims.out_w = cfg->proj_width;
+    p.dims.out_h = cfg->proj_height;
   } else {
-    h->key_cells = cam_px;
-    h->out_w = cfg->cam_width;
-    h->out_h = cfg->cam_height;
+    p.dims.key_cells = cam_px;
+    p.dims.out_w = cfg->cam_width;
+    p.dims.out_h = cfg->cam_height;
   }
   return XM_OK;
 }
 
-// K1 LDS windows (w_ts X-map columns, w_x camera columns) within the LDS budget, and the widest column tile
-void size_k1_windows(xm_handle* h, const CreateOpts& o) {
-  const xm_config* cfg = &h->cfg;
-  const int xmap_h = cfg->xmap_height;
-  // C-1M needs 44 KB (w_ts = 5, w_x = 16): three blocks per CU beside K2's 12 KB blocks
-  size_t budget = 76 * 1024;
-  int w_ts = 5, w_x = o.k1_wx;  // 5 time columns, 16 camera columns: 70 KB at C-1M
-  auto need = [&](int wt, int wx) {
-    // must mirror the carve-up at the top of k_scatter_tiled (uint4 units, +1 uint4 of alignment slack per band)
-    const size_t win_words = cfg->view == XM_VIEW_PROJECTOR ? (size_t)wt * xmap_h : (size_t)wx * cfg->cam_height;
-    constexpr size_t slack = 64;  // LDS-direct band loads write whole waves: one wave of slack behind each band
-    const size_t win_q = (win_words + 3) / 4, lut_q = ((size_t)wx * cfg->cam_height + 3) / 4 + 1 + slack,
-                 xm_q = ((size_t)wt * xmap_h + 7) / 8 + 1 + slack;
-    return 16 * (std::max(win_q, lut_q) + xm_q + 1 + slack);  // slots and LUT band share a region; +1 (+ a wave): dump area of the band loads
-  };
-  while (need(w_ts, w_x) > budget && (w_ts > 1 || w_x > 1)) {
-    if (w_ts * xmap_h * 6 >= w_x * cfg->cam_height * 4 && w_ts > 1) w_ts -= 1;
-    else if (w_x > 1) w_x /= 2;
-    else w_ts -= 1;
-  }
-  if (need(w_ts, w_x) <= budget && w_ts >= 1 && w_x >= 1) {
-    h->w_ts = w_ts;
-    h->w_x = w_x;
-    h->k1_lds = need(w_ts, w_x);
-  } else {
-    h->k1_direct = true;  // tables too tall for LDS: every event takes the direct path
-  }
-  // column tiles: the widest tile whose bands + slots fit the same budget (the LUT band is the tiled kernel's)
-  if (h->cols_ok && !h->k1_direct && h->w_x > 0) {
-    int wm = 0;
-    while (wm < 16 && cols_lds_bytes(h, wm + 1) <= budget) wm += 1;
-    h->cols_w_max = wm;
-  }
-  if (h->cols_w_max < 1 && !h->own_mode) h->cols_ok = false;
+// K1 LDS windows and the widest column tile (size_k1_windows, xm_plan.hpp) into the plan
+void apply_k1_windows(RigPlan& p, const CreateOpts& o) {
+  const K1Windows w = size_k1_windows(p, o.k1_wx);
+  p.k1.w_ts = w.w_ts;
+  p.k1.w_x = w.w_x;
+  p.k1.lds = w.lds;
+  p.modes.k1_direct = w.k1_direct;
+  p.cols.w_max = w.cols_w_max;
+  p.cols.ok = w.cols_ok;
 }
 
 // The pipelined K2's live-slot masks (xm_k2_live.hpp), for both of its geometries.  Derived only where this handle's column-tile
 // K1 is the sole writer of the frames that kernel reads: a group's K2 (launch_k2_batch<2> / <2, 2>) reads the slots' frame16,
-// which k_scatter_cols / k_scatter_cols_batch write through cols_cell() with h->tb and h->cols_xr_min, lone frames and groups
+// which k_scatter_cols / k_scatter_cols_batch write through cols_cell() with h->tb and the plan's cols.xr_min, lone frames and groups
 // alike, and which nothing else stores into after the memset of create_slots.  Owner-tile rigs (another flush, a sheared frame),
 // rigs without column tiles and "XM_K2_LIVE"=0 get all ones.  After classify_rig and size_k1_windows: both decide cols_ok.
-int build_k2_live(xm_handle* h, const CreateOpts& o) {
+int build_k2_live(xm_handle* h, const RigPlan& p, const CreateOpts& o) {
   const xm_config* cfg = &h->cfg;
-  const bool derive = h->k2_live && h->cols_ok && !h->own_mode && h->k2_pipe_rig_ok;
+  const bool derive = p.k2pipe.live && p.cols.ok && !p.cols.own_mode && p.k2pipe.rig_ok;
   for (int g = 1; g < 3; ++g) {
     const std::vector<int4>& tiles = o.k2_tiles[g];
     if (tiles.empty()) {  // (a rig without a projector map has no K2 tables at all; with them, the pipelined kernel must find its masks)
-      if (h->d_k2_tiles[g]) return fail(XM_ERR_INVALID, "no tile records for the pipelined K2's live-slot masks (geometry %d)", g);
+      if (p.k2.has_tables) return fail(XM_ERR_INVALID, "no tile records for the pipelined K2's live-slot masks (geometry %d)", g);
       continue;
     }
     std::vector<uint32_t> mask(tiles.size() * (size_t)K2L_WORDS, ~0u);
@@ -315,12 +284,12 @@ int build_k2_live(xm_handle* h, const CreateOpts& o) {
       static_assert(K2L_THREADS == K2_TX * K2_TY && K2L_UN == K2P_UN && sizeof(K2LiveTile) == sizeof(int4), "xm_k2_live.hpp restates the loader's geometry");
       K2LiveRig rig;
       rig.xmap = cfg->proj_x_map; rig.xmap_w = cfg->xmap_width; rig.xmap_h = cfg->xmap_height;
-      rig.x_offset = cfg->x_offset; rig.xr_min = h->cols_xr_min; rig.rect_w = cfg->rect_width; rig.rect_h = cfg->rect_height;
+      rig.x_offset = cfg->x_offset; rig.xr_min = p.cols.xr_min; rig.rect_w = cfg->rect_width; rig.rect_h = cfg->rect_height;
       rig.shear_m = h->tb.shear_m; rig.shear_bias = h->tb.shear_bias; rig.shear_extra = h->tb.shear_extra;
       std::vector<K2LiveTile> recs(tiles.size());
       for (size_t i = 0; i < tiles.size(); ++i) recs[i] = K2LiveTile{tiles[i].x, tiles[i].y, tiles[i].z, tiles[i].w};
       k2_live_mask(rig, recs.data(), recs.size(), mask);
-      if (h->k2_live_report) {
+      if (p.k2pipe.live_report) {
         const K2LiveStats st = k2_live_stats(rig, recs.data(), recs.size());
         fprintf(stderr, "[xm] K2 live quads, tiles of %d x 16 pixels: frame cells %.4f quads %.4f lines %.4f; loader slots %.4f, their lines %.4f\n",
                 16 << g, st.cells, st.quads, st.lines, st.slot_quads, st.slot_lines);
@@ -333,7 +302,7 @@ int build_k2_live(xm_handle* h, const CreateOpts& o) {
 }
 
 // the slot states, then per slot: its stream, key frames, flags; every slot reset on its own stream
-int create_slots(xm_handle* h, [[maybe_unused]] const CreateOpts& o) {
+int create_slots(xm_handle* h, const RigPlan& p, [[maybe_unused]] const CreateOpts& o) {
   const xm_config* cfg = &h->cfg;
   const int n_slots = cfg->n_slots;
 #ifdef XM_ABLATE
@@ -366,26 +335,26 @@ int create_slots(xm_handle* h, [[maybe_unused]] const CreateOpts& o) {
       else if (cfg->flags & XM_FLAG_DEFAULT_STREAMS) HIP_TRY(s.stream.create(hipStreamNonBlocking));
       else HIP_TRY(s.stream.create_with_priority(hipStreamNonBlocking, hi));
     }
-    HIP_TRY(s.key_frame.alloc(h->key_cells));
-    if (h->key32_ok) {
-      HIP_TRY(s.key32.alloc(h->key_cells));
-      HIP_TRY(hipMemset(s.key32, 0, h->key_cells * sizeof(u32)));
+    HIP_TRY(s.key_frame.alloc(p.dims.key_cells));
+    if (p.compact.key32_ok) {
+      HIP_TRY(s.key32.alloc(p.dims.key_cells));
+      HIP_TRY(hipMemset(s.key32, 0, p.dims.key_cells * sizeof(u32)));
     }
-    if (h->cols_ok) {  // cells no (row, column) pair maps to are never written: they stay 0 from here on
+    if (p.cols.ok) {  // cells no (row, column) pair maps to are never written: they stay 0 from here on
       const size_t bytes = cols_frame_bytes(frame16_cells(h->tb), cfg->xmap_width);  // frame + K0b's bounds and thresholds
       HIP_TRY(s.frame16.alloc((bytes + 1) / sizeof(uint16_t)));
       HIP_TRY(hipMemset(s.frame16, 0, bytes));
     }
-    if (cfg->view == XM_VIEW_PROJECTOR && h->k2_flags) HIP_TRY(s.dirty.alloc(((h->key_cells + 15) >> 4) + 64));
+    if (cfg->view == XM_VIEW_PROJECTOR && p.modes.k2_flags) HIP_TRY(s.dirty.alloc(((p.dims.key_cells + 15) >> 4) + 64));
     s.st = h->d_states + i;
-    if (h->try_sorted) {
+    if (p.modes.try_sorted) {
       HIP_TRY(s.h_flags.alloc(16, hipHostMallocMapped));
       s.h_flags[0] = s.h_flags[1] = 0;
       u32* d_flags = s.h_flags.device_ptr();
       if (!d_flags) return fail(XM_ERR_HIP, "hipHostGetDevicePointer failed for a slot's flag words");
       HIP_TRY(hipMemcpy(&s.st->host_flags, &d_flags, sizeof d_flags, hipMemcpyHostToDevice));
     }
-    hipLaunchKernelGGL(k_reset_slot, dim3(1024), dim3(BLOCK), 0, s.stream.get(), s.st, s.key_frame.get(), (u64)h->key_cells, s.dirty.get());
+    hipLaunchKernelGGL(k_reset_slot, dim3(1024), dim3(BLOCK), 0, s.stream.get(), s.st, s.key_frame.get(), (u64)p.dims.key_cells, s.dirty.get());
     HIP_TRY(hipGetLastError());
   }
   hipLaunchKernelGGL(k_reset_slot, dim3(1), dim3(BLOCK), 0, h->slots[0].stream.get(), h->aux_st, (u64*)nullptr, (u64)0,

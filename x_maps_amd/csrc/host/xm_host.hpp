@@ -55,17 +55,6 @@ struct DevBuf {  // grow-only device scratch: grows by a quarter beyond what was
   }
 };
 
-struct EventsView {
-  const uint16_t* x = nullptr;
-  const uint16_t* y = nullptr;
-  const void* t = nullptr;
-  const int16_t* p = nullptr;
-  const void* aos = nullptr;
-  size_t n = 0;
-  int t_dtype = XM_T_INT64;
-  bool use_p = false;
-};
-
 struct HipOrderOps {  // SlotOrder's calls on the HIP runtime
   static int rc(hipError_t e, const char* call) { return e == hipSuccess ? XM_OK : fail(XM_ERR_HIP, "%s failed: %s", call, hipGetErrorString(e)); }
   static hipEvent_t ev(void* e) { return static_cast<hipEvent_t>(e); }
@@ -160,6 +149,12 @@ struct Worker {
 
 struct xm_handle {
   xm_config cfg{};
+  // What xm_create decided about the rig (xm_plan.hpp): filled by its stages through plan_in_create(), read-only from
+  // create_slots on.  Every path and shape rule reads this and nothing else of the handle.
+  const RigPlan& plan() const { return plan_; }
+  RigPlan& plan_in_create() { return plan_; }  // (xm_create and its stages up to apply_k1_windows, own_setup through them)
+
+  // ---- owners of device memory, streams and events ----
   // the handle's own streams and events come before its buffers, which are therefore released first; a Slot orders its own
   // members the same way (every stream has been synchronised by xm_destroy before any of this runs: see xm_res.hpp)
   std::vector<Stream> gstreams;  // default-priority streams the hipGraph batches are captured on and launched from
@@ -181,78 +176,37 @@ struct xm_handle {
   // ([2]: four pixels per thread, 64 x 16 tiles -- the pipelined kernel on rigs whose patches are small against the tile)
   DevMem<int4> d_k2_tiles[3];  // [g]: tiles of 16 << g pixels x 16 rows (owners; tb.k2_tiles1 / tb.k2_tiles view [0] / [1])
   DevMem<u32> d_k2_pix[3];     // (owners; tb.k2_pix1 / tb.k2_pix view [0] / [1])
-  DevMem<uint16_t> d_k2_pix16[3];  // the pipelined K2's copy: u16, rows padded to k2_pix_stride
+  DevMem<uint16_t> d_k2_pix16[3];  // the pipelined K2's copy: u16, rows padded to plan().k2pipe.pix_stride
   // the pipelined K2's live-slot masks (xm_k2_live.hpp): per tile, wave and loader register the lanes whose quad some (row, time
   // column) pair of the column tiles can store into; all ones where that is not known (owner tiles, "XM_K2_LIVE"=0)
   DevMem<uint4> d_k2_live[3];
-  bool k2_live = true;                 // "XM_K2_LIVE"=0: all ones (the same kernel, for tests and A/B runs)
-  bool k2_live_report = false;         // "XM_K2_LIVE"=2: the derived masks, and their live fractions on stderr (profiles)
-  int k2_pix_stride = 0;
-  int k2_consec = -1;  // k_frame_proj_pipe<PPT, true>: PPT consecutive pixels per thread; -1 = where it measured faster (PPT = 4), XM_K2_CONSEC=0|1 forces
-  int k2_tile_cap[3] = {K2_TILE_MAX, K2_TILE_MAX, K2_TILE_MAX};  // cells of the largest K2 patch (multiple of 8)
-  int k2_pipe_g = 1;  // the pipelined kernel's geometry: tiles of 16 << g pixels x 16 rows (2 / 4 pixels per thread)
-  int k2_patch_cols_max = 0;  // widest patch of the 16 x 16 / 32 x 16 tiles (-1: some patch does not fit LDS)
-  int k2_force_ppt = 0;                             // XM_K2_PPT=1/2: experiments
-  // pipelined K2 of the group launches (xmaps_k2pipe.hpp): table entries kept in LDS, CUs of the device, switch (XM_K2_PIPE=0: off)
-  int k2_pipe_nlds = 0, n_cus = 256;
-  uint64_t k2_pipe_frames = 0;  // frames finished by the pipelined K2 since xm_create (xm_debug_k2_pipe_frames)
-  int k2_per_cu_max = 8;        // "XM_K2_PER_CU": the pipelined K2's blocks per CU at most (what it leaves, the next group's K1 can take)
-  // "XM_K2_CHAIN": the pipelined K2 launches of different groups (different streams) wait for each other -- one K2 at a time, at
-  // k2_per_cu_max blocks per CU, and the following groups' boundary pass and K1 in what it leaves (profiles/r05_own_tiles.md)
-  bool k2_chain = false;
-  std::mutex k2_chain_mu;
-  unsigned k2_chain_n = 0;
-  bool k2_pipe_force = false;   // XM_K2_PIPE=2 (tests): also for groups too small for the pipeline to matter
-  int k2_pipe_blocks = 0;       // "XM_K2_PIPE_BLOCKS" (tests): at most this many persistent blocks, so that each walks several items; 0 = no cap
-  bool k2_pipe = true, k2_pipe_rig_ok = false;  // (rig_ok: every tile's patch fits the pipelined loader, rect_h % 8 == 0)
   DevMem<ulonglong2> d_zero16;  // 16 zero bytes: what K2 reads instead of a clean key-frame line
   DevMem<SlotState> d_states;  // n_slots + 1 (last = aux state for stage / shard calls)
   SlotState* aux_st = nullptr;  // view: the last entry of d_states
   DevMem<u64> d_shard_n;  // shards on the column tiles: the piece's own event count (device) + its FrameDesc behind it
   std::vector<Slot> slots;
-  int next_slot = 0;
-  int last_slot = 0;
-  size_t key_cells = 0;   // cells of the fused path's key frame (rect or camera frame)
-  int out_w = 0, out_h = 0;
   DevMem<u64> stage_frame;  // lazily allocated scratch for the stage API (max(rect, cam) cells)
   size_t stage_cells = 0;
   SurfaceScratch surf;      // xm_process_time_surfaces
-  // K1 tiling: LDS windows (time columns / camera columns) and the dynamic LDS they need; 0 = direct kernel
-  int w_ts = 0, w_x = 0;
-  size_t k1_lds = 0;
-  bool k1_direct = false, k2_direct = false;
-  bool k2_flags = false;      // XM_K2_FLAGS=1: K1 marks dirty 128-byte lines of the key frame, K2 skips clean ones.
-                              // Measured: K2 fetches 37 % fewer bytes but is not faster (it is latency, not bandwidth bound)
   std::vector<std::unique_ptr<Worker>> workers;  // one per slot stream (empty: launches happen in the calling thread)
-  bool key32_ok = false;      // the rig qualifies for the compact key frame (projector view, rect_h % 4 == 0, disparities < 4096)
-  // column-tile K1 (xmaps_k1cols.hpp): the rig qualifies (projector view, cell(row, column) injective, no int16 wrap in the
-  // disparity arithmetic), smallest rectified x of the LUT, widest tile the LDS budget allows, events a tile should hold
-  bool cols_ok = false;
-  bool cols_single = false;  // XM_COLS=2: also for single-frame calls (default: groups of frames only -- a single frame's third
-                             // launch, the boundary pass, costs the pipelined one-frame-per-call path more than the tiles save)
-  int cols_xr_min = 0, cols_w_max = 0, cols_target = 3700;
-  int lut_xr_max = 0;  // largest rectified x of the LUT (cols_xr_min: its smallest): the ingest's FirstEventPerYT cell map is this + 1 wide
-  int cols_lds_pad = 0;  // XM_COLS_LDS_PAD (experiments): bytes of dynamic LDS a column-tile block asks for beyond its carve-up
-  int cols_flags = 0;  // COLS_F_ALL_IN_FRAME when no live (row, column) pair of the rig maps outside the frame
-  // owner tiles (xmaps_k1own.hpp): the rig's (row, column) -> cell map is not injective (the reference's own calibration), but
-  // every cell's columns lie within a few (<= 7) columns of its first one: cols_ok with own_mode set; tile widths and halos per plan
-  bool own_mode = false;
-  // up to three plans (own_setup), by falling tile width: ownership per 8-row group on tiles of 20 and of 16 columns -- frames
-  // whose tiles fit one event pass of a block --, then ownership per row on tiles of 8 -- denser frames, and rigs whose slant
-  // rules the first two out.  All write the same frame (every cell a pair maps to, every frame), so consecutive frames of a slot
-  // may take different plans.
-  static constexpr int OWN_PLANS = 3;
-  struct OwnSet {
-    bool ok = false, all_in = false;
-    int w = 0, halo = 0, extras = 0;
-    int r_lo = 0, hr = 0, hrp = 0, rp = 0, grouped = 0, nxs_max = 0, extra_max = 0;
+  struct OwnSet {  // the device tables of the owner tiles' plan i (its scalars: plan().own[i])
     DevMem<uint16_t> d_xmap_own;
     DevMem<uint16_t> d_xmap_extra;
     DevMem<int4> d_tiles;
     DevMem<u32> d_bm;
     DevMem<u32> d_extra_cells;
   } own[OWN_PLANS];
-  int own_ept_forced = 0;  // "XM_OWN_EPT" (experiments): 4 = four events per thread where a tile then fits one pass
+  // multi-frame launches (xm_process_batch, batched hipGraphs, ingest): frame descriptors.  Eager batches stage them
+  // through a ring of pinned host entries -> device entries (one memcpy per batch, stream-ordered before its kernels).
+  PinnedMem<FrameDesc> h_descs;  // pinned  [DESC_RING][n_slots]
+  DevMem<FrameDesc> d_descs;     // device  [DESC_RING][n_slots]
+  std::vector<hipStream_t> streams;  // views: the distinct slot streams
+
+  // ---- run-time state: what changes with the calls.  Written by the API thread (the one inside XM_ENTER) unless said otherwise ----
+  int next_slot = 0;
+  int last_slot = 0;
+  bool capturing = false;     // inside xm_graph_create's stream capture (no host-side redo possible there)
+  uint64_t sorted_fallbacks = 0;
   // XM_FLAG_ADAPTIVE_BATCH: asynchronous device-pointer frames are submitted as GROUPS (multi-frame launches) whenever the GPU
   // is still busy with earlier ones: a frame is launched at once when no group is in flight (an idle GPU -- the 60 Hz live
   // case -- never waits), otherwise it joins the pending list, which goes out as one group with the first call that finds the
@@ -263,31 +217,29 @@ struct xm_handle {
     uint8_t* bgr;
   };
   std::vector<Deferred> pending;
-  int ab_max = 0;                                  // 0: off
+  int ab_max = 0;                                  // 0: off (set by xm_create, constant afterwards)
   hipEvent_t ab_inflight[4] = {nullptr, nullptr, nullptr, nullptr};  // views (events of batch_ev): end-of-group events of the last four groups submitted this way
   uint64_t ab_groups = 0, ab_frames = 0;
-  std::atomic<uint64_t> path_counts[4] = {};  // frames enqueued per K1 variant (xm_path_counts)
-  // (atomics: with XM_FLAG_LAUNCH_WORKERS the launch threads and the API thread all pass through enqueue_frame)
-  std::atomic<int> key32_score{0};  // raised by frames that failed the compact path, decays with every frame that took it
-  std::atomic<int> key32_pause{0};  // frames for which the compact path stays switched off (it kept failing: sparse / noisy stream)
-  bool time_sorted = false;   // XM_FLAG_TIME_SORTED
-  bool try_sorted = false;    // XM_FLAG_TRY_SORTED
-  bool capturing = false;     // inside xm_graph_create's stream capture (no host-side redo possible there)
-  uint64_t sorted_fallbacks = 0;
-  // multi-frame launches (xm_process_batch, batched hipGraphs, ingest): frame descriptors.  Eager batches stage them
-  // through a ring of pinned host entries -> device entries (one memcpy per batch, stream-ordered before its kernels).
-  PinnedMem<FrameDesc> h_descs;  // pinned  [DESC_RING][n_slots]
-  DevMem<FrameDesc> d_descs;     // device  [DESC_RING][n_slots]
-  bool desc_used[DESC_RING] = {};
+  bool desc_used[DESC_RING] = {};  // the descriptor ring
   int desc_next = 0;
   uint64_t batch_counter = 0;
-  std::vector<hipStream_t> streams;  // views: the distinct slot streams
   std::vector<int> batch_ev_next;
   unsigned graph_ev_next = 0;
-  // dynamic-LDS caps already raised on this handle's device, per kernel function (launch workers call concurrently)
+  // API thread and, with XM_FLAG_LAUNCH_WORKERS, the launch threads (all pass through enqueue_frame): atomics
+  std::atomic<uint64_t> path_counts[4] = {};  // frames enqueued per K1 variant (xm_path_counts)
+  std::atomic<int> key32_score{0};  // raised by frames that failed the compact path, decays with every frame that took it
+  std::atomic<int> key32_pause{0};  // frames for which the compact path stays switched off (it kept failing: sparse / noisy stream)
+  // whichever thread launches a group's K2 (launch_k2_pipe)
+  uint64_t k2_pipe_frames = 0;  // frames finished by the pipelined K2 since xm_create (xm_debug_k2_pipe_frames)
+  std::mutex k2_chain_mu;       // "XM_K2_CHAIN": guards k2_chain_n and the order of the chained launches
+  unsigned k2_chain_n = 0;
+  // dynamic-LDS caps already raised on this handle's device, per kernel function (launch workers call concurrently: lds_mu)
   std::mutex lds_mu;
   std::vector<std::pair<const void*, size_t>> lds_caps;
   int ensure_lds(const void* fn, size_t bytes);
+
+ private:
+  RigPlan plan_;
 };
 
 struct xm_graph {
@@ -334,20 +286,13 @@ thread_local ProfCtx g_prof;
       hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__);                                    \
   } while (0)
 
-inline unsigned grid_for(u64 items, unsigned per_block) {
-  u64 g = (items + per_block - 1) / per_block;
-  return (unsigned)(g ? g : 1);
-}
-
-inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
-
 size_t t_size(int t_dtype) { return t_dtype == XM_T_FLOAT32 ? 4 : 8; }
 
-int reset_slot(xm_handle* h, Slot& s, hipStream_t stream = nullptr) {
+int reset_slot(const RigPlan& pl, Slot& s, hipStream_t stream = nullptr) {
   if (!stream) stream = s.stream;
-  hipLaunchKernelGGL(k_reset_slot, dim3(1024), dim3(BLOCK), 0, stream, s.st, s.key_frame, (u64)h->key_cells, s.dirty);
+  hipLaunchKernelGGL(k_reset_slot, dim3(1024), dim3(BLOCK), 0, stream, s.st, s.key_frame, (u64)pl.dims.key_cells, s.dirty);
   HIP_TRY(hipGetLastError());
-  if (s.key32) HIP_TRY(hipMemsetAsync(s.key32, 0, h->key_cells * sizeof(u32), stream));
+  if (s.key32) HIP_TRY(hipMemsetAsync(s.key32, 0, pl.dims.key_cells * sizeof(u32), stream));
   s.key32_valid_from = 0;
   s.last.host_tag = 0;
   s.last.api_tag = 0;

@@ -101,7 +101,7 @@ int ingest_create_device_rings(IngestFixed& fx) {
   HIP_TRY(fx.h_verdicts.alloc(ING_VRING, hipHostMallocMapped));
   memset(fx.h_verdicts, 0, sizeof(IngVerdict) * ING_VRING);
   HIP_TRY(hipHostGetDevicePointer((void**)&fx.d_verdicts, fx.h_verdicts, 0));
-  HIP_TRY(fx.d_key_frame.alloc(h->key_cells));
+  HIP_TRY(fx.d_key_frame.alloc(h->plan().dims.key_cells));
   HIP_TRY(fx.d_slot.alloc(1));
   d.key_frame = fx.d_key_frame.get();
   d.slot = fx.d_slot.get();
@@ -109,7 +109,7 @@ int ingest_create_device_rings(IngestFixed& fx) {
   // (a memset of device memory may return before it has run and the ingest's streams do not wait for the default stream:
   //  k_reset_slot initialises the extrema slots inside these bytes -- seen once as a first frame with a wrong time normalisation)
   HIP_TRY(hipDeviceSynchronize());
-  hipLaunchKernelGGL(k_reset_slot, dim3(1024), dim3(BLOCK), 0, fx.frame_stream, d.slot, d.key_frame, (u64)h->key_cells, (unsigned char*)nullptr);
+  hipLaunchKernelGGL(k_reset_slot, dim3(1024), dim3(BLOCK), 0, fx.frame_stream, d.slot, d.key_frame, (u64)h->plan().dims.key_cells, (unsigned char*)nullptr);
   HIP_TRY(hipGetLastError());
   // (the staging entries' pinned twins, IngestCaller::h_pkt[], are allocated by the first PAGEABLE push: callers that push pinned
   //  packets or RAW words never pay for 16 x max_packet x 16 bytes of page-locked memory)
@@ -121,7 +121,7 @@ int ingest_create_device_rings(IngestFixed& fx) {
 // the pinned result ring, the device-side output frames, one warm-up copy into every ring entry
 int ingest_create_result_ring(IngestFixed& fx, IngestShared& sh) {
   const xm_ingest_config& cfg = fx.cfg;
-  const size_t px = (size_t)fx.h->out_w * fx.h->out_h;
+  const size_t px = (size_t)fx.h->plan().dims.out_w * fx.h->plan().dims.out_h;
   HIP_TRY(fx.h_status.alloc(fx.ring, hipHostMallocMapped));
   memset(fx.h_status, 0, sizeof(IngestStatus) * fx.ring);
   sh.h_depth.assign(fx.ring, nullptr);

@@ -46,7 +46,7 @@ int ingest_issue_frame(xm_ingest* g, uint64_t push_no, u64 n) {
   const int flt = la.push_filter[vi] & 7;
   const FrameDesc* desc = flt ? g->ff.d_descs + vi : cut;
   if (la.frames_since_clear >= fx.clear_every) {  // (stream-ordered behind every frame so far)
-    hipLaunchKernelGGL(k_reset_slot, dim3(1024), dim3(BLOCK), 0, s, fx.dev.slot, fx.dev.key_frame, (u64)h->key_cells, (unsigned char*)nullptr);
+    hipLaunchKernelGGL(k_reset_slot, dim3(1024), dim3(BLOCK), 0, s, fx.dev.slot, fx.dev.key_frame, (u64)h->plan().dims.key_cells, (unsigned char*)nullptr);
     la.frames_since_clear = 0;
   }
   la.frames_since_clear += 1;
@@ -63,7 +63,7 @@ int ingest_issue_frame(xm_ingest* g, uint64_t push_no, u64 n) {
   // K0 (general path: the cut frame is sorted whenever the camera stream is, but nothing here relies on it)
   launch_k0<long long, true, false>(one, s);
   // K1: tiled where a group of such frames would be, else one thread per event
-  if (int rc = launch_k1<long long, true, false>(h, one, batch_path(h, n), false, false, s)) return rc;
+  if (int rc = launch_k1<long long, true, false>(h, one, batch_path(h->plan(), n), false, false, s)) return rc;
   // the ingest stream must not append over the frame's events (dead, but still in the ring) before K1 has read them: whatever
   // is issued on it from now on waits for this event; what has been issued already fits the room k_ing_segment keeps (`ahead`)
   if (!flt) {
@@ -82,7 +82,7 @@ int ingest_issue_frame(xm_ingest* g, uint64_t push_no, u64 n) {
     la.t_out_wait_s += ingest_now() - tw;
     HIP_TRY(hipStreamWaitEvent(s, fx.out_ev[o], 0));
   }
-  if (h->cfg.view == XM_VIEW_PROJECTOR && h->k2_direct) return fail(XM_ERR_INVALID, "ingest needs the tiled frame kernel (XM_K2_DIRECT is set)");
+  if (h->cfg.view == XM_VIEW_PROJECTOR && h->plan().modes.k2_direct) return fail(XM_ERR_INVALID, "ingest needs the tiled frame kernel (XM_K2_DIRECT is set)");
   launch_frame_kernel(h, one, KM_KEY64, s);
   // the frame's statistics into its status entry while the slot's counters and the frame's events are still the frame's ...
   hipLaunchKernelGGL(k_ing_publish, dim3(1), dim3(64), 0, s, fx.dev.st, desc, (const IngFrameInfo*)(fx.d_infos + vi), (IngestStatus*)fx.h_status, (u64)push_no,

@@ -45,7 +45,7 @@ int ingest_out_frame(xm_ingest* g, const OutJob& j) {
   }
   const double t0 = ingest_now();
   HIP_TRY(hipStreamWaitEvent(os, fx.k2_ev[j.o], 0));
-  const size_t px = (size_t)h->out_w * h->out_h;
+  const size_t px = (size_t)h->plan().dims.out_w * h->plan().dims.out_h;
   // In pieces of 4 MB: with one frame per packet (EVT 3.0 period chunks) whole 6 MB copies gave 620-870 Mev/s in an ingest's first
   // minutes and 1170-1210 later, pieces 1130 every time (tools/esl_evt3_probe.py); 1 MB pieces overflow a queue of the runtime
   // and stall for milliseconds (tools/ubench/dma_mix.cpp), so the option does not go below 2 MB.
@@ -141,7 +141,7 @@ xm_frame_pool* pool_of(xm_ingest* g) {
   xm_frame_pool* pl = new (std::nothrow) xm_frame_pool();
   if (!pl) return nullptr;
   pl->device = g->fx.h->cfg.device;
-  const size_t px = (size_t)g->fx.h->out_w * g->fx.h->out_h;
+  const size_t px = (size_t)g->fx.h->plan().dims.out_w * g->fx.h->plan().dims.out_h;
   pl->bytes[0] = px * 4;
   pl->bytes[1] = px * 3;
   pl->cap = 1024;

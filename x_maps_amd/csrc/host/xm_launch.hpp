@@ -35,10 +35,6 @@ constexpr bool is_lone = std::is_same<F, LoneFrame>::value;
 unsigned frames(const LoneFrame&) { return 1; }
 unsigned frames(const FrameGroup& g) { return (unsigned)g.n; }
 
-// SoA columns that take 16-byte loads
-bool ev_vec16(const EventsView& ev) {
-  return !ev.aos && aligned(ev.x, 16) && aligned(ev.y, 16) && aligned(ev.t, 16) && (!ev.use_p || aligned(ev.p, 16));
-}
 bool vec16(const LoneFrame& f) { return ev_vec16(f.ev); }
 bool vec16(const FrameGroup& g) { return g.all_vec16; }
 
@@ -73,14 +69,8 @@ template <typename E>
 constexpr bool tile_types = std::is_same<typename E::T, long long>::value && !E::HAS_P;
 
 // ---- K0 (extrema) ---------------------------------------------------------------------------------------------------------------
-// blocks per frame: ~2048 events per thread-block iteration keeps every CU busy without drowning the 32 atomic slots (VEC2: K0_UN
-// loads x 2 events per thread per sweep); a grid-stride kernel, so the grid is capped
-unsigned k0_blocks(u64 n, bool vec2, unsigned cap) {
-  const unsigned g = grid_for(n, BLOCK * (vec2 ? 2 * K0_UN : 4));
-  return g > cap ? cap : g;
-}
 // VEC2 (16-byte loads of int64 SoA time stamps): a lone frame needs its t (and p) aligned, a group every column of every frame
-bool k0_vec2(const LoneFrame& f) { return aligned(f.ev.t, 16) && (!f.ev.use_p || aligned(f.ev.p, 4)); }
+bool k0_vec2(const LoneFrame& f) { return xm::k0_vec2(f.ev); }
 bool k0_vec2(const FrameGroup& g) { return g.all_vec16; }
 
 // COND = 1: the redo node of a captured group (cap = 64: usually every block returns at once)
@@ -109,28 +99,12 @@ void launch_minmax(const EventsView& ev, SlotState* st, u32 tag_override, hipStr
 }
 
 // ---- K1 (scatter): tiled, or one thread per event --------------------------------------------------------------------------------
-// The tiled kernel pays a fixed price per block (copy the bands, clear + scan w_ts * xmap_h slots), so it needs blocks of >= 1024
-// events whose time slice still fits the LDS window of w_ts X-map columns.  A frame of n events spreads over xmap_w columns: a
-// block of E events spans about E * xmap_w / n of them.  Dense frames (C-1M: 1 M events / 640 columns) get 4096-event blocks;
-// sparse ones (ESL-like: 150 K events / 1080 columns, < 1 event per slot, nothing to de-duplicate) go to the one-thread-per-event
-// kernel, whose cost is proportional to n.
-double k1_block_events(const xm_handle* h, u64 n) {  // the most events a block of a frame of n events may take
-  return h->tb.xmap_w > 0 ? (h->w_ts - 1.5) * (double)n / (double)h->tb.xmap_w : 0.0;
-}
-bool tiled_path(const xm_handle* h, u64 n) {  // dense enough for the tiled K1?
-  return !h->k1_direct && h->w_ts > 0 && h->w_x > 0 && k1_block_events(h, n) >= 1024.0;
-}
-unsigned k1_threads(const xm_handle* h, u64 n) {  // the tiled K1's block for frames of n events
-  const double max_ev = k1_block_events(h, n);
-  unsigned threads = TILE_THREADS;
-  while (threads > 1024 / TILE_EPT && (double)(threads * TILE_EPT) > max_ev) threads >>= 1;  // smallest block: 1024 events
-  return threads;
-}
-
+// (when a frame takes the tiled kernel, and its block: tiled_path / k1_tiled_shape, xm_plan.hpp)
 // tiled: the tiled kernel (key32: onto the compact key frame), else one thread per event.  COND = 1: the redo node of a captured
 // group (projector view, 64-bit keys, at most 32 blocks per frame)
 template <typename T, bool AOS, bool HAS_P, int COND = 0, typename F>
 int launch_k1(xm_handle* h, const F& fr, bool tiled, bool key32, bool sorted, hipStream_t stream) {
+  const RigPlan& pl = h->plan();
   auto go = [&](auto view_tag) -> int {
     constexpr int VIEW = decltype(view_tag)::value;
     if (!tiled) {
@@ -138,20 +112,20 @@ int launch_k1(xm_handle* h, const F& fr, bool tiled, bool key32, bool sorted, hi
         const EventsView& ev = fr.ev;
         const bool vec = !AOS && aligned(ev.x, 8) && aligned(ev.y, 8) && aligned(ev.t, 16) && (!HAS_P || aligned(ev.p, 8));
         if constexpr (AOS)
-          XM_LAUNCH((k_scatter<T, true, HAS_P, 1, VIEW>), dim3(grid_for(ev.n, BLOCK)), dim3(BLOCK), 0, stream,
+          XM_LAUNCH((k_scatter<T, true, HAS_P, 1, VIEW>), dim3(k1_direct_blocks(ev.n, false)), dim3(BLOCK), 0, stream,
                     (const uint16_t*)nullptr, (const uint16_t*)nullptr, (const T*)nullptr, (const int16_t*)nullptr,
                     (const uint4*)ev.aos, ev.n, fr.idx_offset, h->tb, fr.st, fr.tag_override, fr.mm_lo, fr.mm_hi, fr.mm_ext,
                     (u64*)fr.frame, fr.dirty, sorted ? 1 : 0);
         else if (vec)
-          XM_LAUNCH((k_scatter<T, false, HAS_P, 4, VIEW>), dim3(grid_for(ev.n, BLOCK * 4)), dim3(BLOCK), 0, stream, ev.x, ev.y,
+          XM_LAUNCH((k_scatter<T, false, HAS_P, 4, VIEW>), dim3(k1_direct_blocks(ev.n, true)), dim3(BLOCK), 0, stream, ev.x, ev.y,
                     (const T*)ev.t, ev.p, (const uint4*)nullptr, ev.n, fr.idx_offset, h->tb, fr.st, fr.tag_override, fr.mm_lo,
                     fr.mm_hi, fr.mm_ext, (u64*)fr.frame, fr.dirty, sorted ? 1 : 0);
         else
-          XM_LAUNCH((k_scatter<T, false, HAS_P, 1, VIEW>), dim3(grid_for(ev.n, BLOCK)), dim3(BLOCK), 0, stream, ev.x, ev.y,
+          XM_LAUNCH((k_scatter<T, false, HAS_P, 1, VIEW>), dim3(k1_direct_blocks(ev.n, false)), dim3(BLOCK), 0, stream, ev.x, ev.y,
                     (const T*)ev.t, ev.p, (const uint4*)nullptr, ev.n, fr.idx_offset, h->tb, fr.st, fr.tag_override, fr.mm_lo,
                     fr.mm_hi, fr.mm_ext, (u64*)fr.frame, fr.dirty, sorted ? 1 : 0);
       } else {  // grid = (blocks of the largest frame, frames)
-        XM_LAUNCH((k_scatter_direct_batch<T, AOS, HAS_P, VIEW>), dim3(grid_for(fr.n_max(), BLOCK), fr.n), dim3(BLOCK), 0, stream,
+        XM_LAUNCH((k_scatter_direct_batch<T, AOS, HAS_P, VIEW>), dim3(k1_direct_blocks(fr.n_max(), false), fr.n), dim3(BLOCK), 0, stream,
                   fr.descs, h->tb, sorted ? 1 : 0);
       }
       return XM_OK;
@@ -178,23 +152,20 @@ int launch_k1(xm_handle* h, const F& fr, bool tiled, bool key32, bool sorted, hi
       }
     }
     // raise the kernel's dynamic-LDS cap once per (handle = device, kernel instantiation); gfx950: 160 KB / CU
-    int rc = h->ensure_lds(reinterpret_cast<const void*>(kern), h->k1_lds);
+    const K1TiledShape sh = k1_tiled_shape(pl, fr.n_max(), fr.n_mean(), COND == 1);
+    int rc = h->ensure_lds(reinterpret_cast<const void*>(kern), sh.lds);
     if (rc) return rc;
-    // block size from the mean frame: a sparser frame of a group only sends more of its events down the direct path in the kernel
-    const unsigned threads = k1_threads(h, fr.n_mean());
-    unsigned gx = grid_for(fr.n_max(), threads * TILE_EPT);
-    if (COND == 1) gx = std::min(gx, 32u);
     if constexpr (is_lone<F>) {
       const EventsView& ev = fr.ev;
-      XM_LAUNCH(kern, dim3(gx), dim3(threads), h->k1_lds, stream, ev.x, ev.y, (const T*)ev.t, ev.p, (const uint4*)ev.aos, ev.n,
-                fr.idx_offset, h->tb, fr.st, fr.tag_override, fr.mm_lo, fr.mm_hi, fr.mm_ext, (u64*)fr.frame, fr.dirty, h->w_ts,
-                h->w_x, sorted ? 1 : 0);
+      XM_LAUNCH(kern, dim3(sh.gx), dim3(sh.threads), sh.lds, stream, ev.x, ev.y, (const T*)ev.t, ev.p, (const uint4*)ev.aos, ev.n,
+                fr.idx_offset, h->tb, fr.st, fr.tag_override, fr.mm_lo, fr.mm_hi, fr.mm_ext, (u64*)fr.frame, fr.dirty, pl.k1.w_ts,
+                pl.k1.w_x, sorted ? 1 : 0);
     } else {
-      XM_LAUNCH(kern, dim3(gx, fr.n), dim3(threads), h->k1_lds, stream, fr.descs, h->tb, h->w_ts, h->w_x, sorted ? 1 : 0);
+      XM_LAUNCH(kern, dim3(sh.gx, fr.n), dim3(sh.threads), sh.lds, stream, fr.descs, h->tb, pl.k1.w_ts, pl.k1.w_x, sorted ? 1 : 0);
     }
     return XM_OK;
   };
-  if (COND == 1 || h->cfg.view == XM_VIEW_PROJECTOR) return go(std::integral_constant<int, 0>{});
+  if (COND == 1 || pl.dims.projector) return go(std::integral_constant<int, 0>{});
   if constexpr (COND == 0) return go(std::integral_constant<int, 1>{});
   return XM_OK;
 }
@@ -205,79 +176,48 @@ int launch_scatter(xm_handle* h, const EventsView& ev, SlotState* st, u32 tag_ov
   const LoneFrame fr{ev, st, tag_override, frame, dirty, nullptr, nullptr, idx_offset, mm_lo, mm_hi, mm_ext};
   return with_event_types(ev, [&](auto ty) -> int {
     using E = decltype(ty);
-    return launch_k1<typename E::T, E::AOS, E::HAS_P>(h, fr, tiled_path(h, ev.n), key32, sorted, stream);
+    return launch_k1<typename E::T, E::AOS, E::HAS_P>(h, fr, tiled_path(h->plan(), ev.n), key32, sorted, stream);
   });
 }
 
-// kmode of a frame: 0 = 64-bit key frame (general), 1 = compact 32-bit key frame, 2 = column tiles + plain u16 frame
-enum { KM_KEY64 = 0, KM_KEY32 = 1, KM_COLS = 2 };
-
 // ---- K2 launches (tiled frame kernel, projector view) -----------------------------------------------------------------------
-// Pixels per thread of a launch over n_frames frames: two (32 x 16-pixel tiles) when the launch fills the chip several times
-// over -- a K2 wave is a chain of dependent round trips, what it costs there is resident waves x lifetime, so each wave carries
-// two pixels through the chain --, one (16 x 16) for a lone small frame, where the chain's length IS the kernel's duration and
-// twice the blocks start at once (C-1M, one frame: 7.3 us with one pixel per thread, 12.3 with two).
-int k2_ppt(const xm_handle* h, int n_frames) {
-  if (h->k2_force_ppt == 1 || h->k2_force_ppt == 2) return h->k2_force_ppt;
-  const u64 blocks2 = (u64)grid_for(h->tb.proj_w, 2 * K2_TX) * grid_for(h->tb.proj_h, K2_TY) * (u64)std::max(n_frames, 1);
-  // measured at C-1M (600 blocks of 32 x 16 pixels per frame, tools/ppt_threshold.sh), K2 us per launch with one / two pixels per
-  // thread: 1 frame 5.3 / 7.2, 2 frames 8.7 / 8.6, 3: 11.1 / 10.6, 8: 23.4 / 21.3, 16: 47.5 / 41.1 -- the crossover is at about
-  // four blocks per CU
-  return blocks2 >= 1024 ? 2 : 1;
-}
-
-// K2's dynamic LDS: the tile's patch of u16 disparities (the row maxima replace it in place) + the overrun of its last read
-size_t k2_lds_bytes(const xm_handle* h, int ppt) {
-  return (size_t)(h->k2_tile_cap[ppt - 1] + 32) * sizeof(uint16_t);
-}
-
+// (pixels per thread, grid and LDS of a launch: k2_tiled_shape, xm_plan.hpp)
 template <int FMT>
 void launch_k2(xm_handle* h, hipStream_t stream, const u64* key_frame, SlotState* st, u32 tag_override, const unsigned char* dirty,
                float* depth, uint8_t* bgr, bool unsheared = false, int col_lo = 0, int col_hi = 0) {
-  const int ppt = k2_ppt(h, 1);
-  const dim3 grid(grid_for(h->tb.proj_w, K2_TX * ppt), grid_for(h->tb.proj_h, K2_TY));
+  const K2TiledShape sh = k2_tiled_shape(h->plan(), 1);
+  const dim3 grid(sh.gx, sh.gy);
   DevTables tb = h->tb;
   if (unsheared) tb.shear_m = tb.shear_bias = tb.shear_extra = 0;  // a plain [rect_w][rect_h] u16 frame (shards), not a slot's frame16
-  if (ppt == 1)
-    XM_LAUNCH((k_frame_proj_tiled<FMT, 1>), grid, dim3(K2_TX * K2_TY), k2_lds_bytes(h, 1), stream, key_frame, tb, st, tag_override,
-              dirty, (const ulonglong2*)h->d_zero16, depth, bgr, h->k2_tile_cap[0], col_lo, col_hi);
+  if (sh.ppt == 1)
+    XM_LAUNCH((k_frame_proj_tiled<FMT, 1>), grid, dim3(sh.threads), sh.lds, stream, key_frame, tb, st, tag_override,
+              dirty, (const ulonglong2*)h->d_zero16, depth, bgr, sh.tile_cap, col_lo, col_hi);
   else
-    XM_LAUNCH((k_frame_proj_tiled<FMT, 2>), grid, dim3(K2_TX * K2_TY), k2_lds_bytes(h, 2), stream, key_frame, tb, st, tag_override,
-              dirty, (const ulonglong2*)h->d_zero16, depth, bgr, h->k2_tile_cap[1], col_lo, col_hi);
+    XM_LAUNCH((k_frame_proj_tiled<FMT, 2>), grid, dim3(sh.threads), sh.lds, stream, key_frame, tb, st, tag_override,
+              dirty, (const ulonglong2*)h->d_zero16, depth, bgr, sh.tile_cap, col_lo, col_hi);
 }
 
-// the software-pipelined K2 (persistent blocks walking (frame, tile) items): groups on the plain u16 frame, two pixels per thread
-size_t k2_pipe_lds_bytes(const xm_handle* h, int g) {
-  return (size_t)((h->k2_tile_cap[g] + 32 + 7) & ~7) * sizeof(uint16_t) + (size_t)h->k2_pipe_nlds * sizeof(uint2);
-}
-
+// the software-pipelined K2 (persistent blocks walking (frame, tile) items): whether a group takes it, and its shape, is
+// k2_pipe_shape's (xm_plan.hpp); false = the group goes to the tiled K2
 template <int COND = 0>
 bool launch_k2_pipe(xm_handle* h, hipStream_t stream, const FrameDesc* d_descs, int n_frames) {
-  if (!h->k2_pipe || !h->k2_pipe_rig_ok || h->k2_pipe_nlds < 1 || (k2_ppt(h, n_frames) != 2 && !h->k2_pipe_force)) return false;
-  const int g = h->k2_pipe_g, ppt = 1 << g;
-  const u32 gx = grid_for(h->tb.proj_w, K2_TX * ppt), gy = grid_for(h->tb.proj_h, K2_TY);
-  const u64 total = (u64)gx * gy * (u64)n_frames;
-  const size_t lds = k2_pipe_lds_bytes(h, g);
-  const unsigned per_cu = (unsigned)std::max<size_t>(1, std::min<size_t>((size_t)h->k2_per_cu_max, (160 * 1024) / (lds + 2048)));
-  unsigned blocks = (unsigned)h->n_cus * per_cu / 8 * 8;
-  if (total < 3ull * blocks && !h->k2_pipe_force) return false;  // too few items per block for the pipeline to matter: one block per tile
-  blocks = (unsigned)std::min<u64>(blocks, std::max<u64>(total, 1));
-  if (h->k2_pipe_blocks > 0) blocks = std::min(blocks, (unsigned)h->k2_pipe_blocks);  // (tests: any grid is legal -- items are (f, b) with stride gridDim.x)
-  // divmod(tile, gx) by a multiply in the kernel: exact while tile * gx < 2^32
-  const u32 gx_magic = gx > 1 && (u64)gx * gy * gx < (1ull << 32) ? (u32)(((1ull << 32) + gx - 1) / gx) : 0u;
-  const bool cs = (h->k2_consec < 0 ? g >= 2 : h->k2_consec != 0) && h->d_k2_pix16[g];  // default: consecutive pixels on the 64 x 16 tiles
+  const RigPlan& pl = h->plan();
+  const K2PipeShape sh = k2_pipe_shape(pl, n_frames);
+  if (!sh.use) return false;
+  const int g = sh.g;
+  const bool cs = sh.consecutive;
   const void* fn = g == 2 ? (cs ? reinterpret_cast<const void*>(k_frame_proj_pipe<4, true, COND>) : reinterpret_cast<const void*>(k_frame_proj_pipe<4, false, COND>))
                           : (cs ? reinterpret_cast<const void*>(k_frame_proj_pipe<2, true, COND>) : reinterpret_cast<const void*>(k_frame_proj_pipe<2, false, COND>));
-  if (h->ensure_lds(fn, lds) != XM_OK) return false;
+  if (h->ensure_lds(fn, sh.lds) != XM_OK) return false;
   K2PipeArgs pa;
   pa.proj_w = h->tb.proj_w; pa.proj_h = h->tb.proj_h; pa.rect_w = h->tb.rect_w; pa.rect_h = h->tb.rect_h;
   pa.shear_m = h->tb.shear_m; pa.shear_bias = h->tb.shear_bias;
 #define XM_K2P_LAUNCH(P, C)                                                                                                          \
-  XM_LAUNCH((k_frame_proj_pipe<P, C, COND>), dim3(blocks), dim3(K2_TX * K2_TY), lds, stream, d_descs, (const int4*)h->d_k2_tiles[g],      \
-            (const u32*)h->d_k2_pix[g], (const uint16_t*)h->d_k2_pix16[g], h->k2_pix_stride, h->tb.dlut, pa, h->k2_tile_cap[g],      \
-            (u32)n_frames, gx, gy, h->k2_pipe_nlds, gx_magic, (const uint4*)h->d_k2_live[g])
+  XM_LAUNCH((k_frame_proj_pipe<P, C, COND>), dim3(sh.blocks), dim3(K2_TX * K2_TY), sh.lds, stream, d_descs, (const int4*)h->d_k2_tiles[g], \
+            (const u32*)h->d_k2_pix[g], (const uint16_t*)h->d_k2_pix16[g], pl.k2pipe.pix_stride, h->tb.dlut, pa, pl.k2.tile_cap[g],  \
+            (u32)n_frames, sh.gx, sh.gy, pl.k2pipe.nlds, sh.gx_magic, (const uint4*)h->d_k2_live[g])
   std::unique_lock<std::mutex> chain_lock(h->k2_chain_mu, std::defer_lock);
-  if (h->k2_chain && COND == 0) {  // one K2 at a time: wait for the one launched last (whatever its stream)
+  if (pl.k2pipe.chain && COND == 0) {  // one K2 at a time: wait for the one launched last (whatever its stream)
     chain_lock.lock();
     if (h->k2_chain_n) (void)hipStreamWaitEvent(stream, h->k2_chain_ev[(h->k2_chain_n - 1) % 16], 0);
   }
@@ -303,46 +243,46 @@ void launch_k2_batch(xm_handle* h, hipStream_t stream, const FrameDesc* d_descs,
   if constexpr (FMT == 2 && (COND == 0 || COND == 2)) {  // (COND = 2: the attempt's K2 node of a captured batch)
     if (launch_k2_pipe<COND>(h, stream, d_descs, n_frames)) return;
   }
-  const int ppt = k2_ppt(h, n_frames);
-  dim3 grid(grid_for(h->tb.proj_w, K2_TX * ppt), grid_for(h->tb.proj_h, K2_TY), n_frames);
-  if (COND == 1) grid = dim3(std::min(grid.x * grid.y, 32u), 1, n_frames);  // redo node: a few blocks per frame walk its tiles
-  if (ppt == 1)
-    XM_LAUNCH((k_frame_proj_tiled_batch<FMT, COND, 1>), grid, dim3(K2_TX * K2_TY), k2_lds_bytes(h, 1), stream, d_descs, h->tb,
-              (const ulonglong2*)h->d_zero16, h->k2_tile_cap[0]);
+  const K2TiledShape sh = k2_tiled_shape(h->plan(), n_frames, COND == 1);  // (redo node: a few blocks per frame walk its tiles)
+  const dim3 grid(sh.gx, sh.gy, sh.gz);
+  if (sh.ppt == 1)
+    XM_LAUNCH((k_frame_proj_tiled_batch<FMT, COND, 1>), grid, dim3(sh.threads), sh.lds, stream, d_descs, h->tb,
+              (const ulonglong2*)h->d_zero16, sh.tile_cap);
   else
-    XM_LAUNCH((k_frame_proj_tiled_batch<FMT, COND, 2>), grid, dim3(K2_TX * K2_TY), k2_lds_bytes(h, 2), stream, d_descs, h->tb,
-              (const ulonglong2*)h->d_zero16, h->k2_tile_cap[1]);
+    XM_LAUNCH((k_frame_proj_tiled_batch<FMT, COND, 2>), grid, dim3(sh.threads), sh.lds, stream, d_descs, h->tb,
+              (const ulonglong2*)h->d_zero16, sh.tile_cap);
 }
 
-// K2 of a frame or a group by view and key format (kmode).  Projector view: the tiled frame kernel (a lone frame: k2_ppt(h, 1);
+// K2 of a frame or a group by view and key format (kmode).  Projector view: the tiled frame kernel (a lone frame: k2_ppt(plan, 1);
 // under XM_K2_DIRECT the per-pixel kernel, under XM_K2_FLAGS with the dirty map); camera view: k_frame_cam32 on the compact key
 // frame, k_frame_direct otherwise
 template <typename F>
 void launch_frame_kernel(xm_handle* h, const F& fr, int kmode, hipStream_t stream) {
-  const bool proj = h->cfg.view == XM_VIEW_PROJECTOR, key32 = kmode == KM_KEY32;
-  const u64 px = (u64)h->tb.cam_w * h->tb.cam_h;
-  const dim3 g32(grid_for(h->tb.cam_w, CAM32_T), grid_for(h->tb.cam_h, CAM32_T), frames(fr));
+  const RigPlan& pl = h->plan();
+  const bool proj = pl.dims.projector, key32 = kmode == KM_KEY32;
+  const u64 px = cam_pixels(pl);
+  const dim3 g32(cam32_gx(pl), cam32_gy(pl), frames(fr));
   if constexpr (is_lone<F>) {
     const u64* keys = static_cast<const u64*>(fr.frame);
     const KeyCells cells{keys, 0};
-    if (proj && h->k2_direct)
-      XM_LAUNCH((k_frame_proj<KeyCells, 0>), dim3(grid_for((u64)h->tb.proj_w * h->tb.proj_h, BLOCK)), dim3(BLOCK), 0, stream, cells,
+    if (proj && pl.modes.k2_direct)
+      XM_LAUNCH((k_frame_proj<KeyCells, 0>), dim3(pixel_blocks((u64)pl.dims.proj_w * pl.dims.proj_h)), dim3(BLOCK), 0, stream, cells,
                 h->tb, fr.st, fr.tag_override, fr.depth, fr.bgr);
     else if (proj && kmode == KM_COLS) launch_k2<2>(h, stream, keys, fr.st, fr.tag_override, nullptr, fr.depth, fr.bgr);
     else if (proj && key32) launch_k2<1>(h, stream, keys, fr.st, fr.tag_override, nullptr, fr.depth, fr.bgr);
-    else if (proj) launch_k2<0>(h, stream, keys, fr.st, fr.tag_override, h->k2_flags ? fr.dirty : nullptr, fr.depth, fr.bgr);
+    else if (proj) launch_k2<0>(h, stream, keys, fr.st, fr.tag_override, pl.modes.k2_flags ? fr.dirty : nullptr, fr.depth, fr.bgr);
     else if (key32)  // camera view, compact frame: (event index + 1) << 12 | disparity, zeroed as it is read
       XM_LAUNCH(k_frame_cam32, g32, dim3(BLOCK), 0, stream, static_cast<u32*>(fr.frame), h->tb.cam_w, h->tb.cam_h, fr.st, h->tb.dlut,
                 fr.depth, fr.bgr);
     else
-      XM_LAUNCH((k_frame_direct<KeyCells>), dim3(grid_for(px, BLOCK)), dim3(BLOCK), 0, stream, cells, px, h->tb.p03, h->tb.z_near,
+      XM_LAUNCH((k_frame_direct<KeyCells>), dim3(pixel_blocks(px)), dim3(BLOCK), 0, stream, cells, px, h->tb.p03, h->tb.z_near,
                 h->tb.z_far, fr.st, fr.tag_override, 1, h->tb.dlut, fr.depth, fr.bgr);
   } else {
     if (proj && kmode == KM_COLS) launch_k2_batch<2>(h, stream, fr.descs, fr.n);
     else if (proj && key32) launch_k2_batch<1>(h, stream, fr.descs, fr.n);
     else if (proj) launch_k2_batch<0>(h, stream, fr.descs, fr.n);
     else if (key32) XM_LAUNCH(k_frame_cam32_batch, g32, dim3(BLOCK), 0, stream, fr.descs, h->tb.cam_w, h->tb.cam_h, h->tb.dlut);
-    else XM_LAUNCH(k_frame_direct_batch, dim3(grid_for(px, BLOCK), fr.n), dim3(BLOCK), 0, stream, fr.descs, px, h->tb.dlut);
+    else XM_LAUNCH(k_frame_direct_batch, dim3(pixel_blocks(px), fr.n), dim3(BLOCK), 0, stream, fr.descs, px, h->tb.dlut);
   }
 }
 
@@ -357,19 +297,6 @@ void launch_frame_filter(const FrameFilterDev& f, u64 n_bound, hipStream_t strea
   XM_LAUNCH(k_ff_scatter, dim3(ge), dim3(FF_THREADS), 0, stream, f);
   XM_LAUNCH(k_ff_count, dim3(gc), dim3(FF_BLOCK), 0, stream, f);
   XM_LAUNCH(k_ff_emit, dim3(gc), dim3(FF_BLOCK), 0, stream, f, (u32)gc);
-}
-
-size_t cols_lds_bytes(const xm_handle* h, int W) {  // mirrors the carve-up at the top of scatter_cols_body
-  const size_t lut_q = ((size_t)h->w_x * h->tb.cam_h + 3) / 4 + 1 + 64, xm_q = ((size_t)W * h->tb.xmap_h + 7) / 8 + 1 + 64,
-               slot_q = ((size_t)W * h->tb.xmap_h + 3) / 4;
-  return 16 * (lut_q + xm_q + slot_q);
-}
-
-size_t own_plan_lds_bytes(int nxs_max, int rp, int hrp, int extra_max, bool grouped) {  // mirrors the carve-up at the top of scatter_own_body
-  return (size_t)4 * nxs_max * rp + (size_t)4 * extra_max + (size_t)4 * own_tab_words(hrp, grouped);
-}
-size_t own_lds_bytes(const xm_handle::OwnSet& os) {
-  return own_plan_lds_bytes(os.nxs_max, os.rp, os.hrp, os.extra_max, os.grouped != 0);
 }
 
 

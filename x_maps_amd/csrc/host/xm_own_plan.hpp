@@ -241,7 +241,6 @@ void own_plan_as(const xm_config* cfg, int xmap_h, int xr_min, bool grouped, int
 // !ok entries behind the last one.  Default: ownership per 8-row group at 20 and at 16 columns (the halo of 4-7 columns costs
 // 1.35 x / 1.44 x event reads, against 1.9 x at 8) where the rig allows it, then ownership per row at 8 columns.  "XM_OWN_W" /
 // "XM_OWN_GROUPED=0" (experiments / tests): one plan, that width / per row only.
-constexpr int OWN_PLANS = xm_handle::OWN_PLANS;
 void own_plans(const xm_config* cfg, int xmap_h, int xr_min, OwnPlan (&out)[OWN_PLANS]) {
   for (OwnPlan& p : out) p = OwnPlan{};
   const char* eg = dbg_opt("XM_OWN_GROUPED");
@@ -265,23 +264,24 @@ void own_plans(const xm_config* cfg, int xmap_h, int xr_min, OwnPlan (&out)[OWN_
 }
 
 // a plan's device tables and geometry into the kernel argument
-void own_apply(const xm_handle::OwnSet& os, DevTables& tb) {
+void own_apply(const RigPlan::Own& op, const xm_handle::OwnSet& os, DevTables& tb) {
   tb.xmap_own = os.d_xmap_own;
   tb.xmap_extra = os.d_xmap_extra;
   tb.own_tiles = os.d_tiles;
   tb.own_bm = os.d_bm;
   tb.own_extra_cells = os.d_extra_cells;
-  tb.own_r_lo = os.r_lo;
-  tb.own_hr = os.hr;
-  tb.own_hrp = os.hrp;
-  tb.own_rp = os.rp;
-  tb.own_grouped = os.grouped;
-  tb.own_nxs_max = os.nxs_max;
-  tb.own_extra_max = os.extra_max;
+  tb.own_r_lo = op.r_lo;
+  tb.own_hr = op.hr;
+  tb.own_hrp = op.hrp;
+  tb.own_rp = op.rp;
+  tb.own_grouped = op.grouped;
+  tb.own_nxs_max = op.nxs_max;
+  tb.own_extra_max = op.extra_max;
 }
 
-// Returns XM_OK whether or not the rig qualifies (h->own_mode says); an error only for HIP failures.
-int own_setup(xm_handle* h, const xm_config* cfg, int xr_min) {
+// Uploads the plans' tables and writes their scalars into the rig plan (one of xm_create's stages calls it: classify_rig).
+// Returns XM_OK whether or not the rig qualifies (plan.cols.own_mode says); an error only for HIP failures.
+int own_setup(xm_handle* h, RigPlan& plan, const xm_config* cfg, int xr_min) {
   OwnPlan pls[OWN_PLANS];
   own_plans(cfg, h->tb.xmap_h, xr_min, pls);
   if (!pls[0].ok) return XM_OK;
@@ -293,6 +293,9 @@ int own_setup(xm_handle* h, const xm_config* cfg, int xr_min) {
     const OwnPlan& pl = pls[i];
     if (!pl.ok) continue;
     xm_handle::OwnSet& os = h->own[i];
+    RigPlan::Own& op = plan.own[i];
+    if (own_tab_words(pl.hrp, pl.grouped) != pl_own_tab_words(pl.hrp, pl.grouped))
+      return fail(XM_ERR_INVALID, "xm_plan.hpp restates own_tab_words differently from the kernel's");
     HIP_TRY(up(os.d_xmap_own, pl.packed));
     HIP_TRY(up(os.d_xmap_extra, pl.xextra));
     HIP_TRY(up(os.d_tiles, pl.tiles));
@@ -316,20 +319,20 @@ int own_setup(xm_handle* h, const xm_config* cfg, int xr_min) {
       HIP_TRY(up(os.d_bm, tab));
     }
     HIP_TRY(up(os.d_extra_cells, pl.extra_flat));
-    os.extras = (int)pl.extra_flat.size() - 1;
-    os.w = pl.W; os.halo = pl.halo; os.all_in = pl.all_in;
-    os.r_lo = pl.r_lo; os.hr = pl.hr; os.hrp = pl.hrp; os.rp = pl.rp; os.grouped = pl.grouped ? 1 : 0;
-    os.nxs_max = pl.nxs_max; os.extra_max = pl.extra_max;
-    os.ok = true;
+    op.extras = (int)pl.extra_flat.size() - 1;
+    op.w = pl.W; op.halo = pl.halo; op.all_in = pl.all_in;
+    op.r_lo = pl.r_lo; op.hr = pl.hr; op.hrp = pl.hrp; op.rp = pl.rp; op.grouped = pl.grouped ? 1 : 0;
+    op.nxs_max = pl.nxs_max; op.extra_max = pl.extra_max;
+    op.ok = true;
   }
   // (the frame's shear is the rig's: the same in every plan)
   h->tb.shear_m = pls[0].m;
   h->tb.shear_bias = pls[0].bias;
   h->tb.shear_extra = pls[0].extra_cols;
-  own_apply(h->own[0], h->tb);  // (K2 and the other kernels read none of these fields; a launch of K0b / K1 applies its frame's plan)
-  h->own_mode = true;
-  if (const char* e = dbg_opt("XM_OWN_EPT")) h->own_ept_forced = atoi(e);
-  if (pls[0].all_in) h->cols_flags |= COLS_F_ALL_IN_FRAME;
+  own_apply(plan.own[0], h->own[0], h->tb);  // (K2 and the other kernels read none of these fields; a launch of K0b / K1 applies its frame's plan)
+  plan.cols.own_mode = true;
+  if (const char* e = dbg_opt("XM_OWN_EPT")) plan.cols.own_ept_forced = atoi(e);
+  if (pls[0].all_in) plan.cols.flags |= COLS_F_ALL_IN_FRAME;
   return XM_OK;
 }
 

@@ -227,7 +227,7 @@ int shard_exchange_keys(ShardPeers& P, xm_handle* h, const uint16_t* x, const ui
   if (!rc) rc = xm_shard_scatter_device(h, x, y, t, p, n_own, t_dtype, first_index, mm, tag, key);
   if (!rc) rc = P.mark(2, st);
   if ((rc = P.enter(2, rc))) return rc;
-  if ((rc = P.all_reduce(key, h->key_cells, RcclApi::Uint64, RcclApi::Max, st))) return rc;
+  if ((rc = P.all_reduce(key, h->plan().dims.key_cells, RcclApi::Uint64, RcclApi::Max, st))) return rc;
   if ((rc = P.mark(3, st))) return rc;
   return depth_out || bgr_out ? xm_shard_finish(h, key, tag, depth_out, bgr_out) : XM_OK;
 }

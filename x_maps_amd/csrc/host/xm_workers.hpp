@@ -54,7 +54,7 @@ int run_frame(xm_handle* h, Slot& s, const EventsView& ev, float* depth, uint8_t
               const Event* prof = nullptr, bool allow_sorted = true) {
   if (int rc = enqueue_frame(h, s, ev, depth, bgr, prof, allow_sorted)) return rc;
   s.last.api_tag = s.last.host_tag;
-  const size_t px = (size_t)h->out_w * h->out_h;
+  const size_t px = (size_t)h->plan().dims.out_w * h->plan().dims.out_h;
   if (host_depth) HIP_TRY(hipMemcpyAsync(host_depth, depth, px * 4, hipMemcpyDeviceToHost, s.stream));
   if (host_bgr) HIP_TRY(hipMemcpyAsync(host_bgr, bgr, px * 3, hipMemcpyDeviceToHost, s.stream));
   return XM_OK;
@@ -126,7 +126,7 @@ int process_common(xm_handle* h, EventsView ev, int mem, float* depth_out, uint8
   HIP_TRY(hipSetDevice(h->cfg.device));
   int rc = check_events(ev);
   if (rc) return rc;
-  const size_t px = (size_t)h->out_w * h->out_h;
+  const size_t px = (size_t)h->plan().dims.out_w * h->plan().dims.out_h;
   if (h->ab_max >= 2 && mem == XM_MEM_DEVICE && !profile && !h->capturing && !stats) {  // adaptive batching (see xm_handle::pending)
     // One group = one kernel template (AoS or SoA, the time stamps' type, polarity column or not), chosen from its first frame:
     // a frame of another layout closes the group that is pending and opens its own.
@@ -154,7 +154,7 @@ int process_common(xm_handle* h, EventsView ev, int mem, float* depth_out, uint8
   if (s.worker >= 0 && mem == XM_MEM_DEVICE && !profile && !h->capturing) {
     // asynchronous device-pointer frame: the launches are the worker's job
     post_frame(h, s, ev, depth_out, bgr_out, true);
-    if (s.h_flags) s.prev.set(ev, depth_out, bgr_out, nullptr, nullptr, s.last.api_tag, s.stream, h->try_sorted && sorted_path(h, ev));
+    if (s.h_flags) s.prev.set(ev, depth_out, bgr_out, nullptr, nullptr, s.last.api_tag, s.stream, h->plan().modes.try_sorted && sorted_path(h->plan(), path_now(h), ev));
     return XM_OK;
   }
   if (s.worker >= 0 && (rc = drain_workers(h, s.worker))) return rc;  // this call uses the slot's stream itself
@@ -196,7 +196,7 @@ int process_common(xm_handle* h, EventsView ev, int mem, float* depth_out, uint8
     // asynchronous call: the slot is not reused before this frame has reached K2 (keeps the host from running queues
     // deep ahead of the GPU, which made the frame rate uneven), and a try-sorted verdict is read then
     // (ev: device pointers -- the slot's staging buffers for pinned host input)
-    s.prev.set(ev, d_depth, d_bgr, host_depth, host_bgr, s.last.host_tag, s.stream, h->try_sorted && s.last.sorted);
+    s.prev.set(ev, d_depth, d_bgr, host_depth, host_bgr, s.last.host_tag, s.stream, h->plan().modes.try_sorted && s.last.sorted);
   }
   if (mem == XM_MEM_HOST || profile) {
     if ((rc = s.order.host_wait())) return rc;
