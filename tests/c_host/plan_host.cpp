@@ -585,7 +585,60 @@ static void create_arithmetic() {
   EQ("wrap past -32768", classify_tables(ext(0, 32767, -2, 10), 0, true, 1320, 2048).no_wrap, 0);
 }
 
+// The dynamic LDS of the five kernels whose layout the host sizes, at shapes where each rounding term of a layout bites.  The
+// literals are what the host formulas gave while they still restated the kernels' carve-ups (evaluated from that text).
+static void lds_layouts() {
+  // column tiles: w_x * cam_h = 1443 (not a multiple of 4); W * xmap_h = 3963 (odd), 1324 (a multiple of 4, not of 8), 2644 likewise
+  EQ("cols lds, odd bands", cols_lds_bytes_at(3, 481, 1321, 3), 31648);
+  EQ("cols lds, X-map band 4 mod 8", cols_lds_bytes_at(3, 481, 1324, 1), 15808);
+  EQ("cols lds, LUT band whole quads, X-map band 4 mod 8", cols_lds_bytes_at(2, 482, 1322, 2), 21808);
+  EQ("cols lds, one cell", cols_lds_bytes_at(1, 1, 1, 1), 2128);
+  EQ("cols lds, C-1M tile", cols_lds_bytes_at(16, 480, 1320, 2), 48640);
+  // owner tiles: the table's pad to 4 words -- grouped: 2 * hrp / 8 = 6 -> 8, 10 -> 12, 330 -> 332; per row: 13 -> 16, 1320 as it is
+  EQ("own lds, grouped 6 words", own_plan_lds_bytes(17, 24, 24, 5, true), 1684);
+  EQ("own lds, grouped 10 words", own_plan_lds_bytes(17, 24, 40, 5, true), 1700);
+  EQ("own lds, grouped 330 words", own_plan_lds_bytes(17, 24, 1320, 5, true), 2980);
+  EQ("own lds, per row 13 words", own_plan_lds_bytes(8, 16, 13, 7, false), 604);
+  EQ("own lds, per row 16 words", own_plan_lds_bytes(8, 16, 16, 7, false), 604);
+  EQ("own lds, per row 1320 words", own_plan_lds_bytes(8, 16, 1320, 7, false), 5820);
+  // K2 tiled and pipelined: tile_cap + 32 = 2836 (4 mod 8), 6113 (odd), 10224 (a multiple of 8)
+  RigPlan p;
+  p.k2.tile_cap[0] = 2804, p.k2.tile_cap[1] = 6081, p.k2.tile_cap[2] = 10192, p.k2pipe.nlds = 1585;
+  EQ("k2 lds, 4 mod 8", k2_lds_bytes(p, 1), 5672);
+  EQ("k2 lds, odd", k2_lds_bytes(p, 2), 12226);
+  EQ("k2 pipe lds, 4 mod 8", k2_pipe_lds_bytes(p, 0), 18360);
+  EQ("k2 pipe lds, odd", k2_pipe_lds_bytes(p, 1), 24920);
+  EQ("k2 pipe lds, a multiple of 8", k2_pipe_lds_bytes(p, 2), 33128);
+  p.k2.tile_cap[1] = 6084, p.k2pipe.nlds = 3;
+  EQ("k2 pipe lds, small table", k2_pipe_lds_bytes(p, 1), 12264);
+  // tiled K1: the region the slots and the LUT band share takes the larger of the two
+  struct Case {
+    const char* name;
+    bool projector;
+    int cam_h, xmap_h, k1_wx, w_ts, w_x;
+    size_t lds;
+    int cols_w_max;
+  };
+  const Case cases[] = {{"projector view, LUT band larger", true, 481, 1321, 16, 5, 16, 47120, 5},   // 1652 slots' quads < 1989
+                        {"projector view, slots larger", true, 101, 1321, 16, 5, 16, 41728, 8},      // 1652 > 469
+                        {"projector view, slots larger, narrow LUT", true, 99, 2001, 3, 5, 3, 62128, 6},
+                        {"camera view: always the LUT band", false, 481, 1321, 16, 5, 16, 47120, 5},
+                        {"camera view, short X-map", false, 483, 101, 16, 5, 16, 35056, 16}};
+  for (const Case& c : cases) {
+    RigPlan r;
+    r.dims.cam_w = 640, r.dims.cam_h = c.cam_h, r.dims.xmap_w = 640, r.dims.xmap_h = c.xmap_h, r.dims.projector = c.projector;
+    r.cols.ok = true;
+    const K1Windows w = size_k1_windows(r, c.k1_wx);
+    EQ(c.name, w.w_ts, c.w_ts);
+    EQ(c.name, w.w_x, c.w_x);
+    EQ(c.name, w.lds, c.lds);
+    EQ(c.name, w.k1_direct, 0);
+    EQ(c.name, w.cols_w_max, c.cols_w_max);
+  }
+}
+
 int main() {
+  lds_layouts();
   real_rig_c1m();
   real_rig_esl();
   k1_thresholds();

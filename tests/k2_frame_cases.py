@@ -97,7 +97,7 @@ def sparse_frame(rng, rect_w, rect_h, fill):
 
 
 # ---- which loader of the tiled K2 a tile takes ----------------------------------------------------------------------------------
-K2_TX, K2_TY, K2_TILE_MAX = 16, 16, 10240  # xmaps_k2.hpp: a block is 16 x 16 threads, a patch at most 10240 cells of LDS
+K2_TX, K2_TY, K2_TILE_MAX = 16, 16, 10240  # xmaps_geometry.hpp: a block is 16 x 16 threads, a patch at most 10240 cells of LDS
 
 
 def classify_tiles(tb, ppt):

@@ -240,7 +240,7 @@ def test_shapes_sit_astride_the_kernels_tiles():
     import re
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     src = open(os.path.join(root, "x_maps_amd", "csrc", "xmaps_eslinit.hpp")).read()
-    common = open(os.path.join(root, "x_maps_amd", "csrc", "xmaps_common.hpp")).read()
+    common = open(os.path.join(root, "x_maps_amd", "csrc", "xmaps_geometry.hpp")).read()  # (BLOCK: shared with the host's plan)
     assert re.search(r"constexpr int BLOCK = 256;", common)
     assert re.search(r"constexpr int ESL_TX = BLOCK;", src) and re.search(r"constexpr int ESL_CHUNK = 1024;", src)
     assert re.search(r"constexpr int ESL_FW = 64, ESL_FR = BLOCK / 64;", src)

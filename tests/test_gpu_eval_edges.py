@@ -194,7 +194,7 @@ def test_no_positive_ground_truth_and_a_perfect_estimate(filt):
 def test_shapes_cross_the_loop_bounds():
     """CPU: the constants of k_eval_stats' launch, read from the sources, and what each shape is for"""
     host = open(os.path.join(ROOT, "x_maps_amd", "csrc", "host", "xm_api_misc.hpp")).read()
-    common = open(os.path.join(ROOT, "x_maps_amd", "csrc", "xmaps_common.hpp")).read()
+    common = open(os.path.join(ROOT, "x_maps_amd", "csrc", "xmaps_geometry.hpp")).read()  # (BLOCK: shared with the host's plan)
     block = int(re.search(r"constexpr\s+int\s+(?:\w+\s*=\s*\d+\s*,\s*)*BLOCK\s*=\s*(\d+)", common).group(1))
     body = host[host.index("int xm_eval_stats("):]
     per_block = re.search(r"grid\s*=\s*grid_for\(n,\s*BLOCK\s*\*\s*(\d+)\)", body)

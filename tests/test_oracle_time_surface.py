@@ -128,7 +128,7 @@ def test_negative_zero_is_no_event():
 def test_differential_cameras_cross_the_loop_bounds():
     """the constants time_surface_cases.geometry() restates, and what each camera of the GPU tests is for"""
     src = open(os.path.join(ROOT, "x_maps_amd", "csrc", "xmaps_surface.hpp")).read()
-    kern = open(os.path.join(ROOT, "x_maps_amd", "csrc", "xmaps_common.hpp")).read()
+    kern = open(os.path.join(ROOT, "x_maps_amd", "csrc", "xmaps_geometry.hpp")).read()  # (BLOCK: shared with the host's plan)
 
     def const(name, text=src):
         return int(re.search(r"constexpr\s+int\s+(?:\w+\s*=\s*\d+\s*,\s*)*" + name + r"\s*=\s*(\d+)", text).group(1))

@@ -281,7 +281,7 @@ int build_k2_live(xm_handle* h, const RigPlan& p, const CreateOpts& o) {
     }
     std::vector<uint32_t> mask(tiles.size() * (size_t)K2L_WORDS, ~0u);
     if (derive) {
-      static_assert(K2L_THREADS == K2_TX * K2_TY && K2L_UN == K2P_UN && sizeof(K2LiveTile) == sizeof(int4), "xm_k2_live.hpp restates the loader's geometry");
+      static_assert(sizeof(K2LiveTile) == sizeof(int4), "xm_k2_live.hpp restates a record of k2_tiles");
       K2LiveRig rig;
       rig.xmap = cfg->proj_x_map; rig.xmap_w = cfg->xmap_width; rig.xmap_h = cfg->xmap_height;
       rig.x_offset = cfg->x_offset; rig.xr_min = p.cols.xr_min; rig.rect_w = cfg->rect_width; rig.rect_h = cfg->rect_height;

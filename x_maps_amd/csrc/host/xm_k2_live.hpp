@@ -13,10 +13,12 @@
 #include <cstdint>
 #include <vector>
 
+#include "../xmaps_geometry.hpp"  // K2_TX, K2_TY, K2P_UN
+
 namespace xm {
 
-constexpr int K2L_THREADS = 256;  // K2_TX * K2_TY: threads of a K2 block
-constexpr int K2L_UN = 4;         // K2P_UN: loader slots per thread, slot s = tid + j * K2L_THREADS
+constexpr int K2L_THREADS = K2_TX * K2_TY;  // threads of a K2 block
+constexpr int K2L_UN = K2P_UN;              // loader slots per thread, slot s = tid + j * K2L_THREADS
 constexpr int K2L_WAVE = 64;
 constexpr int K2L_WORDS = K2L_THREADS / K2L_WAVE * K2L_UN * 2;  // dwords per tile: [wave][j] a 64-bit lane mask {lo, hi}
 

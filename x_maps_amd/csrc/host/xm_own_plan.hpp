@@ -1,6 +1,7 @@
 // xm_own_plan.hpp -- owner tiles: the rig's ownership tables, worked out once on the host (own_plan, pure host code) and uploaded (own_setup)
 // (part of libxmaps_hip.so's host side: included by ../xmaps_hip.hip, one translation unit; see that file for the order)
 #pragma once
+#include "../xmaps_geometry.hpp"  // own_tab_words, OWN_BW
 
 namespace {
 
@@ -294,8 +295,6 @@ int own_setup(xm_handle* h, RigPlan& plan, const xm_config* cfg, int xr_min) {
     if (!pl.ok) continue;
     xm_handle::OwnSet& os = h->own[i];
     RigPlan::Own& op = plan.own[i];
-    if (own_tab_words(pl.hrp, pl.grouped) != pl_own_tab_words(pl.hrp, pl.grouped))
-      return fail(XM_ERR_INVALID, "xm_plan.hpp restates own_tab_words differently from the kernel's");
     HIP_TRY(up(os.d_xmap_own, pl.packed));
     HIP_TRY(up(os.d_xmap_extra, pl.xextra));
     HIP_TRY(up(os.d_tiles, pl.tiles));

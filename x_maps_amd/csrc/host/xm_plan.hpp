@@ -5,57 +5,16 @@
 // they return values and touch nothing.  The launchers (xm_launch.hpp, xm_enqueue.hpp) choose the template instance and pass
 // the arguments; every number of a launch comes from here.
 //
-// The kernels' constants the rules need are restated below (PL_*); xmaps_hip.hip includes this file in front of the device
-// headers and asserts each against the kernel's own, so a build that overrides one (-DXM_TILE_THREADS=1024 ...) reads the
-// same macro in both places, and one that changes a kernel's constant alone does not compile.
+// The kernels' constants and LDS layouts the rules need are the kernels' own: ../xmaps_geometry.hpp defines each once, for both.
 #pragma once
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
 
 #include "../../../include/xmaps.h"
+#include "../xmaps_geometry.hpp"
 
 namespace xm {
-
-// ---- the kernels' constants (asserted in xmaps_hip.hip) ---------------------------------------------------------------------
-constexpr int PL_BLOCK = 256;  // BLOCK
-#ifdef XM_K0_UN
-constexpr int PL_K0_UN = XM_K0_UN;
-#else
-constexpr int PL_K0_UN = 8;
-#endif
-#ifdef XM_TILE_THREADS
-constexpr int PL_TILE_THREADS = XM_TILE_THREADS;
-#else
-constexpr int PL_TILE_THREADS = 512;
-#endif
-#ifdef XM_TILE_EPT
-constexpr int PL_TILE_EPT = XM_TILE_EPT;
-#else
-constexpr int PL_TILE_EPT = 4096 / PL_TILE_THREADS;
-#endif
-constexpr int PL_COLS_EPT = 8;
-#ifdef XM_COLS_MAX_THREADS
-constexpr int PL_COLS_MAX_THREADS = XM_COLS_MAX_THREADS;
-#else
-constexpr int PL_COLS_MAX_THREADS = 512;
-#endif
-#ifdef XM_K2_TX
-constexpr int PL_K2_TX = XM_K2_TX, PL_K2_TY = XM_K2_TY;
-#else
-constexpr int PL_K2_TX = 16, PL_K2_TY = 16;
-#endif
-#ifdef XM_K2_TILE_MAX
-constexpr int PL_K2_TILE_MAX = XM_K2_TILE_MAX;
-#else
-constexpr int PL_K2_TILE_MAX = 10240;
-#endif
-constexpr int PL_CAM32_T = 32;
-constexpr unsigned PL_KEY32_DISP_BITS = 12, PL_KEY32_TILE_BITS = 16, PL_CAM32_MAX_EVENTS = (1u << 20) - 1u;
-constexpr int PL_OWN_BW = 4;
-constexpr int PL_COLS_F_ALL_IN_FRAME = 2;
-constexpr int pl_cols_bounds_per_block(int G) { return 256 / G; }  // cols_bounds_per_block
-constexpr int pl_own_tab_words(int hrp, bool grouped) { return ((grouped ? (hrp >> 3) * 2 : hrp) + 3) & ~3; }  // own_tab_words (own_setup compares)
 
 constexpr int OWN_PLANS = 3;  // owner tiles: up to three plans by falling tile width (xm_own_plan.hpp)
 
@@ -111,7 +70,7 @@ struct RigPlan {
   } own[OWN_PLANS];
   struct K2 {
     bool has_tables = false;  // the tiled frame kernel's per-tile / per-pixel tables exist (a projector map: d_k2_tiles)
-    int tile_cap[3] = {PL_K2_TILE_MAX, PL_K2_TILE_MAX, PL_K2_TILE_MAX};  // cells of the largest K2 patch (multiple of 8), per geometry
+    int tile_cap[3] = {K2_TILE_MAX, K2_TILE_MAX, K2_TILE_MAX};  // cells of the largest K2 patch (multiple of 8), per geometry
     int patch_cols_max = 0;  // widest patch of the 16 x 16 / 32 x 16 tiles (-1: some patch does not fit LDS)
     int force_ppt = 0;       // "XM_K2_PPT"=1/2: experiments
   } k2;
@@ -168,7 +127,7 @@ inline bool ev_vec16(const EventsView& ev) {
 // blocks per frame: ~2048 events per thread-block iteration keeps every CU busy without drowning the 32 atomic slots (VEC2: K0_UN
 // loads x 2 events per thread per sweep); a grid-stride kernel, so the grid is capped
 inline unsigned k0_blocks(uint64_t n, bool vec2, unsigned cap) {
-  const unsigned g = grid_for(n, PL_BLOCK * (vec2 ? 2 * PL_K0_UN : 4));
+  const unsigned g = grid_for(n, BLOCK * (vec2 ? 2 * K0_UN : 4));
   return g > cap ? cap : g;
 }
 // VEC2 (16-byte loads of int64 SoA time stamps): a lone frame needs its t (and p) aligned (a group: every column of every frame)
@@ -188,8 +147,8 @@ inline bool tiled_path(const RigPlan& p, uint64_t n) {  // dense enough for the 
 }
 inline unsigned k1_threads(const RigPlan& p, uint64_t n) {  // the tiled K1's block for frames of n events
   const double max_ev = k1_block_events(p, n);
-  unsigned threads = PL_TILE_THREADS;
-  while (threads > 1024 / PL_TILE_EPT && (double)(threads * PL_TILE_EPT) > max_ev) threads >>= 1;  // smallest block: 1024 events
+  unsigned threads = TILE_THREADS;
+  while (threads > 1024 / TILE_EPT && (double)(threads * TILE_EPT) > max_ev) threads >>= 1;  // smallest block: 1024 events
   return threads;
 }
 // the tiled K1's launch: block size from the mean frame (a sparser frame of a group only sends more of its events down the direct
@@ -201,13 +160,13 @@ struct K1TiledShape {
 inline K1TiledShape k1_tiled_shape(const RigPlan& p, uint64_t n_max, uint64_t n_mean, bool redo) {
   K1TiledShape s;
   s.threads = k1_threads(p, n_mean);
-  s.gx = grid_for(n_max, s.threads * PL_TILE_EPT);
+  s.gx = grid_for(n_max, s.threads * TILE_EPT);
   if (redo) s.gx = std::min(s.gx, 32u);
   s.lds = p.k1.lds;
   return s;
 }
 // the one-thread-per-event K1: blocks of a frame of n events (vec4: the lone frame's kernel that takes four events per thread)
-inline unsigned k1_direct_blocks(uint64_t n, bool vec4) { return grid_for(n, vec4 ? PL_BLOCK * 4 : PL_BLOCK); }
+inline unsigned k1_direct_blocks(uint64_t n, bool vec4) { return grid_for(n, vec4 ? BLOCK * 4 : BLOCK); }
 
 // ---- column / owner tiles ------------------------------------------------------------------------------------------------------------
 // owner tiles: the plan a frame of n events takes -- the default plan (wide tiles) while a tile's own + halo columns fit ONE event
@@ -217,7 +176,7 @@ inline int own_pick(const RigPlan& p, uint64_t n) {
   const double per_col = (double)n / (double)p.dims.xmap_w;
   int pick = 0;  // (the mean tile: measured on the ESL-like frames at 94 % of a block's events, the fuller tiles' second pass included)
   while (pick + 1 < OWN_PLANS && p.own[pick + 1].ok &&
-         per_col * (p.own[pick].w + p.own[pick].halo) > (double)(PL_COLS_EPT * PL_COLS_MAX_THREADS))
+         per_col * (p.own[pick].w + p.own[pick].halo) > (double)(COLS_EPT * COLS_MAX_THREADS))
     pick += 1;
   return pick;
 }
@@ -249,34 +208,33 @@ inline int own_index(const RigPlan& p, int W) {
 inline int own_ept(const RigPlan& p, uint64_t n, int W, bool vec16) {
   if (vec16 || p.cols.own_ept_forced != 4) return 8;
   const double per = (double)n / (double)p.dims.xmap_w * (W + p.own[own_index(p, W)].halo);
-  return per * 1.12 <= 4.0 * PL_COLS_MAX_THREADS ? 4 : 8;
+  return per * 1.12 <= 4.0 * COLS_MAX_THREADS ? 4 : 8;
 }
 
-inline unsigned cols_threads(const RigPlan& p, uint64_t n, int W, int ept = PL_COLS_EPT) {
+inline unsigned cols_threads(const RigPlan& p, uint64_t n, int W, int ept = COLS_EPT) {
   if (p.cols.own_mode) {  // own + halo columns in one pass where 512 threads hold them
     const double per = (double)n / (double)p.dims.xmap_w * (W + p.own[own_index(p, W)].halo);
     const unsigned t = ((unsigned)(per * 1.12 / ept) + 63u) / 64u * 64u;
-    return std::max(128u, std::min(t, (unsigned)PL_COLS_MAX_THREADS));
+    return std::max(128u, std::min(t, (unsigned)COLS_MAX_THREADS));
   }
   const double per_tile = (double)n / (double)p.dims.xmap_w * W;
   // one pass for a tile 12 % above the mean (Poisson spread of an evenly filled scan); fuller tiles take a second pass.
   // Tiles of more than 2048 events get the full 512 threads even when 448 would hold them: three blocks per CU are then
   // 24 waves = every wave slot the kernel's 80 VGPRs allow (measured at C-1M, 3125 events per tile: 4.35 instead of 4.63 us
   // per frame at full occupancy; 384 threads = two passes: 5.9 us)
-  unsigned t = ((unsigned)(per_tile * 1.12 / PL_COLS_EPT) + 63u) / 64u * 64u;
-  if (t > 256u) t = PL_COLS_MAX_THREADS;
-  return std::max(128u, std::min(t, (unsigned)PL_COLS_MAX_THREADS));
+  unsigned t = ((unsigned)(per_tile * 1.12 / COLS_EPT) + 63u) / 64u * 64u;
+  if (t > 256u) t = COLS_MAX_THREADS;
+  return std::max(128u, std::min(t, (unsigned)COLS_MAX_THREADS));
 }
 
-inline size_t cols_lds_bytes_at(int w_x, int cam_h, int xmap_h, int W) {  // mirrors the carve-up at the top of scatter_cols_body
-  const size_t lut_q = ((size_t)w_x * cam_h + 3) / 4 + 1 + 64, xm_q = ((size_t)W * xmap_h + 7) / 8 + 1 + 64,
-               slot_q = ((size_t)W * xmap_h + 3) / 4;
-  return 16 * (lut_q + xm_q + slot_q);
+// dynamic LDS of a column-tile block and of an owner-tile block: the pieces the kernels carve (xmaps_geometry.hpp), summed
+inline size_t cols_lds_bytes_at(int w_x, int cam_h, int xmap_h, int W) {
+  return 16 * ((size_t)band_lut_q(w_x, cam_h) + (size_t)band_xm_q(W, xmap_h) + (size_t)cols_slot_q(W, xmap_h));
 }
 inline size_t cols_lds_bytes(const RigPlan& p, int W) { return cols_lds_bytes_at(p.k1.w_x, p.dims.cam_h, p.dims.xmap_h, W); }
 
-inline size_t own_plan_lds_bytes(int nxs_max, int rp, int hrp, int extra_max, bool grouped) {  // mirrors the carve-up at the top of scatter_own_body
-  return (size_t)4 * nxs_max * rp + (size_t)4 * extra_max + (size_t)4 * pl_own_tab_words(hrp, grouped);
+inline size_t own_plan_lds_bytes(int nxs_max, int rp, int hrp, int extra_max, bool grouped) {
+  return 4 * ((size_t)own_band_words(nxs_max, rp) + (size_t)own_extra_words(extra_max) + (size_t)own_tab_words(hrp, grouped));
 }
 inline size_t own_lds_bytes(const RigPlan::Own& os) {
   return own_plan_lds_bytes(os.nxs_max, os.rp, os.hrp, os.extra_max, os.grouped != 0);
@@ -297,7 +255,7 @@ inline BoundsShape cols_bounds_shape(const RigPlan& p, int W) {
   s.split = s.own >= 0 ? p.own[s.own].halo : 0;
   s.nb = (s.split ? 2u : 1u) * grid_for(p.dims.xmap_w, W);
   s.lanes = !s.split && W <= 16 ? 16 : 32;
-  s.gx = grid_for(s.nb + 1, pl_cols_bounds_per_block(s.lanes));
+  s.gx = grid_for(s.nb + 1, cols_bounds_per_block(s.lanes));
   return s;
 }
 
@@ -323,7 +281,7 @@ inline TilesK1Shape tiles_k1_shape(const RigPlan& p, uint64_t n_mean, int W, boo
   } else {
     s.own = -1;
     s.halo = 0;
-    s.ept = PL_COLS_EPT;
+    s.ept = COLS_EPT;
     s.lds = cols_lds_bytes(p, W) + lds_pad;
     s.threads = cols_threads(p, n_mean, W);
   }
@@ -341,8 +299,8 @@ inline bool key32_path(const RigPlan& p, PathNow now, const EventsView& ev, bool
   if (!sorted || !p.compact.key32_ok || !p.modes.try_sorted || now.capturing || now.compact_paused || p.modes.k2_direct ||
       p.modes.k2_flags || !tiled_path(p, ev.n))
     return false;
-  if (!p.dims.projector) return ev.n <= (uint64_t)PL_CAM32_MAX_EVENTS;  // the key's order field is the event index
-  return ev.n / (uint64_t)(1024 / PL_TILE_EPT * PL_TILE_EPT) < (1ull << PL_KEY32_TILE_BITS);  // tiles of >= 1024 events
+  if (!p.dims.projector) return ev.n <= (uint64_t)CAM32_MAX_EVENTS;  // the key's order field is the event index
+  return ev.n / (uint64_t)(1024 / TILE_EPT * TILE_EPT) < (1ull << KEY32_TILE_BITS);  // tiles of >= 1024 events
 }
 
 // the column tiles' conditions on a frame: int64 time stamps, no polarity column, dense enough for a tile width of its own
@@ -424,7 +382,7 @@ inline FramePath frame_path(const RigPlan& rp, PathNow now, const EventsView* ev
 // twice the blocks start at once (C-1M, one frame: 7.3 us with one pixel per thread, 12.3 with two).
 inline int k2_ppt(const RigPlan& p, int n_frames) {
   if (p.k2.force_ppt == 1 || p.k2.force_ppt == 2) return p.k2.force_ppt;
-  const uint64_t blocks2 = (uint64_t)grid_for(p.dims.proj_w, 2 * PL_K2_TX) * grid_for(p.dims.proj_h, PL_K2_TY) * (uint64_t)std::max(n_frames, 1);
+  const uint64_t blocks2 = (uint64_t)grid_for(p.dims.proj_w, 2 * K2_TX) * grid_for(p.dims.proj_h, K2_TY) * (uint64_t)std::max(n_frames, 1);
   // measured at C-1M (600 blocks of 32 x 16 pixels per frame, tools/ppt_threshold.sh), K2 us per launch with one / two pixels per
   // thread: 1 frame 5.3 / 7.2, 2 frames 8.7 / 8.6, 3: 11.1 / 10.6, 8: 23.4 / 21.3, 16: 47.5 / 41.1 -- the crossover is at about
   // four blocks per CU
@@ -432,7 +390,7 @@ inline int k2_ppt(const RigPlan& p, int n_frames) {
 }
 
 // K2's dynamic LDS: the tile's patch of u16 disparities (the row maxima replace it in place) + the overrun of its last read
-inline size_t k2_lds_bytes(const RigPlan& p, int ppt) { return (size_t)(p.k2.tile_cap[ppt - 1] + 32) * sizeof(uint16_t); }
+inline size_t k2_lds_bytes(const RigPlan& p, int ppt) { return (size_t)k2_patch_hw(p.k2.tile_cap[ppt - 1]) * sizeof(uint16_t); }
 
 // the tiled K2's launch over n_frames frames (a lone frame: 1): blocks of K2_TX * K2_TY threads.  redo: the redo node of a captured
 // group -- a few blocks per frame walk its tiles
@@ -446,18 +404,18 @@ inline K2TiledShape k2_tiled_shape(const RigPlan& p, int n_frames, bool redo = f
   K2TiledShape s;
   s.ppt = k2_ppt(p, n_frames);
   s.tile_cap = p.k2.tile_cap[s.ppt - 1];
-  s.gx = grid_for(p.dims.proj_w, PL_K2_TX * s.ppt);
-  s.gy = grid_for(p.dims.proj_h, PL_K2_TY);
+  s.gx = grid_for(p.dims.proj_w, K2_TX * s.ppt);
+  s.gy = grid_for(p.dims.proj_h, K2_TY);
   s.gz = (unsigned)n_frames;
   if (redo) s.gx = std::min(s.gx * s.gy, 32u), s.gy = 1;
-  s.threads = PL_K2_TX * PL_K2_TY;
+  s.threads = K2_TX * K2_TY;
   s.lds = k2_lds_bytes(p, s.ppt);
   return s;
 }
 
 // the software-pipelined K2 (persistent blocks walking (frame, tile) items): groups on the plain u16 frame
 inline size_t k2_pipe_lds_bytes(const RigPlan& p, int g) {
-  return (size_t)((p.k2.tile_cap[g] + 32 + 7) & ~7) * sizeof(uint16_t) + (size_t)p.k2pipe.nlds * 8 /* uint2 */;
+  return (size_t)k2p_dlut_off_hw(p.k2.tile_cap[g]) * sizeof(uint16_t) + (size_t)p.k2pipe.nlds * K2P_DLUT_ENTRY_BYTES;
 }
 
 // does a group of n_frames take the pipelined K2, and in which shape?  (use = false: the tiled K2, one block per tile)
@@ -475,7 +433,7 @@ inline K2PipeShape k2_pipe_shape(const RigPlan& p, int n_frames) {
   const RigPlan::K2Pipe& k = p.k2pipe;
   if (!k.on || !k.rig_ok || k.nlds < 1 || (k2_ppt(p, n_frames) != 2 && !k.force)) return s;
   s.g = k.g, s.ppt = 1 << s.g;
-  s.gx = grid_for(p.dims.proj_w, PL_K2_TX * s.ppt), s.gy = grid_for(p.dims.proj_h, PL_K2_TY);
+  s.gx = grid_for(p.dims.proj_w, K2_TX * s.ppt), s.gy = grid_for(p.dims.proj_h, K2_TY);
   const uint64_t total = (uint64_t)s.gx * s.gy * (uint64_t)n_frames;
   s.lds = k2_pipe_lds_bytes(p, s.g);
   const unsigned per_cu = (unsigned)std::max<size_t>(1, std::min<size_t>((size_t)k.per_cu_max, (160 * 1024) / (s.lds + 2048)));
@@ -491,11 +449,11 @@ inline K2PipeShape k2_pipe_shape(const RigPlan& p, int n_frames) {
 
 // ---- the frame kernels without tiles ------------------------------------------------------------------------------------------------
 // camera view on the compact key frame: blocks of CAM32_T x CAM32_T pixels
-inline unsigned cam32_gx(const RigPlan& p) { return grid_for(p.dims.cam_w, PL_CAM32_T); }
-inline unsigned cam32_gy(const RigPlan& p) { return grid_for(p.dims.cam_h, PL_CAM32_T); }
+inline unsigned cam32_gx(const RigPlan& p) { return grid_for(p.dims.cam_w, CAM32_T); }
+inline unsigned cam32_gy(const RigPlan& p) { return grid_for(p.dims.cam_h, CAM32_T); }
 // one thread per pixel: camera view on the 64-bit keys, projector view under "XM_K2_DIRECT"
 inline uint64_t cam_pixels(const RigPlan& p) { return (uint64_t)p.dims.cam_w * p.dims.cam_h; }
-inline unsigned pixel_blocks(uint64_t px) { return grid_for(px, PL_BLOCK); }
+inline unsigned pixel_blocks(uint64_t px) { return grid_for(px, BLOCK); }
 
 // ---- xm_create's arithmetic ---------------------------------------------------------------------------------------------------------
 // smallest / largest entry of the LUT's rectified x and of the X-map
@@ -531,7 +489,7 @@ struct RigClass {
 inline RigClass classify_tables(const TableExtrema& e, int x_offset, bool projector, int rect_h, int nlds_max) {
   RigClass c;
   c.max_disp = std::max<long>((long)std::max(e.xp_max, 0) - e.xr_min - x_offset, (long)0 - e.xr_min - x_offset);
-  c.key32_ok = (!projector || (rect_h & 3) == 0) && c.max_disp < (1l << PL_KEY32_DISP_BITS);
+  c.key32_ok = (!projector || (rect_h & 3) == 0) && c.max_disp < (1l << KEY32_DISP_BITS);
   c.k2_pipe_nlds = (int)std::max<long>(1, std::min<long>(std::min<long>(c.max_disp + 1, 65536), nlds_max));
   c.no_wrap = (long)e.xp_max - e.xr_min - x_offset <= 32767 && (long)e.xp_min - e.xr_max - x_offset >= -32768;
   return c;
@@ -552,13 +510,9 @@ inline K1Windows size_k1_windows(const RigPlan& p, int k1_wx) {
   // C-1M needs 44 KB (w_ts = 5, w_x = 16): three blocks per CU beside K2's 12 KB blocks
   const size_t budget = 76 * 1024;
   int w_ts = 5, w_x = k1_wx;  // 5 time columns, 16 camera columns: 70 KB at C-1M
-  auto need = [&](int wt, int wx) {
-    // must mirror the carve-up at the top of k_scatter_tiled (uint4 units, +1 uint4 of alignment slack per band)
-    const size_t win_words = p.dims.projector ? (size_t)wt * xmap_h : (size_t)wx * cam_h;
-    constexpr size_t slack = 64;  // LDS-direct band loads write whole waves: one wave of slack behind each band
-    const size_t win_q = (win_words + 3) / 4, lut_q = ((size_t)wx * cam_h + 3) / 4 + 1 + slack,
-                 xm_q = ((size_t)wt * xmap_h + 7) / 8 + 1 + slack;
-    return 16 * (std::max(win_q, lut_q) + xm_q + 1 + slack);  // slots and LUT band share a region; +1 (+ a wave): dump area of the band loads
+  auto need = [&](int wt, int wx) {  // the pieces k_scatter_tiled carves (xmaps_geometry.hpp), summed
+    const int head_q = tiled_head_q(tiled_win_q(p.dims.projector, wt, wx, cam_h, xmap_h), band_lut_q(wx, cam_h));
+    return 16 * ((size_t)head_q + (size_t)band_xm_q(wt, xmap_h) + (size_t)tiled_dump_q());
   };
   while (need(w_ts, w_x) > budget && (w_ts > 1 || w_x > 1)) {
     if (w_ts * xmap_h * 6 >= w_x * cam_h * 4 && w_ts > 1) w_ts -= 1;

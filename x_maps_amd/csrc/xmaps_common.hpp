@@ -3,11 +3,13 @@
 // arithmetic of K1 (event_disparity*, event_cell: cam_proj_calibration.py:277-281 / 299-303, x_maps_disparity.py:23-29), the XCD
 // work orders, the wave reductions, and the XM_ABLATE experiment globals.  (gfx950 / MI355X)
 //
-// Needs nothing of the project; every other xmaps_*.hpp includes it.
+// Needs xmaps_geometry.hpp only (standard C++: what the kernels share with the host's plan); every other xmaps_*.hpp includes it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include <stdint.h>
+
+#include "xmaps_geometry.hpp"  // BLOCK, the KEY32 fields, every constant and LDS layout the host's plan reads too
 
 namespace xm {
 
@@ -20,7 +22,6 @@ constexpr u32 KEY_MAX_TAG = (1u << 19) - 1;
 constexpr int MM_SLOTS = 32;   // spread the min/max atomics over 32 addresses: one contended word retires only
                                // ~88 atomics/us on this chip (8 slots measured +3 us on K0)
 constexpr int CNT_SLOTS = 64;  // same for the counters
-constexpr int BLOCK = 256;
 
 enum { CNT_USED = 0, CNT_INLIER = 1, CNT_OOB = 2, CNT_UNSORTED = 3, CNT_STRIDE = 4 };
 
@@ -162,7 +163,7 @@ __host__ __device__ inline unsigned char dirty_byte(u32 tag) { return (unsigned 
 // Camera view (VIEW == 1 with KEY32): the cell is the event's own pixel, written by events of ANY tile, so the order field is the
 // event itself: key = (event index + 1) << 12 | disparity -- exact for every frame of < 2^20 events whatever their order, strays
 // included; no tag: the frame kernel, which reads every pixel of the 1.2 MB frame exactly once, zeroes what it has read.
-constexpr u32 KEY32_DISP_BITS = 12, KEY32_TILE_BITS = 16, CAM32_MAX_EVENTS = (1u << 20) - 1u;
+// (KEY32_DISP_BITS, KEY32_TILE_BITS, CAM32_MAX_EVENTS: xmaps_geometry.hpp)
 __host__ __device__ inline u32 key32_tag(u32 tag) { return (tag % 15u + 1u) << 28; }
 __device__ inline uint16_t key_disp32(u32 k, u32 tag4) { return (k & 0xf0000000u) == tag4 ? (uint16_t)(k & 0xfffu) : (uint16_t)0; }
 

@@ -2,10 +2,8 @@
 // Written for MI355X (gfx950) only: build with
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -shared xmaps_hip.hip -o libxmaps_hip.so
 // -ffp-contract=off keeps the time normalisation (divide, multiply, rint) unfused = bit-exact with NumPy.
-// In front of everything: the rig plan and the path / launch-shape rules (standard C++ only), so that its restatement of the
-// kernels' constants reads the command line's -DXM_... overrides and nothing a device header defines; asserted below.
-#include "host/xm_plan.hpp"
-// The device side, one header per kernel (each includes what it needs):
+// The device side, one header per kernel (each includes what it needs; xmaps_geometry.hpp, standard C++ only, holds the
+// constants and the LDS layouts they share with the host's plan):
 #include "xmaps_kernels.hpp"        // common ABI, K0, K1 direct / event tiles, K2, stage, X-map builder, filters, eval, slots
 #include "xmaps_k1cols.hpp"         // K1 on column tiles + the boundary pass
 #include "xmaps_k1own.hpp"          // K1 on owner tiles
@@ -42,30 +40,8 @@
 
 using namespace xm;
 
-// xm_plan.hpp restates the kernels' constants (it is also built alone, for the CPU tests): each against the kernel's own
-#define XM_PLAN_SAME(plan_c, kernel_c) static_assert((plan_c) == (kernel_c), "host/xm_plan.hpp: " #plan_c " differs from the kernel's " #kernel_c)
-XM_PLAN_SAME(PL_BLOCK, BLOCK);
-XM_PLAN_SAME(PL_K0_UN, K0_UN);
-XM_PLAN_SAME(PL_TILE_THREADS, TILE_THREADS);
-XM_PLAN_SAME(PL_TILE_EPT, TILE_EPT);
-XM_PLAN_SAME(PL_COLS_EPT, COLS_EPT);
-XM_PLAN_SAME(PL_COLS_MAX_THREADS, COLS_MAX_THREADS);
-XM_PLAN_SAME(PL_K2_TX, K2_TX);
-XM_PLAN_SAME(PL_K2_TY, K2_TY);
-XM_PLAN_SAME(PL_K2_TILE_MAX, K2_TILE_MAX);
-XM_PLAN_SAME(PL_CAM32_T, CAM32_T);
-XM_PLAN_SAME(PL_CAM32_MAX_EVENTS, CAM32_MAX_EVENTS);
-XM_PLAN_SAME(PL_KEY32_DISP_BITS, KEY32_DISP_BITS);
-XM_PLAN_SAME(PL_KEY32_TILE_BITS, KEY32_TILE_BITS);
-XM_PLAN_SAME(PL_OWN_BW, OWN_BW);
-XM_PLAN_SAME(PL_COLS_F_ALL_IN_FRAME, COLS_F_ALL_IN_FRAME);
-XM_PLAN_SAME(pl_cols_bounds_per_block(16), cols_bounds_per_block(16));
-XM_PLAN_SAME(pl_cols_bounds_per_block(32), cols_bounds_per_block(32));
-XM_PLAN_SAME(sizeof(uint2), 8);  // k2_pipe_lds_bytes: an entry of the per-disparity table
-#undef XM_PLAN_SAME
-// (own_tab_words is no constant expression: own_setup compares it with pl_own_tab_words for every plan it uploads)
-
 // The host side is one translation unit, split by concern (each file closes the namespaces / linkage blocks it opens):
+#include "host/xm_plan.hpp"         // the rig plan and the path / launch-shape rules (standard C++ only)
 #include "host/xm_queue.hpp"        // the host threads' job queues and first-error latches (standard C++ only)
 #include "host/xm_agree.hpp"        // the agreement among a sharded handle's device threads (standard C++ only)
 #include "host/xm_res.hpp"          // owners of device / pinned memory, streams and events (RAII)

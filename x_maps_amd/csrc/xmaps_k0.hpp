@@ -13,10 +13,7 @@ namespace xm {
 //   AoS : EventCD records, one 16-byte load per event
 // Also: advances the slot's frame tag (block 0) and counts the used events.
 // =====================================================================================================
-#ifndef XM_K0_UN
-#define XM_K0_UN 8
-#endif
-constexpr int K0_UN = XM_K0_UN;  // 16-byte loads of t in flight per thread (vector path)
+// (K0_UN, 16-byte loads of t in flight per thread on the vector path: xmaps_geometry.hpp)
 template <typename T, bool AOS, bool HAS_P, int VEC>
 __device__ __forceinline__ void minmax_body(const T* __restrict__ t, const int16_t* __restrict__ p,
                                             const uint4* __restrict__ aos, u64 n, SlotState* st, u32 tag_override,

@@ -57,8 +57,7 @@ typedef XM_GLOBAL SlotState* gp_state;
 #define XM_CSTAMP(ph) do { } while (0)
 #endif
 
-constexpr int COLS_EPT = 8;          // events per thread and pass
-enum { COLS_F_DEVICE_REDO = 1, COLS_F_ALL_IN_FRAME = 2, COLS_F_EXT_EXTREMA = 4 };
+// (COLS_EPT, COLS_MAX_THREADS and the COLS_F_* flags: xmaps_geometry.hpp)
 // COLS_F_EXT_EXTREMA (shards: a contiguous piece of a frame's sorted stream): the FRAME's extrema come from a 16-byte device buffer
 // {tmin, -tmax} (FrameDesc.p carries its address; the path has no polarity column) instead of the piece's first / last stamp, and a
 // piece without events still writes its zeros
@@ -171,8 +170,7 @@ __device__ __forceinline__ int cols_x_at(gp_u16 xs, gp_u4 aos, int i) {
 // (the stamps at its two ends say where in it the threshold falls: G * FIN consecutive events around that place; an evenly filled
 // scan misses such a window by ~16 events rms) -- ten lines per boundary instead of twenty-two, K0b 16.9 -> 13.0 us, the step
 // 0.1930 -> 0.1908 ms.  At most three interpolated windows, then the even splits: what is read decides, the stamps only guess.
-constexpr int COLS_BOUNDS_FIN = 4;
-constexpr int cols_bounds_per_block(int G) { return 256 / G; }
+constexpr int COLS_BOUNDS_FIN = 4;  // (cols_bounds_per_block: xmaps_geometry.hpp)
 
 // probes of one round, FIN per lane in probing order (lane-major), act[k] / pr[k] = probed / at or past the boundary, q[k] their
 // positions (non-decreasing in probing order): narrow (lo, hi).  Executed by the whole wave; gl = the group's first lane.
@@ -416,11 +414,10 @@ __device__ __forceinline__ void scatter_cols_body(gp_u16 xs, gp_u16 ys, gp_i64 t
   const size_t key_cells = frame16_cells(tb);
   gp_i4 bounds = (gp_i4)((const XM_GLOBAL unsigned char*)frame16 + cols_bounds_offset(key_cells));
   const XM_GLOBAL u32* thr = (const XM_GLOBAL u32*)((const XM_GLOBAL unsigned char*)frame16 + cols_thr_offset(key_cells, tb.xmap_w));
-  // LDS carve-up (uint4 units; each band keeps 1 quad of alignment slack in front and a wave of slack behind it for the
-  // LDS-direct loads, which write whole waves).  Mirrored by cols_lds_bytes() on the host.
-  const int lut_q = ((w_x * tb.cam_h + 3) >> 2) + 1 + 64;
-  const int xm_q = ((W * tb.xmap_h + 7) >> 3) + 1 + 64;
-  const int slot_q = (W * tb.xmap_h + 3) >> 2;
+  // LDS carve-up, in uint4 units (the pieces and their sizes: xmaps_geometry.hpp)
+  const int lut_q = band_lut_q(w_x, tb.cam_h);
+  const int xm_q = band_xm_q(W, tb.xmap_h);
+  const int slot_q = cols_slot_q(W, tb.xmap_h);
   u32* lut_base = reinterpret_cast<u32*>(smem);
   int16_t* xm_base = reinterpret_cast<int16_t*>(lut_base + 4 * lut_q);
   u32* slots = reinterpret_cast<u32*>(xm_base + 8 * xm_q);
@@ -770,10 +767,6 @@ __device__ __forceinline__ void scatter_cols_body(gp_u16 xs, gp_u16 ys, gp_i64 t
   if (tid == 0) flush_counts(st->cnt[parity][blk % CNT_SLOTS], s_in, s_oob);
 }
 
-#ifndef XM_COLS_MAX_THREADS
-#define XM_COLS_MAX_THREADS 512
-#endif
-constexpr int COLS_MAX_THREADS = XM_COLS_MAX_THREADS;
 #ifndef XM_COLS_WAVES_PER_EU
 #define XM_COLS_WAVES_PER_EU 6
 #endif

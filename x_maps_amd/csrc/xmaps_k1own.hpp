@@ -39,12 +39,9 @@
 
 namespace xm {
 
-constexpr int OWN_BW = 4;         // tile widths are multiples of it (K0b finds two boundaries per tile: its first column and the end of its halo)
 constexpr int OWN_MAX_DELTA = 7;  // 3 bits in the packed X-map
 constexpr int OWN_XP_BITS = 13;   // xp < 8192
 constexpr int OWN_MAX_NXS = 16;   // sheared frame columns per tile with per-row ownership (the masks are u16; 32 per 8-row group)
-// a tile's band table (own_bm, own_setup): a u32 per row -- or, with ownership per 8-row group, two per group --, padded to 16 bytes
-__host__ __device__ inline int own_tab_words(int hrp, bool grouped) { return ((grouped ? (hrp >> 3) * 2 : hrp) + 3) & ~3; }
 constexpr int OWN_MAX_COLS = 72;  // own + halo columns of a tile (W <= 64, halo <= 8)
 constexpr int OWN_MAX_ROW_PASSES = 4;         // a tile's rows go through its LDS slots in up to this many passes (own_plan)
 constexpr size_t OWN_LDS_TARGET = 32 * 1024;  // ... as many as it takes to bring a block's LDS down to this
@@ -71,14 +68,14 @@ __device__ __forceinline__ void scatter_own_body(gp_u16 xs, gp_u16 ys, gp_i64 ts
   gp_i4 bounds = (gp_i4)((const XM_GLOBAL unsigned char*)frame16 + cols_bounds_offset(cells16));
   const XM_GLOBAL u32* thr = (const XM_GLOBAL u32*)((const XM_GLOBAL unsigned char*)frame16 + cols_thr_offset(cells16, tb.xmap_w));
   const int HRp = tb.own_hrp, r_lo = tb.own_r_lo;
-  // LDS carve-up (mirrored by own_lds_bytes() on the host): band slots [nxs_max][RP] | extra slots [extra_max] | per row: first
+  // LDS carve-up (the pieces and their sizes: xmaps_geometry.hpp): band slots [nxs_max][RP] | extra slots [extra_max] | per row: first
   // frame column of the band, ownership mask.  RP = rows per pass: the tile's rows go through the band slots in ceil(HRp / RP)
   // passes (events and gathers stay in registers in between) -- a block's LDS is what limits the tiles a CU holds at once
   u32* slots = reinterpret_cast<u32*>(smem);
   const int RP = tb.own_rp;
-  const int n_band_max = tb.own_nxs_max * RP;
+  const int n_band_max = own_band_words(tb.own_nxs_max, RP);
   u32* slots_x = slots + n_band_max;
-  u32* s_tab = slots_x + tb.own_extra_max;  // the tile's band table (own_tab_words): band positions and ownership per row / per 8-row group
+  u32* s_tab = slots_x + own_extra_words(tb.own_extra_max);  // the tile's band table (own_tab_words): band positions and ownership per row / per 8-row group
   const bool grouped = tb.own_grouped != 0;
   const int ent_sh = grouped ? 3 : 0, n_ent = HRp >> ent_sh, tab_words = own_tab_words(HRp, grouped);
 

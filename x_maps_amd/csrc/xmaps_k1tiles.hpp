@@ -24,17 +24,7 @@ namespace xm {
 // the same kernel: always correct, only slower.  Camera view: slot = (row, x - x_lo), frame row-major.
 // =====================================================================================================
 
-#ifndef XM_TILE_THREADS
-#define XM_TILE_THREADS 512
-#endif
-constexpr int TILE_THREADS = XM_TILE_THREADS;   // 512 x 8 or 1024 x 4 events: same LDS tile, different latency/issue trade
-#ifdef XM_TILE_EPT  // experiments: events per thread decoupled from the block size (smaller tiles)
-constexpr int TILE_EPT = XM_TILE_EPT;
-#else
-constexpr int TILE_EPT = 4096 / XM_TILE_THREADS;
-#endif
-constexpr int TILE_EVENTS = TILE_THREADS * TILE_EPT;  // largest block: 4096 events (the LDS slots hold (local idx + 1) << 16)
-
+// (TILE_THREADS, TILE_EPT, TILE_EVENTS: xmaps_geometry.hpp)
 // VEC: SoA columns 16-byte aligned -> each thread loads TILE_EPT consecutive events with 8/16-byte loads.  A compile-time
 // switch, not a per-block branch: with both load paths in one kernel the compiler's wait-count bookkeeping at the join
 // put full vmcnt waits in front of the event loads and of the extrema reduction (seen in the ISA).
@@ -56,17 +46,16 @@ __device__ __forceinline__ void scatter_tiled_body(
   static_assert(!(AOS && VEC), "AoS records are loaded one per lane");
   constexpr bool PROJ32 = KEY32 && VIEW == 0, CAM32 = KEY32 && VIEW == 1;  // (see KEY32_DISP_BITS)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  // LDS carve-up (16-byte aligned pieces; the two bands keep 16 B of slack for their alignment shift).  The LUT band and
-  // the winner slots SHARE one region: the band is only read by the first gather of the fast path, the slots only written
-  // after it -- two extra barriers buy 26 KB per block, i.e. a third resident block per CU (block residency is what bounds
-  // the pipelined frame rate: tools/block_timeline.py).
-  const int win_words = VIEW == 0 ? w_ts * tb.xmap_h : w_x * tb.cam_h;
-  const int win_q = (win_words + 3) >> 2;  // uint4 count
-  // LDS-direct band loads write whole waves (64 x 16 B): each band keeps one wave of slack behind it (k1_lds_bytes())
-  const int lut_q = ((w_x * tb.cam_h + 3) >> 2) + 1 + 64;
+  // LDS carve-up (the pieces and their sizes: xmaps_geometry.hpp).  The LUT band and the winner slots SHARE one region: the
+  // band is only read by the first gather of the fast path, the slots only written after it -- two extra barriers buy 26 KB
+  // per block, i.e. a third resident block per CU (block residency is what bounds the pipelined frame rate:
+  // tools/block_timeline.py).
+  const int win_words = tiled_win_words(VIEW == 0, w_ts, w_x, tb.cam_h, tb.xmap_h);
+  const int win_q = tiled_win_q(VIEW == 0, w_ts, w_x, tb.cam_h, tb.xmap_h);
+  const int lut_q = band_lut_q(w_x, tb.cam_h);
   u32* win = reinterpret_cast<u32*>(smem);
   u32* lut_base = win;
-  int16_t* xm_base = reinterpret_cast<int16_t*>(win + 4 * max(win_q, lut_q));
+  int16_t* xm_base = reinterpret_cast<int16_t*>(win + 4 * tiled_head_q(win_q, lut_q));
   __shared__ u32 s_in, s_oob;
 
   const int tid = threadIdx.x;
@@ -313,7 +302,7 @@ __device__ __forceinline__ void scatter_tiled_body(
   constexpr int UL_L = TILE_THREADS >= 1024 ? 2 : 4, UL_X = TILE_THREADS >= 1024 ? 1 : 2;
   const int dma_q0 = tid & ~63;  // first band quad of this wave in pass 0
   const int dma_lane = tid & 63;
-  uint4* l_dmy = l_xm + (((w_ts * tb.xmap_h + 7) >> 3) + 1 + 64);  // where waves past the end of a band dump their load
+  uint4* l_dmy = l_xm + band_xm_q(w_ts, tb.xmap_h);  // the dump area (tiled_dump_q): where waves past the end of a band dump their load
   {
 #pragma unroll
     for (int k = 0; k < UL_L; ++k) {

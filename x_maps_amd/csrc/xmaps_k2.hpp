@@ -142,22 +142,13 @@ __global__ __launch_bounds__(BLOCK) void k_frame_proj(Cells cells, DevTables tb,
 //   3. every pixel then needs 7 LDS reads (one per window column) instead of 49.
 // PMC on the 49-tap version: SQ_LDS_IDX_ACTIVE 3.1 M cycles / dispatch -- it was LDS-bound.
 // Falls back to global reads when the patch does not fit (wild maps).
-#ifndef XM_K2_TILE_MAX
-#define XM_K2_TILE_MAX 10240
-#endif
-#ifndef XM_K2_TX
-#define XM_K2_TX 16
-#define XM_K2_TY 16
-#endif
 #ifdef XM_ABLATE  // experiments (tools/k2_timeline.py): s_memtime stamps of thread 0 of 64 tiles in the middle of frame 30's K2
 #define XM_K2STAMP(ph) do { if (threadIdx.x == 0 && blockIdx.z == 30 && blockIdx.y == 15 && blockIdx.x < 40) g_timeline[blockIdx.x][9 + (ph)] = __builtin_amdgcn_s_memtime(); } while (0)  /* columns 9..15: K1's stamps keep 0..8 */
 #else
 #define XM_K2STAMP(ph) do { } while (0)
 #endif
 // pixels per thread (template parameter PPT of the K2 kernels: 2 for launches that fill the chip, 1 for a lone frame): a block's
-// tile is K2_TX * PPT x K2_TY pixels, thread (tx, ty) takes columns tx + j * K2_TX
-constexpr int K2_TX = XM_K2_TX, K2_TY = XM_K2_TY, K2_TILE_MAX = XM_K2_TILE_MAX;  // at most 20 KB of u16 per block (the rig's
-                                                                    // largest patch sizes the dynamic LDS: 10.5 KB at C-1M)
+// tile is K2_TX * PPT x K2_TY pixels, thread (tx, ty) takes columns tx + j * K2_TX  (K2_TX, K2_TY, K2_TILE_MAX: xmaps_geometry.hpp)
 
 __device__ inline uint16_t key_disp(u64 k, u32 tag) { return (u32)(k >> KEY_TAG_SHIFT) == tag ? (uint16_t)(k & 0xffff) : (uint16_t)0; }
 
@@ -300,7 +291,7 @@ __device__ __forceinline__ void frame_proj_tiled_body(const u64* __restrict__ ke
   constexpr bool KEY32 = FMT == 1, U16 = FMT == 2;
   constexpr int K2_PPT = PPT, K2_TW = K2_TX * PPT;
   extern __shared__ __attribute__((aligned(16))) uint16_t k2_lds[];
-  uint16_t* tile = k2_lds;  // [tile_cap + 16]  (+16: the last 16-byte read may overrun)
+  uint16_t* tile = k2_lds;  // [k2_patch_hw(tile_cap)]: the patch and the overrun of its last 16-byte reads
   uint16_t* vmax = tile;  // the row maxima replace the patch IN PLACE: half the LDS per block = more blocks per CU
   constexpr int NT = K2_TX * K2_TY, NW = NT / 64;
   __shared__ __attribute__((aligned(16))) uint8_t s_bgr[K2_TY][K2_TW * 3];
@@ -805,7 +796,7 @@ __global__ __launch_bounds__(BLOCK) void k_frame_direct_batch(const FrameDesc* _
 // (u32[cam_w][cam_h]: K1's flush walks consecutive rows of one window column -- 64 lanes = 256 contiguous bytes per atomic
 // instruction instead of four 64-byte row pieces), the outputs are row-major: a block takes a 32 x 32-pixel tile, reads it
 // along the columns, hands the 12-bit disparities over through LDS and writes rows (128 bytes of depth, 96 of BGR per row).
-constexpr int CAM32_T = 32;
+// (CAM32_T: xmaps_geometry.hpp)
 __device__ __forceinline__ void frame_cam32_body(u32* __restrict__ frame32, const int cam_w, const int cam_h, SlotState* st,
                                                  const uint2* __restrict__ dlut, float* __restrict__ depth, uint8_t* __restrict__ bgr,
                                                  const u32 tile_x, const u32 tile_y) {

@@ -31,10 +31,10 @@
 
 namespace xm {
 
-// 16-byte patch loads per thread kept in registers: thread slot s = tid + j * 256 holds quad s of the patch in memory order
-// (column s / oct, row octet s % oct, oct = rows / 8), so a patch of q quads needs ceil(q / 256) of them: four cover 8192 cells
-constexpr int K2P_UN = 4;
+// K2P_UN (xmaps_geometry.hpp) 16-byte patch loads per thread are kept in registers: thread slot s = tid + j * 256 holds quad s of the
+// patch in memory order (column s / oct, row octet s % oct, oct = rows / 8)
 static_assert(K2P_UN % 2 == 0, "the live masks come as 16-byte pairs of loader registers");
+static_assert(sizeof(uint2) == K2P_DLUT_ENTRY_BYTES, "an entry of the per-disparity table in LDS");
 
 // Can every tile of the rig take the pipelined kernel?  (decided once in xm_create from the tile table; rows a multiple of 8 --
 // then every 8-row octet of a patch lies entirely inside or outside the frame -- and at most 128)
@@ -121,8 +121,8 @@ __global__ __launch_bounds__(K2_TX* K2_TY) void k_frame_proj_pipe(const FrameDes
   //  every LDS wait would drain the prefetch.)
   constexpr int NT = K2_TX * K2_TY, K2_TW = K2_TX * PPT;
   extern __shared__ __attribute__((aligned(16))) uint16_t k2_lds[];
-  uint16_t* tile = k2_lds;                                                         // [tile_cap + 32]
-  uint2* s_dlut = reinterpret_cast<uint2*>(k2_lds + ((tile_cap + 32 + 7) & ~7));  // [n_lds] {f32 depth bits, BGR word}
+  uint16_t* tile = k2_lds;                                                      // [k2_patch_hw(tile_cap)]
+  uint2* s_dlut = reinterpret_cast<uint2*>(k2_lds + k2p_dlut_off_hw(tile_cap));  // [n_lds] {f32 depth bits, BGR word}
   __shared__ __attribute__((aligned(16))) uint8_t s_out[K2_TY][K2_TW * 3];
   const int tid = threadIdx.x, tx = tid & (K2_TX - 1), ty = tid / K2_TX;
   const u32 wave = __builtin_amdgcn_readfirstlane((u32)tid >> 6);  // (uniform: the live masks below are scalar loads)
