@@ -704,7 +704,7 @@ int xm_process_time_surfaces(xm_handle* h, const void* surfaces, int dtype, int 
                              float* cloud_out, xm_surface_stats* stats_out);
 
 /* ---- ESL-init: the baseline of the reference's evaluation table, on the device ------------------------------------------------
- * What python/eval/compute_depth_esl.py:204-226 computes up to depth_init (the optimisation behind it and MC3D stay out of scope),
+ * What python/eval/compute_depth_esl.py:204-226 computes up to depth_init (the optimisation behind it stays out of scope; MC3D: xm_mc3d_* below),
  * for a GROUP of camera time surfaces in one device call.  Per surface:
  *   1. lo / hi over the non-zero pixels, v' = ((double)v - lo) / (hi - lo), negatives to 0 -- widened to float64 first, exactly
  *      as xm_process_time_surfaces does (golden G7's convention);
@@ -751,6 +751,62 @@ int xm_esl_init_time_surfaces(xm_esl_init* e, const void* surfaces, int dtype, i
 /* Step 3 alone, on a caller-supplied rectified camera image (host, f64 [rect_height][rect_width]) against the object's proj_rect:
  * the reference's disparity_init as a function -> u16 [rect_height][rect_width] (host).  Synchronous. */
 int xm_esl_init_stage_disparity(xm_esl_init* e, const double* cam_rect_host, uint16_t* disparity_rect_out);
+
+/* ---- MC3D: the other baseline of the reference's evaluation table, on the device -------------------------------------------------
+ * What python/eval/mc3d_baseline.py:40-78,129-140 computes, for a GROUP of camera time surfaces in one device call.  With
+ * (W, H) = (proj_width, proj_height), per surface (used as stored: no normalisation):
+ *   1. v = median of the 3 x 3 neighbourhood, borders replicated, the exact median of nine (cv2.medianBlur(., 3): UNPINNED against
+ *      a cv2 run), taken in the surface's own type; XM_MC3D_NO_BLUR: v = the pixel itself;
+ *   2. for every pixel with v > 0: (xc, yc) = cam_map[i][j]; dropped unless 0 < xc < rect_x_limit and 0 < yc < rect_y_limit;
+ *      id = (int)(W * H * v), the product a float32 multiply for XM_T_FLOAT32 and a float64 multiply for XM_T_FLOAT64; dropped if
+ *      id >= W * H (v >= 1, +inf); proj_x = id / H, proj_y = id % H; over y in [max(proj_y - nc, 0), min(proj_y + nc, H)), with
+ *      (xp, yp) = proj_map[y][proj_x], the FIRST minimum of |yc - yp| wins; it is accepted if <= max_row_diff; then
+ *      disp = xp - xc, stored only if > 0.  Only that one candidate is ever examined;
+ *   3. depth = (float)(p1_03 / (double)disp), 0 where the disparity is 0 (never inf).
+ * The maps are int32 pairs, the reference's int(map[..]) -- truncation toward zero -- done by the table builder
+ * (x_maps_amd/mc3d.py mc3d_int_maps).  XM_MC3D_POISON in either component marks a NaN / +-inf entry: in cam_map it drops the
+ * pixel, in proj_map INSIDE a pixel's window it drops that pixel (the reference's swallowed exception), outside it has no effect.
+ * Finite entries beyond +-2^30 saturate there (the builder's, and again at create).  That cannot change a result: the rect limits
+ * and max_row_diff are at most 2^29, so xc and yc lie below 2^29; a camera entry at the bound fails the limits either way; a
+ * projector yp at or beyond +-2^30 is more than 2^29 away from every admissible yc, so its cost is never <= max_row_diff; and an
+ * xp there gives a disparity that is negative or beyond 2^29 either way, and
+ * a disparity above 65535 cannot be stored as u16; it is DEFINED as 0 (depth 0) and counted in n_disp_overflow.
+ * An all-zero surface gives zero maps and zero counts (the reference skips it); not an error.  NaN surfaces are out of contract;
+ * they neither fault nor index outside a table.  No kernel has atomics or waits for another block.  No xm_handle is involved;
+ * an object serves one thread at a time. */
+#define XM_MC3D_POISON INT32_MIN
+#define XM_MC3D_NO_BLUR 1
+typedef struct xm_mc3d xm_mc3d;
+typedef struct xm_mc3d_config {
+  uint32_t struct_size; /* sizeof(xm_mc3d_config) */
+  int32_t cam_width, cam_height;
+  int32_t proj_width, proj_height;    /* the reference: 1080 x 1920; proj_width * proj_height <= 2^24 */
+  int32_t nc;                         /* 0 = (int)(proj_height / 15); invalid: nc < 0, 2 * nc > proj_height */
+  int32_t max_row_diff;               /* 0 = 50; invalid: < 0, > 2^29, or a search key beyond 32 bits (mc3d_key_fits) */
+  int32_t rect_x_limit, rect_y_limit; /* 0, 0 = 3 * proj_height, 3 * proj_width: swapped, as the reference; each 1 .. 2^29 */
+  int32_t reserved;
+  double p1_03;                       /* P1[0, 3] of the rectification (either sign; 0 gives zero depth) */
+  const int32_t* cam_map;             /* host, [cam_height][cam_width][2]   (x, y), truncated toward zero */
+  const int32_t* proj_map;            /* host, [proj_height][proj_width][2] (x, y), the reference's orientation */
+} xm_mc3d_config;                     /* both tables are copied to the device (the projector's by column); the caller keeps ownership */
+typedef struct xm_mc3d_stats {
+  uint64_t n_nonzero;       /* pixels != 0, before the blur                                            */
+  uint64_t n_positive;      /* pixels with v > 0, after it                                             */
+  uint64_t n_in_rect;       /* ... whose camera entry passes the rect limits                           */
+  uint64_t n_out_of_range;  /* ... of which id >= W * H                                                */
+  uint64_t n_poisoned;      /* searched pixels whose window holds a poisoned entry                     */
+  uint64_t n_matched;       /* pixels with a stored disparity (1 .. 65535)                             */
+  uint64_t n_disp_overflow; /* accepted winners whose disparity exceeds 65535: stored as 0             */
+} xm_mc3d_stats;
+int xm_mc3d_create(int device, const xm_mc3d_config* cfg, xm_mc3d** out);
+void xm_mc3d_destroy(xm_mc3d* m);
+/* surfaces: [n_surfaces][cam_height][cam_width], XM_T_FLOAT32 or XM_T_FLOAT64.  depth_out: f32, the same shape.  disp_out (may be
+ * NULL): u16, the same shape.  stats_out (may be NULL): xm_mc3d_stats[n_surfaces].  flags: 0 or XM_MC3D_NO_BLUR.  mem ==
+ * XM_MEM_HOST: every pointer is host memory; XM_MEM_DEVICE: every pointer is device memory of the object's device.  Synchronous
+ * in both.  Scratch is allocated by the first call and grown when a larger group arrives.  XM_ERR_INVALID: a dtype other than the
+ * two float types, n_surfaces <= 0, unknown flags. */
+int xm_mc3d_time_surfaces(xm_mc3d* m, const void* surfaces, int dtype, int n_surfaces, int mem, int flags, float* depth_out,
+                          uint16_t* disp_out, xm_mc3d_stats* stats_out);
 
 /* ---- pinned host memory for XM_MEM_HOST_PINNED ------------------------------------------------------------- */
 int xm_host_alloc(xm_handle* h, size_t bytes, void** out);

@@ -19,7 +19,8 @@ the evaluation's tables (from_ESL_yaml, rect = 3 x projector, scan downwards) ->
 table's ground truth, which the reference's ESL optimisation writes (out of scope here: without it the depth maps are written and
 the row is reported as not computable) -- next to the published Book-Duck cell, FR 0.91 / RMSE 0.31 cm.  With --esl-init the
 same scans also go through the ESL-init baseline on the device (x_maps_amd/esl_init.py) -> `<scans>/esl/depth_init/scansNNN.npy`
-and the table's "ESL (init)" row is printed beside the X-maps one.
+and the table's "ESL (init)" row is printed beside the X-maps one; with --mc3d they go through the MC3D baseline
+(x_maps_amd/mc3d.py) -> `<scans>/mc3d/depth/scansNNN.npy` and the "MC3D" and "MC3D (1 sec)" rows are printed too.
 
 Tables come from the cv2-free builder (x_maps_amd/calibration.py: rectifying rotations pinned to OpenCV's on this calibration,
 map rounding unpinned): a difference from the published numbers on the real data is therefore a finding about that builder or
@@ -209,6 +210,42 @@ def esl_init_from_scans(object_dir, eval_calib, proj_w, proj_h, num_scans=0, sta
             "unpinned": "the int16 rounding of the two remap tables (np.rint) has not been compared with a cv2.remap run"}
 
 
+def mc3d_from_scans(object_dir, eval_calib, proj_w, proj_h, num_scans=0, start_scan=0, device=0, tables=None, group=8):
+    """Part B for the other baseline: mc3d_baseline.py:116-140.  Every scan of <scans>/scans_np through x_maps_amd.mc3d in groups
+    of `group` -> <scans>/mc3d/depth/scansNNN.npy (an all-zero scan is skipped, :129).  -> report"""
+    from x_maps_amd import calibration as C
+    from x_maps_amd.mc3d import Mc3d, build_mc3d_tables
+    names = sorted(glob.glob(os.path.join(object_dir, "scans_np", "*.npy")))
+    if not names:
+        return {"error": f"no camera files found in {os.path.join(object_dir, 'scans_np')}"}
+    depth_dir = os.path.join(object_dir, "mc3d", "depth")
+    os.makedirs(depth_dir, exist_ok=True)
+    t0 = time.perf_counter()
+    if tables is None:
+        tables = build_mc3d_tables(C.CamProjCalibrationParams.from_ESL_yaml(eval_calib, 640, 480, proj_w, proj_h))
+    last = len(names) if not num_scans else min(len(names), start_scan + num_scans)
+    per, skipped, filled = [], 0, []
+    with Mc3d(tables, device=device) as mc:
+        t_setup = time.perf_counter() - t0
+        for g0 in range(start_scan, last, max(1, group)):
+            idx = range(g0, min(last, g0 + max(1, group)))
+            surfs = [np.load(names[i]) for i in idx]
+            c0 = time.perf_counter()
+            out = mc.depths_from_time_surfaces(surfs)
+            dt = (time.perf_counter() - c0) / len(idx)
+            for i, (depth, _, st) in zip(idx, out):
+                if st.n_nonzero == 0:
+                    skipped += 1
+                    continue
+                per.append(dt)
+                np.save(os.path.join(depth_dir, "scans" + str(i).zfill(3) + ".npy"), depth)
+                filled.append(float((depth > 0).mean()))
+    return {"scans_found": len(names), "scans_processed": len(per), "scans_empty": skipped, "setup_seconds": round(t_setup, 3),
+            "ms_per_scan_depth": round(float(np.mean(per)) * 1e3, 4) if per else None,
+            "mean_fraction_of_pixels_with_depth": round(float(np.mean(filled)), 4) if filled else None, "depth_dir": depth_dir,
+            "unpinned": "cv2.medianBlur(., 3) and the float maps of cv2.undistortPoints have not been compared with a cv2 run"}
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--raw", help="Prophesee RAW recording (EVT 3.0 / 2.0), e.g. /ESL_data/static/seq1/data.raw")
@@ -233,6 +270,8 @@ def main(argv=None):
     ap.add_argument("--surface-group", type=int, default=8, help="scans per group with --surfaces-on-device")
     ap.add_argument("--esl-init", action="store_true",
                     help="part B: also write <scans>/esl/depth_init/scansNNN.npy (the ESL-init baseline on the device) and print its row")
+    ap.add_argument("--mc3d", action="store_true",
+                    help="part B: also write <scans>/mc3d/depth/scansNNN.npy (the MC3D baseline on the device) and print its two rows")
     ap.add_argument("--min-depth", type=float, default=20)
     ap.add_argument("--max-depth", type=float, default=500, help="eval/x-map-eval.sh:72 passes 500 (the table script's own default is 120)")
     ap.add_argument("--save-frames", type=int, default=0, help="part A: keep the first N BGR frames as frame_NNN.npy beside --out")
@@ -273,6 +312,13 @@ def main(argv=None):
             if "error" not in report["esl_init_from_scans"]:
                 from x_maps_amd.eval_table import esl_init_table_row
                 report["table_1_row_esl_init"] = esl_init_table_row(a.scans, a.min_depth, a.max_depth, device=a.device)
+        if a.mc3d:
+            report["mc3d_from_scans"] = mc3d_from_scans(a.scans, a.eval_calib, a.projector_width, a.projector_height, a.num_scans,
+                                                        a.start_scan, a.device, group=a.surface_group)
+            if "error" not in report["mc3d_from_scans"]:
+                from x_maps_amd.eval_table import mc3d_table_rows
+                rows = mc3d_table_rows(a.scans, a.min_depth, a.max_depth, device=a.device)
+                report["table_1_row_mc3d"], report["table_1_row_mc3d_1s"] = rows["mc3d"], rows["mc3d_1s"]
     txt = json.dumps(report, indent=1)
     print(txt)
     if a.out:

@@ -147,6 +147,22 @@ class xm_esl_init_stats(C.Structure):
                 ("lo", C.c_double), ("hi", C.c_double)]
 
 
+XM_MC3D_POISON = -2 ** 31
+XM_MC3D_NO_BLUR = 1
+
+
+class xm_mc3d_config(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("cam_width", C.c_int32), ("cam_height", C.c_int32),
+                ("proj_width", C.c_int32), ("proj_height", C.c_int32), ("nc", C.c_int32), ("max_row_diff", C.c_int32),
+                ("rect_x_limit", C.c_int32), ("rect_y_limit", C.c_int32), ("reserved", C.c_int32), ("p1_03", C.c_double),
+                ("cam_map", C.c_void_p), ("proj_map", C.c_void_p)]
+
+
+class xm_mc3d_stats(C.Structure):
+    _fields_ = [("n_nonzero", C.c_uint64), ("n_positive", C.c_uint64), ("n_in_rect", C.c_uint64), ("n_out_of_range", C.c_uint64),
+                ("n_poisoned", C.c_uint64), ("n_matched", C.c_uint64), ("n_disp_overflow", C.c_uint64)]
+
+
 # every symbol include/xmaps.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -255,6 +271,9 @@ SYMBOLS = {
     "xm_esl_init_destroy": (None, [_P]),
     "xm_esl_init_time_surfaces": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "xm_esl_init_stage_disparity": (C.c_int, [_P, _P, _P]),
+    "xm_mc3d_create": (C.c_int, [C.c_int, C.POINTER(xm_mc3d_config), C.POINTER(_P)]),
+    "xm_mc3d_destroy": (None, [_P]),
+    "xm_mc3d_time_surfaces": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "xm_stream": (_P, [_P, C.c_int]),
     "xm_host_alloc": (C.c_int, [_P, C.c_size_t, C.POINTER(_P)]),
     "xm_host_free": (C.c_int, [_P, _P]),

@@ -64,6 +64,30 @@ constexpr int CAM32_T = 32;  // camera view on the compact key frame: blocks of 
 // the compact (32-bit) key frame's fields (key32_tag, xmaps_common.hpp) and the largest frame its camera-view form orders exactly
 constexpr unsigned KEY32_DISP_BITS = 12, KEY32_TILE_BITS = 16, CAM32_MAX_EVENTS = (1u << 20) - 1u;
 
+// MC3D baseline (xmaps_mc3d.hpp): a wave takes MC3D_FW camera pixels of a row, a block MC3D_FR rows; MC3D_N_CNT counts per block
+constexpr int MC3D_FW = 64, MC3D_FR = BLOCK / 64, MC3D_N_CNT = 7;
+#ifndef XM_MC3D_GL
+#define XM_MC3D_GL 16
+#endif
+constexpr unsigned MC3D_GL = XM_MC3D_GL;  // ... lanes of a wave that share one pixel's window (a power of two, 2 .. 64)
+static_assert(MC3D_GL >= 2 && MC3D_GL <= 64 && (MC3D_GL & (MC3D_GL - 1)) == 0, "XM_MC3D_GL");
+#ifndef XM_MC3D_UN
+#define XM_MC3D_UN 16
+#endif
+constexpr unsigned MC3D_UN = XM_MC3D_UN;  // ... window entries a lane has in flight per trip
+// ... its int32 maps: MC3D_POISON marks a NaN / +-inf entry, finite entries saturate at +-MC3D_SAT (== XM_MC3D_POISON, xmaps.h)
+constexpr int MC3D_POISON = -2147483647 - 1, MC3D_SAT = 1 << 30;
+constexpr unsigned MC3D_NO_BLUR = 1;  // == XM_MC3D_NO_BLUR
+// ... its search key: 1 + (min(cost, max_row_diff + 1) << pos_bits | position in a window of `span` entries), 0 = poison, in 32 bits
+XM_HD constexpr unsigned mc3d_pos_bits(unsigned span) {
+  unsigned b = 0;
+  while (b < 32 && (1ull << b) < span) ++b;
+  return b;
+}
+XM_HD constexpr bool mc3d_key_fits(unsigned max_row_diff, unsigned span) {  // (the largest key is (max_row_diff + 2) << pos_bits)
+  return (((unsigned long long)max_row_diff + 2ull) << mc3d_pos_bits(span)) < (1ull << 32);
+}
+
 // ---- dynamic LDS layouts: every piece one function of plain ints ---------------------------------------------------------------
 // Units: _q = 16-byte quads, _words = 4 bytes, _hw = 2 bytes.  Plain int arithmetic, as the kernels do it: a table's height
 // fits int16 indices and a window is at most 64 columns wide, so no product comes near 2^31; the host sums the pieces in size_t.

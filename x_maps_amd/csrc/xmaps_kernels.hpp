@@ -33,3 +33,4 @@
 #include "xmaps_eval.hpp"       // evaluation metrics
 #include "xmaps_slots.hpp"      // slot reset, redo preparation
 #include "xmaps_eslinit.hpp"    // the ESL-init baseline: disparity search per rectified / per camera pixel (brings xmaps_surface.hpp)
+#include "xmaps_mc3d.hpp"       // the MC3D baseline: median, projector-column window search and depth per camera pixel

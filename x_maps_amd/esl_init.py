@@ -3,8 +3,8 @@ to depth_init; create_evaluation_table.py's "ESL (init)" row).  Camera time surf
 by nearest remap, disparity_init's search over the rectified projector time surface, remap back to the camera, P1[0,3] / disparity
 -- in one device call per group of surfaces (xm_esl_init_time_surfaces; kernels in csrc/xmaps_eslinit.hpp).
 
-In scope: this initialisation.  Out of scope: ESL's optimisation behind it (scipy minimize_scalar, bilateral filter, TV denoising)
-and the MC3D baseline.
+In scope: this initialisation.  Out of scope: ESL's optimisation behind it (scipy minimize_scalar, bilateral filter, TV denoising).
+The MC3D baseline is mc3d.py.
 
 UNPINNED: the float -> int16 rounding of the two remap tables (mapf_to_i16, np.rint as for every other map of this build) stands
 in for cv2.remap(INTER_NEAREST) on float maps; it has not been compared with a cv2 run.  The search itself

@@ -13,9 +13,10 @@ depth maps and point clouds out, nothing on the host in between, no atomics; cam
 before normalising it (the reference normalises a float32 file in float32: the last bit of t can differ; golden G7 pins
 this build's choice), and both give the same depth maps and clouds bit for bit.
 
-The baseline of the same evaluation, ESL-init (compute_depth_esl.py up to depth_init), takes the same surfaces: esl_init.py.
+The baseline of the same evaluation, ESL-init (compute_depth_esl.py up to depth_init), takes the same surfaces: esl_init.py; so does the
+MC3D baseline (mc3d_baseline.py): mc3d.py.
 
-Out of scope: file handling, ESL's optimisation (which produces the table's ground truth) and the MC3D baseline, a
+Out of scope: file handling, ESL's optimisation (which produces the table's ground truth), a
 projector-view surface path.  (The metrics of eval/ are in eval_metrics.py.)
 """
 from __future__ import annotations

@@ -1,10 +1,11 @@
-"""The X-maps row and the "ESL (init)" row of the reference's Table 1, from files on disk
+"""The X-maps, "ESL (init)", "MC3D" and "MC3D (1 sec)" rows of the reference's Table 1, from files on disk
 (python/eval/create_evaluation_table.py:57-62,84-180 and the ground-truth combination it borrows from python/eval/esl_utilities.py:153-175), for one sequence directory laid out as the
 reference's evaluation leaves it:
 
     <seq>/scans_np/*.npy                   camera time surfaces (input of compute_depth_x_maps.py)
     <seq>/x_maps/depth_init/scansNNN.npy   X-maps depth per scan        (written by x_maps_amd / tools/run_esl_on_arrival.py)
     <seq>/esl/depth_init/scansNNN.npy      ESL-init depth per scan      (x_maps_amd.esl_init / tools/run_esl_on_arrival.py --esl-init)
+    <seq>/mc3d/depth/scansNNN.npy          MC3D depth per scan          (x_maps_amd.mc3d / tools/run_esl_on_arrival.py --mc3d)
     <seq>/esl/depth_optim_filtered/*.npy   ESL's optimised depth = the table's ground truth (written by the reference's
                                            compute_depth_esl.py's optimisation -- out of scope here: when the directory
                                            is absent the row cannot be computed and the caller says so)
@@ -97,3 +98,25 @@ def esl_init_table_row(seq_dir: str, min_depth: float = 20, max_depth: float = 1
     """The "ESL (init)" row (create_evaluation_table.py:143-180): <seq>/esl/depth_init -- what x_maps_amd.esl_init /
     tools/run_esl_on_arrival.py --esl-init write -- against the same ground truth."""
     return depth_table_row(seq_dir, ("esl", "depth_init"), "esl_init_files", min_depth, max_depth, device)
+
+
+def mc3d_table_rows(seq_dir: str, min_depth: float = 20, max_depth: float = 120, device: int = 0) -> dict:
+    """The "MC3D" and "MC3D (1 sec)" rows (create_evaluation_table.py:126-161) -> {"mc3d": row, "mc3d_1s": row}.  "mc3d":
+    <seq>/mc3d/depth -- what x_maps_amd.mc3d / tools/run_esl_on_arrival.py --mc3d write -- scan by scan, as every other method.
+    "mc3d_1s": combine_depth_maps of ALL those files (:128), which is NOT passed through load_and_filter, scored against every
+    filtered ground-truth scan (:151)."""
+    row = depth_table_row(seq_dir, ("mc3d", "depth"), "mc3d_files", min_depth, max_depth, device)
+    if "error" in row:
+        return {"mc3d": row, "mc3d_1s": dict(row)}
+    gt_files = sorted(glob.glob(os.path.join(seq_dir, "esl", "depth_optim_filtered", "*.npy")))
+    est_files = sorted(glob.glob(os.path.join(seq_dir, "mc3d", "depth", "*.npy")))
+    combined, _, _ = combine_depth_maps(est_files, min_depth, max_depth)
+    gt_combined, _, avg_depth = combine_depth_maps(gt_files, min_depth, max_depth)
+    rows = []
+    for g in gt_files:
+        s = evaluation_stats(combined, load_and_filter(g, gt_combined, min_depth, max_depth), device=device)
+        rows.append((s.fillrate, s.rmse))
+    fr, rmse = np.mean(np.array(rows, np.float64), axis=0)
+    return {"mc3d": row,
+            "mc3d_1s": {"scans": len(rows), "mean_depth": round(avg_depth, 3), "fill_rate": float(fr), "rmse": float(rmse),
+                        "table_cell": f"{round(float(fr), 2)} & {round(float(rmse), 2)}"}}
