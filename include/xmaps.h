@@ -704,7 +704,7 @@ int xm_process_time_surfaces(xm_handle* h, const void* surfaces, int dtype, int 
                              float* cloud_out, xm_surface_stats* stats_out);
 
 /* ---- ESL-init: the baseline of the reference's evaluation table, on the device ------------------------------------------------
- * What python/eval/compute_depth_esl.py:204-226 computes up to depth_init (the optimisation behind it stays out of scope; MC3D: xm_mc3d_* below),
+ * What python/eval/compute_depth_esl.py:204-226 computes up to depth_init (the optimisation behind it: xm_esl_optim_* below; MC3D: xm_mc3d_*),
  * for a GROUP of camera time surfaces in one device call.  Per surface:
  *   1. lo / hi over the non-zero pixels, v' = ((double)v - lo) / (hi - lo), negatives to 0 -- widened to float64 first, exactly
  *      as xm_process_time_surfaces does (golden G7's convention);
@@ -751,6 +751,68 @@ int xm_esl_init_time_surfaces(xm_esl_init* e, const void* surfaces, int dtype, i
 /* Step 3 alone, on a caller-supplied rectified camera image (host, f64 [rect_height][rect_width]) against the object's proj_rect:
  * the reference's disparity_init as a function -> u16 [rect_height][rect_width] (host).  Synchronous. */
 int xm_esl_init_stage_disparity(xm_esl_init* e, const double* cam_rect_host, uint16_t* disparity_rect_out);
+
+/* ---- ESL depth optimisation: the solver behind ESL-init, on the device ----------------------------------------------------------
+ * What python/eval/compute_depth_esl.py:104-129 (depth_optimization, with cost_calculator :45-69 and project_and_backproject_punkt
+ * :27-42) computes for a GROUP of camera time surfaces and their depth_init maps in one device call: the maps the reference stores
+ * as esl/depth_optim.  The bilateral filter and the TV denoiser behind it (:243-244, cv2 / pylops) stay out of scope, and with them
+ * esl/depth_optim_filtered.  Per surface s with depth_init d0 (f32, as xm_esl_init_time_surfaces writes it):
+ *   1. v' = max(((double)v - lo) / (hi - lo), 0) with lo / hi over the non-zero pixels, exactly as xm_esl_init_time_surfaces step 1;
+ *   2. f = 1.0 / v'[0][0] (+inf when that is 0, as NumPy); every v' == 0 becomes f (:212).  The image is NOT rectified;
+ *   3. pixels y in [ws, cam_height - ws), x in [ws, cam_width - ws) with d0 > 0 are optimised, ws = window_size; every other pixel
+ *      is written 0.  The patch half-width is w = ws / 2 (integer division): the reference's border and patch (:107-108, :53);
+ *   4. diff = (double)(d0 * d0) / p1_03 -- a float32 product, a float64 quotient, as NumPy evaluates depth**2 / P1[0, 3];
+ *      a = (double)d0 - diff, b = (double)d0 + diff.  Where scipy raises (a or b not finite, a > b) the pixel is written 0 and
+ *      counted in n_bad_bounds;
+ *   5. xf = scipy.optimize.minimize_scalar(cost, bounds = (a, b), method = "bounded"), xatol and at most max_iter evaluations:
+ *      _minimize_scalar_bounded of scipy 1.15 restated operation for operation in float64 without contraction (golden section,
+ *      parabolic fit and its three acceptance tests, the tol1 step near a bound, np.sign / np.maximum with their NaN propagation,
+ *      every branch of the three-point bookkeeping, the num >= maxfun exit).  (float)xf is stored;
+ *   6. cost(rho): pu = the pixel (float32) through undistortPoints(cam_K, cam_D, P = cam_K) -- five fixed-point rounds, the result
+ *      rounded to float32; X = ((pu_x - cx) / fx) * rho, Y likewise, Z = rho; Xp = R' (X, Y, Z) + t with Rt = {R' row-major, t};
+ *      perspective divide, Brown distortion proj_D, proj_K; (xp, yp) = truncation toward zero to int32 (not finite or not
+ *      representable: outside); inside iff yp - w > 0 && yp + w < proj_height && xp - w > 0 && xp + w < proj_width; inside:
+ *      sqrt(sum d^2) over the (2w+1)^2 patch in raster order, d = cam'[y+i][x+j] - (double)proj[yp+i][xp+j], the sum accumulated
+ *      as s = fma(d, d, s) from 0 (np.linalg.norm's dot); outside: 100000.
+ * Rt is the caller's: the reference sends the float32-rounded rotation through cv2.Rodrigues and back and adds the float32-rounded
+ * translation (x_maps_amd/esl_optim.py make_rt).  PINNED against the reference's own depth_optimization running on the installed
+ * scipy: the solver, the cost, the truncation, the fill and the bounds (golden G13, bit for bit).  UNPINNED: the three geometry
+ * functions against a real cv2.
+ * Defined, not errors: an all-zero surface and one with hi == lo give zero maps and zero counts.  NaN / +-inf surfaces are out of
+ * contract; they neither fault nor index outside a table.  No kernel has atomics or waits for another block; every loop is bounded
+ * by max_iter.  No xm_handle is involved; an object serves one thread at a time. */
+typedef struct xm_esl_optim xm_esl_optim;
+typedef struct xm_esl_optim_config {
+  uint32_t struct_size; /* sizeof(xm_esl_optim_config) */
+  int32_t cam_width, cam_height;   /* each at least 2 * window_size + 1 */
+  int32_t proj_width, proj_height; /* the reference: 1080 x 1920 */
+  int32_t window_size;             /* 0 = the reference's 3; odd, at most 7 */
+  int32_t max_iter;                /* 0 = scipy's 500; 1 .. 65535 (the solver evaluates at least twice) */
+  int32_t reserved;
+  double xatol;                    /* 0 = scipy's 1e-5; positive and finite */
+  double p1_03;                    /* P1[0, 3] of the rectification; finite and non-zero (a negative one inverts every bound) */
+  double cam_K[9], cam_D[5];       /* row-major K; k1 k2 p1 p2 k3 */
+  double proj_K[9], proj_D[5];
+  double Rt[12];                   /* R' row-major, then t: camera frame -> projector frame */
+  const float* proj_surface;       /* host, [proj_height][proj_width]: get_projector_time_surface (:94-101), unrectified */
+} xm_esl_optim_config;             /* the surface is copied to the device; the caller keeps ownership */
+typedef struct xm_esl_optim_stats {
+  uint64_t n_optimised;  /* pixels minimised                                                                */
+  uint64_t n_evals;      /* cost evaluations over them                                                      */
+  uint64_t n_hit_limit;  /* ... of which left the solver through num >= max_iter                            */
+  uint64_t n_bad_bounds; /* pixels inside the border with d0 > 0 whose bounds scipy would refuse: written 0 */
+  double lo, hi;         /* extrema of the non-zero pixels (0, 0 for an all-zero surface)                   */
+} xm_esl_optim_stats;
+int xm_esl_optim_create(int device, const xm_esl_optim_config* cfg, xm_esl_optim** out);
+void xm_esl_optim_destroy(xm_esl_optim* e);
+/* surfaces: [n_surfaces][cam_height][cam_width], XM_T_FLOAT32 or XM_T_FLOAT64.  depth_init, depth_optim_out: f32, the same shape.
+ * nfev_out (may be NULL): u16, the same shape: the evaluations of each pixel, 0 where none ran.  stats_out (may be NULL):
+ * xm_esl_optim_stats[n_surfaces].  mem == XM_MEM_HOST: every pointer is host memory; XM_MEM_DEVICE: every pointer is device memory
+ * of the object's device -- depth_init may be the buffer xm_esl_init_time_surfaces has just filled.  Synchronous in both.  Scratch
+ * is allocated by the first call and grown when a larger group arrives; a group of any size is accepted.  XM_ERR_INVALID: a dtype
+ * other than the two float types, n_surfaces <= 0. */
+int xm_esl_optim_time_surfaces(xm_esl_optim* e, const void* surfaces, int dtype, int n_surfaces, int mem, const float* depth_init,
+                               float* depth_optim_out, uint16_t* nfev_out, xm_esl_optim_stats* stats_out);
 
 /* ---- MC3D: the other baseline of the reference's evaluation table, on the device -------------------------------------------------
  * What python/eval/mc3d_baseline.py:40-78,129-140 computes, for a GROUP of camera time surfaces in one device call.  With

@@ -16,11 +16,15 @@ Part B -- the accuracy row (eval/x-map-eval.sh:24-72 -> python/eval/compute_dept
 python/eval/create_evaluation_table.py:84-180): every `<scans>/scans_np/*.npy` time surface -> X-maps depth in camera view on
 the evaluation's tables (from_ESL_yaml, rect = 3 x projector, scan downwards) -> `<scans>/x_maps/depth_init/scansNNN.npy`
 (+ point clouds as PLY with --point-clouds), then fill rate / RMSE against `<scans>/esl/depth_optim_filtered/*.npy` -- the
-table's ground truth, which the reference's ESL optimisation writes (out of scope here: without it the depth maps are written and
-the row is reported as not computable) -- next to the published Book-Duck cell, FR 0.91 / RMSE 0.31 cm.  With --esl-init the
+table's ground truth, which the reference's ESL optimisation and its two filters write (the filters are not part of this build:
+without that directory the depth maps are written and the row is reported as not computable) -- next to the published Book-Duck cell, FR 0.91 / RMSE 0.31 cm.  With --esl-init the
 same scans also go through the ESL-init baseline on the device (x_maps_amd/esl_init.py) -> `<scans>/esl/depth_init/scansNNN.npy`
 and the table's "ESL (init)" row is printed beside the X-maps one; with --mc3d they go through the MC3D baseline
-(x_maps_amd/mc3d.py) -> `<scans>/mc3d/depth/scansNNN.npy` and the "MC3D" and "MC3D (1 sec)" rows are printed too.
+(x_maps_amd/mc3d.py) -> `<scans>/mc3d/depth/scansNNN.npy` and the "MC3D" and "MC3D (1 sec)" rows are printed too.  With
+--esl-optim (which implies --esl-init) every group's depth_init stays on the device and goes straight into ESL's depth optimisation
+(x_maps_amd/esl_optim.py) -> `<scans>/esl/depth_optim/scansNNN.npy`, the reference's directory and naming
+(compute_depth_esl.py:236).  `esl/depth_optim_filtered` still needs the bilateral and TV filters behind it: nothing is scored
+without them, and the report says so.
 
 Tables come from the cv2-free builder (x_maps_amd/calibration.py: rectifying rotations pinned to OpenCV's on this calibration,
 map rounding unpinned): a difference from the published numbers on the real data is therefore a finding about that builder or
@@ -210,6 +214,82 @@ def esl_init_from_scans(object_dir, eval_calib, proj_w, proj_h, num_scans=0, sta
             "unpinned": "the int16 rounding of the two remap tables (np.rint) has not been compared with a cv2.remap run"}
 
 
+OPTIM_STATS = np.dtype([("n_optimised", "<u8"), ("n_evals", "<u8"), ("n_hit_limit", "<u8"), ("n_bad_bounds", "<u8"), ("lo", "<f8"),
+                        ("hi", "<f8")])  # xm_esl_optim_stats
+
+
+def esl_optim_from_scans(object_dir, eval_calib, proj_w, proj_h, num_scans=0, start_scan=0, device=0, init_tables=None,
+                         optim_tables=None, group=8):
+    """Part B for the ground truth's solver: compute_depth_esl.py:204-236.  Every scan of <scans>/scans_np through x_maps_amd.esl_init
+    and, chained on the device, x_maps_amd.esl_optim in groups of `group` -> <scans>/esl/depth_init/scansNNN.npy and
+    <scans>/esl/depth_optim/scansNNN.npy (an all-zero scan is skipped, :205).  -> (the ESL-init report, the optimisation's report)"""
+    import torch
+    from x_maps_amd import calibration as C
+    from x_maps_amd.esl_init import EslInit, build_esl_init_tables
+    from x_maps_amd.esl_optim import EslOptim, build_esl_optim_tables
+    names = sorted(glob.glob(os.path.join(object_dir, "scans_np", "*.npy")))
+    if not names:
+        err = {"error": f"no camera files found in {os.path.join(object_dir, 'scans_np')}"}
+        return err, err
+    init_dir, optim_dir = os.path.join(object_dir, "esl", "depth_init"), os.path.join(object_dir, "esl", "depth_optim")
+    os.makedirs(init_dir, exist_ok=True)
+    os.makedirs(optim_dir, exist_ok=True)
+    t0 = time.perf_counter()
+    if init_tables is None or optim_tables is None:
+        cp = C.CamProjCalibrationParams.from_ESL_yaml(eval_calib, 640, 480, proj_w, proj_h)
+        init_tables = build_esl_init_tables(cp) if init_tables is None else init_tables
+        optim_tables = build_esl_optim_tables(cp) if optim_tables is None else optim_tables
+    last = len(names) if not num_scans else min(len(names), start_scan + num_scans)
+    dev = torch.device("cuda", device)
+    per_init, per_optim, skipped, filled_init, filled_optim = [], [], 0, [], []
+    totals = {k: 0 for k in OPTIM_STATS.names[:4]}
+    with EslInit(init_tables, device=device) as esl, EslOptim(optim_tables, device=device) as opt:
+        t_setup = time.perf_counter() - t0
+        for g0 in range(start_scan, last, max(1, group)):
+            loaded = [(i, np.load(names[i])) for i in range(g0, min(last, g0 + max(1, group)))]
+            live = [(i, s) for i, s in loaded if np.count_nonzero(s) > 0]
+            skipped += len(loaded) - len(live)
+            if not live:
+                continue
+            dt = np.float32 if all(s.dtype == np.float32 for _, s in live) else np.float64
+            grp = np.ascontiguousarray(np.stack([s.astype(dt, copy=False) for _, s in live]))
+            n = len(live)
+            d_in = torch.from_numpy(grp).to(dev)
+            d_init = torch.empty(grp.shape, dtype=torch.float32, device=dev)
+            d_optim = torch.empty(grp.shape, dtype=torch.float32, device=dev)
+            d_stats = torch.zeros(n * OPTIM_STATS.itemsize, dtype=torch.uint8, device=dev)
+            torch.cuda.synchronize(dev)
+            c0 = time.perf_counter()
+            esl.time_surfaces_device(d_in.data_ptr(), dt, n, d_init.data_ptr())
+            c1 = time.perf_counter()
+            opt.time_surfaces_device(d_in.data_ptr(), dt, n, d_init.data_ptr(), d_optim.data_ptr(), None, d_stats.data_ptr())
+            c2 = time.perf_counter()
+            init, optim = d_init.cpu().numpy(), d_optim.cpu().numpy()
+            stats = d_stats.cpu().numpy().view(OPTIM_STATS)
+            for k, (i, _) in enumerate(live):
+                np.save(os.path.join(init_dir, "scans" + str(i).zfill(3) + ".npy"), init[k])
+                np.save(os.path.join(optim_dir, "scans" + str(i).zfill(3) + ".npy"), optim[k])
+                per_init.append((c1 - c0) / n)
+                per_optim.append((c2 - c1) / n)
+                filled_init.append(float((init[k] > 0).mean()))
+                filled_optim.append(float((optim[k] > 0).mean()))
+                for key in totals:
+                    totals[key] += int(stats[k][key])
+    mean = lambda v, scale=1.0: round(float(np.mean(v)) * scale, 4) if v else None
+    common = {"scans_found": len(names), "scans_processed": len(per_init), "scans_empty": skipped, "setup_seconds": round(t_setup, 3)}
+    rep_init = dict(common, ms_per_scan_depth_init=mean(per_init, 1e3), mean_fraction_of_pixels_with_depth=mean(filled_init),
+                    paper_esl_init_ms_rtx4090=18.99, depth_dir=init_dir,
+                    unpinned="the int16 rounding of the two remap tables (np.rint) has not been compared with a cv2.remap run")
+    rep_optim = dict(common, ms_per_scan_depth_optim=mean(per_optim, 1e3), mean_fraction_of_pixels_with_depth=mean(filled_optim),
+                     depth_dir=optim_dir, **totals,
+                     evaluations_per_optimised_pixel=round(totals["n_evals"] / totals["n_optimised"], 2) if totals["n_optimised"] else None,
+                     still_needed="esl/depth_optim_filtered, the table's ground truth, is these maps behind cv2.bilateralFilter(., 5, 3, 3) and "
+                                  "the pylops TV denoiser (compute_depth_esl.py:243-247); neither filter is part of this build, so "
+                                  "nothing is scored from them",
+                     unpinned="cv2.undistortPoints, cv2.Rodrigues and cv2.projectPoints have not been compared with a cv2 run")
+    return rep_init, rep_optim
+
+
 def mc3d_from_scans(object_dir, eval_calib, proj_w, proj_h, num_scans=0, start_scan=0, device=0, tables=None, group=8):
     """Part B for the other baseline: mc3d_baseline.py:116-140.  Every scan of <scans>/scans_np through x_maps_amd.mc3d in groups
     of `group` -> <scans>/mc3d/depth/scansNNN.npy (an all-zero scan is skipped, :129).  -> report"""
@@ -270,6 +350,9 @@ def main(argv=None):
     ap.add_argument("--surface-group", type=int, default=8, help="scans per group with --surfaces-on-device")
     ap.add_argument("--esl-init", action="store_true",
                     help="part B: also write <scans>/esl/depth_init/scansNNN.npy (the ESL-init baseline on the device) and print its row")
+    ap.add_argument("--esl-optim", action="store_true",
+                    help="part B: implies --esl-init; also write <scans>/esl/depth_optim/scansNNN.npy (ESL's depth optimisation, chained "
+                         "on the device behind ESL-init; esl/depth_optim_filtered still needs the two filters behind it)")
     ap.add_argument("--mc3d", action="store_true",
                     help="part B: also write <scans>/mc3d/depth/scansNNN.npy (the MC3D baseline on the device) and print its two rows")
     ap.add_argument("--min-depth", type=float, default=20)
@@ -306,9 +389,13 @@ def main(argv=None):
             row = x_maps_table_row(a.scans, a.min_depth, a.max_depth, device=a.device)
             row["published_cell_seq1"] = "{fill_rate} & {rmse_cm}".format(**PUBLISHED["seq1_book_duck"])
             report["table_1_row_x_maps"] = row
-        if a.esl_init:
+        if a.esl_optim:
+            report["esl_init_from_scans"], report["esl_optim_from_scans"] = esl_optim_from_scans(
+                a.scans, a.eval_calib, a.projector_width, a.projector_height, a.num_scans, a.start_scan, a.device, group=a.surface_group)
+        elif a.esl_init:
             report["esl_init_from_scans"] = esl_init_from_scans(a.scans, a.eval_calib, a.projector_width, a.projector_height,
                                                                 a.num_scans, a.start_scan, a.device, group=a.surface_group)
+        if a.esl_init or a.esl_optim:
             if "error" not in report["esl_init_from_scans"]:
                 from x_maps_amd.eval_table import esl_init_table_row
                 report["table_1_row_esl_init"] = esl_init_table_row(a.scans, a.min_depth, a.max_depth, device=a.device)

@@ -158,6 +158,19 @@ class xm_mc3d_config(C.Structure):
                 ("cam_map", C.c_void_p), ("proj_map", C.c_void_p)]
 
 
+class xm_esl_optim_config(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("cam_width", C.c_int32), ("cam_height", C.c_int32),
+                ("proj_width", C.c_int32), ("proj_height", C.c_int32), ("window_size", C.c_int32), ("max_iter", C.c_int32),
+                ("reserved", C.c_int32), ("xatol", C.c_double), ("p1_03", C.c_double),
+                ("cam_K", C.c_double * 9), ("cam_D", C.c_double * 5), ("proj_K", C.c_double * 9), ("proj_D", C.c_double * 5),
+                ("Rt", C.c_double * 12), ("proj_surface", C.c_void_p)]
+
+
+class xm_esl_optim_stats(C.Structure):
+    _fields_ = [("n_optimised", C.c_uint64), ("n_evals", C.c_uint64), ("n_hit_limit", C.c_uint64), ("n_bad_bounds", C.c_uint64),
+                ("lo", C.c_double), ("hi", C.c_double)]
+
+
 class xm_mc3d_stats(C.Structure):
     _fields_ = [("n_nonzero", C.c_uint64), ("n_positive", C.c_uint64), ("n_in_rect", C.c_uint64), ("n_out_of_range", C.c_uint64),
                 ("n_poisoned", C.c_uint64), ("n_matched", C.c_uint64), ("n_disp_overflow", C.c_uint64)]
@@ -271,6 +284,9 @@ SYMBOLS = {
     "xm_esl_init_destroy": (None, [_P]),
     "xm_esl_init_time_surfaces": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "xm_esl_init_stage_disparity": (C.c_int, [_P, _P, _P]),
+    "xm_esl_optim_create": (C.c_int, [C.c_int, C.POINTER(xm_esl_optim_config), C.POINTER(_P)]),
+    "xm_esl_optim_destroy": (None, [_P]),
+    "xm_esl_optim_time_surfaces": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "xm_mc3d_create": (C.c_int, [C.c_int, C.POINTER(xm_mc3d_config), C.POINTER(_P)]),
     "xm_mc3d_destroy": (None, [_P]),
     "xm_mc3d_time_surfaces": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),

@@ -73,3 +73,4 @@ using namespace xm;
 #include "host/xm_api_surface.hpp"  // a group of camera time surfaces -> depth maps + point clouds (the evaluation caller's entry)
 #include "host/xm_api_eslinit.hpp"  // the ESL-init baseline on the same surfaces: depth_init maps, disparity_init alone
 #include "host/xm_api_mc3d.hpp"     // the MC3D baseline on the same surfaces
+#include "host/xm_api_esloptim.hpp" // the ESL depth optimisation behind ESL-init: depth_optim maps

@@ -34,3 +34,4 @@
 #include "xmaps_slots.hpp"      // slot reset, redo preparation
 #include "xmaps_eslinit.hpp"    // the ESL-init baseline: disparity search per rectified / per camera pixel (brings xmaps_surface.hpp)
 #include "xmaps_mc3d.hpp"       // the MC3D baseline: median, projector-column window search and depth per camera pixel
+#include "xmaps_esloptim.hpp"   // the ESL depth optimisation: one bounded scalar minimisation per camera pixel

@@ -3,7 +3,8 @@ to depth_init; create_evaluation_table.py's "ESL (init)" row).  Camera time surf
 by nearest remap, disparity_init's search over the rectified projector time surface, remap back to the camera, P1[0,3] / disparity
 -- in one device call per group of surfaces (xm_esl_init_time_surfaces; kernels in csrc/xmaps_eslinit.hpp).
 
-In scope: this initialisation.  Out of scope: ESL's optimisation behind it (scipy minimize_scalar, bilateral filter, TV denoising).
+In scope: this initialisation.  ESL's optimisation behind it (scipy minimize_scalar) is esl_optim.py; its bilateral filter and TV
+denoising are out of scope.
 The MC3D baseline is mc3d.py.
 
 UNPINNED: the float -> int16 rounding of the two remap tables (mapf_to_i16, np.rint as for every other map of this build) stands

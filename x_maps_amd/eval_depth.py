@@ -14,10 +14,10 @@ before normalising it (the reference normalises a float32 file in float32: the l
 this build's choice), and both give the same depth maps and clouds bit for bit.
 
 The baseline of the same evaluation, ESL-init (compute_depth_esl.py up to depth_init), takes the same surfaces: esl_init.py; so does the
-MC3D baseline (mc3d_baseline.py): mc3d.py.
+MC3D baseline (mc3d_baseline.py): mc3d.py.  ESL's depth optimisation behind ESL-init (depth_optimization): esl_optim.py.
 
-Out of scope: file handling, ESL's optimisation (which produces the table's ground truth), a
-projector-view surface path.  (The metrics of eval/ are in eval_metrics.py.)
+Out of scope: file handling, the bilateral and TV filters behind ESL's optimisation (which turn its maps into the
+table's ground truth), a projector-view surface path.  (The metrics of eval/ are in eval_metrics.py.)
 """
 from __future__ import annotations
 
