@@ -755,8 +755,8 @@ int xm_esl_init_stage_disparity(xm_esl_init* e, const double* cam_rect_host, uin
 /* ---- ESL depth optimisation: the solver behind ESL-init, on the device ----------------------------------------------------------
  * What python/eval/compute_depth_esl.py:104-129 (depth_optimization, with cost_calculator :45-69 and project_and_backproject_punkt
  * :27-42) computes for a GROUP of camera time surfaces and their depth_init maps in one device call: the maps the reference stores
- * as esl/depth_optim.  The bilateral filter and the TV denoiser behind it (:243-244, cv2 / pylops) stay out of scope, and with them
- * esl/depth_optim_filtered.  Per surface s with depth_init d0 (f32, as xm_esl_init_time_surfaces writes it):
+ * as esl/depth_optim.  The bilateral filter and the TV denoiser behind it (:243-244), hence esl/depth_optim_filtered, are
+ * xm_esl_filter_* below, which takes this call's output buffer as it is.  Per surface s with depth_init d0 (f32, as xm_esl_init_time_surfaces writes it):
  *   1. v' = max(((double)v - lo) / (hi - lo), 0) with lo / hi over the non-zero pixels, exactly as xm_esl_init_time_surfaces step 1;
  *   2. f = 1.0 / v'[0][0] (+inf when that is 0, as NumPy); every v' == 0 becomes f (:212).  The image is NOT rectified;
  *   3. pixels y in [ws, cam_height - ws), x in [ws, cam_width - ws) with d0 > 0 are optimised, ws = window_size; every other pixel
@@ -813,6 +813,75 @@ void xm_esl_optim_destroy(xm_esl_optim* e);
  * other than the two float types, n_surfaces <= 0. */
 int xm_esl_optim_time_surfaces(xm_esl_optim* e, const void* surfaces, int dtype, int n_surfaces, int mem, const float* depth_init,
                                float* depth_optim_out, uint16_t* nfev_out, xm_esl_optim_stats* stats_out);
+
+/* ---- ESL ground truth: the bilateral filter and the TV denoiser behind the depth optimisation, on the device ---------------------
+ * What python/eval/compute_depth_esl.py:243-244 computes for a GROUP of depth_optim maps (f32 [n][height][width]) in one device
+ * call: cv2.bilateralFilter(depth_optim, 5, 3, 3), then esl_utilities.py:194-224 denoise_tv(., mu = 0.5) -> the maps the
+ * reference stores as esl/depth_optim_filtered (f64: pylops returns float64).  This text is the contract of both stages;
+ * tests/esl_filter_ref.py states it in NumPy.
+ * Stage 1 (float32 throughout, no contraction; OpenCV's 32F bilateral filter as documented):
+ *   lo / hi = the map's extrema.  hi - lo < FLT_EPSILON: the map is copied.  Otherwise radius = d / 2, and the taps are the (i, j)
+ *   in [-radius, radius]^2 with sqrt(i*i + j*j) <= radius (13 for d = 5) in raster order, the border BORDER_REFLECT_101; space
+ *   weight ws = (float)exp(r*r * -0.5 / sigma_space^2); len = (float)(hi - lo), scale = 4096 / len; colour table of 4098 entries,
+ *   lut[i] = (float)exp(t*t * -0.5 / sigma_color^2) with t = (double)((float)i / scale), taken in float64; per tap a = |v - v0| *
+ *   scale, idx = (int)a, w = ws * (lut[idx] + (a - idx) * (lut[idx + 1] - lut[idx])), sum = sum + v * w, wsum = wsum + w; out =
+ *   sum / wsum.  |v - v0| = len reaches lut[4097].  Where OpenCV's code may differ from this text (UNPINNED):
+ *   its builds take the centre tap first with weight 1 and vectorise the sums with fused multiply-adds, which moves last bits only.
+ * Stage 2 (float64 throughout): split Bregman as pylops 1.18 runs it for Op = Identity and two L1 regularisers, around scipy
+ *   1.15's lsqr.  With N = height * width, the flat index k = row * width + col, and Hs = HEIGHT (the reference hands pylops
+ *   dims = (ny, nx) with nx, ny = y.shape, so the image is differenced as if it were width x height):
+ *     D0 x[k] = x[k] - x[k - Hs] for k >= Hs, else 0;  D1 x[k] = x[k] - x[k - 1] for k % Hs != 0, else 0;
+ *     A = [I; e0 D0; e1 D1], e_i = sqrt(lambda_i / 2) / sqrt(mu / 2);  A v = [v; e0 (D0 v); e1 (D1 v)];
+ *     A'u = (u0 + e0 (D0'u1)) + e1 (D1'u2);
+ *     x = 0, xold = inf, b_i = d_i = 0; while norm(x - xold) > tol and it < niter_outer: xold = x; niter_inner times {
+ *     rhs = [y; e_i (d_i - b_i)] - A x; x = x + lsqr(A, rhs, damp, atol = btol = 1e-6, conlim = 1e8, iter_lim)[0];
+ *     d_i = max(|D_i x + b_i| - lambda_i, 0) * sign(D_i x + b_i) }; b_i = b_i + tau (D_i x - d_i).
+ *   lsqr is scipy's restated operation for operation: _sym_ortho, the damping rotation, the anorm / ddnorm / xnorm / acond
+ *   recurrences, all seven stopping tests in their order, the beta > 0 and alfa > 0 guards and the arnorm == 0 return.  Every
+ *   vector norm is a sum over fixed tiles of pixels in a fixed order: the result of a map depends neither on the group it arrives
+ *   in nor on its neighbours there, and differs from a NumPy run by the summation order alone (about 1e-14 on the maps of the tests;
+ *   the trip counts are equal).
+ * PINNED (golden G14): the reference's own denoise_tv -- its call, the dims swap, every parameter -- on scipy's own lsqr.
+ * UNPINNED: pylops' loop, stacking, stencil and threshold; its float32 operator dtype; cv2's bilateral filter.
+ * Defined, not errors: an all-zero map (lsqr returns x = 0; one outer iteration) and a constant map (two).  NaN / +-inf maps are out
+ * of contract; they neither fault nor index outside a table.  No kernel has atomics or waits for another block; the host issues a
+ * fixed schedule of launches -- 3 + niter_outer * niter_inner * (2 * iter_lim + 4) + 1 for both stages -- and reads nothing back
+ * inside it.  No xm_handle is involved; an object serves one thread at a time. */
+#define XM_ESL_FILTER_NO_BILATERAL 1u /* stage 2 alone: it takes the f32 input cast to f64 */
+#define XM_ESL_FILTER_NO_TV 2u        /* stage 1 alone: filtered_out is its f32 result cast to f64 */
+typedef struct xm_esl_filter xm_esl_filter;
+typedef struct xm_esl_filter_config {
+  uint32_t struct_size;         /* sizeof(xm_esl_filter_config) */
+  int32_t width, height;        /* of a map; width * height at most 2^30 */
+  uint32_t flags;               /* XM_ESL_FILTER_* */
+  int32_t d;                    /* 0 = the reference's 5; 1, 3 or 5 */
+  int32_t niter_outer;          /* 0 = 20; at most 255 */
+  int32_t niter_inner;          /* 0 = 10; at most 255 */
+  int32_t iter_lim;             /* 0 = 5; at most 254 (a trip count is a u8, 0xFF = no call) */
+  double sigma_color, sigma_space; /* 0 = 3, 3; positive */
+  double mu, lambda0, lambda1;  /* 0 = 0.5, 0.1, 0.1; positive */
+  double tol, tau, damp;        /* 0 = 1e-4, 1, 1e-4; non-negative */
+} xm_esl_filter_config;
+typedef struct xm_esl_filter_stats {
+  double lo, hi;            /* extrema of the input map                                           */
+  double final_norm;        /* norm(x - xold) behind the last outer iteration that ran            */
+  uint32_t n_outer;         /* outer iterations run                                               */
+  uint32_t n_lsqr;          /* lsqr calls                                                         */
+  uint32_t sum_itn;         /* ... their iterations                                               */
+  uint32_t reserved;
+  uint32_t istop_count[8];  /* ... by scipy's istop                                               */
+} xm_esl_filter_stats;
+int xm_esl_filter_create(int device, const xm_esl_filter_config* cfg, xm_esl_filter** out);
+void xm_esl_filter_destroy(xm_esl_filter* e);
+/* depth_optim: f32 [n_maps][height][width].  filtered_out: f64, the same shape.  bilateral_out (may be NULL): f32, the same shape,
+ * stage 1's result.  trips_out (may be NULL): u8 [n_maps][niter_outer * niter_inner], lsqr's itn of every inner call in order, 0xFF
+ * where none ran.  stats_out (may be NULL): xm_esl_filter_stats[n_maps].  mem as for xm_esl_optim_time_surfaces: with
+ * XM_MEM_DEVICE depth_optim may be the buffer xm_esl_optim_time_surfaces has just filled.  Synchronous.  Scratch (about 13
+ * float64 per pixel of the group) is allocated by the first call and grown.  At most 65535 maps per call (XM_ERR_TOO_MANY). */
+int xm_esl_filter_maps(xm_esl_filter* e, const float* depth_optim, int n_maps, int mem, double* filtered_out, float* bilateral_out,
+                       uint8_t* trips_out, xm_esl_filter_stats* stats_out);
+/* kernel launches of the object's last call */
+int xm_esl_filter_last_launches(xm_esl_filter* e, uint64_t* out);
 
 /* ---- MC3D: the other baseline of the reference's evaluation table, on the device -------------------------------------------------
  * What python/eval/mc3d_baseline.py:40-78,129-140 computes, for a GROUP of camera time surfaces in one device call.  With

@@ -8,6 +8,7 @@ python/depth_reprojection_pipe.py:65-67,116-117).  Neither is installed here, so
 "unpinned" (DESIGN.md section 5).  Run this ONCE on a machine that has them -- a reference installation:
 
     python tools/pin_thirdparty.py            # writes tests/golden/g9_cv2.npz and / or tests/golden/g10_metavision.npz
+                                              # and / or tests/golden/g14_esl_filter_thirdparty.npz (cv2 and / or pylops)
 
 and commit the files.  tests/test_thirdparty_pins.py skips while they are absent and, once they exist, compares the oracle
 (CPU tests) AND the HIP path (-m gpu tests) with them.  The script imports numpy, cv2 and metavision_* only -- never a file of
@@ -92,6 +93,47 @@ def pin_cv2():
     path = os.path.join(GOLDEN, "g9_cv2.npz")
     np.savez_compressed(path, **out)
     print(f"wrote {path} ({os.path.getsize(path) / 1e6:.2f} MB, OpenCV {cv2.__version__})")
+
+
+# ---- the ESL filters: cv2.bilateralFilter and pylops' SplitBregman ----------------------------------------------------------------
+def pin_esl_filters():
+    """Both filters' outputs on the inputs of golden G14 (tests/golden/g14_esl_filter.npz: seeded depth_optim maps), as
+    python/eval/compute_depth_esl.py:243-244 and esl_utilities.py:194-224 call them -- restated here, arguments and dims swap
+    included.  Whichever of cv2 / pylops is installed is recorded; tests/test_esl_filter_ref_cpu.py compares the restatement with
+    the file once it exists."""
+    have = {}
+    try:
+        import cv2
+        have["cv2"] = cv2
+    except ImportError as e:
+        print(f"esl filters: cv2 not installed here ({e})")
+    try:
+        import pylops
+        have["pylops"] = pylops
+    except ImportError as e:
+        print(f"esl filters: pylops not installed here ({e})")
+    if not have:
+        raise ImportError("neither cv2 nor pylops")
+    g = np.load(os.path.join(GOLDEN, "g14_esl_filter.npz"))
+    out = {}
+    for name in ("a", "b", "c"):
+        img = g[f"{name}_input"]
+        if "cv2" in have:
+            out["cv2_version"] = np.array(have["cv2"].__version__)
+            out[f"{name}_cv2_bilateral"] = have["cv2"].bilateralFilter(img, 5, 3, 3)
+        if "pylops" in have:
+            pl = have["pylops"]
+            out["pylops_version"] = np.array(pl.__version__)
+            y = g[f"{name}_bilateral"]  # (the restatement's stage 1, so the two filters are pinned apart)
+            nx, ny = y.shape
+            Dop = [pl.FirstDerivative(ny * nx, dims=(ny, nx), dir=0, edge=False, kind="backward", dtype=np.float32),
+                   pl.FirstDerivative(ny * nx, dims=(ny, nx), dir=1, edge=False, kind="backward", dtype=np.float32)]
+            xinv, niter = pl.optimization.sparsity.SplitBregman(pl.Identity(nx * ny), Dop, y.flatten(), 20, 10, mu=0.5, epsRL1s=[0.1, 0.1],
+                                                                tol=1e-4, tau=1.0, show=False, **dict(iter_lim=5, damp=1e-4))
+            out[f"{name}_pylops_tv"], out[f"{name}_pylops_niter"] = xinv.reshape(y.shape), np.array(niter)
+    path = os.path.join(GOLDEN, "g14_esl_filter_thirdparty.npz")
+    np.savez_compressed(path, **out)
+    print(f"wrote {path} ({os.path.getsize(path) / 1e6:.2f} MB, {sorted(have)})")
 
 
 # ---- Metavision -------------------------------------------------------------------------------------------------------------
@@ -213,7 +255,7 @@ def pin_metavision():
 
 def main():
     done = 0
-    for name, fn in (("cv2", pin_cv2), ("metavision", pin_metavision)):
+    for name, fn in (("cv2", pin_cv2), ("metavision", pin_metavision), ("esl filters", pin_esl_filters)):
         try:
             fn()
             done += 1

@@ -24,7 +24,9 @@ and the table's "ESL (init)" row is printed beside the X-maps one; with --mc3d t
 --esl-optim (which implies --esl-init) every group's depth_init stays on the device and goes straight into ESL's depth optimisation
 (x_maps_amd/esl_optim.py) -> `<scans>/esl/depth_optim/scansNNN.npy`, the reference's directory and naming
 (compute_depth_esl.py:236).  `esl/depth_optim_filtered` still needs the bilateral and TV filters behind it: nothing is scored
-without them, and the report says so.
+without them, and the report says so.  With --esl-filter (which implies --esl-optim) the optimisation's device buffer goes on
+through both filters (x_maps_amd/esl_filter.py) -> `<scans>/esl/depth_optim_filtered/scansNNN.npy` (:247), and every row is then
+scored against it.
 
 Tables come from the cv2-free builder (x_maps_amd/calibration.py: rectifying rotations pinned to OpenCV's on this calibration,
 map rounding unpinned): a difference from the published numbers on the real data is therefore a finding about that builder or
@@ -33,6 +35,7 @@ build's own encoder writes; with the real files present (XM_ESL_DATA=/ESL_data/s
 from __future__ import annotations
 
 import argparse
+import contextlib
 import glob
 import json
 import os
@@ -214,26 +217,34 @@ def esl_init_from_scans(object_dir, eval_calib, proj_w, proj_h, num_scans=0, sta
             "unpinned": "the int16 rounding of the two remap tables (np.rint) has not been compared with a cv2.remap run"}
 
 
+FILTER_STATS = np.dtype([("lo", "<f8"), ("hi", "<f8"), ("final_norm", "<f8"), ("n_outer", "<u4"), ("n_lsqr", "<u4"), ("sum_itn", "<u4"),
+                         ("reserved", "<u4"), ("istop_count", "<u4", (8,))])  # xm_esl_filter_stats
 OPTIM_STATS = np.dtype([("n_optimised", "<u8"), ("n_evals", "<u8"), ("n_hit_limit", "<u8"), ("n_bad_bounds", "<u8"), ("lo", "<f8"),
                         ("hi", "<f8")])  # xm_esl_optim_stats
 
 
 def esl_optim_from_scans(object_dir, eval_calib, proj_w, proj_h, num_scans=0, start_scan=0, device=0, init_tables=None,
-                         optim_tables=None, group=8):
+                         optim_tables=None, group=8, esl_filter=False):
     """Part B for the ground truth's solver: compute_depth_esl.py:204-236.  Every scan of <scans>/scans_np through x_maps_amd.esl_init
     and, chained on the device, x_maps_amd.esl_optim in groups of `group` -> <scans>/esl/depth_init/scansNNN.npy and
-    <scans>/esl/depth_optim/scansNNN.npy (an all-zero scan is skipped, :205).  -> (the ESL-init report, the optimisation's report)"""
+    <scans>/esl/depth_optim/scansNNN.npy (an all-zero scan is skipped, :205).  esl_filter: the optimisation's device buffer goes on
+    into x_maps_amd.esl_filter (:243-247) -> <scans>/esl/depth_optim_filtered/scansNNN.npy, the table's ground truth.
+    -> (the ESL-init report, the optimisation's report[, the filters' report])"""
     import torch
     from x_maps_amd import calibration as C
     from x_maps_amd.esl_init import EslInit, build_esl_init_tables
     from x_maps_amd.esl_optim import EslOptim, build_esl_optim_tables
+    from x_maps_amd.esl_filter import EslFilter
     names = sorted(glob.glob(os.path.join(object_dir, "scans_np", "*.npy")))
     if not names:
         err = {"error": f"no camera files found in {os.path.join(object_dir, 'scans_np')}"}
-        return err, err
+        return (err, err, err) if esl_filter else (err, err)
     init_dir, optim_dir = os.path.join(object_dir, "esl", "depth_init"), os.path.join(object_dir, "esl", "depth_optim")
     os.makedirs(init_dir, exist_ok=True)
     os.makedirs(optim_dir, exist_ok=True)
+    filtered_dir = os.path.join(object_dir, "esl", "depth_optim_filtered")
+    if esl_filter:
+        os.makedirs(filtered_dir, exist_ok=True)
     t0 = time.perf_counter()
     if init_tables is None or optim_tables is None:
         cp = C.CamProjCalibrationParams.from_ESL_yaml(eval_calib, 640, 480, proj_w, proj_h)
@@ -243,7 +254,10 @@ def esl_optim_from_scans(object_dir, eval_calib, proj_w, proj_h, num_scans=0, st
     dev = torch.device("cuda", device)
     per_init, per_optim, skipped, filled_init, filled_optim = [], [], 0, [], []
     totals = {k: 0 for k in OPTIM_STATS.names[:4]}
-    with EslInit(init_tables, device=device) as esl, EslOptim(optim_tables, device=device) as opt:
+    per_filter, outer, trips = [], [], []
+    with contextlib.ExitStack() as stack:
+        esl, opt = stack.enter_context(EslInit(init_tables, device=device)), stack.enter_context(EslOptim(optim_tables, device=device))
+        flt = stack.enter_context(EslFilter(opt.cam_w, opt.cam_h, device=device)) if esl_filter else None
         t_setup = time.perf_counter() - t0
         for g0 in range(start_scan, last, max(1, group)):
             loaded = [(i, np.load(names[i])) for i in range(g0, min(last, g0 + max(1, group)))]
@@ -264,11 +278,23 @@ def esl_optim_from_scans(object_dir, eval_calib, proj_w, proj_h, num_scans=0, st
             c1 = time.perf_counter()
             opt.time_surfaces_device(d_in.data_ptr(), dt, n, d_init.data_ptr(), d_optim.data_ptr(), None, d_stats.data_ptr())
             c2 = time.perf_counter()
+            if flt is not None:
+                d_filtered = torch.empty(grp.shape, dtype=torch.float64, device=dev)
+                d_fstats = torch.zeros(n * FILTER_STATS.itemsize, dtype=torch.uint8, device=dev)
+                torch.cuda.synchronize(dev)
+                flt.maps_device(d_optim.data_ptr(), n, d_filtered.data_ptr(), None, None, d_fstats.data_ptr())
+                c3 = time.perf_counter()
+                filtered, fstats = d_filtered.cpu().numpy(), d_fstats.cpu().numpy().view(FILTER_STATS)
             init, optim = d_init.cpu().numpy(), d_optim.cpu().numpy()
             stats = d_stats.cpu().numpy().view(OPTIM_STATS)
             for k, (i, _) in enumerate(live):
                 np.save(os.path.join(init_dir, "scans" + str(i).zfill(3) + ".npy"), init[k])
                 np.save(os.path.join(optim_dir, "scans" + str(i).zfill(3) + ".npy"), optim[k])
+                if flt is not None:
+                    np.save(os.path.join(filtered_dir, "scans" + str(i).zfill(3) + ".npy"), filtered[k])
+                    per_filter.append((c3 - c2) / n)
+                    outer.append(int(fstats[k]["n_outer"]))
+                    trips.append(int(fstats[k]["sum_itn"]))
                 per_init.append((c1 - c0) / n)
                 per_optim.append((c2 - c1) / n)
                 filled_init.append(float((init[k] > 0).mean()))
@@ -287,7 +313,14 @@ def esl_optim_from_scans(object_dir, eval_calib, proj_w, proj_h, num_scans=0, st
                                   "the pylops TV denoiser (compute_depth_esl.py:243-247); neither filter is part of this build, so "
                                   "nothing is scored from them",
                      unpinned="cv2.undistortPoints, cv2.Rodrigues and cv2.projectPoints have not been compared with a cv2 run")
-    return rep_init, rep_optim
+    if not esl_filter:
+        return rep_init, rep_optim
+    del rep_optim["still_needed"]
+    rep_filter = dict(common, ms_per_scan_filters=mean(per_filter, 1e3), mean_outer_iterations=mean(outer), mean_lsqr_iterations=mean(trips),
+                      depth_dir=filtered_dir,
+                      unpinned="cv2.bilateralFilter and pylops' SplitBregman (its loop, stacking, stencil, threshold and float32 operator "
+                               "dtype) have not been compared with a cv2 / pylops run; scipy's lsqr and the reference's call are pinned")
+    return rep_init, rep_optim, rep_filter
 
 
 def mc3d_from_scans(object_dir, eval_calib, proj_w, proj_h, num_scans=0, start_scan=0, device=0, tables=None, group=8):
@@ -353,6 +386,9 @@ def main(argv=None):
     ap.add_argument("--esl-optim", action="store_true",
                     help="part B: implies --esl-init; also write <scans>/esl/depth_optim/scansNNN.npy (ESL's depth optimisation, chained "
                          "on the device behind ESL-init; esl/depth_optim_filtered still needs the two filters behind it)")
+    ap.add_argument("--esl-filter", action="store_true",
+                    help="part B: implies --esl-optim; also write <scans>/esl/depth_optim_filtered/scansNNN.npy (the bilateral filter and "
+                         "the TV denoiser, chained on the device behind the optimisation): the ground truth every row is scored against")
     ap.add_argument("--mc3d", action="store_true",
                     help="part B: also write <scans>/mc3d/depth/scansNNN.npy (the MC3D baseline on the device) and print its two rows")
     ap.add_argument("--min-depth", type=float, default=20)
@@ -389,13 +425,21 @@ def main(argv=None):
             row = x_maps_table_row(a.scans, a.min_depth, a.max_depth, device=a.device)
             row["published_cell_seq1"] = "{fill_rate} & {rmse_cm}".format(**PUBLISHED["seq1_book_duck"])
             report["table_1_row_x_maps"] = row
-        if a.esl_optim:
+        if a.esl_filter:
+            report["esl_init_from_scans"], report["esl_optim_from_scans"], report["esl_filter_from_scans"] = esl_optim_from_scans(
+                a.scans, a.eval_calib, a.projector_width, a.projector_height, a.num_scans, a.start_scan, a.device, group=a.surface_group,
+                esl_filter=True)
+            if "table_1_row_x_maps" in report:  # (the ground truth exists only now)
+                row = x_maps_table_row(a.scans, a.min_depth, a.max_depth, device=a.device)
+                row["published_cell_seq1"] = "{fill_rate} & {rmse_cm}".format(**PUBLISHED["seq1_book_duck"])
+                report["table_1_row_x_maps"] = row
+        elif a.esl_optim:
             report["esl_init_from_scans"], report["esl_optim_from_scans"] = esl_optim_from_scans(
                 a.scans, a.eval_calib, a.projector_width, a.projector_height, a.num_scans, a.start_scan, a.device, group=a.surface_group)
         elif a.esl_init:
             report["esl_init_from_scans"] = esl_init_from_scans(a.scans, a.eval_calib, a.projector_width, a.projector_height,
                                                                 a.num_scans, a.start_scan, a.device, group=a.surface_group)
-        if a.esl_init or a.esl_optim:
+        if a.esl_init or a.esl_optim or a.esl_filter:
             if "error" not in report["esl_init_from_scans"]:
                 from x_maps_amd.eval_table import esl_init_table_row
                 report["table_1_row_esl_init"] = esl_init_table_row(a.scans, a.min_depth, a.max_depth, device=a.device)

@@ -171,6 +171,21 @@ class xm_esl_optim_stats(C.Structure):
                 ("lo", C.c_double), ("hi", C.c_double)]
 
 
+XM_ESL_FILTER_NO_BILATERAL, XM_ESL_FILTER_NO_TV = 1, 2
+
+
+class xm_esl_filter_config(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32), ("flags", C.c_uint32), ("d", C.c_int32),
+                ("niter_outer", C.c_int32), ("niter_inner", C.c_int32), ("iter_lim", C.c_int32),
+                ("sigma_color", C.c_double), ("sigma_space", C.c_double), ("mu", C.c_double), ("lambda0", C.c_double),
+                ("lambda1", C.c_double), ("tol", C.c_double), ("tau", C.c_double), ("damp", C.c_double)]
+
+
+class xm_esl_filter_stats(C.Structure):
+    _fields_ = [("lo", C.c_double), ("hi", C.c_double), ("final_norm", C.c_double), ("n_outer", C.c_uint32), ("n_lsqr", C.c_uint32),
+                ("sum_itn", C.c_uint32), ("reserved", C.c_uint32), ("istop_count", C.c_uint32 * 8)]
+
+
 class xm_mc3d_stats(C.Structure):
     _fields_ = [("n_nonzero", C.c_uint64), ("n_positive", C.c_uint64), ("n_in_rect", C.c_uint64), ("n_out_of_range", C.c_uint64),
                 ("n_poisoned", C.c_uint64), ("n_matched", C.c_uint64), ("n_disp_overflow", C.c_uint64)]
@@ -287,6 +302,10 @@ SYMBOLS = {
     "xm_esl_optim_create": (C.c_int, [C.c_int, C.POINTER(xm_esl_optim_config), C.POINTER(_P)]),
     "xm_esl_optim_destroy": (None, [_P]),
     "xm_esl_optim_time_surfaces": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "xm_esl_filter_create": (C.c_int, [C.c_int, C.POINTER(xm_esl_filter_config), C.POINTER(_P)]),
+    "xm_esl_filter_destroy": (None, [_P]),
+    "xm_esl_filter_maps": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "xm_esl_filter_last_launches": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "xm_mc3d_create": (C.c_int, [C.c_int, C.POINTER(xm_mc3d_config), C.POINTER(_P)]),
     "xm_mc3d_destroy": (None, [_P]),
     "xm_mc3d_time_surfaces": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),

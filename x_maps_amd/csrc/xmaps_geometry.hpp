@@ -78,6 +78,13 @@ constexpr unsigned MC3D_UN = XM_MC3D_UN;  // ... window entries a lane has in fl
 // ... its int32 maps: MC3D_POISON marks a NaN / +-inf entry, finite entries saturate at +-MC3D_SAT (== XM_MC3D_POISON, xmaps.h)
 constexpr int MC3D_POISON = -2147483647 - 1, MC3D_SAT = 1 << 30;
 constexpr unsigned MC3D_NO_BLUR = 1;  // == XM_MC3D_NO_BLUR
+
+// ESL filters (xmaps_eslfilter.hpp).  Bilateral filter: a block takes ESLF_BW x ESLF_BH pixels with a halo of ESLF_HALO (d <= 5);
+// ESLF_BINS colour-table bins (+ 2 entries); extrema: ESLF_RED_CHUNK pixels per block.  TV denoiser: a surface's flat vector is cut
+// into tiles of ESLF_TILE pixels -- the unit of every partial sum, so it fixes the summation order: results move with it.
+constexpr int ESLF_BW = 32, ESLF_BH = BLOCK / ESLF_BW, ESLF_HALO = 2, ESLF_MAX_TAPS = 25, ESLF_BINS = 4096;
+constexpr int ESLF_RED_CHUNK = BLOCK * 8, ESLF_TILE = BLOCK * 4;
+constexpr unsigned ESLF_NO_BILATERAL = 1, ESLF_NO_TV = 2;  // == XM_ESL_FILTER_*
 // ... its search key: 1 + (min(cost, max_row_diff + 1) << pos_bits | position in a window of `span` entries), 0 = poison, in 32 bits
 XM_HD constexpr unsigned mc3d_pos_bits(unsigned span) {
   unsigned b = 0;

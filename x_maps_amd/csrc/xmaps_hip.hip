@@ -74,3 +74,4 @@ using namespace xm;
 #include "host/xm_api_eslinit.hpp"  // the ESL-init baseline on the same surfaces: depth_init maps, disparity_init alone
 #include "host/xm_api_mc3d.hpp"     // the MC3D baseline on the same surfaces
 #include "host/xm_api_esloptim.hpp" // the ESL depth optimisation behind ESL-init: depth_optim maps
+#include "host/xm_api_eslfilter.hpp" // the bilateral filter and the TV denoiser behind it: depth_optim_filtered maps

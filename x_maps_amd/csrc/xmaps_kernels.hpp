@@ -35,3 +35,4 @@
 #include "xmaps_eslinit.hpp"    // the ESL-init baseline: disparity search per rectified / per camera pixel (brings xmaps_surface.hpp)
 #include "xmaps_mc3d.hpp"       // the MC3D baseline: median, projector-column window search and depth per camera pixel
 #include "xmaps_esloptim.hpp"   // the ESL depth optimisation: one bounded scalar minimisation per camera pixel
+#include "xmaps_eslfilter.hpp"  // the ESL filters behind it: bilateral filter and TV denoiser (split Bregman around lsqr)

@@ -5,8 +5,8 @@ minimisation (scipy's minimize_scalar(method="bounded"), restated) of the patch 
 projector's at the pixel's projection -- in one device call per group of surfaces (xm_esl_optim_time_surfaces; kernels in
 csrc/xmaps_esloptim.hpp).
 
-In scope: this solver.  Out of scope: the bilateral filter and the TV denoiser behind it (:243-244, cv2.bilateralFilter and
-pylops), hence esl/depth_optim_filtered, the evaluation's ground truth.
+In scope: this solver.  The bilateral filter and the TV denoiser behind it (:243-244), hence esl/depth_optim_filtered, the
+evaluation's ground truth: x_maps_amd/esl_filter.py, which takes this module's device buffer as it is.
 
 PINNED against the reference's own depth_optimization on the installed scipy (golden G13): the solver, the cost with its truncation
 and patch norm, the fill and the bounds.  UNPINNED: undistortPoints, Rodrigues and projectPoints against a real cv2 (DESIGN.md

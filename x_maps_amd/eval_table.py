@@ -9,8 +9,9 @@ reference's evaluation leaves it:
     <seq>/esl/depth_optim/scansNNN.npy     ESL's optimised depth before its filters (x_maps_amd.esl_optim /
                                            tools/run_esl_on_arrival.py --esl-optim)
     <seq>/esl/depth_optim_filtered/*.npy   the same behind cv2.bilateralFilter and the pylops TV denoiser = the table's ground
-                                           truth (compute_depth_esl.py:243-247; the two filters are not part of this build: when
-                                           the directory is absent the row cannot be computed and the caller says so)
+                                           truth (compute_depth_esl.py:243-247; x_maps_amd.esl_filter /
+                                           tools/run_esl_on_arrival.py --esl-filter; when the directory is absent the row cannot
+                                           be computed and the caller says so)
 
 The metrics themselves run on the GPU (x_maps_amd.eval_metrics, pinned by golden G8); what is restated here is the file-level
 recipe: the per-pixel mean of the filtered ground-truth scans, median-filtered 3 x 3 (cv2.medianBlur: unpinned against a cv2
@@ -76,7 +77,7 @@ def depth_table_row(seq_dir: str, est_subdir, files_key: str, min_depth: float =
     if not gt_files:
         return {"error": f"no ground truth under {os.path.join(seq_dir, 'esl', 'depth_optim_filtered')} (the reference's "
                          f"compute_depth_esl.py writes it: esl/depth_optim, which x_maps_amd.esl_optim computes, behind the bilateral "
-                         f"and TV filters, which are left)", files_key: len(est_files)}
+                         f"and TV filters: x_maps_amd.esl_filter, tools/run_esl_on_arrival.py --esl-filter)", files_key: len(est_files)}
     if len(gt_files) != len(est_files):
         return {"error": "frames are missing", "gt_files": len(gt_files), files_key: len(est_files)}
     gt_combined, _, avg_depth = combine_depth_maps(gt_files, min_depth, max_depth)
