@@ -27,6 +27,8 @@ for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")):
     if p not in sys.path:
         sys.path.insert(0, p)
 
+from _timing import clock_state, cycle, timed  # noqa: E402
+
 N_DISTINCT = 8
 W, H = 640, 480
 
@@ -38,7 +40,6 @@ def main(argv=None):
     ap.add_argument("--groups", type=int, nargs="+", default=[8, 32])
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
-    from esl_optim_time import clock_state, timed
     clocks = clock_state()
     import torch
     if not torch.cuda.is_available():
@@ -55,7 +56,7 @@ def main(argv=None):
     dev = torch.device("cuda", a.device)
     with EslFilter(W, H, device=a.device) as flt, EslFilter(W, H, device=a.device, flags=NO_TV) as bil:
         for n in a.groups:
-            grp = np.ascontiguousarray(np.stack([base[i % N_DISTINCT] for i in range(n)]))
+            grp = cycle(base, n)
             d_in = torch.from_numpy(grp).to(dev)
             d_out = torch.empty(grp.shape, dtype=torch.float64, device=dev)
             torch.cuda.synchronize(dev)
@@ -65,14 +66,14 @@ def main(argv=None):
             launches = flt.last_launches()
             assert np.array_equal(d_out.cpu().numpy().view(np.uint64), np.stack([o[0] for o in out]).view(np.uint64))
             ev1 = timed(lambda: bil.maps_device(d_in.data_ptr(), n, d_out.data_ptr()), a.repeats, warmup=2)
-            host = timed(lambda: flt.filter_maps(grp), max(3, a.repeats // 3), warmup=1)
+            host = timed(lambda: flt.filter_maps(grp), max(3, a.repeats // 3), warmup=1).host
             res["groups"][str(n)] = {
-                "ms_per_call_device_resident": round(ev[0], 3), "ms_per_surface_device_resident": round(ev[0] / n, 4),
-                "min_max_ms_per_call": [round(ev[1], 3), round(ev[2], 3)], "ms_per_call_host_clock": round(ev[3], 3),
-                "ms_per_surface_from_host_memory": round(host[3] / n, 4), "launches_per_call": launches,
-                "us_per_launch": round(ev[0] * 1e3 / launches, 2),
-                "ms_per_call_stage_1_alone": round(ev1[0], 4), "stage_1_launches": bil.last_launches(),
-                "stage_1_share_percent": round(100.0 * ev1[0] / ev[0], 2),
+                "ms_per_call_device_resident": round(ev.ev, 3), "ms_per_surface_device_resident": round(ev.ev / n, 4),
+                "min_max_ms_per_call": [round(ev.ev_min, 3), round(ev.ev_max, 3)], "ms_per_call_host_clock": round(ev.host, 3),
+                "ms_per_surface_from_host_memory": round(host / n, 4), "launches_per_call": launches,
+                "us_per_launch": round(ev.ev * 1e3 / launches, 2),
+                "ms_per_call_stage_1_alone": round(ev1.ev, 4), "stage_1_launches": bil.last_launches(),
+                "stage_1_share_percent": round(100.0 * ev1.ev / ev.ev, 2),
                 "outer_iterations_per_surface": round(float(np.mean([s.n_outer for s in st])), 2),
                 "lsqr_calls_per_surface": round(float(np.mean([s.n_lsqr for s in st])), 1),
                 "lsqr_iterations_per_surface": round(float(np.mean([s.sum_itn for s in st])), 1),

@@ -18,52 +18,19 @@ from __future__ import annotations
 import argparse
 import json
 import os
-import subprocess
 import sys
 import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "tests")):
+for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")):
     if p not in sys.path:
         sys.path.insert(0, p)
 
+from _timing import clock_state, cycle, render_surfaces, timed  # noqa: E402
+
 PAPER_MS = 18.99  # X-maps paper, Table 2: ESL-init in the authors' CUDA on an RTX 4090
-
-
-def clock_state() -> str:
-    """what the box says about its clocks (read-only query); 'unknown' when the tool is not there"""
-    try:
-        r = subprocess.run(["rocm-smi", "--showclocks", "--showperflevel"], capture_output=True, text=True, timeout=30)
-        lines = [" ".join(ln.split()) for ln in r.stdout.splitlines() if "GPU[0]" in ln and ("sclk" in ln or "mclk" in ln or "Performance" in ln)]
-        return "; ".join(lines) if lines else "unknown (no clock lines in the query's output)"
-    except Exception as e:  # noqa: BLE001
-        return f"unknown ({type(e).__name__})"
-
-
-def median_ms(fn, repeats, warmup=3):
-    for _ in range(warmup):
-        fn()
-    ts = []
-    for _ in range(repeats):
-        t0 = time.perf_counter()
-        fn()
-        ts.append((time.perf_counter() - t0) * 1e3)
-    ts = np.array(ts)
-    return float(np.median(ts)), float(ts.min()), float(ts.max())
-
-
-def render_surfaces(cp, tables, n_distinct, n):
-    """n float32 time surfaces (microsecond stamps, 0 = no event), n_distinct of them different renderings"""
-    from x_maps_amd import rig
-    base = []
-    for k in range(n_distinct):
-        evs, _ = rig.render_events(cp, tables, row_stride=3, scan_upwards=False, seed=k)
-        s = np.zeros((cp.camera_height, cp.camera_width), np.float32)
-        s[evs["y"], evs["x"]] = (evs["t"] - evs["t"].min() + 1).astype(np.float32)  # (the last event of a pixel stays)
-        base.append(s)
-    return np.ascontiguousarray(np.stack([base[i % n_distinct] for i in range(n)]))
 
 
 def walked(surface, t):
@@ -106,7 +73,7 @@ def main(argv=None):
     t = build_esl_init_tables(cp)
     t_tables = time.perf_counter() - t0
     n_max = max(a.groups)
-    surfaces = render_surfaces(cp, t, min(8, n_max), n_max)
+    surfaces = cycle(render_surfaces(cp, t, min(8, n_max)), n_max)
     px = cp.camera_width * cp.camera_height
     res = {"geometry": {"camera": [640, 480], "projector": [1080, 1920], "rectified": [3240, 5760]},
            "surfaces": "rendered from rig.py's ESL-like stand-in (float32 microsecond stamps); NOT the ESL recordings",
@@ -123,29 +90,29 @@ def main(argv=None):
             d_in = torch.from_numpy(grp).cuda(a.device)
             d_depth = torch.empty(grp.shape, dtype=torch.float32, device=d_in.device)
             torch.cuda.synchronize()
-            dev = median_ms(lambda: esl.time_surfaces_device(d_in.data_ptr(), np.float32, n, d_depth.data_ptr()), a.repeats)
-            host = median_ms(lambda: esl.depths_from_time_surfaces(grp), a.repeats)
+            dev = timed(lambda: esl.time_surfaces_device(d_in.data_ptr(), np.float32, n, d_depth.data_ptr()), a.repeats)
+            host = timed(lambda: esl.depths_from_time_surfaces(grp), a.repeats).host
             assert np.array_equal(d_depth.cpu().numpy(), np.stack([o[0] for o in out]))
             # bytes: the surface is read by the extrema pass and gathered (px * 4 each), the back map (px * 4), one forward-map
             # entry and one window per searched pixel, the depth map out
             compulsory = n * (px * 4 * 2 + px * 4 + px * 4) + searched * 4
             res["fused"][str(n)] = {
-                "ms_per_call_device_resident": round(dev[0], 4), "ms_per_surface_device_resident": round(dev[0] / n, 4),
-                "min_max_ms_per_call": [round(dev[1], 4), round(dev[2], 4)],
-                "ms_per_surface_from_host_memory": round(host[0] / n, 4),
+                "ms_per_call_device_resident": round(dev.host, 4), "ms_per_surface_device_resident": round(dev.host / n, 4),
+                "min_max_ms_per_call": [round(dev.host_min, 4), round(dev.host_max, 4)],
+                "ms_per_surface_from_host_memory": round(host / n, 4),
                 "pixels_searched_per_surface": searched // n, "matched_per_surface": sum(st.n_matched for _, _, st in out) // n,
                 "candidate_evaluations_per_surface": entries // n,
-                "candidate_evaluations_per_second": round(entries / (dev[0] * 1e-3), 0),
+                "candidate_evaluations_per_second": round(entries / (dev.host * 1e-3), 0),
                 "bytes_requested_by_the_windows": entries * 4, "bytes_tables_surfaces_and_outputs": compulsory}
         # the stage entry: one rectified frame
         v, _ = R.normalise(surfaces[0])
         cam_rect = R.remap_nearest_i16(v, t["cam_to_rect_map"])
-        st_ms = median_ms(lambda: esl.disparity_init(cam_rect), max(3, a.repeats // 4), warmup=1)
+        st_ms = timed(lambda: esl.disparity_init(cam_rect), max(3, a.repeats // 4), warmup=1).host
         disp = esl.disparity_init(cam_rect)
         live = cam_rect > 0
         cols = np.nonzero(live)[1]
         st_entries = int(np.clip(np.minimum(cols + 900, 3240) - (cols + 5), 0, None).sum())
-        res["stage"] = {"ms_per_frame_with_its_host_copies": round(st_ms[0], 3), "bytes_copied_in": cam_rect.nbytes, "bytes_copied_out": disp.nbytes,
+        res["stage"] = {"ms_per_frame_with_its_host_copies": round(st_ms, 3), "bytes_copied_in": cam_rect.nbytes, "bytes_copied_out": disp.nbytes,
                         "pixels_searched": int(live.sum()), "matched": int(np.count_nonzero(disp)), "candidate_evaluations": st_entries}
         # NumPy restatement on a crop (6 rows around the busiest one)
         r0 = int(np.argmax(live.sum(1)))
@@ -164,8 +131,8 @@ def main(argv=None):
         with XMapsEngine(tb, camera_perspective=True, device=a.device) as eng:
             for n in a.groups:
                 grp = surfaces[:n]
-                ms = median_ms(lambda: eng.process_time_surfaces(grp), a.repeats)
-                res["x_maps"][str(n)] = {"ms_per_surface_from_host_memory": round(ms[0] / n, 4)}
+                ms = timed(lambda: eng.process_time_surfaces(grp), a.repeats).host
+                res["x_maps"][str(n)] = {"ms_per_surface_from_host_memory": round(ms / n, 4)}
     txt = json.dumps(res, indent=1)
     print(txt)
     if a.md:

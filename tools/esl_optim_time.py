@@ -19,60 +19,20 @@ from __future__ import annotations
 import argparse
 import json
 import os
-import subprocess
 import sys
 import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "tests")):
+for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")):
     if p not in sys.path:
         sys.path.insert(0, p)
 
+from _timing import clock_state, cycle, render_surfaces, timed  # noqa: E402
+
 N_DISTINCT = 8
 N_SAMPLE = 48
-
-
-def clock_state() -> str:
-    """what the box says about its clocks (read-only query); 'unknown' when the tool is not there"""
-    try:
-        r = subprocess.run(["rocm-smi", "--showclocks", "--showperflevel"], capture_output=True, text=True, timeout=30)
-        lines = [" ".join(ln.split()) for ln in r.stdout.splitlines() if "GPU[0]" in ln and ("sclk" in ln or "mclk" in ln or "Performance" in ln)]
-        return "; ".join(lines) if lines else "unknown (no clock lines in the query's output)"
-    except Exception as e:  # noqa: BLE001
-        return f"unknown ({type(e).__name__})"
-
-
-def timed(fn, repeats, warmup=3):
-    """-> (median, min, max) ms between device events, median ms by the host clock; fn ends in a device synchronise"""
-    import torch
-    for _ in range(warmup):
-        fn()
-    ev, host = [], []
-    for _ in range(repeats):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        t0 = time.perf_counter()
-        fn()
-        host.append((time.perf_counter() - t0) * 1e3)
-        b.record()
-        b.synchronize()
-        ev.append(a.elapsed_time(b))
-    ev = np.array(ev)
-    return float(np.median(ev)), float(ev.min()), float(ev.max()), float(np.median(host))
-
-
-def render_surfaces(cp, tables, n_distinct):
-    """float32 time surfaces (microsecond stamps, 0 = no event) as tools/esl_init_time.py renders them"""
-    from x_maps_amd import rig
-    base = []
-    for k in range(n_distinct):
-        evs, _ = rig.render_events(cp, tables, row_stride=3, scan_upwards=False, seed=k)
-        s = np.zeros((cp.camera_height, cp.camera_width), np.float32)
-        s[evs["y"], evs["x"]] = (evs["t"] - evs["t"].min() + 1).astype(np.float32)  # (the last event of a pixel stays)
-        base.append(s)
-    return base
 
 
 def main(argv=None):
@@ -108,7 +68,7 @@ def main(argv=None):
     dev = torch.device("cuda", a.device)
     with EslInit(t_init, device=a.device) as esl, EslOptim(t_opt, device=a.device) as opt:
         for n in a.groups:
-            grp = np.ascontiguousarray(np.stack([base[i % N_DISTINCT] for i in range(n)]))
+            grp = cycle(base, n)
             d_in = torch.from_numpy(grp).to(dev)
             d_init = torch.empty(grp.shape, dtype=torch.float32, device=dev)
             d_out = torch.empty(grp.shape, dtype=torch.float32, device=dev)
@@ -120,17 +80,17 @@ def main(argv=None):
             n_opt, n_ev = sum(s.n_optimised for s in st), sum(s.n_evals for s in st)
             call = lambda: opt.time_surfaces_device(d_in.data_ptr(), np.float32, n, d_init.data_ptr(), d_out.data_ptr())
             ev = timed(call, a.repeats)
-            host = timed(lambda: opt.depths_from_time_surfaces(grp, init), max(3, a.repeats // 4), warmup=1)
+            host = timed(lambda: opt.depths_from_time_surfaces(grp, init), max(3, a.repeats // 4), warmup=1).host
             assert np.array_equal(d_out.cpu().numpy().view(np.uint32), np.stack([o[0] for o in out]).view(np.uint32))
             nfev0 = out[0][1]
             res["groups"][str(n)] = {
-                "ms_per_call_device_resident": round(ev[0], 4), "ms_per_surface_device_resident": round(ev[0] / n, 4),
-                "min_max_ms_per_call": [round(ev[1], 4), round(ev[2], 4)], "ms_per_call_host_clock": round(ev[3], 4),
-                "ms_per_surface_from_host_memory": round(host[3] / n, 4),
+                "ms_per_call_device_resident": round(ev.ev, 4), "ms_per_surface_device_resident": round(ev.ev / n, 4),
+                "min_max_ms_per_call": [round(ev.ev_min, 4), round(ev.ev_max, 4)], "ms_per_call_host_clock": round(ev.host, 4),
+                "ms_per_surface_from_host_memory": round(host / n, 4),
                 "depth_init_pixels_per_surface": int(np.count_nonzero(init > 0)) // n, "optimised_per_surface": n_opt // n,
                 "evaluations_per_optimised_pixel": round(n_ev / max(n_opt, 1), 2), "max_evaluations_of_a_pixel": int(max(o[1].max() for o in out)),
                 "n_hit_limit": sum(s.n_hit_limit for s in st), "n_bad_bounds": sum(s.n_bad_bounds for s in st),
-                "evaluations_per_second": round(n_ev / (ev[0] * 1e-3), 0),
+                "evaluations_per_second": round(n_ev / (ev.ev * 1e-3), 0),
                 "bytes_surfaces_depths_in_and_out": n * px * 4 * 4}
         # a sample of the first surface's optimised pixels against the scalar restatement
         cam, _ = R.normalise_and_fill(base[0])

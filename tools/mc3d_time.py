@@ -28,36 +28,16 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "tests")):
+for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")):
     if p not in sys.path:
         sys.path.insert(0, p)
+
+from _timing import clock_state, cycle, timed  # noqa: E402
 
 HBM_BYTES_PER_S = 6.29e12  # measured streaming rate of an MI355X (float4 copy)
 L2_BYTES_PER_S = 34.5e12   # aggregate L2 rate of its eight XCDs
 N_DISTINCT = 8
 TRIED = "## What was tried\n"
-
-
-def clock_state() -> str:
-    """what the box says about its clocks (read-only query); 'unknown' when the tool is not there"""
-    try:
-        r = subprocess.run(["rocm-smi", "--showclocks", "--showperflevel"], capture_output=True, text=True, timeout=30)
-        lines = [" ".join(ln.split()) for ln in r.stdout.splitlines() if "GPU[0]" in ln and ("sclk" in ln or "mclk" in ln or "Performance" in ln)]
-        return "; ".join(lines) if lines else "unknown (no clock lines in the query's output)"
-    except Exception as e:  # noqa: BLE001
-        return f"unknown ({type(e).__name__})"
-
-
-def median_ms(fn, repeats, warmup=3):
-    for _ in range(warmup):
-        fn()
-    ts = []
-    for _ in range(repeats):
-        t0 = time.perf_counter()
-        fn()
-        ts.append((time.perf_counter() - t0) * 1e3)
-    ts = np.array(ts)
-    return float(np.median(ts)), float(ts.min()), float(ts.max())
 
 
 def make_inputs(path):
@@ -103,7 +83,7 @@ def step(inputs, n, repeats, device):
     d = np.load(inputs)
     cam_map, proj_map, p1_03 = d["cam_map"], d["proj_map"], float(d["p1_03"])
     base = d["surfaces"]
-    grp = np.ascontiguousarray(np.stack([base[i % len(base)] for i in range(n)]))
+    grp = cycle(base, n)
     per = [walked(s, cam_map) for s in base[:min(n, len(base))]]
     searched = sum(per[i % len(per)][0] for i in range(n))
     entries = sum(per[i % len(per)][1] for i in range(n))
@@ -121,23 +101,23 @@ def step(inputs, n, repeats, device):
         d_in = torch.from_numpy(grp).cuda(device)
         d_depth = torch.empty(grp.shape, dtype=torch.float32, device=d_in.device)
         torch.cuda.synchronize()
-        dev = median_ms(lambda: mc.time_surfaces_device(d_in.data_ptr(), np.float32, n, d_depth.data_ptr()), repeats)
-        host = median_ms(lambda: mc.depths_from_time_surfaces(grp), repeats)
+        dev = timed(lambda: mc.time_surfaces_device(d_in.data_ptr(), np.float32, n, d_depth.data_ptr()), repeats)
+        host = timed(lambda: mc.depths_from_time_surfaces(grp), repeats).host
         assert np.array_equal(d_depth.cpu().numpy(), np.stack([o[0] for o in out]))
     px = 640 * 480
     positive = sum(st.n_positive for _, _, st in out)
     # bytes that must move per group: every surface in, every depth map out, a camera entry per positive pixel; the projector
     # table (8.3 MB of yp, read many times over) once
     compulsory = n * px * 4 * 2 + positive * 8 + 1080 * 1920 * 4
-    res = {"n": n, "ms_per_call_device_resident": round(dev[0], 4), "ms_per_surface_device_resident": round(dev[0] / n, 4),
-           "min_max_ms_per_call": [round(dev[1], 4), round(dev[2], 4)], "ms_per_surface_from_host_memory": round(host[0] / n, 4),
+    res = {"n": n, "ms_per_call_device_resident": round(dev.host, 4), "ms_per_surface_device_resident": round(dev.host / n, 4),
+           "min_max_ms_per_call": [round(dev.host_min, 4), round(dev.host_max, 4)], "ms_per_surface_from_host_memory": round(host / n, 4),
            "lit_per_surface": int(sum((s != 0).sum() for s in grp)) // n, "positive_after_blur_per_surface": positive // n,
            "pixels_searched_per_surface": searched // n, "matched_per_surface": sum(st.n_matched for _, _, st in out) // n,
            "poisoned_per_surface": sum(st.n_poisoned for _, _, st in out) // n,
-           "window_entries_per_surface": entries // n, "window_entries_per_second": round(entries / (dev[0] * 1e-3), 0),
-           "window_bytes_per_second_over_L2_rate": round(entries * 4 / (dev[0] * 1e-3) / L2_BYTES_PER_S, 4),
+           "window_entries_per_surface": entries // n, "window_entries_per_second": round(entries / (dev.host * 1e-3), 0),
+           "window_bytes_per_second_over_L2_rate": round(entries * 4 / (dev.host * 1e-3) / L2_BYTES_PER_S, 4),
            "compulsory_bytes_per_group": compulsory,
-           "hbm_roofline_share": round(compulsory / HBM_BYTES_PER_S / (dev[0] * 1e-3), 4),
+           "hbm_roofline_share": round(compulsory / HBM_BYTES_PER_S / (dev.host * 1e-3), 4),
            "band_checked_against_restatement": [r0 + 1, r0 + 7]}
     print("MC3D_STEP " + json.dumps(res), flush=True)
 

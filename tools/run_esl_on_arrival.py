@@ -128,9 +128,9 @@ def depth_from_scans(object_dir, eval_calib, proj_w, proj_h, num_scans=0, start_
     from x_maps_amd.cam_proj_calibration import CamProjMaps
     from x_maps_amd.eval_depth import compute_depth_from_time_surface, compute_depths_from_time_surfaces
     from x_maps_amd.x_maps_disparity import XMapsDisparity
-    names = sorted(glob.glob(os.path.join(object_dir, "scans_np", "*.npy")))
-    if not names:
-        return {"error": f"no camera files found in {os.path.join(object_dir, 'scans_np')}"}
+    names, err = scan_files(object_dir)
+    if err:
+        return err
     depth_dir = os.path.join(object_dir, "x_maps", "depth_init")
     cloud_dir = os.path.join(object_dir, "x_maps", "pointcloud_init")
     os.makedirs(depth_dir, exist_ok=True)
@@ -143,18 +143,16 @@ def depth_from_scans(object_dir, eval_calib, proj_w, proj_h, num_scans=0, start_
     maps = CamProjMaps(tables, camera_perspective=True, device=device)
     xd = XMapsDisparity(maps)
     t_setup = time.perf_counter() - t0
-    last = len(names) if not num_scans else min(len(names), start_scan + num_scans)
     per, skipped, filled = [], 0, []
     def results():
         if not surfaces_on_device:
-            for i in range(start_scan, last):
+            for (i,) in scan_groups(names, start_scan, num_scans, 1):
                 surf = np.load(names[i])
                 c0 = time.perf_counter()
                 depth, cloud = compute_depth_from_time_surface(maps, xd, surf, want_point_cloud=point_clouds)
                 yield i, depth, cloud, time.perf_counter() - c0
             return
-        for g0 in range(start_scan, last, max(1, group)):
-            idx = range(g0, min(last, g0 + max(1, group)))
+        for idx in scan_groups(names, start_scan, num_scans, group):
             surfs = [np.load(names[i]) for i in idx]
             c0 = time.perf_counter()
             out = compute_depths_from_time_surfaces(maps, surfs, want_point_cloud=point_clouds)
@@ -168,16 +166,70 @@ def depth_from_scans(object_dir, eval_calib, proj_w, proj_h, num_scans=0, start_
                 skipped += 1
                 continue
             per.append(seconds)
-            np.save(os.path.join(depth_dir, "scans" + str(i).zfill(3) + ".npy"), depth)
+            np.save(os.path.join(depth_dir, scan_name(i)), depth)
             filled.append(float((depth > 0).mean()))
             if point_clouds:
                 write_ply(os.path.join(cloud_dir, "scans" + str(i).zfill(3) + ".ply"), cloud)
     finally:
         maps.engine.close()
-    return {"scans_found": len(names), "scans_processed": len(per), "scans_empty": skipped, "setup_seconds": round(t_setup, 3),
-            "ms_per_scan_disparity_to_depth": round(float(np.mean(per)) * 1e3, 4) if per else None,
-            "mean_fraction_of_pixels_with_depth": round(float(np.mean(filled)), 4) if filled else None,
-            "reference_published_ms_per_frame": PUBLISHED["ms_per_frame"], "depth_dir": depth_dir}
+    return dict(common_keys(names, len(per), skipped, t_setup), ms_per_scan_disparity_to_depth=mean(per, 1e3),
+                mean_fraction_of_pixels_with_depth=mean(filled), reference_published_ms_per_frame=PUBLISHED["ms_per_frame"],
+                depth_dir=depth_dir)
+
+
+def scan_files(object_dir):
+    """-> (the sorted scans of <object_dir>/scans_np, None), or ([], the report that says there are none)"""
+    names = sorted(glob.glob(os.path.join(object_dir, "scans_np", "*.npy")))
+    return names, None if names else {"error": f"no camera files found in {os.path.join(object_dir, 'scans_np')}"}
+
+
+def scan_groups(names, start_scan, num_scans, group):
+    """the scans start_scan .. start_scan + num_scans (0 = to the end) in index ranges of at most `group`"""
+    last = len(names) if not num_scans else min(len(names), start_scan + num_scans)
+    for g0 in range(start_scan, last, max(1, group)):
+        yield range(g0, min(last, g0 + max(1, group)))
+
+
+def scan_name(i):
+    return "scans" + str(i).zfill(3) + ".npy"
+
+
+def mean(v, scale=1.0):
+    return round(float(np.mean(v)) * scale, 4) if v else None
+
+
+def common_keys(names, processed, skipped, t_setup):
+    return {"scans_found": len(names), "scans_processed": processed, "scans_empty": skipped, "setup_seconds": round(t_setup, 3)}
+
+
+def baseline_from_scans(object_dir, depth_dir, make_object, num_scans, start_scan, group, ms_key, unpinned, **more):
+    """What ESL-init and MC3D do alike: every scan of <scans>/scans_np through make_object()'s depths_from_time_surfaces in groups
+    of `group` -> depth_dir/scansNNN.npy (an all-zero scan is skipped).  -> report: the common keys, ms_key, the fill, `more`, depth_dir, unpinned"""
+    names, err = scan_files(object_dir)
+    if err:
+        return err
+    os.makedirs(depth_dir, exist_ok=True)
+    t0 = time.perf_counter()
+    per, skipped, filled = [], 0, []
+    with make_object() as obj:
+        t_setup = time.perf_counter() - t0
+        for idx in scan_groups(names, start_scan, num_scans, group):
+            surfs = [np.load(names[i]) for i in idx]
+            c0 = time.perf_counter()
+            out = obj.depths_from_time_surfaces(surfs)
+            dt = (time.perf_counter() - c0) / len(idx)
+            for i, (depth, _, st) in zip(idx, out):
+                if st.n_nonzero == 0:
+                    skipped += 1
+                    continue
+                per.append(dt)
+                np.save(os.path.join(depth_dir, scan_name(i)), depth)
+                filled.append(float((depth > 0).mean()))
+    return dict(common_keys(names, len(per), skipped, t_setup), **{ms_key: mean(per, 1e3)}, mean_fraction_of_pixels_with_depth=mean(filled),
+                **more, depth_dir=depth_dir, unpinned=unpinned)
+
+
+ESL_INIT_UNPINNED = "the int16 rounding of the two remap tables (np.rint) has not been compared with a cv2.remap run"
 
 
 def esl_init_from_scans(object_dir, eval_calib, proj_w, proj_h, num_scans=0, start_scan=0, device=0, tables=None, group=8):
@@ -185,42 +237,14 @@ def esl_init_from_scans(object_dir, eval_calib, proj_w, proj_h, num_scans=0, sta
     x_maps_amd.esl_init in groups of `group` -> <scans>/esl/depth_init/scansNNN.npy (an all-zero scan is skipped, :205).  -> report"""
     from x_maps_amd import calibration as C
     from x_maps_amd.esl_init import EslInit, build_esl_init_tables
-    names = sorted(glob.glob(os.path.join(object_dir, "scans_np", "*.npy")))
-    if not names:
-        return {"error": f"no camera files found in {os.path.join(object_dir, 'scans_np')}"}
     depth_dir = os.path.join(object_dir, "esl", "depth_init")
-    os.makedirs(depth_dir, exist_ok=True)
-    t0 = time.perf_counter()
-    if tables is None:
-        tables = build_esl_init_tables(C.CamProjCalibrationParams.from_ESL_yaml(eval_calib, 640, 480, proj_w, proj_h))
-    last = len(names) if not num_scans else min(len(names), start_scan + num_scans)
-    per, skipped, filled = [], 0, []
-    with EslInit(tables, device=device) as esl:
-        t_setup = time.perf_counter() - t0
-        for g0 in range(start_scan, last, max(1, group)):
-            idx = range(g0, min(last, g0 + max(1, group)))
-            surfs = [np.load(names[i]) for i in idx]
-            c0 = time.perf_counter()
-            out = esl.depths_from_time_surfaces(surfs)
-            dt = (time.perf_counter() - c0) / len(idx)
-            for i, (depth, _, st) in zip(idx, out):
-                if st.n_nonzero == 0:
-                    skipped += 1
-                    continue
-                per.append(dt)
-                np.save(os.path.join(depth_dir, "scans" + str(i).zfill(3) + ".npy"), depth)
-                filled.append(float((depth > 0).mean()))
-    return {"scans_found": len(names), "scans_processed": len(per), "scans_empty": skipped, "setup_seconds": round(t_setup, 3),
-            "ms_per_scan_depth_init": round(float(np.mean(per)) * 1e3, 4) if per else None,
-            "mean_fraction_of_pixels_with_depth": round(float(np.mean(filled)), 4) if filled else None,
-            "paper_esl_init_ms_rtx4090": 18.99, "depth_dir": depth_dir,
-            "unpinned": "the int16 rounding of the two remap tables (np.rint) has not been compared with a cv2.remap run"}
 
+    def make():
+        t = build_esl_init_tables(C.CamProjCalibrationParams.from_ESL_yaml(eval_calib, 640, 480, proj_w, proj_h)) if tables is None else tables
+        return EslInit(t, device=device)
 
-FILTER_STATS = np.dtype([("lo", "<f8"), ("hi", "<f8"), ("final_norm", "<f8"), ("n_outer", "<u4"), ("n_lsqr", "<u4"), ("sum_itn", "<u4"),
-                         ("reserved", "<u4"), ("istop_count", "<u4", (8,))])  # xm_esl_filter_stats
-OPTIM_STATS = np.dtype([("n_optimised", "<u8"), ("n_evals", "<u8"), ("n_hit_limit", "<u8"), ("n_bad_bounds", "<u8"), ("lo", "<f8"),
-                        ("hi", "<f8")])  # xm_esl_optim_stats
+    return baseline_from_scans(object_dir, depth_dir, make, num_scans, start_scan, group, "ms_per_scan_depth_init",
+                               ESL_INIT_UNPINNED, paper_esl_init_ms_rtx4090=18.99)
 
 
 def esl_optim_from_scans(object_dir, eval_calib, proj_w, proj_h, num_scans=0, start_scan=0, device=0, init_tables=None,
@@ -231,13 +255,15 @@ def esl_optim_from_scans(object_dir, eval_calib, proj_w, proj_h, num_scans=0, st
     into x_maps_amd.esl_filter (:243-247) -> <scans>/esl/depth_optim_filtered/scansNNN.npy, the table's ground truth.
     -> (the ESL-init report, the optimisation's report[, the filters' report])"""
     import torch
+    from x_maps_amd import _native as N
     from x_maps_amd import calibration as C
+    from x_maps_amd._group import stats_dtype, surface_group
     from x_maps_amd.esl_init import EslInit, build_esl_init_tables
     from x_maps_amd.esl_optim import EslOptim, build_esl_optim_tables
     from x_maps_amd.esl_filter import EslFilter
-    names = sorted(glob.glob(os.path.join(object_dir, "scans_np", "*.npy")))
-    if not names:
-        err = {"error": f"no camera files found in {os.path.join(object_dir, 'scans_np')}"}
+    optim_stats, filter_stats = stats_dtype(N.xm_esl_optim_stats), stats_dtype(N.xm_esl_filter_stats)
+    names, err = scan_files(object_dir)
+    if err:
         return (err, err, err) if esl_filter else (err, err)
     init_dir, optim_dir = os.path.join(object_dir, "esl", "depth_init"), os.path.join(object_dir, "esl", "depth_optim")
     os.makedirs(init_dir, exist_ok=True)
@@ -250,28 +276,26 @@ def esl_optim_from_scans(object_dir, eval_calib, proj_w, proj_h, num_scans=0, st
         cp = C.CamProjCalibrationParams.from_ESL_yaml(eval_calib, 640, 480, proj_w, proj_h)
         init_tables = build_esl_init_tables(cp) if init_tables is None else init_tables
         optim_tables = build_esl_optim_tables(cp) if optim_tables is None else optim_tables
-    last = len(names) if not num_scans else min(len(names), start_scan + num_scans)
     dev = torch.device("cuda", device)
     per_init, per_optim, skipped, filled_init, filled_optim = [], [], 0, [], []
-    totals = {k: 0 for k in OPTIM_STATS.names[:4]}
+    totals = {k: 0 for k in optim_stats.names[:4]}
     per_filter, outer, trips = [], [], []
     with contextlib.ExitStack() as stack:
         esl, opt = stack.enter_context(EslInit(init_tables, device=device)), stack.enter_context(EslOptim(optim_tables, device=device))
         flt = stack.enter_context(EslFilter(opt.cam_w, opt.cam_h, device=device)) if esl_filter else None
         t_setup = time.perf_counter() - t0
-        for g0 in range(start_scan, last, max(1, group)):
-            loaded = [(i, np.load(names[i])) for i in range(g0, min(last, g0 + max(1, group)))]
+        for idx in scan_groups(names, start_scan, num_scans, group):
+            loaded = [(i, np.load(names[i])) for i in idx]
             live = [(i, s) for i, s in loaded if np.count_nonzero(s) > 0]
             skipped += len(loaded) - len(live)
             if not live:
                 continue
-            dt = np.float32 if all(s.dtype == np.float32 for _, s in live) else np.float64
-            grp = np.ascontiguousarray(np.stack([s.astype(dt, copy=False) for _, s in live]))
-            n = len(live)
+            grp = surface_group([s for _, s in live], opt.cam_h, opt.cam_w)
+            n, dt = len(live), grp.dtype
             d_in = torch.from_numpy(grp).to(dev)
             d_init = torch.empty(grp.shape, dtype=torch.float32, device=dev)
             d_optim = torch.empty(grp.shape, dtype=torch.float32, device=dev)
-            d_stats = torch.zeros(n * OPTIM_STATS.itemsize, dtype=torch.uint8, device=dev)
+            d_stats = torch.zeros(n * optim_stats.itemsize, dtype=torch.uint8, device=dev)
             torch.cuda.synchronize(dev)
             c0 = time.perf_counter()
             esl.time_surfaces_device(d_in.data_ptr(), dt, n, d_init.data_ptr())
@@ -280,18 +304,18 @@ def esl_optim_from_scans(object_dir, eval_calib, proj_w, proj_h, num_scans=0, st
             c2 = time.perf_counter()
             if flt is not None:
                 d_filtered = torch.empty(grp.shape, dtype=torch.float64, device=dev)
-                d_fstats = torch.zeros(n * FILTER_STATS.itemsize, dtype=torch.uint8, device=dev)
+                d_fstats = torch.zeros(n * filter_stats.itemsize, dtype=torch.uint8, device=dev)
                 torch.cuda.synchronize(dev)
                 flt.maps_device(d_optim.data_ptr(), n, d_filtered.data_ptr(), None, None, d_fstats.data_ptr())
                 c3 = time.perf_counter()
-                filtered, fstats = d_filtered.cpu().numpy(), d_fstats.cpu().numpy().view(FILTER_STATS)
+                filtered, fstats = d_filtered.cpu().numpy(), d_fstats.cpu().numpy().view(filter_stats)
             init, optim = d_init.cpu().numpy(), d_optim.cpu().numpy()
-            stats = d_stats.cpu().numpy().view(OPTIM_STATS)
+            stats = d_stats.cpu().numpy().view(optim_stats)
             for k, (i, _) in enumerate(live):
-                np.save(os.path.join(init_dir, "scans" + str(i).zfill(3) + ".npy"), init[k])
-                np.save(os.path.join(optim_dir, "scans" + str(i).zfill(3) + ".npy"), optim[k])
+                np.save(os.path.join(init_dir, scan_name(i)), init[k])
+                np.save(os.path.join(optim_dir, scan_name(i)), optim[k])
                 if flt is not None:
-                    np.save(os.path.join(filtered_dir, "scans" + str(i).zfill(3) + ".npy"), filtered[k])
+                    np.save(os.path.join(filtered_dir, scan_name(i)), filtered[k])
                     per_filter.append((c3 - c2) / n)
                     outer.append(int(fstats[k]["n_outer"]))
                     trips.append(int(fstats[k]["sum_itn"]))
@@ -301,11 +325,9 @@ def esl_optim_from_scans(object_dir, eval_calib, proj_w, proj_h, num_scans=0, st
                 filled_optim.append(float((optim[k] > 0).mean()))
                 for key in totals:
                     totals[key] += int(stats[k][key])
-    mean = lambda v, scale=1.0: round(float(np.mean(v)) * scale, 4) if v else None
-    common = {"scans_found": len(names), "scans_processed": len(per_init), "scans_empty": skipped, "setup_seconds": round(t_setup, 3)}
+    common = common_keys(names, len(per_init), skipped, t_setup)
     rep_init = dict(common, ms_per_scan_depth_init=mean(per_init, 1e3), mean_fraction_of_pixels_with_depth=mean(filled_init),
-                    paper_esl_init_ms_rtx4090=18.99, depth_dir=init_dir,
-                    unpinned="the int16 rounding of the two remap tables (np.rint) has not been compared with a cv2.remap run")
+                    paper_esl_init_ms_rtx4090=18.99, depth_dir=init_dir, unpinned=ESL_INIT_UNPINNED)
     rep_optim = dict(common, ms_per_scan_depth_optim=mean(per_optim, 1e3), mean_fraction_of_pixels_with_depth=mean(filled_optim),
                      depth_dir=optim_dir, **totals,
                      evaluations_per_optimised_pixel=round(totals["n_evals"] / totals["n_optimised"], 2) if totals["n_optimised"] else None,
@@ -328,35 +350,14 @@ def mc3d_from_scans(object_dir, eval_calib, proj_w, proj_h, num_scans=0, start_s
     of `group` -> <scans>/mc3d/depth/scansNNN.npy (an all-zero scan is skipped, :129).  -> report"""
     from x_maps_amd import calibration as C
     from x_maps_amd.mc3d import Mc3d, build_mc3d_tables
-    names = sorted(glob.glob(os.path.join(object_dir, "scans_np", "*.npy")))
-    if not names:
-        return {"error": f"no camera files found in {os.path.join(object_dir, 'scans_np')}"}
     depth_dir = os.path.join(object_dir, "mc3d", "depth")
-    os.makedirs(depth_dir, exist_ok=True)
-    t0 = time.perf_counter()
-    if tables is None:
-        tables = build_mc3d_tables(C.CamProjCalibrationParams.from_ESL_yaml(eval_calib, 640, 480, proj_w, proj_h))
-    last = len(names) if not num_scans else min(len(names), start_scan + num_scans)
-    per, skipped, filled = [], 0, []
-    with Mc3d(tables, device=device) as mc:
-        t_setup = time.perf_counter() - t0
-        for g0 in range(start_scan, last, max(1, group)):
-            idx = range(g0, min(last, g0 + max(1, group)))
-            surfs = [np.load(names[i]) for i in idx]
-            c0 = time.perf_counter()
-            out = mc.depths_from_time_surfaces(surfs)
-            dt = (time.perf_counter() - c0) / len(idx)
-            for i, (depth, _, st) in zip(idx, out):
-                if st.n_nonzero == 0:
-                    skipped += 1
-                    continue
-                per.append(dt)
-                np.save(os.path.join(depth_dir, "scans" + str(i).zfill(3) + ".npy"), depth)
-                filled.append(float((depth > 0).mean()))
-    return {"scans_found": len(names), "scans_processed": len(per), "scans_empty": skipped, "setup_seconds": round(t_setup, 3),
-            "ms_per_scan_depth": round(float(np.mean(per)) * 1e3, 4) if per else None,
-            "mean_fraction_of_pixels_with_depth": round(float(np.mean(filled)), 4) if filled else None, "depth_dir": depth_dir,
-            "unpinned": "cv2.medianBlur(., 3) and the float maps of cv2.undistortPoints have not been compared with a cv2 run"}
+
+    def make():
+        t = build_mc3d_tables(C.CamProjCalibrationParams.from_ESL_yaml(eval_calib, 640, 480, proj_w, proj_h)) if tables is None else tables
+        return Mc3d(t, device=device)
+
+    return baseline_from_scans(object_dir, depth_dir, make, num_scans, start_scan, group, "ms_per_scan_depth",
+                               "cv2.medianBlur(., 3) and the float maps of cv2.undistortPoints have not been compared with a cv2 run")
 
 
 def main(argv=None):

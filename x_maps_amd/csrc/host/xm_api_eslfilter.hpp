@@ -7,9 +7,7 @@ static_assert(sizeof(xm_esl_filter_stats) == sizeof(EslfStats), "xm_esl_filter_s
 static_assert(XM_ESL_FILTER_NO_BILATERAL == ESLF_NO_BILATERAL && XM_ESL_FILTER_NO_TV == ESLF_NO_TV, "xmaps.h and xmaps_geometry.hpp");
 static_assert(ESLF_BW * ESLF_BH == BLOCK && ESLF_TILE % BLOCK == 0, "one pixel per lane; whole passes per tile");
 
-struct xm_esl_filter {
-  int device = 0;
-  Stream stream;  // (before the buffers: released after them)
+struct xm_esl_filter : GroupObj {
   int W = 0, H = 0;
   u32 flags = 0, niter_outer = 0, niter_inner = 0;
   double color_coeff = 0.0;
@@ -22,17 +20,10 @@ struct xm_esl_filter {
 
 extern "C" {
 
-void xm_esl_filter_destroy(xm_esl_filter* e) {
-  if (!e) return;
-  (void)hipSetDevice(e->device);
-  if (e->stream) (void)hipStreamSynchronize(e->stream);
-  delete e;
-}
+void xm_esl_filter_destroy(xm_esl_filter* e) { group_destroy(e); }
 
 int xm_esl_filter_create(int device, const xm_esl_filter_config* cfg, xm_esl_filter** out) {
-  if (!cfg || !out) return fail(XM_ERR_INVALID, "NULL argument");
-  *out = nullptr;
-  if (cfg->struct_size != sizeof(xm_esl_filter_config)) return fail(XM_ERR_INVALID, "xm_esl_filter_config.struct_size mismatch");
+  if (int rc = group_create_args(cfg, out, "xm_esl_filter_config")) return rc;
   if (cfg->width <= 0 || cfg->height <= 0) return fail(XM_ERR_INVALID, "dimensions must be positive");
   if ((u64)cfg->width * (u64)cfg->height > (1ull << 30)) return fail(XM_ERR_INVALID, "map too large");
   if (cfg->flags & ~(XM_ESL_FILTER_NO_BILATERAL | XM_ESL_FILTER_NO_TV)) return fail(XM_ERR_INVALID, "unknown flag");
@@ -48,14 +39,9 @@ int xm_esl_filter_create(int device, const xm_esl_filter_config* cfg, xm_esl_fil
   const double pos[] = {sc, ss, mu, l0, l1, tol, tau, damp};
   for (double v : pos)
     if (!(v > 0.0) || !std::isfinite(v)) return fail(XM_ERR_INVALID, "sigmas, mu, lambdas, tol, tau and damp must be positive and finite");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(XM_ERR_HIP, "no HIP device visible");
-  if (device < 0 || device >= ndev) return fail(XM_ERR_INVALID, "no device %d", device);
-  HIP_TRY(hipSetDevice(device));
-  Owned<xm_esl_filter, xm_esl_filter_destroy> e(new (std::nothrow) xm_esl_filter);
-  if (!e) return fail(XM_ERR_NOMEM, "out of host memory");
-  e->device = device;
-  HIP_TRY(e->stream.create());
+  Owned<xm_esl_filter, xm_esl_filter_destroy> e;
+  if (int rc = group_open(device, e)) return rc;
+  e->noun = "maps", e->px = (size_t)cfg->width * cfg->height, e->total_log2 = 36;
   e->W = cfg->width, e->H = cfg->height, e->flags = cfg->flags, e->niter_outer = (u32)n_out, e->niter_inner = (u32)n_in;
   e->color_coeff = -0.5 / (sc * sc);
   const int radius = d / 2;
@@ -87,41 +73,32 @@ int xm_esl_filter_last_launches(xm_esl_filter* e, uint64_t* out) {
 
 int xm_esl_filter_maps(xm_esl_filter* e, const float* depth_optim, int n_maps, int mem, double* filtered_out, float* bilateral_out,
                        uint8_t* trips_out, xm_esl_filter_stats* stats_out) {
-  if (!e) return fail(XM_ERR_INVALID, "NULL object");
-  if (n_maps <= 0) return fail(XM_ERR_INVALID, "n_maps must be positive");
-  if (n_maps > 65535) return fail(XM_ERR_TOO_MANY, "group too large (at most 65535 maps per call)");
-  if (mem != XM_MEM_HOST && mem != XM_MEM_DEVICE) return fail(XM_ERR_INVALID, "mem must be XM_MEM_HOST or XM_MEM_DEVICE");
+  if (int rc = group_enter(e, n_maps, mem)) return rc;
   if (!depth_optim || !filtered_out) return fail(XM_ERR_INVALID, "NULL argument");
-  HIP_TRY(hipSetDevice(e->device));
-  const size_t n = (size_t)n_maps, px = (size_t)e->W * e->H, total = n * px;
-  if (total >= (1ull << 36)) return fail(XM_ERR_TOO_MANY, "group too large");
-  const bool host = mem == XM_MEM_HOST, do_bil = !(e->flags & XM_ESL_FILTER_NO_BILATERAL), do_tv = !(e->flags & XM_ESL_FILTER_NO_TV);
+  const size_t n = (size_t)n_maps, px = e->px, total = n * px;
+  const bool do_bil = !(e->flags & XM_ESL_FILTER_NO_BILATERAL), do_tv = !(e->flags & XM_ESL_FILTER_NO_TV);
   const u32 nb_red = grid_for(px, ESLF_RED_CHUNK), nb_lut = grid_for(ESLF_BINS + 2, BLOCK);
   const u32 tiles_x = grid_for(e->W, ESLF_BW), tiles_y = grid_for(e->H, ESLF_BH);
   if (tiles_y > 65535) return fail(XM_ERR_INVALID, "map too tall (at most %d rows)", 65535 * ESLF_BH);
   EslfTv p = e->tv;
   const size_t n_tiles = (size_t)p.n_tiles;
   constexpr size_t N_VEC = 13;
-  const size_t need[] = {n * nb_red * sizeof(float2), n * (ESLF_BINS + 2) * sizeof(float), n * sizeof(EslfExt),
-                         do_tv ? N_VEC * total * sizeof(double) : 0, do_tv ? 2 * n * sizeof(EslfCtl) : 0,
-                         do_tv ? 2 * n * 2 * n_tiles * sizeof(double) : 0, do_tv ? n * p.n_calls : 0, n * sizeof(EslfStats),
-                         host ? total * 4 : 0, do_bil && (host || !bilateral_out) ? total * 4 : 0, host ? total * 8 : 0};
-  DevBuf* const bufs[] = {&e->red, &e->lut, &e->ext, &e->vec, &e->ctl, &e->part, &e->trips, &e->stats, &e->in, &e->bil, &e->out};
-  int rc;
-  for (int i = 0; i < 11; ++i)  // (every call is synchronous: nothing in flight can still use a buffer that grows)
-    if (need[i] && (rc = bufs[i]->reserve(need[i]))) return rc;
-
   hipStream_t stream = e->stream;
+  GroupCall c{stream, mem == XM_MEM_HOST};
+  const float* d_in = c.in(e->in, depth_optim, total * 4);
+  double* d_out = c.out(e->out, filtered_out, total * 8);
+  // stage 1's result: stage 2 reads it, so it exists whether or not the caller asked for it
+  float* d_bil = c.out(e->bil, do_bil ? bilateral_out : nullptr, total * 4, do_bil);
+  if (int rc = c.start({{e->red, n * nb_red * sizeof(float2)},
+                     {e->lut, n * (ESLF_BINS + 2) * sizeof(float)},
+                     {e->ext, n * sizeof(EslfExt)},
+                     {e->vec, do_tv ? N_VEC * total * sizeof(double) : 0},
+                     {e->ctl, do_tv ? 2 * n * sizeof(EslfCtl) : 0},
+                     {e->part, do_tv ? 2 * n * 2 * n_tiles * sizeof(double) : 0},
+                     {e->trips, do_tv ? n * p.n_calls : 0},
+                     {e->stats, n * sizeof(EslfStats)}}))
+    return rc;
   u64 launches = 0;
-  const float* d_in = depth_optim;
-  double* d_out = filtered_out;
-  float* d_bil = bilateral_out;
-  if (host) {
-    HIP_TRY(hipMemcpyAsync(e->in.p, depth_optim, total * 4, hipMemcpyHostToDevice, stream));
-    d_in = (const float*)e->in.p;
-    d_out = (double*)e->out.p;
-  }
-  if (do_bil && (host || !bilateral_out)) d_bil = (float*)e->bil.p;
   float2* red = (float2*)e->red.p;
   float* lut = (float*)e->lut.p;
   EslfExt* ext = (EslfExt*)e->ext.p;
@@ -176,13 +153,9 @@ int xm_esl_filter_maps(xm_esl_filter* e, const float* depth_optim, int n_maps, i
   }
   HIP_TRY(hipGetLastError());
   e->last_launches = launches;
-  const hipMemcpyKind back = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-  if (host) HIP_TRY(hipMemcpyAsync(filtered_out, d_out, total * 8, hipMemcpyDeviceToHost, stream));
-  if (bilateral_out && do_bil && d_bil != bilateral_out) HIP_TRY(hipMemcpyAsync(bilateral_out, d_bil, total * 4, back, stream));
-  if (trips_out && do_tv) HIP_TRY(hipMemcpyAsync(trips_out, e->trips.p, n * p.n_calls, back, stream));
-  if (stats_out) HIP_TRY(hipMemcpyAsync(stats_out, d_stats, n * sizeof(EslfStats), back, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
-  return XM_OK;
+  if (do_tv) c.back(trips_out, e->trips.p, n * p.n_calls);
+  c.back(stats_out, d_stats, n * sizeof(EslfStats));
+  return c.finish();
 }
 
 }  // extern "C"

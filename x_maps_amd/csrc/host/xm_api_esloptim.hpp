@@ -5,9 +5,7 @@
 
 static_assert(sizeof(xm_esl_optim_stats) == sizeof(EslOptStats), "xm_esl_optim_stats is what k_esl_optim_stats writes");
 
-struct xm_esl_optim {
-  int device = 0;
-  Stream stream;  // (before the buffers: released after them)
+struct xm_esl_optim : GroupObj {
   EslOptTables tb{};
   DevMem<float> d_proj;
   DevBuf part1, cnt, stats;       // device-side intermediates of a group
@@ -35,17 +33,10 @@ EslOptPinhole eslo_pinhole(const double* K, const double* D) { return EslOptPinh
 
 extern "C" {
 
-void xm_esl_optim_destroy(xm_esl_optim* e) {
-  if (!e) return;
-  (void)hipSetDevice(e->device);
-  if (e->stream) (void)hipStreamSynchronize(e->stream);
-  delete e;
-}
+void xm_esl_optim_destroy(xm_esl_optim* e) { group_destroy(e); }
 
 int xm_esl_optim_create(int device, const xm_esl_optim_config* cfg, xm_esl_optim** out) {
-  if (!cfg || !out) return fail(XM_ERR_INVALID, "NULL argument");
-  *out = nullptr;
-  if (cfg->struct_size != sizeof(xm_esl_optim_config)) return fail(XM_ERR_INVALID, "xm_esl_optim_config.struct_size mismatch");
+  if (int rc = group_create_args(cfg, out, "xm_esl_optim_config")) return rc;
   if (!cfg->proj_surface) return fail(XM_ERR_INVALID, "NULL table");
   if (cfg->cam_width <= 0 || cfg->cam_height <= 0 || cfg->proj_width <= 0 || cfg->proj_height <= 0)
     return fail(XM_ERR_INVALID, "dimensions must be positive");
@@ -65,14 +56,10 @@ int xm_esl_optim_create(int device, const xm_esl_optim_config* cfg, xm_esl_optim
   for (int i = 0; i < 12; ++i) finite = finite && std::isfinite(cfg->Rt[i]);
   if (!finite) return fail(XM_ERR_INVALID, "the calibration must be finite");
   if (cfg->cam_K[0] == 0.0 || cfg->cam_K[4] == 0.0) return fail(XM_ERR_INVALID, "the camera's focal lengths must not be zero");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(XM_ERR_HIP, "no HIP device visible");
-  if (device < 0 || device >= ndev) return fail(XM_ERR_INVALID, "no device %d", device);
-  HIP_TRY(hipSetDevice(device));
-  Owned<xm_esl_optim, xm_esl_optim_destroy> e(new (std::nothrow) xm_esl_optim);
-  if (!e) return fail(XM_ERR_NOMEM, "out of host memory");
-  e->device = device;
-  HIP_TRY(e->stream.create());
+  Owned<xm_esl_optim, xm_esl_optim_destroy> e;
+  if (int rc = group_open(device, e)) return rc;
+  e->px = (size_t)cfg->cam_width * cfg->cam_height;
+  e->max_n = 0;  // (a group beyond ESLO_GRID_CAP goes in several launches)
   const size_t proj_px = (size_t)cfg->proj_width * cfg->proj_height;
   HIP_TRY(e->d_proj.alloc(proj_px));
   HIP_TRY(hipMemcpy(e->d_proj, cfg->proj_surface, proj_px * sizeof(float), hipMemcpyHostToDevice));
@@ -90,68 +77,42 @@ int xm_esl_optim_create(int device, const xm_esl_optim_config* cfg, xm_esl_optim
 
 int xm_esl_optim_time_surfaces(xm_esl_optim* e, const void* surfaces, int dtype, int n_surfaces, int mem, const float* depth_init,
                                float* depth_optim_out, uint16_t* nfev_out, xm_esl_optim_stats* stats_out) {
-  if (!e) return fail(XM_ERR_INVALID, "NULL object");
-  if (dtype != XM_T_FLOAT32 && dtype != XM_T_FLOAT64) return fail(XM_ERR_INVALID, "a time surface is XM_T_FLOAT32 or XM_T_FLOAT64");
-  if (n_surfaces <= 0) return fail(XM_ERR_INVALID, "n_surfaces must be positive");
-  if (mem != XM_MEM_HOST && mem != XM_MEM_DEVICE) return fail(XM_ERR_INVALID, "mem must be XM_MEM_HOST or XM_MEM_DEVICE");
+  if (int rc = group_enter(e, n_surfaces, mem, &dtype)) return rc;
   if (!surfaces || !depth_init || !depth_optim_out) return fail(XM_ERR_INVALID, "NULL argument");
-  HIP_TRY(hipSetDevice(e->device));
   const EslOptTables& tb = e->tb;
-  const size_t n = (size_t)n_surfaces, px = (size_t)tb.cam_w * tb.cam_h, esz = t_size(dtype);
+  const size_t n = (size_t)n_surfaces, px = e->px, esz = t_size(dtype);
   const u32 nb_red = grid_for(px, SURF_RED_CHUNK);
   const u32 tiles_x = grid_for(tb.cam_w, ESLO_FW), tiles_y = grid_for(tb.cam_h, ESLO_FR), n_cnt = tiles_x * tiles_y;
   if (tiles_y > 65535) return fail(XM_ERR_INVALID, "camera frame too tall (at most %d rows)", 65535 * ESLO_FR);
-  if (n * px >= (1ull << 40)) return fail(XM_ERR_TOO_MANY, "group too large");
   hipStream_t stream = e->stream;
-  const bool host = mem == XM_MEM_HOST;
-  const size_t need[] = {n * nb_red * sizeof(SurfPart1), n * n_cnt * sizeof(EslOptCnt), n * sizeof(EslOptStats), host ? n * px * esz : 0,
-                         host ? n * px * 4 : 0, host ? n * px * 4 : 0, host && nfev_out ? n * px * 2 : 0};
-  DevBuf* const bufs[] = {&e->part1, &e->cnt, &e->stats, &e->in, &e->d0, &e->depth, &e->nfev};
-  int rc;
-  for (int i = 0; i < 7; ++i)  // (every call is synchronous: nothing in flight can still use a buffer that grows)
-    if (need[i] && (rc = bufs[i]->reserve(need[i]))) return rc;
-
-  const char* d_in = (const char*)surfaces;
-  const float* d_d0 = depth_init;
-  float* d_depth = depth_optim_out;
-  uint16_t* d_nfev = nfev_out;
-  if (host) {
-    HIP_TRY(hipMemcpyAsync(e->in.p, surfaces, n * px * esz, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(e->d0.p, depth_init, n * px * 4, hipMemcpyHostToDevice, stream));
-    d_in = (const char*)e->in.p;
-    d_d0 = (const float*)e->d0.p;
-    d_depth = (float*)e->depth.p;
-    if (nfev_out) d_nfev = (uint16_t*)e->nfev.p;
-  }
+  GroupCall c{stream, mem == XM_MEM_HOST};
+  const char* d_in = (const char*)c.in(e->in, surfaces, n * px * esz);
+  const float* d_d0 = c.in(e->d0, depth_init, n * px * 4);
+  float* d_depth = c.out(e->depth, depth_optim_out, n * px * 4);
+  uint16_t* d_nfev = c.out(e->nfev, nfev_out, n * px * 2);
+  if (int rc = c.start({{e->part1, n * nb_red * sizeof(SurfPart1)}, {e->cnt, n * n_cnt * sizeof(EslOptCnt)}, {e->stats, n * sizeof(EslOptStats)}}))
+    return rc;
   SurfPart1* p1 = (SurfPart1*)e->part1.p;
   EslOptCnt* cnt = (EslOptCnt*)e->cnt.p;
   EslOptStats* d_stats = (EslOptStats*)e->stats.p;
   for (size_t s0 = 0; s0 < n; s0 += ESLO_GRID_CAP) {  // a group beyond the grid's cap goes in several launches
     const unsigned m = (unsigned)(n - s0 < ESLO_GRID_CAP ? n - s0 : ESLO_GRID_CAP);
     const dim3 g_red(nb_red, m), g_px(tiles_x, tiles_y, m);
-    const void* in = d_in + s0 * px * esz;
     SurfPart1* p1s = p1 + s0 * nb_red;
     EslOptCnt* cnts = cnt + s0 * n_cnt;
     uint16_t* nf = d_nfev ? d_nfev + s0 * px : nullptr;
-    if (dtype == XM_T_FLOAT32) {
-      hipLaunchKernelGGL((k_surf_extrema<float>), g_red, dim3(BLOCK), 0, stream, (const float*)in, (u32)px, p1s);
-      eslo_launch<float>(tb, g_px, stream, (const float*)in, d_d0 + s0 * px, p1s, nb_red, d_depth + s0 * px, nf, cnts);
-    } else {
-      hipLaunchKernelGGL((k_surf_extrema<double>), g_red, dim3(BLOCK), 0, stream, (const double*)in, (u32)px, p1s);
-      eslo_launch<double>(tb, g_px, stream, (const double*)in, d_d0 + s0 * px, p1s, nb_red, d_depth + s0 * px, nf, cnts);
-    }
+    by_dtype(dtype, [&](auto t) {
+      using T = decltype(t);
+      const T* in = (const T*)(d_in + s0 * px * esz);
+      hipLaunchKernelGGL((k_surf_extrema<T>), g_red, dim3(BLOCK), 0, stream, in, (u32)px, p1s);
+      eslo_launch<T>(tb, g_px, stream, in, d_d0 + s0 * px, p1s, nb_red, d_depth + s0 * px, nf, cnts);
+    });
     hipLaunchKernelGGL(k_esl_optim_stats, dim3(m), dim3(BLOCK), 0, stream, (const SurfPart1*)p1s, nb_red, (const EslOptCnt*)cnts, n_cnt,
                        d_stats + s0);
   }
   HIP_TRY(hipGetLastError());
-  if (host) {
-    HIP_TRY(hipMemcpyAsync(depth_optim_out, d_depth, n * px * 4, hipMemcpyDeviceToHost, stream));
-    if (nfev_out) HIP_TRY(hipMemcpyAsync(nfev_out, d_nfev, n * px * 2, hipMemcpyDeviceToHost, stream));
-  }
-  if (stats_out)
-    HIP_TRY(hipMemcpyAsync(stats_out, d_stats, n * sizeof(EslOptStats), host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
-  return XM_OK;
+  c.back(stats_out, d_stats, n * sizeof(EslOptStats));
+  return c.finish();
 }
 
 }  // extern "C"

@@ -6,9 +6,7 @@
 static_assert(sizeof(xm_mc3d_stats) == sizeof(Mc3dStats), "xm_mc3d_stats is what k_mc3d_stats writes");
 static_assert(XM_MC3D_POISON == MC3D_POISON && XM_MC3D_NO_BLUR == MC3D_NO_BLUR, "xmaps.h and xmaps_geometry.hpp agree");
 
-struct xm_mc3d {
-  int device = 0;
-  Stream stream;  // (before the buffers: released after them)
+struct xm_mc3d : GroupObj {
   Mc3dTables tb{};
   DevMem<int2> d_cam_map;
   DevMem<int> d_yp_t, d_xp_t;
@@ -18,17 +16,10 @@ struct xm_mc3d {
 
 extern "C" {
 
-void xm_mc3d_destroy(xm_mc3d* m) {
-  if (!m) return;
-  (void)hipSetDevice(m->device);
-  if (m->stream) (void)hipStreamSynchronize(m->stream);
-  delete m;
-}
+void xm_mc3d_destroy(xm_mc3d* m) { group_destroy(m); }
 
 int xm_mc3d_create(int device, const xm_mc3d_config* cfg, xm_mc3d** out) {
-  if (!cfg || !out) return fail(XM_ERR_INVALID, "NULL argument");
-  *out = nullptr;
-  if (cfg->struct_size != sizeof(xm_mc3d_config)) return fail(XM_ERR_INVALID, "xm_mc3d_config.struct_size mismatch");
+  if (int rc = group_create_args(cfg, out, "xm_mc3d_config")) return rc;
   if (!cfg->cam_map || !cfg->proj_map) return fail(XM_ERR_INVALID, "NULL table");
   if (cfg->cam_width <= 0 || cfg->cam_height <= 0 || cfg->proj_width <= 0 || cfg->proj_height <= 0)
     return fail(XM_ERR_INVALID, "dimensions must be positive");
@@ -46,14 +37,8 @@ int xm_mc3d_create(int device, const xm_mc3d_config* cfg, xm_mc3d** out) {
     return fail(XM_ERR_INVALID, "rect limits must lie in 1 .. 2^29 (got %d, %d)", x_lim, y_lim);
   if (!mc3d_key_fits((u32)mrd, 2u * (u32)nc))
     return fail(XM_ERR_INVALID, "(max_row_diff + 2) * the window's size rounded up to a power of two must stay below 2^32");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(XM_ERR_HIP, "no HIP device visible");
-  if (device < 0 || device >= ndev) return fail(XM_ERR_INVALID, "no device %d", device);
-  HIP_TRY(hipSetDevice(device));
-  Owned<xm_mc3d, xm_mc3d_destroy> m(new (std::nothrow) xm_mc3d);
-  if (!m) return fail(XM_ERR_NOMEM, "out of host memory");
-  m->device = device;
-  HIP_TRY(m->stream.create());
+  Owned<xm_mc3d, xm_mc3d_destroy> m;
+  if (int rc = group_open(device, m)) return rc;
   const size_t cam_px = (size_t)cfg->cam_width * cfg->cam_height;
   // the tables as the kernel reads them: saturated, the projector's by (proj_x, y) with poison folded into yp
   auto sat = [](int32_t v) { return v == MC3D_POISON ? v : v > MC3D_SAT ? MC3D_SAT : v < -MC3D_SAT ? -MC3D_SAT : v; };
@@ -79,59 +64,37 @@ int xm_mc3d_create(int device, const xm_mc3d_config* cfg, xm_mc3d** out) {
   HIP_TRY(hipMemcpy(m->d_xp_t, xp_t.data(), proj_px * sizeof(int), hipMemcpyHostToDevice));
   m->tb = Mc3dTables{m->d_cam_map.get(), m->d_yp_t.get(), m->d_xp_t.get(), cfg->cam_width, cfg->cam_height, W, H, nc, mrd, x_lim, y_lim,
                      mc3d_pos_bits(2u * (u32)nc), cfg->p1_03};
+  m->px = cam_px;
   *out = m.release();
   return XM_OK;
 }
 
 int xm_mc3d_time_surfaces(xm_mc3d* m, const void* surfaces, int dtype, int n_surfaces, int mem, int flags, float* depth_out,
                           uint16_t* disp_out, xm_mc3d_stats* stats_out) {
-  if (!m) return fail(XM_ERR_INVALID, "NULL object");
-  if (dtype != XM_T_FLOAT32 && dtype != XM_T_FLOAT64) return fail(XM_ERR_INVALID, "a time surface is XM_T_FLOAT32 or XM_T_FLOAT64");
-  if (n_surfaces <= 0) return fail(XM_ERR_INVALID, "n_surfaces must be positive");
-  if (mem != XM_MEM_HOST && mem != XM_MEM_DEVICE) return fail(XM_ERR_INVALID, "mem must be XM_MEM_HOST or XM_MEM_DEVICE");
+  if (int rc = group_enter(m, n_surfaces, mem, &dtype)) return rc;
   if (flags & ~(int)XM_MC3D_NO_BLUR) return fail(XM_ERR_INVALID, "unknown flags");
   if (!surfaces || !depth_out) return fail(XM_ERR_INVALID, "NULL argument");
-  HIP_TRY(hipSetDevice(m->device));
   const Mc3dTables& tb = m->tb;
-  const size_t n = (size_t)n_surfaces, px = (size_t)tb.cam_w * tb.cam_h, esz = t_size(dtype);
+  const size_t n = (size_t)n_surfaces, px = m->px;
   const u32 tiles_x = grid_for(tb.cam_w, MC3D_FW), tiles_y = grid_for(tb.cam_h, MC3D_FR), n_cnt = tiles_x * tiles_y;
   if (tiles_y > 65535) return fail(XM_ERR_INVALID, "camera frame too tall (at most %d rows)", 65535 * MC3D_FR);
-  if (n > 65535 || n * px >= (1ull << 40)) return fail(XM_ERR_TOO_MANY, "group too large (at most 65535 surfaces per call)");
   hipStream_t stream = m->stream;
-  const bool host = mem == XM_MEM_HOST;
-  const size_t need[] = {n * n_cnt * sizeof(Mc3dCnt), n * sizeof(Mc3dStats), host ? n * px * esz : 0, host ? n * px * 4 : 0,
-                         host && disp_out ? n * px * 2 : 0};
-  DevBuf* const bufs[] = {&m->cnt, &m->stats, &m->in, &m->depth, &m->disp};
-  int rc;
-  for (int i = 0; i < 5; ++i)  // (every call is synchronous: nothing in flight can still use a buffer that grows)
-    if (need[i] && (rc = bufs[i]->reserve(need[i]))) return rc;
-
-  const void* d_in = surfaces;
-  float* d_depth = depth_out;
-  uint16_t* d_disp = disp_out;
-  if (host) {
-    HIP_TRY(hipMemcpyAsync(m->in.p, surfaces, n * px * esz, hipMemcpyHostToDevice, stream));
-    d_in = m->in.p;
-    d_depth = (float*)m->depth.p;
-    if (disp_out) d_disp = (uint16_t*)m->disp.p;
-  }
+  GroupCall c{stream, mem == XM_MEM_HOST};
+  const void* d_in = c.in(m->in, surfaces, n * px * t_size(dtype));
+  float* d_depth = c.out(m->depth, depth_out, n * px * 4);
+  uint16_t* d_disp = c.out(m->disp, disp_out, n * px * 2);
+  if (int rc = c.start({{m->cnt, n * n_cnt * sizeof(Mc3dCnt)}, {m->stats, n * sizeof(Mc3dStats)}})) return rc;
   Mc3dCnt* cnt = (Mc3dCnt*)m->cnt.p;
   Mc3dStats* d_stats = (Mc3dStats*)m->stats.p;
   const dim3 g_px(tiles_x, tiles_y, (unsigned)n);
-  if (dtype == XM_T_FLOAT32)
-    hipLaunchKernelGGL((k_mc3d<float>), g_px, dim3(BLOCK), 0, stream, (const float*)d_in, tb, (u32)flags, d_depth, d_disp, cnt);
-  else
-    hipLaunchKernelGGL((k_mc3d<double>), g_px, dim3(BLOCK), 0, stream, (const double*)d_in, tb, (u32)flags, d_depth, d_disp, cnt);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((k_mc3d<T>), g_px, dim3(BLOCK), 0, stream, (const T*)d_in, tb, (u32)flags, d_depth, d_disp, cnt);
+  });
   hipLaunchKernelGGL(k_mc3d_stats, dim3((unsigned)n), dim3(BLOCK), 0, stream, (const Mc3dCnt*)cnt, n_cnt, d_stats);
   HIP_TRY(hipGetLastError());
-  if (host) {
-    HIP_TRY(hipMemcpyAsync(depth_out, d_depth, n * px * 4, hipMemcpyDeviceToHost, stream));
-    if (disp_out) HIP_TRY(hipMemcpyAsync(disp_out, d_disp, n * px * 2, hipMemcpyDeviceToHost, stream));
-  }
-  if (stats_out)
-    HIP_TRY(hipMemcpyAsync(stats_out, d_stats, n * sizeof(Mc3dStats), host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
-  return XM_OK;
+  c.back(stats_out, d_stats, n * sizeof(Mc3dStats));
+  return c.finish();
 }
 
 }  // extern "C"

@@ -29,9 +29,8 @@ int xm_process_time_surfaces(xm_handle* h, const void* surfaces, int dtype, int 
                              float* cloud_out, xm_surface_stats* stats_out) {
   if (!h) return fail(XM_ERR_INVALID, "NULL handle");
   if (h->cfg.view != XM_VIEW_CAMERA) return fail(XM_ERR_INVALID, "time surfaces need a camera-view handle (XM_VIEW_CAMERA)");
-  if (dtype != XM_T_FLOAT32 && dtype != XM_T_FLOAT64) return fail(XM_ERR_INVALID, "a time surface is XM_T_FLOAT32 or XM_T_FLOAT64");
-  if (n_surfaces <= 0) return fail(XM_ERR_INVALID, "n_surfaces must be positive");
-  if (mem != XM_MEM_HOST && mem != XM_MEM_DEVICE) return fail(XM_ERR_INVALID, "mem must be XM_MEM_HOST or XM_MEM_DEVICE");
+  int rc;
+  if ((rc = group_args(n_surfaces, mem, &dtype, "surfaces"))) return rc;
   if (!surfaces || !depth_out) return fail(XM_ERR_INVALID, "NULL argument");
   SurfaceScratch& sc = h->surf;
   if (cloud_out && !sc.has_cloud_tables)
@@ -49,19 +48,21 @@ int xm_process_time_surfaces(xm_handle* h, const void* surfaces, int dtype, int 
   const bool host = mem == XM_MEM_HOST;
 
   // scratch: grown when a larger group arrives -- only once nothing that was enqueued earlier can still be using it
-  const size_t need[] = {n * nb_red * sizeof(SurfPart1), n * nb_red * sizeof(SurfPart2), n * n_seg * 4, n * n_seg * 4, n * n_wo * 4,
-                         cloud_out ? n * px * 2 : 0, n * sizeof(SurfStats), host ? n * px * esz : 0, host ? n * px * 4 : 0,
-                         host && cloud_out ? n * px * 12 : 0};
-  DevBuf* const bufs[] = {&sc.part1, &sc.part2, &sc.seg_cnt, &sc.seg_off, &sc.wave_oob, &sc.code, &sc.stats, &sc.in, &sc.depth, &sc.cloud};
-  bool grow = false;
-  for (int i = 0; i < 10; ++i) grow |= need[i] > bufs[i]->cap;
-  if (grow && sc.last_stream) {
+  const std::initializer_list<BufNeed> needs = {{sc.part1, n * nb_red * sizeof(SurfPart1)},
+                                                {sc.part2, n * nb_red * sizeof(SurfPart2)},
+                                                {sc.seg_cnt, n * n_seg * 4},
+                                                {sc.seg_off, n * n_seg * 4},
+                                                {sc.wave_oob, n * n_wo * 4},
+                                                {sc.code, cloud_out ? n * px * 2 : 0},
+                                                {sc.stats, n * sizeof(SurfStats)},
+                                                {sc.in, host ? n * px * esz : 0},
+                                                {sc.depth, host ? n * px * 4 : 0},
+                                                {sc.cloud, host && cloud_out ? n * px * 12 : 0}};
+  if (any_grows(needs) && sc.last_stream) {
     HIP_TRY(hipStreamSynchronize(sc.last_stream));
     sc.last_stream = nullptr;
   }
-  int rc;
-  for (int i = 0; i < 10; ++i)
-    if (need[i] && (rc = bufs[i]->reserve(need[i]))) return rc;
+  if ((rc = reserve_all(needs))) return rc;
   if (!sc.done) HIP_TRY(sc.done.create());
   if (sc.last_stream && sc.last_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, sc.done, 0));
 
@@ -80,19 +81,17 @@ int xm_process_time_surfaces(xm_handle* h, const void* surfaces, int dtype, int 
   SurfPart2* p2 = (SurfPart2*)sc.part2.p;
   u32 *seg_cnt = (u32*)sc.seg_cnt.p, *seg_off = (u32*)sc.seg_off.p, *wave_oob = (u32*)sc.wave_oob.p;
   uint16_t* code = (uint16_t*)sc.code.p;
-#define XM_SURF(T)                                                                                                              \
-  do {                                                                                                                          \
-    XM_LAUNCH((k_surf_extrema<T>), g_red, dim3(BLOCK), 0, stream, (const T*)d_in, (u32)px, p1);                                 \
-    XM_LAUNCH((k_surf_norm_extrema<T>), g_red, dim3(BLOCK), 0, stream, (const T*)d_in, (u32)px, (const SurfPart1*)p1, p2);      \
-    if (cloud_out)                                                                                                              \
-      XM_LAUNCH((k_surf_pixels<T, true>), g_px, dim3(BLOCK), 0, stream, (const T*)d_in, tb, (const SurfPart2*)p2, nb_red,       \
-                d_depth, code, seg_cnt, wave_oob);                                                                              \
-    else                                                                                                                        \
-      XM_LAUNCH((k_surf_pixels<T, false>), g_px, dim3(BLOCK), 0, stream, (const T*)d_in, tb, (const SurfPart2*)p2, nb_red,      \
-                d_depth, (uint16_t*)nullptr, seg_cnt, wave_oob);                                                                \
-  } while (0)
-  if (dtype == XM_T_FLOAT32) XM_SURF(float); else XM_SURF(double);
-#undef XM_SURF
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    XM_LAUNCH((k_surf_extrema<T>), g_red, dim3(BLOCK), 0, stream, (const T*)d_in, (u32)px, p1);
+    XM_LAUNCH((k_surf_norm_extrema<T>), g_red, dim3(BLOCK), 0, stream, (const T*)d_in, (u32)px, (const SurfPart1*)p1, p2);
+    if (cloud_out)
+      XM_LAUNCH((k_surf_pixels<T, true>), g_px, dim3(BLOCK), 0, stream, (const T*)d_in, tb, (const SurfPart2*)p2, nb_red, d_depth, code,
+                seg_cnt, wave_oob);
+    else
+      XM_LAUNCH((k_surf_pixels<T, false>), g_px, dim3(BLOCK), 0, stream, (const T*)d_in, tb, (const SurfPart2*)p2, nb_red, d_depth,
+                (uint16_t*)nullptr, seg_cnt, wave_oob);
+  });
   HIP_TRY(hipGetLastError());
   XM_LAUNCH(k_surf_scan, dim3((unsigned)n), dim3(SURF_SCAN_BLOCK), 0, stream, (const u32*)seg_cnt, n_seg, (const u32*)wave_oob, n_wo,
             (const SurfPart2*)p2, nb_red, seg_off, d_stats);

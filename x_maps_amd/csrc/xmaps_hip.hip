@@ -70,6 +70,7 @@ using namespace xm;
 #include "host/xm_ingest_create.hpp"  // ... the stages of xm_ingest_create
 #include "host/xm_api_ingest.hpp"   // ... its C entry points (records, and EVT words through the decoder)
 #include "host/xm_api_misc.hpp"     // X-map builder, evaluation metrics, memory helpers
+#include "host/xm_group.hpp"        // the skeleton of the group objects below: create / destroy, argument check, staging, dtype dispatch
 #include "host/xm_api_surface.hpp"  // a group of camera time surfaces -> depth maps + point clouds (the evaluation caller's entry)
 #include "host/xm_api_eslinit.hpp"  // the ESL-init baseline on the same surfaces: depth_init maps, disparity_init alone
 #include "host/xm_api_mc3d.hpp"     // the MC3D baseline on the same surfaces

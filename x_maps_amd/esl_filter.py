@@ -15,6 +15,7 @@ import ctypes as C
 import numpy as np
 
 from . import _native as N
+from ._group import GroupObject, map_group, ptr as _ptr
 
 NITER_OUTER, NITER_INNER, ITER_LIM = 20, 10, 5  # esl_utilities.py:208-209, :222
 NO_BILATERAL, NO_TV = N.XM_ESL_FILTER_NO_BILATERAL, N.XM_ESL_FILTER_NO_TV
@@ -33,19 +34,14 @@ class EslFilterStats:
                 f"n_lsqr={self.n_lsqr}, sum_itn={self.sum_itn}, istop_count={self.istop_count})")
 
 
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
-class EslFilter:
+class EslFilter(GroupObject):
     """with EslFilter(width, height) as flt: res = flt.filter_maps(depth_optim)
 
     Keyword parameters default to the reference's call (0 = default): d, sigma_color, sigma_space, mu, lambda0, lambda1,
     niter_outer, niter_inner, iter_lim, tol, tau, damp; flags: NO_BILATERAL | NO_TV runs one stage alone."""
+    _destroy = "xm_esl_filter_destroy"
 
     def __init__(self, width: int, height: int, device: int = 0, flags: int = 0, **params):
-        self._lib = N.load_library()
-        self._h = None
         self.width, self.height, self.flags = int(width), int(height), int(flags)
         ints = {k: int(params.pop(k, 0)) for k in ("d", "niter_outer", "niter_inner", "iter_lim")}
         dbl = {k: float(params.pop(k, 0.0)) for k in ("sigma_color", "sigma_space", "mu", "lambda0", "lambda1", "tol", "tau", "damp")}
@@ -55,35 +51,13 @@ class EslFilter:
         cfg = N.xm_esl_filter_config(C.sizeof(N.xm_esl_filter_config), self.width, self.height, self.flags, ints["d"], ints["niter_outer"],
                                      ints["niter_inner"], ints["iter_lim"], dbl["sigma_color"], dbl["sigma_space"], dbl["mu"],
                                      dbl["lambda0"], dbl["lambda1"], dbl["tol"], dbl["tau"], dbl["damp"])
-        h = C.c_void_p()
-        N.check(self._lib.xm_esl_filter_create(int(device), C.byref(cfg), C.byref(h)))
-        self._h = h
-
-    def close(self):
-        if self._h is not None:
-            self._lib.xm_esl_filter_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create("xm_esl_filter_create", device, cfg)
 
     def filter_maps(self, depth_optim, want_bilateral: bool = False, want_trips: bool = False):
         """A group of depth_optim maps (a list of [height][width] arrays or one 3-D array, float32) in ONE device call ->
         [(depth_optim_filtered f64 [height][width], bilateral f32 | None, trips u8 [niter_outer * niter_inner] | None,
         EslFilterStats)] per map.  trips: lsqr's iterations of every inner call, 0xFF where none ran."""
-        grp = np.asarray(depth_optim) if isinstance(depth_optim, np.ndarray) else np.stack([np.asarray(a) for a in depth_optim])
-        grp = np.ascontiguousarray(grp if grp.ndim == 3 else grp[None], dtype=np.float32)
-        if grp.ndim != 3 or grp.shape[1:] != (self.height, self.width) or grp.shape[0] == 0:
-            raise ValueError(f"maps must be (n, {self.height}, {self.width}), got {grp.shape}")
+        grp = map_group(depth_optim, self.height, self.width, np.float32)
         n = grp.shape[0]
         out = np.full(grp.shape, np.nan, np.float64)
         bil = np.full(grp.shape, np.nan, np.float32) if want_bilateral and not self.flags & NO_BILATERAL else None

@@ -18,6 +18,7 @@ import ctypes as C
 import numpy as np
 
 from . import _native as N
+from ._group import T_DTYPES as _T_DTYPES, GroupObject, ptr as _ptr, surface_group
 from .calibration import (CamProjCalibrationParams, init_undistort_rectify_map, init_undistort_rectify_map_inverse, mapf_to_i16,
                           remap_nearest, stereo_rectify)
 
@@ -74,22 +75,14 @@ class EslInitStats:
                 f"lo={self.lo!r}, hi={self.hi!r})")
 
 
-_T_DTYPES = {np.dtype(np.float32): N.XM_T_FLOAT32, np.dtype(np.float64): N.XM_T_FLOAT64}
-
-
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
-class EslInit:
+class EslInit(GroupObject):
     """with EslInit(tables) as esl: depths = esl.depths_from_time_surfaces(surfaces)
 
     tables: build_esl_init_tables' dict, or any dict with cam_w, cam_h, rect_w, rect_h, cam_to_rect_map int16 [rect_h][rect_w][2],
     rect_to_cam_map int16 [cam_h][cam_w][2], proj_rect float32 [rect_h][rect_w], p1_03 (min_disp / max_disp: 5 / 900)."""
+    _destroy = "xm_esl_init_destroy"
 
     def __init__(self, tables: dict, device: int = 0):
-        self._lib = N.load_library()
-        self._h = None
         self.cam_w, self.cam_h = int(tables["cam_w"]), int(tables["cam_h"])
         self.rect_w, self.rect_h = int(tables["rect_w"]), int(tables["rect_h"])
         c2r = np.ascontiguousarray(tables["cam_to_rect_map"], dtype=np.int16)
@@ -100,47 +93,13 @@ class EslInit:
         self.min_disp, self.max_disp = int(tables.get("min_disp", MIN_DISP)), int(tables.get("max_disp", MAX_DISP))
         cfg = N.xm_esl_init_config(C.sizeof(N.xm_esl_init_config), self.cam_w, self.cam_h, self.rect_w, self.rect_h, self.min_disp,
                                    self.max_disp, 0, float(tables["p1_03"]), _ptr(c2r), _ptr(r2c), _ptr(proj))
-        h = C.c_void_p()
-        N.check(self._lib.xm_esl_init_create(int(device), C.byref(cfg), C.byref(h)))
-        self._h = h
-
-    def close(self):
-        if self._h is not None:
-            self._lib.xm_esl_init_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _group(self, surfaces) -> np.ndarray:
-        if isinstance(surfaces, np.ndarray):
-            grp = surfaces if surfaces.ndim == 3 else surfaces[None]
-        else:
-            arrs = [np.asarray(a) for a in surfaces]
-            if not arrs:
-                raise ValueError("no surfaces")
-            dt = np.float32 if all(a.dtype == np.float32 for a in arrs) else np.float64
-            grp = np.stack([a.astype(dt, copy=False) for a in arrs])
-        if grp.ndim != 3 or grp.shape[1:] != (self.cam_h, self.cam_w) or grp.shape[0] == 0:
-            raise ValueError(f"time surfaces must be (n, {self.cam_h}, {self.cam_w}), got {grp.shape}")
-        if grp.dtype not in _T_DTYPES:
-            grp = grp.astype(np.float64)
-        return np.ascontiguousarray(grp)
+        self._create("xm_esl_init_create", device, cfg)
 
     def depths_from_time_surfaces(self, surfaces, want_disparity: bool = False):
         """A group of camera time surfaces (a list of [cam_h][cam_w] arrays or one 3-D array; float32 or float64, 0 = no event)
         in ONE device call -> [(depth_init f32 [cam_h][cam_w], disp_cam u16 | None, EslInitStats)] per surface.  An all-zero
         surface and one with a single non-zero value give zero maps (n_searched == 0): the reference skips the former."""
-        grp = self._group(surfaces)
+        grp = surface_group(surfaces, self.cam_h, self.cam_w)
         n = grp.shape[0]
         depth = np.empty((n, self.cam_h, self.cam_w), np.float32)
         disp = np.empty((n, self.cam_h, self.cam_w), np.uint16) if want_disparity else None

@@ -19,6 +19,7 @@ import ctypes as C
 import numpy as np
 
 from . import _native as N
+from ._group import T_DTYPES as _T_DTYPES, GroupObject, map_group, ptr as _ptr, surface_group
 from .calibration import CamProjCalibrationParams, rodrigues, stereo_rectify
 from .esl_init import get_projector_time_surface
 
@@ -62,22 +63,14 @@ class EslOptimStats:
                 f"n_bad_bounds={self.n_bad_bounds}, lo={self.lo!r}, hi={self.hi!r})")
 
 
-_T_DTYPES = {np.dtype(np.float32): N.XM_T_FLOAT32, np.dtype(np.float64): N.XM_T_FLOAT64}
-
-
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
-class EslOptim:
+class EslOptim(GroupObject):
     """with EslOptim(tables) as opt: res = opt.depths_from_time_surfaces(surfaces, depth_init)
 
     tables: build_esl_optim_tables' dict, or any dict with cam_w, cam_h, proj_w, proj_h, cam_K, cam_D, proj_K, proj_D, Rt[12], p1_03,
     proj_surface float32 [proj_h][proj_w] (window_size / max_iter / xatol: 3 / 500 / 1e-5)."""
+    _destroy = "xm_esl_optim_destroy"
 
     def __init__(self, tables: dict, device: int = 0):
-        self._lib = N.load_library()
-        self._h = None
         self.cam_w, self.cam_h = int(tables["cam_w"]), int(tables["cam_h"])
         self.proj_w, self.proj_h = int(tables["proj_w"]), int(tables["proj_h"])
         proj = np.ascontiguousarray(tables["proj_surface"], dtype=np.float32)
@@ -93,50 +86,15 @@ class EslOptim:
                                     float(tables["p1_03"]), (C.c_double * 9)(*parts["cam_K"]), (C.c_double * 5)(*parts["cam_D"]),
                                     (C.c_double * 9)(*parts["proj_K"]), (C.c_double * 5)(*parts["proj_D"]), (C.c_double * 12)(*parts["Rt"]),
                                     _ptr(proj))
-        h = C.c_void_p()
-        N.check(self._lib.xm_esl_optim_create(int(device), C.byref(cfg), C.byref(h)))
-        self._h = h
-
-    def close(self):
-        if self._h is not None:
-            self._lib.xm_esl_optim_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _group(self, surfaces) -> np.ndarray:
-        if isinstance(surfaces, np.ndarray):
-            grp = surfaces if surfaces.ndim == 3 else surfaces[None]
-        else:
-            arrs = [np.asarray(a) for a in surfaces]
-            if not arrs:
-                raise ValueError("no surfaces")
-            dt = np.float32 if all(a.dtype == np.float32 for a in arrs) else np.float64
-            grp = np.stack([a.astype(dt, copy=False) for a in arrs])
-        if grp.ndim != 3 or grp.shape[1:] != (self.cam_h, self.cam_w) or grp.shape[0] == 0:
-            raise ValueError(f"time surfaces must be (n, {self.cam_h}, {self.cam_w}), got {grp.shape}")
-        if grp.dtype not in _T_DTYPES:
-            grp = grp.astype(np.float64)
-        return np.ascontiguousarray(grp)
+        self._create("xm_esl_optim_create", device, cfg)
 
     def depths_from_time_surfaces(self, surfaces, depth_init, want_nfev: bool = False):
         """A group of camera time surfaces (a list of [cam_h][cam_w] arrays or one 3-D array; float32 or float64, 0 = no event) and
         their depth_init maps (float32, the same shape) in ONE device call -> [(depth_optim f32 [cam_h][cam_w], nfev u16 | None,
         EslOptimStats)] per surface.  An all-zero surface and one with a single non-zero value give zero maps."""
-        grp = self._group(surfaces)
+        grp = surface_group(surfaces, self.cam_h, self.cam_w)
         n = grp.shape[0]
-        d0 = np.asarray(depth_init) if isinstance(depth_init, np.ndarray) else np.stack([np.asarray(a) for a in depth_init])
-        d0 = np.ascontiguousarray(d0 if d0.ndim == 3 else d0[None], dtype=np.float32)
+        d0 = map_group(depth_init, self.cam_h, self.cam_w, np.float32, "depth_init")
         if d0.shape != grp.shape:
             raise ValueError(f"depth_init must be {grp.shape}, got {d0.shape}")
         depth = np.empty(grp.shape, np.float32)

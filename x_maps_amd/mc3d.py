@@ -16,6 +16,7 @@ import ctypes as C
 import numpy as np
 
 from . import _native as N
+from ._group import T_DTYPES as _T_DTYPES, GroupObject, ptr as _ptr, surface_group
 from .calibration import CamProjCalibrationParams, init_undistort_rectify_map_inverse, stereo_rectify
 
 POISON = N.XM_MC3D_POISON
@@ -73,22 +74,14 @@ class Mc3dStats:
         return "Mc3dStats(" + ", ".join(f"{k}={getattr(self, k)}" for k in self.__slots__) + ")"
 
 
-_T_DTYPES = {np.dtype(np.float32): N.XM_T_FLOAT32, np.dtype(np.float64): N.XM_T_FLOAT64}
-
-
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
-class Mc3d:
+class Mc3d(GroupObject):
     """with Mc3d(tables) as mc: depths = mc.depths_from_time_surfaces(surfaces)
 
     tables: build_mc3d_tables' dict, or any dict with cam_w, cam_h, proj_w, proj_h, cam_map int32 [cam_h][cam_w][2], proj_map
     int32 [proj_h][proj_w][2] (mc3d_int_maps), p1_03 (nc, max_row_diff, rect_x_limit / rect_y_limit: the reference's)."""
+    _destroy = "xm_mc3d_destroy"
 
     def __init__(self, tables: dict, device: int = 0):
-        self._lib = N.load_library()
-        self._h = None
         self.cam_w, self.cam_h = int(tables["cam_w"]), int(tables["cam_h"])
         self.proj_w, self.proj_h = int(tables["proj_w"]), int(tables["proj_h"])
         cam = np.ascontiguousarray(tables["cam_map"], dtype=np.int32)
@@ -98,47 +91,13 @@ class Mc3d:
         cfg = N.xm_mc3d_config(C.sizeof(N.xm_mc3d_config), self.cam_w, self.cam_h, self.proj_w, self.proj_h,
                                int(tables.get("nc", 0)), int(tables.get("max_row_diff", 0)), int(tables.get("rect_x_limit", 0)),
                                int(tables.get("rect_y_limit", 0)), 0, float(tables["p1_03"]), _ptr(cam), _ptr(proj))
-        h = C.c_void_p()
-        N.check(self._lib.xm_mc3d_create(int(device), C.byref(cfg), C.byref(h)))
-        self._h = h
-
-    def close(self):
-        if self._h is not None:
-            self._lib.xm_mc3d_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _group(self, surfaces) -> np.ndarray:
-        if isinstance(surfaces, np.ndarray):
-            grp = surfaces if surfaces.ndim == 3 else surfaces[None]
-        else:
-            arrs = [np.asarray(a) for a in surfaces]
-            if not arrs:
-                raise ValueError("no surfaces")
-            dt = np.float32 if all(a.dtype == np.float32 for a in arrs) else np.float64
-            grp = np.stack([a.astype(dt, copy=False) for a in arrs])
-        if grp.ndim != 3 or grp.shape[1:] != (self.cam_h, self.cam_w) or grp.shape[0] == 0:
-            raise ValueError(f"time surfaces must be (n, {self.cam_h}, {self.cam_w}), got {grp.shape}")
-        if grp.dtype not in _T_DTYPES:
-            grp = grp.astype(np.float64)
-        return np.ascontiguousarray(grp)
+        self._create("xm_mc3d_create", device, cfg)
 
     def depths_from_time_surfaces(self, surfaces, want_disparity: bool = False, blur: bool = True):
         """A group of camera time surfaces (a list of [cam_h][cam_w] arrays or one 3-D array; float32 or float64, used as stored,
         0 = no event) in ONE device call -> [(depth f32 [cam_h][cam_w], disparity u16 | None, Mc3dStats)] per surface.  An
         all-zero surface gives zero maps and zero counts: the reference skips it."""
-        grp = self._group(surfaces)
+        grp = surface_group(surfaces, self.cam_h, self.cam_w)
         n = grp.shape[0]
         depth = np.empty((n, self.cam_h, self.cam_w), np.float32)
         disp = np.empty((n, self.cam_h, self.cam_w), np.uint16) if want_disparity else None
