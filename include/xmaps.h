@@ -939,6 +939,46 @@ void xm_mc3d_destroy(xm_mc3d* m);
 int xm_mc3d_time_surfaces(xm_mc3d* m, const void* surfaces, int dtype, int n_surfaces, int mem, int flags, float* depth_out,
                           uint16_t* disp_out, xm_mc3d_stats* stats_out);
 
+/* ---- the evaluation table's scorer: a sequence's depth maps -> the cells of the reference's Table 1 ------------------------------
+ * python/eval/create_evaluation_table.py:14-62,121-163 with esl_utilities.py:153-175 (combine_mc3d), in one device call.  All
+ * maps are f32 [height][width]; min_depth / max_depth compare as float32 (the reference's 20 / 120).
+ *
+ *   combine(stack) : per pixel, maps in index order: d = v; if (d >= max_depth) d = 0; if (d <= min_depth) d = 0; acc += d (float32);
+ *                    cnt += d > 0.  mean = cnt == 0 ? 0 : acc / cnt, the correctly rounded float32 quotient.  (A NaN follows
+ *                    from these comparisons: acc turns NaN, cnt is untouched.)  combined = the 3 x 3 median of mean, borders
+ *                    replicated, the exact rank-4 value of the nine -- cv2.medianBlur(., 3) for finite values; a NaN in the
+ *                    window is unspecified.  avg_depth = sum(combined[combined > 0]) / #(combined > 0) in float64 (0 when no
+ *                    pixel is positive).
+ *   score          : mask = combine(gt stack).  Per scan s: g = load_and_filter(gt[s], mask) (:57-62: v >= max_depth -> 0,
+ *                    v <= min_depth -> 0, mask == 0 -> 0).  A method's row: e = load_and_filter(est[m][s], mask); its "1 sec" row:
+ *                    e = combine(est[m]), NOT filtered, the same map for every scan (:128,:151).  Then xm_eval_stats'
+ *                    arithmetic on (e, g): float32 difference and square, (double)|d| < margin with margin = 0.01 * sum(g[g > 0])
+ *                    / #(g > 0) in float64 (NaN when no g > 0), the thresholds 1 / 5 / 10, float64 sums.
+ * Every sum is made of per-tile partial sums folded in one fixed order: no atomics, no block that waits for another, a fixed
+ * schedule of launches with no readback.  A cell's bits therefore depend on the maps alone -- not on the run, on XM_MEM_HOST or
+ * XM_MEM_DEVICE, on the alignment of a pointer or on which other methods are in the call.  (xm_eval_stats, which accumulates
+ * with atomics, agrees to the last few bits of margin and RMSE and, where no pixel's error sits on the margin, in every count.)
+ * No xm_handle is involved; an object serves one thread at a time.  Synchronous. */
+typedef struct xm_eval_table_config { uint32_t struct_size; int32_t height, width; float min_depth, max_depth; uint32_t reserved; } xm_eval_table_config;
+typedef struct xm_eval_sums { double sum_gt, sum_sq; uint64_t n_gt_pos, n_gt_zero, n_close, n_valid, n1, n5, n10; } xm_eval_sums;
+typedef struct xm_eval_table xm_eval_table;
+/* XM_ERR_INVALID: NULL, struct_size mismatch, a non-positive dimension, height beyond 65535 * 8 */
+int xm_eval_table_create(int device, const xm_eval_table_config* cfg, xm_eval_table** out);
+void xm_eval_table_destroy(xm_eval_table* e);
+/* maps [n_maps][h][w] f32, host or device by `mem`; combined_out / mean_out (before the median; nullable) follow `mem`;
+   avg_depth_out (nullable) is host memory */
+int xm_eval_table_combine(xm_eval_table* e, const float* maps, int n_maps, int mem, float* combined_out, float* mean_out,
+                          double* avg_depth_out);
+/* gt [n_scans][h][w]; est: n_methods pointers (a host array) to [n_scans][h][w]; bit m of one_sec_mask adds a "1 sec" row for
+   method m.  Rows: methods 0..M-1, then the 1-sec rows by ascending m.  results_out / sums_out (nullable) are host arrays
+   [rows][n_scans]; mask_out (nullable, follows `mem`) is the combined ground truth; avg_depth_out (nullable, host) its mean depth.
+   The six floats of a result come from its sums through the same expressions as xm_eval_stats'.  1 <= n_methods <= 8; the bits
+   of one_sec_mask lie below n_methods; n_scans >= 1: otherwise, and for a NULL gt / est / est[m], XM_ERR_INVALID before any GPU
+   work.  XM_ERR_TOO_MANY: more than 65535 scans, or n_scans * h * w >= 2^40. */
+int xm_eval_table_score(xm_eval_table* e, const float* gt, const float* const* est, int n_methods, uint32_t one_sec_mask,
+                        int n_scans, int mem, xm_eval_result* results_out, xm_eval_sums* sums_out, float* mask_out,
+                        double* avg_depth_out);
+
 /* ---- pinned host memory for XM_MEM_HOST_PINNED ------------------------------------------------------------- */
 int xm_host_alloc(xm_handle* h, size_t bytes, void** out);
 int xm_host_free(xm_handle* h, void* p);

@@ -26,7 +26,9 @@ and the table's "ESL (init)" row is printed beside the X-maps one; with --mc3d t
 (compute_depth_esl.py:236).  `esl/depth_optim_filtered` still needs the bilateral and TV filters behind it: nothing is scored
 without them, and the report says so.  With --esl-filter (which implies --esl-optim) the optimisation's device buffer goes on
 through both filters (x_maps_amd/esl_filter.py) -> `<scans>/esl/depth_optim_filtered/scansNNN.npy` (:247), and every row is then
-scored against it.
+scored against it.  With --table-on-device the rows whose depth maps are on disk are scored once more, all of them in ONE
+device call (x_maps_amd.eval_table.sequence_table: every file read once, no NumPy arithmetic, the same bits every run), and
+reported as `table_1_on_device` beside the per-pair rows, which stay as they are.
 
 Tables come from the cv2-free builder (x_maps_amd/calibration.py: rectifying rotations pinned to OpenCV's on this calibration,
 map rounding unpinned): a difference from the published numbers on the real data is therefore a finding about that builder or
@@ -392,6 +394,9 @@ def main(argv=None):
                          "the TV denoiser, chained on the device behind the optimisation): the ground truth every row is scored against")
     ap.add_argument("--mc3d", action="store_true",
                     help="part B: also write <scans>/mc3d/depth/scansNNN.npy (the MC3D baseline on the device) and print its two rows")
+    ap.add_argument("--table-on-device", action="store_true",
+                    help="part B: also score every row whose depth maps are on disk in ONE device call (x_maps_amd.eval_table."
+                         "sequence_table) and report it as table_1_on_device, when the ground-truth directory exists")
     ap.add_argument("--min-depth", type=float, default=20)
     ap.add_argument("--max-depth", type=float, default=500, help="eval/x-map-eval.sh:72 passes 500 (the table script's own default is 120)")
     ap.add_argument("--save-frames", type=int, default=0, help="part A: keep the first N BGR frames as frame_NNN.npy beside --out")
@@ -451,6 +456,9 @@ def main(argv=None):
                 from x_maps_amd.eval_table import mc3d_table_rows
                 rows = mc3d_table_rows(a.scans, a.min_depth, a.max_depth, device=a.device)
                 report["table_1_row_mc3d"], report["table_1_row_mc3d_1s"] = rows["mc3d"], rows["mc3d_1s"]
+        if a.table_on_device and os.path.isdir(os.path.join(a.scans, "esl", "depth_optim_filtered")):
+            from x_maps_amd.eval_table import sequence_table
+            report["table_1_on_device"] = sequence_table(a.scans, a.min_depth, a.max_depth, device=a.device)
     txt = json.dumps(report, indent=1)
     print(txt)
     if a.out:

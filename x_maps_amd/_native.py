@@ -130,6 +130,16 @@ class xm_eval_result(C.Structure):
                 ("perc_10", C.c_double), ("margin", C.c_double), ("n_valid", C.c_uint64), ("n_gt_zero", C.c_uint64)]
 
 
+class xm_eval_table_config(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("height", C.c_int32), ("width", C.c_int32), ("min_depth", C.c_float),
+                ("max_depth", C.c_float), ("reserved", C.c_uint32)]
+
+
+class xm_eval_sums(C.Structure):
+    _fields_ = [("sum_gt", C.c_double), ("sum_sq", C.c_double), ("n_gt_pos", C.c_uint64), ("n_gt_zero", C.c_uint64),
+                ("n_close", C.c_uint64), ("n_valid", C.c_uint64), ("n1", C.c_uint64), ("n5", C.c_uint64), ("n10", C.c_uint64)]
+
+
 class xm_surface_stats(C.Structure):
     _fields_ = [("n_nonzero", C.c_uint64), ("n_events", C.c_uint64), ("n_inliers", C.c_uint64), ("n_index_errors", C.c_uint64),
                 ("lo", C.c_double), ("hi", C.c_double), ("t_min", C.c_double), ("t_max", C.c_double)]
@@ -309,6 +319,10 @@ SYMBOLS = {
     "xm_mc3d_create": (C.c_int, [C.c_int, C.POINTER(xm_mc3d_config), C.POINTER(_P)]),
     "xm_mc3d_destroy": (None, [_P]),
     "xm_mc3d_time_surfaces": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "xm_eval_table_create": (C.c_int, [C.c_int, C.POINTER(xm_eval_table_config), C.POINTER(_P)]),
+    "xm_eval_table_destroy": (None, [_P]),
+    "xm_eval_table_combine": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.POINTER(C.c_double)]),
+    "xm_eval_table_score": (C.c_int, [_P, _P, C.POINTER(_P), C.c_int, C.c_uint32, C.c_int, C.c_int, _P, _P, _P, C.POINTER(C.c_double)]),
     "xm_stream": (_P, [_P, C.c_int]),
     "xm_host_alloc": (C.c_int, [_P, C.c_size_t, C.POINTER(_P)]),
     "xm_host_free": (C.c_int, [_P, _P]),

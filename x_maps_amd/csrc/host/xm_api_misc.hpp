@@ -2,6 +2,23 @@
 // (part of libxmaps_hip.so's host side: included by ../xmaps_hip.hip, one translation unit; see that file for the order)
 #pragma once
 
+namespace {
+
+// the numbers of evaluation_stats (create_evaluation_table.py:18-42) from the sums over a map of hw pixels: what xm_eval_stats and
+// xm_eval_table_score both report
+void eval_result_from_sums(const EvalAcc& a, double hw, xm_eval_result* out) {
+  out->margin = 0.01 * a.sum_gt / (double)a.n_gt_pos;
+  out->fillrate = ((double)a.n_close - (double)a.n_gt_zero) / (hw - (double)a.n_gt_zero);
+  out->rmse = a.n_valid ? std::sqrt(a.sum_sq / (double)a.n_valid) : 0.0;
+  out->perc_1 = 100.0 * (double)a.n1 / hw;
+  out->perc_5 = 100.0 * (double)a.n5 / hw;
+  out->perc_10 = 100.0 * (double)a.n10 / hw;
+  out->n_valid = a.n_valid;
+  out->n_gt_zero = a.n_gt_zero;
+}
+
+}  // namespace
+
 extern "C" {
 
 // value == NULL removes the option; name == NULL removes all of them
@@ -95,15 +112,7 @@ int xm_eval_stats(int device, const float* estimate, const float* groundtruth, i
   if ((e = hipGetLastError()) != hipSuccess || (e = hipMemcpy(&a, d_a, sizeof a, hipMemcpyDeviceToHost)) != hipSuccess) {
     return fail(XM_ERR_HIP, "xm_eval_stats: %s", hipGetErrorString(e));
   }
-  const double hw = (double)n;
-  out->margin = 0.01 * a.sum_gt / (double)a.n_gt_pos;
-  out->fillrate = ((double)a.n_close - (double)a.n_gt_zero) / (hw - (double)a.n_gt_zero);
-  out->rmse = a.n_valid ? std::sqrt(a.sum_sq / (double)a.n_valid) : 0.0;
-  out->perc_1 = 100.0 * (double)a.n1 / hw;
-  out->perc_5 = 100.0 * (double)a.n5 / hw;
-  out->perc_10 = 100.0 * (double)a.n10 / hw;
-  out->n_valid = a.n_valid;
-  out->n_gt_zero = a.n_gt_zero;
+  eval_result_from_sums(a, (double)n, out);
   return XM_OK;
 }
 

@@ -1,4 +1,4 @@
-// xm_group.hpp -- the host skeleton of the group objects: ESL-init, MC3D, ESL depth optimisation, ESL filters
+// xm_group.hpp -- the host skeleton of the group objects: ESL-init, MC3D, ESL depth optimisation, ESL filters, evaluation table
 // (part of libxmaps_hip.so's host side: included by ../xmaps_hip.hip, one translation unit; see that file for the order)
 //
 // A group object is create(device, cfg) -> object, ONE synchronous call per group of maps on XM_MEM_HOST or XM_MEM_DEVICE
@@ -120,6 +120,7 @@ struct GroupCall {
     void* dst;
     const void* src;
     size_t bytes;
+    bool to_host;  // dst is host memory whatever the call's `mem` says
   };
   static constexpr int MAX_BACK = 6;  // (the filter's four copies back are the most there are)
   Copy backs[MAX_BACK];
@@ -148,11 +149,13 @@ struct GroupCall {
     return static_cast<T*>(buf.p);
   }
   // device memory of the object's that the caller may have asked for (stats, counters): copied to `user` by finish(), host or device
-  void back(void* user, const void* dev, size_t bytes) {
+  void back(void* user, const void* dev, size_t bytes, bool to_host = false) {
     if (!user || rc) return;
     if (n_back == MAX_BACK) rc = fail(XM_ERR_INVALID, "GroupCall: more than %d copies back", MAX_BACK);
-    else backs[n_back++] = Copy{user, dev, bytes};
+    else backs[n_back++] = Copy{user, dev, bytes, to_host};
   }
+  // device memory of the object's that the HOST goes on to use, also in a call on device pointers (the sums a result is made of)
+  void back_host(void* host_dst, const void* dev, size_t bytes) { back(host_dst, dev, bytes, true); }
   // the scratch grows; a call that stops here (or in in() / out()) waits for the copies in it has enqueued, which read the caller's memory
   int start(std::initializer_list<BufNeed> scratch) {
     if (!rc) rc = reserve_all(scratch);
@@ -161,7 +164,7 @@ struct GroupCall {
   }
   int finish() {
     for (int i = 0; i < n_back && !rc; ++i)
-      rc = copy(backs[i].dst, backs[i].src, backs[i].bytes, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice);
+      rc = copy(backs[i].dst, backs[i].src, backs[i].bytes, host || backs[i].to_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice);
     HIP_TRY(hipStreamSynchronize(stream));
     return rc;
   }

@@ -85,6 +85,12 @@ constexpr unsigned MC3D_NO_BLUR = 1;  // == XM_MC3D_NO_BLUR
 constexpr int ESLF_BW = 32, ESLF_BH = BLOCK / ESLF_BW, ESLF_HALO = 2, ESLF_MAX_TAPS = 25, ESLF_BINS = 4096;
 constexpr int ESLF_RED_CHUNK = BLOCK * 8, ESLF_TILE = BLOCK * 4;
 constexpr unsigned ESLF_NO_BILATERAL = 1, ESLF_NO_TV = 2;  // == XM_ESL_FILTER_*
+// Evaluation table (xmaps_evaltable.hpp).  The streams are cut into flat tiles of EVT_TILE pixels: a thread takes EVT_UN quads of
+// four consecutive pixels (16-byte loads where the maps allow them).  The tile is the unit of every partial sum, so it fixes the
+// summation order: the last bits of a margin or an RMSE move with it.  Median: a block takes EVT_MW x EVT_MH pixels.
+constexpr int EVT_UN = 4, EVT_TILE = BLOCK * 4 * EVT_UN;
+constexpr int EVT_MW = 32, EVT_MH = BLOCK / EVT_MW;
+constexpr int EVT_MAX_METHODS = 8, EVT_MAX_ROWS = 2 * EVT_MAX_METHODS, EVT_MAX_STACKS = 1 + EVT_MAX_METHODS;  // every method may add a "1 sec" row
 // ... its search key: 1 + (min(cost, max_row_diff + 1) << pos_bits | position in a window of `span` entries), 0 = poison, in 32 bits
 XM_HD constexpr unsigned mc3d_pos_bits(unsigned span) {
   unsigned b = 0;

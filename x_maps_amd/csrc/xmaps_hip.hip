@@ -76,3 +76,4 @@ using namespace xm;
 #include "host/xm_api_mc3d.hpp"     // the MC3D baseline on the same surfaces
 #include "host/xm_api_esloptim.hpp" // the ESL depth optimisation behind ESL-init: depth_optim maps
 #include "host/xm_api_eslfilter.hpp" // the bilateral filter and the TV denoiser behind it: depth_optim_filtered maps
+#include "host/xm_api_evaltable.hpp" // the evaluation table's scorer: ground truth + every method's maps -> the cells of Table 1

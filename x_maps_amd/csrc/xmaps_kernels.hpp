@@ -36,3 +36,4 @@
 #include "xmaps_mc3d.hpp"       // the MC3D baseline: median, projector-column window search and depth per camera pixel
 #include "xmaps_esloptim.hpp"   // the ESL depth optimisation: one bounded scalar minimisation per camera pixel
 #include "xmaps_eslfilter.hpp"  // the ESL filters behind it: bilateral filter and TV denoiser (split Bregman around lsqr)
+#include "xmaps_evaltable.hpp"  // the evaluation table's scorer: combine, median, the metrics of every (method, scan) cell

@@ -15,14 +15,21 @@ reference's evaluation leaves it:
 
 The metrics themselves run on the GPU (x_maps_amd.eval_metrics, pinned by golden G8); what is restated here is the file-level
 recipe: the per-pixel mean of the filtered ground-truth scans, median-filtered 3 x 3 (cv2.medianBlur: unpinned against a cv2
-run -- OpenCV is not in this image -- replicate border, exact median of nine), as the mask every map is filtered with."""
+run -- OpenCV is not in this image -- replicate border, exact median of nine), as the mask every map is filtered with.
+
+EvalTable / sequence_table (at the end) are the same table from ONE device call: combine, median, filters and the metrics of every
+(method, scan) cell and of the "1 sec" rows on the GPU (xm_eval_table_*), with sums folded in a fixed order.  The functions above
+them stay as the per-pair path and as the NumPy yardstick the tests hold that call to."""
 from __future__ import annotations
 
+import ctypes as C
 import glob
 import os
 
 import numpy as np
 
+from . import _native as N
+from ._group import GroupObject, map_group, ptr as _ptr, stats_dtype
 from .eval_metrics import evaluation_stats
 
 
@@ -124,3 +131,123 @@ def mc3d_table_rows(seq_dir: str, min_depth: float = 20, max_depth: float = 120,
     return {"mc3d": row,
             "mc3d_1s": {"scans": len(rows), "mean_depth": round(avg_depth, 3), "fill_rate": float(fr), "rmse": float(rmse),
                         "table_cell": f"{round(float(fr), 2)} & {round(float(rmse), 2)}"}}
+
+
+# ---- the same table from ONE device call (xm_eval_table_*; kernels in csrc/xmaps_evaltable.hpp, the contract in include/xmaps.h) ----
+
+RESULT_DTYPE = stats_dtype(N.xm_eval_result)
+SUMS_DTYPE = stats_dtype(N.xm_eval_sums)
+MAX_METHODS = 8
+
+
+class EvalTableScore:
+    """What EvalTable.score returns.  rows: the row names (the methods as given, then "<name>_1s" for every 1-sec row, in the
+    methods' order); results / sums: structured arrays [rows][scans] of xm_eval_result / xm_eval_sums; mask: the combined
+    ground truth (None from score_device); avg_depth: its mean depth."""
+    __slots__ = ("rows", "results", "sums", "mask", "avg_depth")
+
+    def __init__(self, rows, results, sums, mask, avg_depth):
+        self.rows, self.results, self.sums, self.mask, self.avg_depth = rows, results, sums, mask, avg_depth
+
+    def row(self, name):
+        """the [scans] results of one row"""
+        return self.results[self.rows.index(name)]
+
+    def mean_fill_rate_and_rmse(self, name):
+        """create_evaluation_table.py:160-163: np.mean(np.array(rows), axis=0) over the scans"""
+        r = self.row(name)
+        fr, rmse = np.mean(np.array(list(zip(r["fillrate"], r["rmse"])), np.float64), axis=0)
+        return float(fr), float(rmse)
+
+
+class EvalTable(GroupObject):
+    """with EvalTable(height, width, min_depth, max_depth) as t: score = t.score(gt_maps, {"x_maps": maps, "mc3d": maps}, one_sec=("mc3d",))
+
+    combine_depth_maps, load_and_filter and evaluation_stats of every (method, scan) pair -- and of the "1 sec" rows, whose
+    estimate is a method's combined map -- in one device call; no NumPy arithmetic, the same bits every run."""
+    _destroy = "xm_eval_table_destroy"
+
+    def __init__(self, height: int, width: int, min_depth: float = 20, max_depth: float = 120, device: int = 0):
+        self.height, self.width = int(height), int(width)
+        cfg = N.xm_eval_table_config(C.sizeof(N.xm_eval_table_config), self.height, self.width, float(min_depth), float(max_depth), 0)
+        self._create("xm_eval_table_create", device, cfg)
+
+    def combine(self, maps, want_mean: bool = False):
+        """combine_depth_maps on the device -> (combined, avg_depth[, the mean before the median])"""
+        grp = map_group(maps, self.height, self.width, np.float32)
+        comb = np.empty((self.height, self.width), np.float32)
+        mean = np.empty((self.height, self.width), np.float32) if want_mean else None
+        avg = C.c_double()
+        N.check(self._lib.xm_eval_table_combine(self._h, _ptr(grp), grp.shape[0], N.XM_MEM_HOST, _ptr(comb), _ptr(mean), C.byref(avg)))
+        return (comb, avg.value, mean) if want_mean else (comb, avg.value)
+
+    @staticmethod
+    def _rows(names, one_sec):
+        names = list(names)
+        unknown = [n for n in one_sec if n not in names]
+        if unknown:
+            raise ValueError(f"one_sec names no method: {unknown}")
+        bits = sum(1 << i for i, n in enumerate(names) if n in one_sec)
+        return names + [f"{n}_1s" for n in names if n in one_sec], bits
+
+    def _call(self, gt_ptr, est_ptrs, n_scans, bits, n_rows, mem, mask_ptr):
+        results = np.zeros((n_rows, n_scans), RESULT_DTYPE)
+        sums = np.zeros((n_rows, n_scans), SUMS_DTYPE)
+        avg = C.c_double()
+        est = (C.c_void_p * len(est_ptrs))(*est_ptrs)
+        N.check(self._lib.xm_eval_table_score(self._h, gt_ptr, est, len(est_ptrs), bits, int(n_scans), mem, _ptr(results), _ptr(sums),
+                                              mask_ptr, C.byref(avg)))
+        return results, sums, avg.value
+
+    def score(self, gt, methods: dict, one_sec=()) -> EvalTableScore:
+        """gt: the ground-truth scans (a list of [height][width] maps or one 3-D array); methods: {name: the estimates, scan by scan};
+        one_sec: the names of the methods that also get a "1 sec" row"""
+        g = map_group(gt, self.height, self.width, np.float32, "ground-truth maps")
+        stacks = [map_group(m, self.height, self.width, np.float32, f"{name} maps") for name, m in methods.items()]
+        for name, s in zip(methods, stacks):
+            if s.shape[0] != g.shape[0]:
+                raise ValueError(f"{name}: {s.shape[0]} maps for {g.shape[0]} ground-truth scans")
+        rows, bits = self._rows(methods, tuple(one_sec))
+        mask = np.empty((self.height, self.width), np.float32)
+        results, sums, avg = self._call(_ptr(g), [s.ctypes.data for s in stacks], g.shape[0], bits, len(rows), N.XM_MEM_HOST, _ptr(mask))
+        return EvalTableScore(rows, results, sums, mask, avg)
+
+    def score_device(self, gt_ptr, est_ptrs: dict, n_scans: int, one_sec=(), mask_ptr=None) -> EvalTableScore:
+        """the same on device memory of this object's device (raw pointers to [n_scans][height][width] float32; synchronous)"""
+        rows, bits = self._rows(est_ptrs, tuple(one_sec))
+        results, sums, avg = self._call(gt_ptr, [int(p) for p in est_ptrs.values()], n_scans, bits, len(rows), N.XM_MEM_DEVICE, mask_ptr)
+        return EvalTableScore(rows, results, sums, None, avg)
+
+
+SEQUENCE_METHODS = (("x_maps", ("x_maps", "depth_init"), "x_maps_files"), ("esl_init", ("esl", "depth_init"), "esl_init_files"),
+                    ("mc3d", ("mc3d", "depth"), "mc3d_files"))
+
+
+def sequence_table(seq_dir: str, min_depth: float = 20, max_depth: float = 120, device: int = 0) -> dict:
+    """x_maps_table_row, esl_init_table_row and mc3d_table_rows of one sequence directory from ONE device call: every file of the
+    four directories is read once, nothing is combined or filtered in NumPy.  -> {"x_maps": row, "esl_init": row, "mc3d": row,
+    "mc3d_1s": row}, the rows shaped like depth_table_row's (a method whose files are missing gets that function's error row)."""
+    gt_files = sorted(glob.glob(os.path.join(seq_dir, "esl", "depth_optim_filtered", "*.npy")))
+    out, stacks = {}, {}
+    for name, sub, files_key in SEQUENCE_METHODS:
+        est_files = sorted(glob.glob(os.path.join(seq_dir, *sub, "*.npy")))
+        if not gt_files:
+            out[name] = {"error": f"no ground truth under {os.path.join(seq_dir, 'esl', 'depth_optim_filtered')} (the reference's "
+                                  f"compute_depth_esl.py writes it: esl/depth_optim, which x_maps_amd.esl_optim computes, behind the bilateral "
+                                  f"and TV filters: x_maps_amd.esl_filter, tools/run_esl_on_arrival.py --esl-filter)", files_key: len(est_files)}
+        elif len(gt_files) != len(est_files):
+            out[name] = {"error": "frames are missing", "gt_files": len(gt_files), files_key: len(est_files)}
+        else:
+            stacks[name] = [np.load(f).astype(np.float32, copy=False) for f in est_files]
+    if stacks:
+        gt = [np.load(f).astype(np.float32, copy=False) for f in gt_files]
+        h, w = gt[0].shape
+        with EvalTable(h, w, min_depth, max_depth, device=device) as table:
+            score = table.score(gt, stacks, one_sec=("mc3d",) if "mc3d" in stacks else ())
+        for name in score.rows:
+            fr, rmse = score.mean_fill_rate_and_rmse(name)
+            out[name] = {"scans": len(gt), "mean_depth": round(score.avg_depth, 3), "fill_rate": fr, "rmse": rmse,
+                         "table_cell": f"{round(fr, 2)} & {round(rmse, 2)}"}
+    if "mc3d_1s" not in out:
+        out["mc3d_1s"] = dict(out["mc3d"])
+    return {k: out[k] for k in ("x_maps", "esl_init", "mc3d", "mc3d_1s")}
