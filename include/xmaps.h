@@ -448,6 +448,95 @@ void* xm_stream(xm_handle* h, int slot);
 int xm_build_x_map(int device, const float* time_map, int height, int width, int x_map_width, int t_px_scale,
                    int x_offset, int num_scanlines, int16_t* x_map_out, float* t_diffs_out);
 
+/* ---- a rig's rectification maps, time map and X-map on the device ------------------------------------------------------
+ * x_maps_amd/calibration.py's init_undistort_rectify_map, init_undistort_rectify_map_inverse, mapf_to_i16 and remap_nearest
+ * (with esl_init._pair_i16 and the linear projector time map), one thread per pixel, float64, every float32 bit equal to that
+ * NumPy code's (csrc/xmaps_rigmaps.hpp states the evaluation order; the pin is to the project's NumPy, not to OpenCV).
+ * stereo_rectify, rodrigues and the 3 x 3 inverse stay with the caller.  Like xm_build_x_map these take a device ordinal, no
+ * xm_handle, and are synchronous.  mem == XM_MEM_HOST: every pointer of cfg / outputs is host memory; XM_MEM_DEVICE: device
+ * memory of `device`.  Matrices are row-major; K = (fx, fy, cx, cy); D = (k1, k2, p1, p2, k3).  Every output is nullable; at
+ * least one must be asked for.  kernel_ms (written by the call): the kernel's time between two HIP events. */
+#define XM_RIG_BORDER_CONSTANT 0
+#define XM_RIG_BORDER_REPLICATE 1
+#define XM_RIG_SRC_NONE 0
+#define XM_RIG_SRC_IMAGE 1       /* src: f32 [src_height][src_width] */
+#define XM_RIG_SRC_LINEAR_TIME 2 /* generate_linear_projector_time_map(src_width, src_height, scan_upwards), evaluated at the
+                                    gathered pixel: (float)((double)(col * H + row') / (double)(W * H)), row' = H - 1 - row when
+                                    scan_upwards; no table exists (esl_init.get_projector_time_surface: scan_upwards = 0) */
+/* Forward map (rectified pixel -> source pixel) of a width x height target frame; ir = inv(P[:3,:3] @ R).  With mapx_in / mapy_in
+ * (both or neither; f32 [height][width], follow `mem`) the map is read instead of computed: remap_nearest on a caller's map.
+ * remap: src sampled at (rint(mapx), rint(mapy)), half to even.  XM_RIG_BORDER_CONSTANT: border_value where that pixel is
+ * outside the source (NaN, +-inf and values beyond int32 are outside).  XM_RIG_BORDER_REPLICATE: clamped by sign, NaN to the
+ * first row / column (NumPy's own result is undefined for NaN, +-inf and beyond int64).  pair_i16: interleaved (x, y), NaN ->
+ * -32768, everything else clipped to int16, then rint.  src_width, src_height <= 2^24; width * height < 2^31. */
+typedef struct xm_rig_forward_config {
+  uint32_t struct_size; /* sizeof(xm_rig_forward_config) */
+  int32_t width, height;
+  int32_t src_kind, src_width, src_height, border, scan_upwards;
+  float border_value;
+  uint32_t reserved;
+  double K[4], D[5], ir[9];
+  const float* src;
+  const float* mapx_in;
+  const float* mapy_in;
+} xm_rig_forward_config;
+typedef struct xm_rig_forward_outputs {
+  float* mapx;
+  float* mapy;
+  int16_t* pair_i16; /* [height][width][2]; 4-byte aligned */
+  float* remap;
+  float kernel_ms;
+  uint32_t reserved;
+} xm_rig_forward_outputs;
+int xm_rig_forward_map(int device, const xm_rig_forward_config* cfg, xm_rig_forward_outputs* outputs, int mem);
+/* Inverse map (source pixel -> rectified coordinates) of a width x height source frame: undistort_points on the float32 pixel
+ * coordinate (five fixed-point rounds), rotated by R, projected with P = (P00, P11, P02, P12).  mapx_i16 / mapy_i16 / pair_i16:
+ * rint, half to even; an entry outside int16 (or NaN) is XM_ERR_INVALID naming the map -- mapf_to_i16's assertion; the float
+ * maps of such a call are still written for XM_MEM_DEVICE. */
+typedef struct xm_rig_inverse_config {
+  uint32_t struct_size; /* sizeof(xm_rig_inverse_config) */
+  int32_t width, height;
+  uint32_t reserved;
+  double K[4], D[5], R[9], P[4];
+} xm_rig_inverse_config;
+typedef struct xm_rig_inverse_outputs {
+  float* mapx;
+  float* mapy;
+  int16_t* mapx_i16;
+  int16_t* mapy_i16;
+  int16_t* pair_i16; /* [height][width][2]; 4-byte aligned */
+  float kernel_ms;
+  uint32_t reserved;
+} xm_rig_inverse_outputs;
+int xm_rig_inverse_map(int device, const xm_rig_inverse_config* cfg, xm_rig_inverse_outputs* outputs, int mem);
+/* calibration.build_tables' chain in one call: the projector's forward map -> the linear time map sampled through it
+ * (time_map_rect, left in device memory) -> xm_build_x_map's kernels on that buffer -> the X-map; the camera's inverse map as
+ * f32 and int16, the projector's as an interleaved int16 pair.  time_map_rect_in (nullable, f32 [rect_height][rect_width]): a
+ * caller-supplied rectified time map, uploaded instead of the forward map.  Every pointer is HOST memory, every output is
+ * required; only these arrays come back.  The X-map's arguments and limits are xm_build_x_map's.  kernel_ms: forward map (0
+ * with time_map_rect_in), X-map, camera inverse map, projector inverse map. */
+typedef struct xm_rig_tables_config {
+  uint32_t struct_size; /* sizeof(xm_rig_tables_config) */
+  int32_t cam_width, cam_height, proj_width, proj_height, rect_width, rect_height;
+  int32_t scan_upwards, border, x_map_width, t_px_scale, x_offset, num_scanlines;
+  uint32_t reserved;
+  double cam_K[4], cam_D[5], cam_R[9], cam_P[4];     /* camera inverse map */
+  double proj_K[4], proj_D[5], proj_R[9], proj_P[4]; /* projector inverse map */
+  double proj_fwd_D[5], proj_ir[9];                  /* projector forward map (its K is proj_K) */
+  const float* time_map_rect_in;
+} xm_rig_tables_config;
+typedef struct xm_rig_tables_outputs {
+  float* time_map_rect;       /* [rect_height][rect_width] */
+  int16_t* x_map;             /* [rect_height][x_map_width] */
+  float* cam_mapx_f32;        /* [cam_height][cam_width], like the next three */
+  float* cam_mapy_f32;
+  int16_t* cam_mapx_i16;
+  int16_t* cam_mapy_i16;
+  int16_t* proj_mapxy_i16;    /* [proj_height][proj_width][2] */
+  float kernel_ms[4];
+} xm_rig_tables_outputs;
+int xm_rig_build_xmaps_tables(int device, const xm_rig_tables_config* cfg, xm_rig_tables_outputs* outputs);
+
 /* ---- evaluation metrics ("next" row N4), python/eval/create_evaluation_table.py:14-63 --------------------------------- */
 /* evaluation_stats(estimate, groundtruth) on two f32 depth maps [height][width] (host pointers, synchronous, no handle):
  * fill rate, RMSE, % of pixels off by more than 1 / 5 / 10 (the script's unit is cm), and the margin (1 % of the mean

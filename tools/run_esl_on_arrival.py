@@ -122,7 +122,7 @@ def write_ply(path, pts):
 
 
 def depth_from_scans(object_dir, eval_calib, proj_w, proj_h, num_scans=0, start_scan=0, point_clouds=False, device=0, tables=None,
-                     surfaces_on_device=False, group=8):
+                     surfaces_on_device=False, group=8, tables_on_device=False):
     """Part B, first half: compute_depth_x_maps.py:22-133.  -> report
     surfaces_on_device: the scans go through the time-surface entry in groups of `group` (surfaces in, depth maps and clouds out
     in one device call each) instead of one scan at a time through the stage sequence; same files."""
@@ -141,7 +141,7 @@ def depth_from_scans(object_dir, eval_calib, proj_w, proj_h, num_scans=0, start_
     t0 = time.perf_counter()
     if tables is None:
         cp = C.CamProjCalibrationParams.from_ESL_yaml(eval_calib, 640, 480, proj_w, proj_h)
-        tables = C.build_eval_tables(cp, device=device)
+        tables = C.build_eval_tables(cp, device=device, maps_on_device=tables_on_device)
     maps = CamProjMaps(tables, camera_perspective=True, device=device)
     xd = XMapsDisparity(maps)
     t_setup = time.perf_counter() - t0
@@ -234,7 +234,8 @@ def baseline_from_scans(object_dir, depth_dir, make_object, num_scans, start_sca
 ESL_INIT_UNPINNED = "the int16 rounding of the two remap tables (np.rint) has not been compared with a cv2.remap run"
 
 
-def esl_init_from_scans(object_dir, eval_calib, proj_w, proj_h, num_scans=0, start_scan=0, device=0, tables=None, group=8):
+def esl_init_from_scans(object_dir, eval_calib, proj_w, proj_h, num_scans=0, start_scan=0, device=0, tables=None, group=8,
+                        tables_on_device=False):
     """Part B for the baseline: compute_depth_esl.py:179-226 up to depth_init.  Every scan of <scans>/scans_np through
     x_maps_amd.esl_init in groups of `group` -> <scans>/esl/depth_init/scansNNN.npy (an all-zero scan is skipped, :205).  -> report"""
     from x_maps_amd import calibration as C
@@ -242,7 +243,8 @@ def esl_init_from_scans(object_dir, eval_calib, proj_w, proj_h, num_scans=0, sta
     depth_dir = os.path.join(object_dir, "esl", "depth_init")
 
     def make():
-        t = build_esl_init_tables(C.CamProjCalibrationParams.from_ESL_yaml(eval_calib, 640, 480, proj_w, proj_h)) if tables is None else tables
+        t = build_esl_init_tables(C.CamProjCalibrationParams.from_ESL_yaml(eval_calib, 640, 480, proj_w, proj_h),
+                                  maps_on_device=tables_on_device, device=device) if tables is None else tables
         return EslInit(t, device=device)
 
     return baseline_from_scans(object_dir, depth_dir, make, num_scans, start_scan, group, "ms_per_scan_depth_init",
@@ -250,7 +252,7 @@ def esl_init_from_scans(object_dir, eval_calib, proj_w, proj_h, num_scans=0, sta
 
 
 def esl_optim_from_scans(object_dir, eval_calib, proj_w, proj_h, num_scans=0, start_scan=0, device=0, init_tables=None,
-                         optim_tables=None, group=8, esl_filter=False):
+                         optim_tables=None, group=8, esl_filter=False, tables_on_device=False):
     """Part B for the ground truth's solver: compute_depth_esl.py:204-236.  Every scan of <scans>/scans_np through x_maps_amd.esl_init
     and, chained on the device, x_maps_amd.esl_optim in groups of `group` -> <scans>/esl/depth_init/scansNNN.npy and
     <scans>/esl/depth_optim/scansNNN.npy (an all-zero scan is skipped, :205).  esl_filter: the optimisation's device buffer goes on
@@ -276,7 +278,7 @@ def esl_optim_from_scans(object_dir, eval_calib, proj_w, proj_h, num_scans=0, st
     t0 = time.perf_counter()
     if init_tables is None or optim_tables is None:
         cp = C.CamProjCalibrationParams.from_ESL_yaml(eval_calib, 640, 480, proj_w, proj_h)
-        init_tables = build_esl_init_tables(cp) if init_tables is None else init_tables
+        init_tables = build_esl_init_tables(cp, maps_on_device=tables_on_device, device=device) if init_tables is None else init_tables
         optim_tables = build_esl_optim_tables(cp) if optim_tables is None else optim_tables
     dev = torch.device("cuda", device)
     per_init, per_optim, skipped, filled_init, filled_optim = [], [], 0, [], []
@@ -347,7 +349,8 @@ def esl_optim_from_scans(object_dir, eval_calib, proj_w, proj_h, num_scans=0, st
     return rep_init, rep_optim, rep_filter
 
 
-def mc3d_from_scans(object_dir, eval_calib, proj_w, proj_h, num_scans=0, start_scan=0, device=0, tables=None, group=8):
+def mc3d_from_scans(object_dir, eval_calib, proj_w, proj_h, num_scans=0, start_scan=0, device=0, tables=None, group=8,
+                    tables_on_device=False):
     """Part B for the other baseline: mc3d_baseline.py:116-140.  Every scan of <scans>/scans_np through x_maps_amd.mc3d in groups
     of `group` -> <scans>/mc3d/depth/scansNNN.npy (an all-zero scan is skipped, :129).  -> report"""
     from x_maps_amd import calibration as C
@@ -355,7 +358,8 @@ def mc3d_from_scans(object_dir, eval_calib, proj_w, proj_h, num_scans=0, start_s
     depth_dir = os.path.join(object_dir, "mc3d", "depth")
 
     def make():
-        t = build_mc3d_tables(C.CamProjCalibrationParams.from_ESL_yaml(eval_calib, 640, 480, proj_w, proj_h)) if tables is None else tables
+        t = build_mc3d_tables(C.CamProjCalibrationParams.from_ESL_yaml(eval_calib, 640, 480, proj_w, proj_h),
+                              maps_on_device=tables_on_device, device=device) if tables is None else tables
         return Mc3d(t, device=device)
 
     return baseline_from_scans(object_dir, depth_dir, make, num_scans, start_scan, group, "ms_per_scan_depth",
@@ -397,6 +401,9 @@ def main(argv=None):
     ap.add_argument("--table-on-device", action="store_true",
                     help="part B: also score every row whose depth maps are on disk in ONE device call (x_maps_amd.eval_table."
                          "sequence_table) and report it as table_1_on_device, when the ground-truth directory exists")
+    ap.add_argument("--tables-on-device", action="store_true",
+                    help="part B: build every table set (X-maps, ESL-init, MC3D) with its maps on the device (maps_on_device=True: "
+                         "x_maps_amd.rig_maps, the same tables bit for bit)")
     ap.add_argument("--min-depth", type=float, default=20)
     ap.add_argument("--max-depth", type=float, default=500, help="eval/x-map-eval.sh:72 passes 500 (the table script's own default is 120)")
     ap.add_argument("--save-frames", type=int, default=0, help="part A: keep the first N BGR frames as frame_NNN.npy beside --out")
@@ -425,7 +432,8 @@ def main(argv=None):
             ap.error("--scans needs --eval-calib (the ESL dataset's calib.yaml)")
         report["depth_from_scans"] = depth_from_scans(a.scans, a.eval_calib, a.projector_width, a.projector_height, a.num_scans,
                                                       a.start_scan, a.point_clouds, a.device,
-                                                      surfaces_on_device=a.surfaces_on_device, group=a.surface_group)
+                                                      surfaces_on_device=a.surfaces_on_device, group=a.surface_group,
+                                                      tables_on_device=a.tables_on_device)
         if "error" not in report["depth_from_scans"]:
             from x_maps_amd.eval_table import x_maps_table_row
             row = x_maps_table_row(a.scans, a.min_depth, a.max_depth, device=a.device)
@@ -434,24 +442,27 @@ def main(argv=None):
         if a.esl_filter:
             report["esl_init_from_scans"], report["esl_optim_from_scans"], report["esl_filter_from_scans"] = esl_optim_from_scans(
                 a.scans, a.eval_calib, a.projector_width, a.projector_height, a.num_scans, a.start_scan, a.device, group=a.surface_group,
-                esl_filter=True)
+                esl_filter=True, tables_on_device=a.tables_on_device)
             if "table_1_row_x_maps" in report:  # (the ground truth exists only now)
                 row = x_maps_table_row(a.scans, a.min_depth, a.max_depth, device=a.device)
                 row["published_cell_seq1"] = "{fill_rate} & {rmse_cm}".format(**PUBLISHED["seq1_book_duck"])
                 report["table_1_row_x_maps"] = row
         elif a.esl_optim:
             report["esl_init_from_scans"], report["esl_optim_from_scans"] = esl_optim_from_scans(
-                a.scans, a.eval_calib, a.projector_width, a.projector_height, a.num_scans, a.start_scan, a.device, group=a.surface_group)
+                a.scans, a.eval_calib, a.projector_width, a.projector_height, a.num_scans, a.start_scan, a.device, group=a.surface_group,
+                tables_on_device=a.tables_on_device)
         elif a.esl_init:
             report["esl_init_from_scans"] = esl_init_from_scans(a.scans, a.eval_calib, a.projector_width, a.projector_height,
-                                                                a.num_scans, a.start_scan, a.device, group=a.surface_group)
+                                                                a.num_scans, a.start_scan, a.device, group=a.surface_group,
+                                                                tables_on_device=a.tables_on_device)
         if a.esl_init or a.esl_optim or a.esl_filter:
             if "error" not in report["esl_init_from_scans"]:
                 from x_maps_amd.eval_table import esl_init_table_row
                 report["table_1_row_esl_init"] = esl_init_table_row(a.scans, a.min_depth, a.max_depth, device=a.device)
         if a.mc3d:
             report["mc3d_from_scans"] = mc3d_from_scans(a.scans, a.eval_calib, a.projector_width, a.projector_height, a.num_scans,
-                                                        a.start_scan, a.device, group=a.surface_group)
+                                                        a.start_scan, a.device, group=a.surface_group,
+                                                        tables_on_device=a.tables_on_device)
             if "error" not in report["mc3d_from_scans"]:
                 from x_maps_amd.eval_table import mc3d_table_rows
                 rows = mc3d_table_rows(a.scans, a.min_depth, a.max_depth, device=a.device)

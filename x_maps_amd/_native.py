@@ -140,6 +140,49 @@ class xm_eval_sums(C.Structure):
                 ("n_close", C.c_uint64), ("n_valid", C.c_uint64), ("n1", C.c_uint64), ("n5", C.c_uint64), ("n10", C.c_uint64)]
 
 
+XM_RIG_BORDER_CONSTANT, XM_RIG_BORDER_REPLICATE = 0, 1
+XM_RIG_SRC_NONE, XM_RIG_SRC_IMAGE, XM_RIG_SRC_LINEAR_TIME = 0, 1, 2
+
+
+class xm_rig_forward_config(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32), ("src_kind", C.c_int32),
+                ("src_width", C.c_int32), ("src_height", C.c_int32), ("border", C.c_int32), ("scan_upwards", C.c_int32),
+                ("border_value", C.c_float), ("reserved", C.c_uint32),
+                ("K", C.c_double * 4), ("D", C.c_double * 5), ("ir", C.c_double * 9),
+                ("src", C.c_void_p), ("mapx_in", C.c_void_p), ("mapy_in", C.c_void_p)]
+
+
+class xm_rig_forward_outputs(C.Structure):
+    _fields_ = [("mapx", C.c_void_p), ("mapy", C.c_void_p), ("pair_i16", C.c_void_p), ("remap", C.c_void_p),
+                ("kernel_ms", C.c_float), ("reserved", C.c_uint32)]
+
+
+class xm_rig_inverse_config(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32), ("reserved", C.c_uint32),
+                ("K", C.c_double * 4), ("D", C.c_double * 5), ("R", C.c_double * 9), ("P", C.c_double * 4)]
+
+
+class xm_rig_inverse_outputs(C.Structure):
+    _fields_ = [("mapx", C.c_void_p), ("mapy", C.c_void_p), ("mapx_i16", C.c_void_p), ("mapy_i16", C.c_void_p),
+                ("pair_i16", C.c_void_p), ("kernel_ms", C.c_float), ("reserved", C.c_uint32)]
+
+
+class xm_rig_tables_config(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("cam_width", C.c_int32), ("cam_height", C.c_int32), ("proj_width", C.c_int32),
+                ("proj_height", C.c_int32), ("rect_width", C.c_int32), ("rect_height", C.c_int32),
+                ("scan_upwards", C.c_int32), ("border", C.c_int32), ("x_map_width", C.c_int32), ("t_px_scale", C.c_int32),
+                ("x_offset", C.c_int32), ("num_scanlines", C.c_int32), ("reserved", C.c_uint32),
+                ("cam_K", C.c_double * 4), ("cam_D", C.c_double * 5), ("cam_R", C.c_double * 9), ("cam_P", C.c_double * 4),
+                ("proj_K", C.c_double * 4), ("proj_D", C.c_double * 5), ("proj_R", C.c_double * 9), ("proj_P", C.c_double * 4),
+                ("proj_fwd_D", C.c_double * 5), ("proj_ir", C.c_double * 9), ("time_map_rect_in", C.c_void_p)]
+
+
+class xm_rig_tables_outputs(C.Structure):
+    _fields_ = [("time_map_rect", C.c_void_p), ("x_map", C.c_void_p), ("cam_mapx_f32", C.c_void_p), ("cam_mapy_f32", C.c_void_p),
+                ("cam_mapx_i16", C.c_void_p), ("cam_mapy_i16", C.c_void_p), ("proj_mapxy_i16", C.c_void_p),
+                ("kernel_ms", C.c_float * 4)]
+
+
 class xm_surface_stats(C.Structure):
     _fields_ = [("n_nonzero", C.c_uint64), ("n_events", C.c_uint64), ("n_inliers", C.c_uint64), ("n_index_errors", C.c_uint64),
                 ("lo", C.c_double), ("hi", C.c_double), ("t_min", C.c_double), ("t_max", C.c_double)]
@@ -303,6 +346,9 @@ SYMBOLS = {
     "xm_ingest_push_evt2": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_int, C.POINTER(C.c_size_t)]),
     "xm_eval_stats": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.POINTER(xm_eval_result)]),
     "xm_build_x_map": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "xm_rig_forward_map": (C.c_int, [C.c_int, C.POINTER(xm_rig_forward_config), C.POINTER(xm_rig_forward_outputs), C.c_int]),
+    "xm_rig_inverse_map": (C.c_int, [C.c_int, C.POINTER(xm_rig_inverse_config), C.POINTER(xm_rig_inverse_outputs), C.c_int]),
+    "xm_rig_build_xmaps_tables": (C.c_int, [C.c_int, C.POINTER(xm_rig_tables_config), C.POINTER(xm_rig_tables_outputs)]),
     "xm_surface_set_cloud_tables": (C.c_int, [_P, _P, _P, _P]),
     "xm_process_time_surfaces": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "xm_esl_init_create": (C.c_int, [C.c_int, C.POINTER(xm_esl_init_config), C.POINTER(_P)]),

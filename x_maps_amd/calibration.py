@@ -10,7 +10,8 @@ principal points, map rounding at exact .5) is checked for geometric self-consis
 forward/inverse round trip) -- "parity unpinned" against cv2, see DESIGN.md.
 
 Host-side NumPy, runs once per session; the heavy step (X-map from the rectified time map) goes to the GPU
-(x_maps_amd.x_map.compute_x_map_from_time_map).
+(x_maps_amd.x_map.compute_x_map_from_time_map).  With maps_on_device=True the maps and the rectified time map go there as well
+(x_maps_amd.rig_maps: the same arrays bit for bit); the functions below stay the definition those kernels are pinned to.
 """
 from __future__ import annotations
 
@@ -344,12 +345,33 @@ def build_eval_tables(cp: CamProjCalibrationParams, **kw) -> dict:
 
 def build_tables(cp: CamProjCalibrationParams, z_near=0.1, z_far=1.2, scan_upwards=True, device: int = 0,
                  x_map_on_gpu: bool = True, projector_time_map_rectified: Optional[np.ndarray] = None,
-                 zero_undistort_proj_map: bool = False, time_map_border: str = "replicate", x_map_fn=None) -> dict:
+                 zero_undistort_proj_map: bool = False, time_map_border: str = "replicate", x_map_fn=None,
+                 maps_on_device: bool = False) -> dict:
     """Everything DepthReprojectionPipe.__post_init__ builds (python/depth_reprojection_pipe.py:69-99), as the
-    tables dict XMapsEngine / RuntimeParams.tables take.  Projector = camera 1 of the stereo pair (calib:194-217)."""
+    tables dict XMapsEngine / RuntimeParams.tables take.  Projector = camera 1 of the stereo pair (calib:194-217).
+    maps_on_device: the maps, the rectified time map and the X-map in one device call (x_maps_amd.rig_maps.build_xmaps_tables:
+    the same dict, bit for bit; stereo_rectify stays here)."""
+    if maps_on_device and x_map_fn is not None:
+        raise ValueError("x_map_fn builds the X-map on the host: it does not go with maps_on_device=True")
     size = (cp.rect_image_width, cp.rect_image_height)
     R1, R2, P1, P2, Q = stereo_rectify(cp.projector_K, cp.projector_D, cp.camera_K, cp.camera_D, size, cp.cam2proj_R,
                                        cp.cam2proj_T)
+    x_off, xw = 4242, cp.projector_width
+    if maps_on_device:
+        from .rig_maps import build_xmaps_tables
+        dev = build_xmaps_tables(cp, R1, R2, P1, P2, scan_upwards=scan_upwards, zero_undistort_proj_map=zero_undistort_proj_map,
+                                 time_map_border=time_map_border, x_map_width=xw, t_px_scale=xw - 1, x_offset=x_off,
+                                 time_map_rect=projector_time_map_rectified, device=device)
+        return {
+            "cam_w": cp.camera_width, "cam_h": cp.camera_height, "proj_w": cp.projector_width, "proj_h": cp.projector_height,
+            "rect_w": cp.rect_image_width, "rect_h": cp.rect_image_height,
+            "cam_mapx_i16": dev["cam_mapx_i16"], "cam_mapy_i16": dev["cam_mapy_i16"],
+            "proj_x_map": dev["x_map"], "disp_proj_mapxy_i16": dev["disp_proj_mapxy_i16"],
+            "x_map_width": xw, "t_px_scale": xw - 1, "x_offset": x_off, "p03": float(P2[0, 3]),
+            "z_near": z_near, "z_far": z_far,
+            "R1": R1, "R2": R2, "P1": P1, "P2": P2, "Q": Q, "time_map_rect": dev["time_map_rect"],
+            "cam_mapx_f32": dev["cam_mapx_f32"], "cam_mapy_f32": dev["cam_mapy_f32"],
+        }
     # forward maps (rectified pixel -> source pixel) for the projector: used to rectify the time map
     # "ESL compatibility: projector distortion is ignored here, but still used in cv2.stereoRectify" (calib:229-230)
     pmx, pmy = init_undistort_rectify_map(cp.projector_K, np.zeros(5) if zero_undistort_proj_map else cp.projector_D, R2, P2, size)
@@ -362,7 +384,6 @@ def build_tables(cp: CamProjCalibrationParams, z_near=0.1, z_far=1.2, scan_upwar
     else:                                         # ProjectorTimeMap.from_calib (:36-44)
         time_map = generate_linear_projector_time_map(cp.projector_width, cp.projector_height, scan_upwards)
         time_map_rect = remap_nearest(time_map, pmx, pmy, time_map_border)  # BORDER_REPLICATE live, BORDER_CONSTANT in eval
-    x_off, xw = 4242, cp.projector_width
     if x_map_fn is not None:  # a caller-supplied builder with the reference's signature (the CPU tests pass the oracle's)
         x_map, _ = x_map_fn(time_map_rect, xw, xw - 1, x_off, cp.projector_width)
     elif x_map_on_gpu:

@@ -17,6 +17,46 @@ void eval_result_from_sums(const EvalAcc& a, double hw, xm_eval_result* out) {
   out->n_gt_zero = a.n_gt_zero;
 }
 
+// xm_build_x_map's argument checks (ptrs_ok: the caller's pointers are there), shared with xm_rig_build_xmaps_tables
+int x_map_check(bool ptrs_ok, int height, int width, int x_map_width, int t_px_scale, int x_offset, int num_scanlines) {
+  if (!ptrs_ok || height <= 0 || width <= 0 || x_map_width <= 0 || t_px_scale <= 0 || num_scanlines <= 0)
+    return fail(XM_ERR_INVALID, "bad argument");
+  if (height > 32767 || width + x_offset > 32767) return fail(XM_ERR_INVALID, "indices must fit int16 (x_maps_disparity.py:52-53)");
+  if ((size_t)width * sizeof(double) > 150 * 1024) return fail(XM_ERR_INVALID, "time-map row does not fit LDS");
+  return XM_OK;
+}
+
+// the X-map kernels on device buffers, enqueued on the null stream (d_time_map f32 [height][width] -> d_x int16, d_d f32 or NULL:
+// [height][x_map_width]); the caller has run x_map_check and synchronises
+int x_map_launch(const float* d_time_map, int height, int width, int x_map_width, int t_px_scale, int x_offset, int num_scanlines,
+                 int16_t* d_x, float* d_d) {
+  hipError_t e;
+  int wp = 2;
+  while (wp < width) wp <<= 1;
+  const char* es = dbg_opt("XM_XMAP_SCAN");  // tests: XM_XMAP_SCAN=1 takes the exhaustive scan (read at every call)
+  const bool brute = es && es[0] == '1';
+  if (wp <= 8192 && !brute) {  // rows of up to 8192 columns: the sorted-row kernel (96 KB of LDS at most)
+    const size_t lds = (size_t)wp * sizeof(u64) + (size_t)width * sizeof(float);
+    if (lds > 64 * 1024 &&
+        (e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_build_x_map_sorted), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 (int)lds)) != hipSuccess) {
+      return fail(XM_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
+    }
+    hipLaunchKernelGGL(k_build_x_map_sorted, dim3(height), dim3(BLOCK), lds, 0, d_time_map, height, width, wp, x_map_width, t_px_scale,
+                       x_offset, 2.0 / (double)num_scanlines, d_x, d_d);
+  } else {
+    const size_t lds = (size_t)width * sizeof(double);
+    if (lds > 64 * 1024 &&
+        (e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_build_x_map), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 (int)lds)) != hipSuccess) {
+      return fail(XM_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
+    }
+    hipLaunchKernelGGL(k_build_x_map, dim3(height), dim3(BLOCK), lds, 0, d_time_map, height, width, x_map_width, t_px_scale,
+                       x_offset, 2.0 / (double)num_scanlines, d_x, d_d);
+  }
+  return XM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -39,10 +79,7 @@ int xm_debug_option(const char* name, const char* value) {
 // ---- N1: X-map construction ----------------------------------------------------------------------------------
 int xm_build_x_map(int device, const float* time_map, int height, int width, int x_map_width, int t_px_scale,
                    int x_offset, int num_scanlines, int16_t* x_map_out, float* t_diffs_out) {
-  if (!time_map || !x_map_out || height <= 0 || width <= 0 || x_map_width <= 0 || t_px_scale <= 0 || num_scanlines <= 0)
-    return fail(XM_ERR_INVALID, "bad argument");
-  if (height > 32767 || width + x_offset > 32767) return fail(XM_ERR_INVALID, "indices must fit int16 (x_maps_disparity.py:52-53)");
-  if ((size_t)width * sizeof(double) > 150 * 1024) return fail(XM_ERR_INVALID, "time-map row does not fit LDS");
+  if (int rc = x_map_check(time_map && x_map_out, height, width, x_map_width, t_px_scale, x_offset, num_scanlines)) return rc;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(XM_ERR_HIP, "no HIP device visible");
   HIP_TRY(hipSetDevice(device));
@@ -55,29 +92,7 @@ int xm_build_x_map(int device, const float* time_map, int height, int width, int
       (e = hipMemcpy(d_in, time_map, n_in * 4, hipMemcpyHostToDevice)) != hipSuccess) {
     return fail(XM_ERR_HIP, "xm_build_x_map: %s", hipGetErrorString(e));
   }
-  int wp = 2;
-  while (wp < width) wp <<= 1;
-  const char* es = dbg_opt("XM_XMAP_SCAN");  // tests: XM_XMAP_SCAN=1 takes the exhaustive scan (read at every call)
-  const bool brute = es && es[0] == '1';
-  if (wp <= 8192 && !brute) {  // rows of up to 8192 columns: the sorted-row kernel (96 KB of LDS at most)
-    const size_t lds = (size_t)wp * sizeof(u64) + (size_t)width * sizeof(float);
-    if (lds > 64 * 1024 &&
-        (e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_build_x_map_sorted), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)lds)) != hipSuccess) {
-      return fail(XM_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    }
-    hipLaunchKernelGGL(k_build_x_map_sorted, dim3(height), dim3(BLOCK), lds, 0, d_in, height, width, wp, x_map_width, t_px_scale,
-                       x_offset, 2.0 / (double)num_scanlines, d_x, d_d);
-  } else {
-    const size_t lds = (size_t)width * sizeof(double);
-    if (lds > 64 * 1024 &&
-        (e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_build_x_map), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)lds)) != hipSuccess) {
-      return fail(XM_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    }
-    hipLaunchKernelGGL(k_build_x_map, dim3(height), dim3(BLOCK), lds, 0, d_in, height, width, x_map_width, t_px_scale,
-                       x_offset, 2.0 / (double)num_scanlines, d_x, d_d);
-  }
+  if (int rc = x_map_launch(d_in, height, width, x_map_width, t_px_scale, x_offset, num_scanlines, d_x, d_d)) return rc;
   if ((e = hipGetLastError()) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess ||
       (e = hipMemcpy(x_map_out, d_x, n_out * 2, hipMemcpyDeviceToHost)) != hipSuccess ||
       (t_diffs_out && (e = hipMemcpy(t_diffs_out, d_d, n_out * 4, hipMemcpyDeviceToHost)) != hipSuccess)) {

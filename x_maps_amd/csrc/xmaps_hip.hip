@@ -4,7 +4,7 @@
 // -ffp-contract=off keeps the time normalisation (divide, multiply, rint) unfused = bit-exact with NumPy.
 // The device side, one header per kernel (each includes what it needs; xmaps_geometry.hpp, standard C++ only, holds the
 // constants and the LDS layouts they share with the host's plan):
-#include "xmaps_kernels.hpp"        // common ABI, K0, K1 direct / event tiles, K2, stage, X-map builder, filters, eval, slots
+#include "xmaps_kernels.hpp"        // common ABI, K0, K1 direct / event tiles, K2, stage, X-map builder, rig maps, filters, eval, slots
 #include "xmaps_k1cols.hpp"         // K1 on column tiles + the boundary pass
 #include "xmaps_k1own.hpp"          // K1 on owner tiles
 #include "xmaps_k2pipe.hpp"         // pipelined K2 on the u16 frame
@@ -70,6 +70,7 @@ using namespace xm;
 #include "host/xm_ingest_create.hpp"  // ... the stages of xm_ingest_create
 #include "host/xm_api_ingest.hpp"   // ... its C entry points (records, and EVT words through the decoder)
 #include "host/xm_api_misc.hpp"     // X-map builder, evaluation metrics, memory helpers
+#include "host/xm_api_rigmaps.hpp"  // a rig's rectification maps, time map and X-map: the table builders' device path
 #include "host/xm_group.hpp"        // the skeleton of the group objects below: create / destroy, argument check, staging, dtype dispatch
 #include "host/xm_api_surface.hpp"  // a group of camera time surfaces -> depth maps + point clouds (the evaluation caller's entry)
 #include "host/xm_api_eslinit.hpp"  // the ESL-init baseline on the same surfaces: depth_init maps, disparity_init alone

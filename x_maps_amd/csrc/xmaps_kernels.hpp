@@ -29,6 +29,7 @@
 #include "xmaps_k2.hpp"         // K2: every frame kernel and its table builders
 #include "xmaps_stage.hpp"      // stage and debug kernels, point cloud
 #include "xmaps_xmapbuild.hpp"  // X-map builder (setup time)
+#include "xmaps_rigmaps.hpp"    // a rig's rectification maps + remap in front of it (setup time): calibration.py's NumPy, bit for bit
 #include "xmaps_filters.hpp"    // frame event filters, pause detection
 #include "xmaps_eval.hpp"       // evaluation metrics
 #include "xmaps_slots.hpp"      // slot reset, redo preparation

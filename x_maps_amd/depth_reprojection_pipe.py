@@ -83,7 +83,8 @@ class DepthReprojectionPipe:
                                                               p.projector_width, p.projector_height)
                 tm = np.load(p.projector_time_map) if p.projector_time_map else None
                 tables = calib.build_tables(cp, z_near=p.z_near, z_far=p.z_far, device=getattr(p, "device", 0),
-                                            projector_time_map_rectified=tm)
+                                            projector_time_map_rectified=tm,
+                                            maps_on_device=bool(getattr(p, "tables_on_device", False)))
                 self.stats_printer.log("tables built by the cv2-free builder")
             else:
                 raise ValueError("RuntimeParams.calib must be a calibration .yaml, an exported tables .npz, or set .tables")

@@ -74,6 +74,10 @@ class RuntimeParams:
     # waits for the first time base) instead of emitted at time base 0.  Which of the two Metavision's reader does is unpinned
     # (tools/pin_thirdparty.py decides); it matters for the first few words of a file only.
     raw_wait_for_time_base: bool = False
+    # `calib` is a calibration YAML: its rectification maps, the rectified time map and the X-map are built in one device call
+    # (calibration.build_tables(maps_on_device=True), x_maps_amd/rig_maps.py) instead of NumPy on the host.  The same tables,
+    # bit for bit.
+    tables_on_device: bool = False
 
     @property
     def should_drop_frames(self):

@@ -40,14 +40,30 @@ def _pair_i16(mapx: np.ndarray, mapy: np.ndarray) -> np.ndarray:
     return np.ascontiguousarray(np.stack((mapf_to_i16(sat(mapx)), mapf_to_i16(sat(mapy))), -1))
 
 
-def build_esl_init_tables(cp: CamProjCalibrationParams) -> dict:
+def build_esl_init_tables(cp: CamProjCalibrationParams, maps_on_device: bool = False, device: int = 0) -> dict:
     """The tables of compute_depth_esl.py:179-201 from a CamProjCalibrationParams.from_ESL_yaml object.  The camera is "camera 0"
     there: it takes R0 / P0, the projector R1 / P1 -- which esl_utilities.py:133-150 (loadCalibParams, alpha = -1, the default
     CALIB_ZERO_DISPARITY) fills with the FIRST and the SECOND pair of cv2.stereoRectify(projector, camera, ...), the same call and
     the same assignment as build_tables makes for X-maps.  The rectified frame is 3 x the projector (cp.rect_image_*), the back
-    map is built at the camera's size, and the projector's distortion is ignored in its map (:197)."""
+    map is built at the camera's size, and the projector's distortion is ignored in its map (:197).
+    maps_on_device: the three maps and the remap on the device (x_maps_amd.rig_maps: the same dict, bit for bit; the projector's
+    forward map and its time surface are never stored, only proj_rect comes back)."""
     size = (cp.rect_image_width, cp.rect_image_height)
     R0, R1, P0, P1, _ = stereo_rectify(cp.projector_K, cp.projector_D, cp.camera_K, cp.camera_D, size, cp.cam2proj_R, cp.cam2proj_T)
+    if maps_on_device:
+        from . import rig_maps
+        c2r = rig_maps.forward_map(cp.camera_K, cp.camera_D, R0, P0, size, want_maps=False, want_pair=True, device=device)["pair_i16"]
+        r2c = rig_maps.inverse_map(cp.camera_K, cp.camera_D, R0, P0, (cp.camera_width, cp.camera_height), want_maps=False,
+                                   want_pair=True, device=device)["pair_i16"]
+        proj_rect = rig_maps.forward_map(cp.projector_K, np.zeros(5), R1, P1, size, want_maps=False,
+                                         linear_time=(cp.projector_width, cp.projector_height, False), border="constant",
+                                         device=device)["remap"]
+        return {
+            "cam_w": cp.camera_width, "cam_h": cp.camera_height, "rect_w": size[0], "rect_h": size[1],
+            "cam_to_rect_map": c2r, "rect_to_cam_map": r2c, "proj_rect": proj_rect,
+            "p1_03": float(P1[0, 3]), "min_disp": MIN_DISP, "max_disp": MAX_DISP,
+            "R0": R0, "R1": R1, "P0": P0, "P1": P1,
+        }
     # rectified view -> image plane (:189-191) and image plane -> rectified plane (:193-198)
     disp_mapx, disp_mapy = init_undistort_rectify_map_inverse(cp.camera_K, cp.camera_D, R0, P0, (cp.camera_width, cp.camera_height))
     img_mapx, img_mapy = init_undistort_rectify_map(cp.camera_K, cp.camera_D, R0, P0, size)

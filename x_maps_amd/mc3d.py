@@ -41,18 +41,22 @@ def mc3d_int_maps(mapx: np.ndarray, mapy: np.ndarray) -> np.ndarray:
     return out
 
 
-def build_mc3d_tables(cp: CamProjCalibrationParams, rectify_size=None) -> dict:
+def build_mc3d_tables(cp: CamProjCalibrationParams, rectify_size=None, maps_on_device: bool = False, device: int = 0) -> dict:
     """The tables of mc3d_baseline.py:99-114 from a CamProjCalibrationParams.from_ESL_yaml object.  esl_utilities.py:133-150
     (loadCalibParams, alpha = -1) calls cv2.stereoRectify(projector, camera, ...) and names its FIRST pair R0 / P0 and its SECOND
     R1 / P1; the camera's map takes R0 / P0 and the projector's R1 / P1 (:109-114) -- the same call and the same assignment as
     build_esl_init_tables makes -- and, unlike ESL-init's map, the projector keeps its own distortion (:109-111).  rectify_size: the image size handed to the rectification; the reference passes the
     PROJECTOR's size there (:99-101) and uses the 3 x frame only for the limits of the search.  The reference builds the camera map
-    at projector size but only its [:cam_h, :cam_w] corner is ever read: it is built at camera size."""
+    at projector size but only its [:cam_h, :cam_w] corner is ever read: it is built at camera size.
+    maps_on_device: the two float maps on the device (x_maps_amd.rig_maps: the same bits); mc3d_int_maps stays NumPy."""
     size = rectify_size or (cp.projector_width, cp.projector_height)
     R0, R1, P0, P1, _ = stereo_rectify(cp.projector_K, cp.projector_D, cp.camera_K, cp.camera_D, size, cp.cam2proj_R, cp.cam2proj_T)
-    proj_mapx, proj_mapy = init_undistort_rectify_map_inverse(cp.projector_K, cp.projector_D, R1, P1,
-                                                              (cp.projector_width, cp.projector_height))
-    img_mapx, img_mapy = init_undistort_rectify_map_inverse(cp.camera_K, cp.camera_D, R0, P0, (cp.camera_width, cp.camera_height))
+    inverse = init_undistort_rectify_map_inverse
+    if maps_on_device:
+        from . import rig_maps
+        inverse = lambda *a: rig_maps.init_undistort_rectify_map_inverse(*a, device=device)
+    proj_mapx, proj_mapy = inverse(cp.projector_K, cp.projector_D, R1, P1, (cp.projector_width, cp.projector_height))
+    img_mapx, img_mapy = inverse(cp.camera_K, cp.camera_D, R0, P0, (cp.camera_width, cp.camera_height))
     return {
         "cam_w": cp.camera_width, "cam_h": cp.camera_height, "proj_w": cp.projector_width, "proj_h": cp.projector_height,
         "cam_map": mc3d_int_maps(img_mapx, img_mapy), "proj_map": mc3d_int_maps(proj_mapx, proj_mapy),
