@@ -160,7 +160,9 @@ typedef struct xm_frame_stats {
  * "XM_K2_PPT", "XM_K2_FLAGS", "XM_K1_DIRECT", "XM_K2_DIRECT", "XM_KEY32", "XM_OWN_W", "XM_OWN_SHEAR", "XM_OWN_GROUPED",
  * "XM_OWN_ROW_PASSES", "XM_OWN_EPT", "XM_K2_PER_CU", "XM_K2_CHAIN", "XM_WORKERS", "XM_XMAP_SCAN",
  * "XM_INGEST_CLEAR_EVERY", "XM_INGEST_TRACE", "XM_INGEST_OUT_PIECE", "XM_INGEST_OUT_SERIAL", "XM_INGEST_OUT_INLINE",
- * "XM_INGEST_OUT_NO_QUERY", "XM_INGEST_EVT3_OUT_STREAM", "XM_INGEST_OWN_STREAMS", "XM_INGEST_PRIOS", "XM_SHARDED_KEYS"; values as text).  Process-wide, read when a handle / an ingest is created (XM_XMAP_SCAN:
+ * "XM_INGEST_OUT_NO_QUERY", "XM_INGEST_EVT3_OUT_STREAM", "XM_INGEST_OWN_STREAMS", "XM_INGEST_PRIOS", "XM_SHARDED_KEYS",
+ * "XM_FS_MAX_BLOCKS" -- the most blocks per frame of the frame -> time surface event pass, read at every group call and when an ingest's
+ * surface stage is first switched on; values as text).  Process-wide, read when a handle / an ingest is created (XM_XMAP_SCAN:
  * at every call).  "XM_K2_LIVE": 0 = the pipelined K2 loads every quad (all ones in its live-slot masks), 1 = the derived masks
  * (default), 2 = the same and their live fractions on stderr, one line per tile geometry.  The library never reads them from the environment.  value == NULL removes an option, name == NULL all. */
 int xm_debug_option(const char* name, const char* value);
@@ -791,6 +793,59 @@ int xm_surface_set_cloud_tables(xm_handle* h, const float* mapx_f32, const float
  * other than the two float types, n_surfaces <= 0. */
 int xm_process_time_surfaces(xm_handle* h, const void* surfaces, int dtype, int n_surfaces, int mem, float* depth_out,
                              float* cloud_out, xm_surface_stats* stats_out);
+
+/* ---- frames of events in, camera time surfaces out: what joins the live half to the evaluation entries -------------------------
+ * For every frame the camera image that holds, per pixel, the time of the event that fired there: the input of
+ * xm_process_time_surfaces, xm_esl_init_*, xm_esl_optim_* and xm_mc3d_* (the `scans_np` files of the ESL dataset), built from a
+ * frame of EventCD records.  This build's own definition -- ESL's events-to-scan converter is not part of the reference
+ * (DESIGN.md section 5).  The surface of one frame on the handle's cam_height x cam_width sensor:
+ *   - with use_polarity != 0 only the events with p == 1 exist at all (as in xm_process_frame_aos); otherwise every event exists;
+ *   - an event TAKES PART iff x < cam_width and y < cam_height; every other existing event is left out and counted in
+ *     n_index_errors (how the ingest's frame filters treat them);
+ *   - base = the smallest t over all existing events, those left out included;
+ *   - per pixel the event with the largest (XM_SURFACE_LAST) or the smallest (XM_SURFACE_FIRST) INDEX in the frame is selected:
+ *     stream order, not time, so the result is defined for any event order;
+ *   - S[y][x] = t_selected - base + 1 in int64, converted ONCE to the output type by the IEEE round-to-nearest-even conversion
+ *     (NumPy's astype).  A frame shorter than 2^24 us -- every frame the trigger finder can cut -- is exact in float32.  A pixel
+ *     without an event holds 0; the + 1 keeps the earliest event apart from "no event";
+ *   - an empty frame is defined: an all-zero surface and zero statistics.
+ * The result depends on the frame alone: not on the run, on the frame's place in a group or on earlier calls.  Winners are picked
+ * by integer atomics on event indices; there is no floating-point atomic and no kernel waits for another block of its launch
+ * (x_maps_amd/csrc/xmaps_framesurface.hpp). */
+#define XM_SURFACE_LAST 1
+#define XM_SURFACE_FIRST 2
+typedef struct xm_frame_surface_stats {
+  uint64_t n_events;       /* existing events (all, or those with p == 1)                                   */
+  uint64_t n_pixels;       /* non-zero pixels of the surface                                                */
+  uint64_t n_index_errors; /* existing events left out (x >= cam_width or y >= cam_height)                  */
+  int64_t t_base;          /* the smallest t over the existing events (0 for a frame without any)           */
+  int64_t t_span;          /* the largest t - t_base over the existing events, those left out included      */
+} xm_frame_surface_stats;
+/* Frame f = records [offsets_host[f], offsets_host[f + 1]) of eventcd16 (16-byte EventCD records; 16-byte aligned in device
+ * memory); a frame holds at most 2^32 - 2 events.  surfaces_out: [n_frames][cam_height][cam_width] of dtype (XM_T_FLOAT32 /
+ * XM_T_FLOAT64).  stats_out (may be NULL): xm_frame_surface_stats[n_frames].  mem == XM_MEM_HOST: records, surfaces and
+ * statistics are host memory, the call is synchronous.  XM_MEM_DEVICE: all three are device memory; everything is enqueued on the
+ * next slot's stream, xm_sync() waits, the buffers stay valid and untouched until then (offsets_host is read inside the call).
+ * Works on handles of either view.  Groups of any length are accepted (they go out as launch sequences of 32 frames).  Scratch is
+ * allocated by the first call and grown when a larger group arrives.  XM_ERR_INVALID: an unknown select or dtype, n_frames <= 0,
+ * decreasing offsets, a mem other than the two. */
+int xm_frames_to_time_surfaces(xm_handle* h, const void* eventcd16, const uint64_t* offsets_host, int n_frames, int use_polarity,
+                               int select, int dtype, int mem, void* surfaces_out, xm_frame_surface_stats* stats_out);
+/* The same as a stage of the device ingest.  Ordered like a push, exactly as xm_ingest_set_frame_filter: the frames cut by packets
+ * pushed AFTER the call get a surface -- built on the frame stream from the CUT frame (every event in the ring has passed the
+ * ingest's polarity and activity filters; use_polarity is therefore not applied again), in front of any frame event filter --
+ * in a ring of `ring` surfaces in device memory (0: the ingest's result_ring).  select == 0 switches the stage off: the ingest
+ * then launches nothing for it.  Scratch and ring are allocated by the first call that switches the stage on, for either dtype;
+ * a later call may change select and dtype, not the ring's length (XM_ERR_INVALID).  The stage's last launch that reads a cut
+ * frame runs in front of the frame's filter / K1, for which the ingest stream waits before it appends over the frame. */
+int xm_ingest_set_surface_output(xm_ingest* g, int select /* 0 = off */, int dtype, int ring);
+/* The surface of frame `seq` (xm_ingest_frame.seq) -> dst ([cam_height][cam_width] of the dtype the frame was built with; host
+ * or device memory by `mem`), its statistics -> *stats (host memory, may be NULL).  Returns 1: copied, and the ring entry was
+ * still intact after the copy; 0: never produced, not complete yet, or already overwritten (dst may have been written);
+ * < 0: an error.  Once xm_ingest_poll* has handed out frame seq its surface is complete.  xm_ingest_reset keeps the stage's setting and drops the ring's contents.  Synchronous. */
+int xm_ingest_copy_surface(xm_ingest* g, uint64_t seq, void* dst, int mem, xm_frame_surface_stats* stats);
+/* the dtype (XM_T_*) the surface of frame seq was built with, or 0 when the ring does not hold it */
+int xm_ingest_surface_dtype(xm_ingest* g, uint64_t seq);
 
 /* ---- ESL-init: the baseline of the reference's evaluation table, on the device ------------------------------------------------
  * What python/eval/compute_depth_esl.py:204-226 computes up to depth_init (the optimisation behind it: xm_esl_optim_* below; MC3D: xm_mc3d_*),

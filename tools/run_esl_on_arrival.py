@@ -11,6 +11,9 @@ filter, trigger finder and the hot path there too (this build's default RuntimeP
 ms per shown frame next to the reference's published 2.67 ms (Threadripper PRO 5955WX, frame stage only), and -- with
 --compare-host-chain -- the same file through the opt-out host chain (NumPy decoder + filters + trigger finder), frame by frame.
 The bias file only configures a live camera (bias_events_iterator.py:69-78): accepted, recorded, not used for a file.
+With --scans-from-raw DIR part A also writes every shown frame's camera time surface to DIR/scans_np/scansNNN.npy (built on the
+device from the cut frame: RuntimeParams.surface_callback) and part B runs on DIR: a recording without the dataset's scans_np -- a
+rig of one's own -- gets its table rows from the RAW file alone.  They are this build's surfaces, not the ESL dataset's.
 
 Part B -- the accuracy row (eval/x-map-eval.sh:24-72 -> python/eval/compute_depth_x_maps.py:22-133 ->
 python/eval/create_evaluation_table.py:84-180): every `<scans>/scans_np/*.npy` time surface -> X-maps depth in camera view on
@@ -64,8 +67,10 @@ def raw_format(path: str) -> int:
 
 
 def replay_raw(raw, calib, proj_w, proj_h, fps, z_near, z_far, camera_perspective=False, device=0, chunk_words=1 << 20,
-               device_ingest=True, keep_frames=0, tables=None, max_chunks=0):
-    """Part A.  -> dict(report), list of (frame checksum, shape) per shown frame, the first `keep_frames` frames"""
+               device_ingest=True, keep_frames=0, tables=None, max_chunks=0, scans_dir=None):
+    """Part A.  -> dict(report), list of (frame checksum, shape) per shown frame, the first `keep_frames` frames
+    scans_dir: every shown frame's camera time surface (RuntimeParams.surface_callback: float32, this build's definition) is
+    written to <scans_dir>/scans_np/scansNNN.npy, N counting the shown frames from 0 -- what part B reads"""
     from x_maps_amd import evt2, evt3
     from x_maps_amd.depth_reprojection_processor import DepthReprojectionProcessor, RuntimeParams
     fmt = raw_format(raw)
@@ -81,10 +86,20 @@ def replay_raw(raw, calib, proj_w, proj_h, fps, z_near, z_far, camera_perspectiv
             if len(kept) < keep_frames:
                 kept.append(np.array(img))
 
+    n_surfaces = [0]
+    surface_cb = None
+    if scans_dir:
+        os.makedirs(os.path.join(scans_dir, "scans_np"), exist_ok=True)
+
+        def surface_cb(surf):
+            np.save(os.path.join(scans_dir, "scans_np", scan_name(n_surfaces[0])), surf)
+            n_surfaces[0] += 1
+
     t_setup = time.perf_counter()
     params = RuntimeParams(camera_width=640, camera_height=480, projector_width=proj_w, projector_height=proj_h, projector_fps=fps,
                            z_near=z_near, z_far=z_far, calib=calib, projector_time_map=None, no_frame_dropping=True,
-                           camera_perspective=camera_perspective, tables=tables, device=device, device_ingest=device_ingest)
+                           camera_perspective=camera_perspective, tables=tables, device=device, device_ingest=device_ingest,
+                           surface_callback=surface_cb)
     n_words = n_chunks = 0
     with DepthReprojectionProcessor(params, window=Window()) as proc:
         t_setup = time.perf_counter() - t_setup
@@ -105,6 +120,11 @@ def replay_raw(raw, calib, proj_w, proj_h, fps, z_near, z_far, camera_perspectiv
            "setup_seconds": round(t_setup, 3), "replay_seconds": round(dt, 4), "frames_shown": len(shown),
            "ms_per_shown_frame": round(dt / max(len(shown), 1) * 1e3, 4), "reference_published_ms_per_frame": PUBLISHED["ms_per_frame"],
            "frame_shape": list(shown[0][0]) if shown else None}
+    if scans_dir:
+        rep["scans_from_raw"] = {"dir": os.path.join(scans_dir, "scans_np"), "surfaces_written": n_surfaces[0],
+                                 "definition": "this build's surfaces (per pixel the stamp of the cut frame's last event there, t - the "
+                                               "frame's first stamp + 1, float32; include/xmaps.h xm_frames_to_time_surfaces), NOT the ESL "
+                                               "dataset's scans_np: ESL's own events-to-scan converter is not part of the reference"}
     if ds is not None:
         rep["device"] = ds
         rep["events_behind_the_filters"] = ds["events_appended"]
@@ -373,6 +393,9 @@ def main(argv=None):
     ap.add_argument("--calib", default=os.path.join(ROOT, "..", "reference", "data", "ESL_calib_hhi.yaml"),
                     help="calibration YAML of the live pipe (the reference's data/ESL_calib_hhi.yaml)")
     ap.add_argument("--scans", help="sequence directory holding scans_np/*.npy (and, for the table row, esl/depth_optim_filtered/*.npy)")
+    ap.add_argument("--scans-from-raw", metavar="DIR",
+                    help="part A also writes every shown frame's camera time surface to DIR/scans_np/scansNNN.npy (this build's "
+                         "surfaces, not the ESL dataset's); part B then runs on --scans DIR unless --scans names another directory")
     ap.add_argument("--eval-calib", help="the ESL dataset's calib.yaml (cam_K, cam_kc, proj_K, proj_kc, R, T) for part B")
     ap.add_argument("--projector-width", type=int, default=1080)
     ap.add_argument("--projector-height", type=int, default=1920)
@@ -412,13 +435,17 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if not a.raw and not a.scans:
         ap.error("nothing to do: give --raw and / or --scans")
+    if a.scans_from_raw and not a.raw:
+        ap.error("--scans-from-raw needs --raw")
     report = {"published": PUBLISHED}
     if a.raw:
         if a.bias:
             report["bias_file"] = {"path": a.bias, "present": os.path.exists(a.bias), "note": "configures a live camera only"}
         rep, shown, kept = replay_raw(a.raw, a.calib, a.projector_width, a.projector_height, a.projector_fps, a.z_near, a.z_far,
-                                      a.camera_perspective, a.device, a.chunk_words, True, a.save_frames)
+                                      a.camera_perspective, a.device, a.chunk_words, True, a.save_frames, scans_dir=a.scans_from_raw)
         report["replay"] = rep
+        if a.scans_from_raw and not a.scans and a.eval_calib:
+            a.scans = a.scans_from_raw  # part B on the surfaces part A has just written
         if a.save_frames and a.out:
             for i, f in enumerate(kept):
                 np.save(os.path.join(os.path.dirname(os.path.abspath(a.out)), f"frame_{i:03d}.npy"), f)

@@ -319,6 +319,84 @@ int xm_ingest_set_frame_filter(xm_ingest* g, int filter, int intended_semantics)
   return ingest_submit(g, j, false);
 }
 
+// the surface stage's scratch and ring, once (IngestSurface)
+static int ingest_surface_alloc(xm_ingest* g, int ring) {
+  IngestSurface& sf = g->sf;
+  const xm_handle* h = g->fx.h;
+  sf.ring = ring;
+  sf.cells = (size_t)h->tb.cam_w * h->tb.cam_h;
+  sf.stride = (sf.cells + FS_CPT - 1) / FS_CPT * FS_CPT;
+  sf.max_chunk_blocks = fs_max_chunk_blocks();
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  HIP_TRY(sf.d_map.alloc(sf.stride));
+  HIP_TRY(sf.d_acc.alloc(1));
+  HIP_TRY(sf.d_stats.alloc(ring));
+  HIP_TRY(sf.d_ring.alloc((size_t)ring * sf.cells * 8));
+  HIP_TRY(sf.h_tag.alloc(ring, hipHostMallocMapped));
+  HIP_TRY(sf.h_stats.alloc(ring, hipHostMallocMapped));
+  memset(sf.h_tag, 0, sizeof(u64) * ring);
+  memset(sf.h_stats, 0, sizeof(FsStats) * ring);
+  HIP_TRY(hipMemset(sf.d_map, 0, sf.stride * sizeof(u32)));
+  HIP_TRY(hipMemset(sf.d_acc, 0, sizeof(FsAcc)));
+  HIP_TRY(hipMemset(sf.d_stats, 0, sizeof(FsStats) * ring));
+  HIP_TRY(hipDeviceSynchronize());  // (default-stream memsets: the ingest's non-blocking streams do not wait for them)
+  sf.ready = true;
+  return XM_OK;
+}
+
+int xm_ingest_set_surface_output(xm_ingest* g, int select, int dtype, int ring) {
+  if (!g) return fail(XM_ERR_INVALID, "NULL argument");
+  if (select != 0 && select != XM_SURFACE_LAST && select != XM_SURFACE_FIRST)
+    return fail(XM_ERR_INVALID, "select must be 0 (off), XM_SURFACE_LAST or XM_SURFACE_FIRST");
+  if (select && dtype != XM_T_FLOAT32 && dtype != XM_T_FLOAT64) return fail(XM_ERR_INVALID, "a time surface is XM_T_FLOAT32 or XM_T_FLOAT64");
+  if (ring < 0 || ring > 65536) return fail(XM_ERR_INVALID, "ring must lie in 0 .. 65536");
+  int rc = ingest_take_error(g);
+  if (rc) return rc;
+  if (select) {
+    const int want = ring ? ring : g->fx.ring;
+    if (!g->sf.ready && (rc = ingest_surface_alloc(g, want))) return rc;
+    if (g->sf.ring != want) return fail(XM_ERR_INVALID, "the surface ring holds %d entries since the first call that switched the stage on", g->sf.ring);
+  }
+  // ordered like a push: the packets handed in before this call keep the setting they were pushed under
+  IngestJob j;
+  j.kind = JobKind::set_surface;
+  j.surf_select = select;
+  j.surf_dtype = select ? dtype : 0;
+  return ingest_submit(g, j, false);
+}
+
+int xm_ingest_surface_dtype(xm_ingest* g, uint64_t seq) {
+  if (!g) return fail(XM_ERR_INVALID, "NULL argument");
+  const IngestSurface& sf = g->sf;
+  if (!sf.ready) return 0;
+  const size_t e = (size_t)(seq % (uint64_t)sf.ring);
+  const u64 t = __atomic_load_n(sf.h_tag + e, __ATOMIC_ACQUIRE);
+  return t >> 2 == seq + 1 ? (int)(t & 3) : 0;
+}
+
+int xm_ingest_copy_surface(xm_ingest* g, uint64_t seq, void* dst, int mem, xm_frame_surface_stats* stats) {
+  if (!g || !dst) return fail(XM_ERR_INVALID, "NULL argument");
+  if (mem != XM_MEM_HOST && mem != XM_MEM_DEVICE) return fail(XM_ERR_INVALID, "mem must be XM_MEM_HOST or XM_MEM_DEVICE");
+  const IngestSurface& sf = g->sf;
+  if (!sf.ready) return 0;
+  const size_t e = (size_t)(seq % (uint64_t)sf.ring);
+  const u64* tag = sf.h_tag + e;
+  // the tag names the frame only between the stage's last launch for it and the first launch of the frame that takes the entry
+  // next (k_fs_events clears it in front of the pixel pass that rewrites the entry): named before AND after the copy = intact
+  const u64 t0 = __atomic_load_n(tag, __ATOMIC_ACQUIRE);
+  if (t0 >> 2 != seq + 1) return 0;
+  const int dt = (int)(t0 & 3);
+  FsStats st;
+  memcpy(&st, sf.h_stats + e, sizeof st);
+  HIP_TRY(hipSetDevice(g->fx.h->cfg.device));
+  HIP_TRY(hipMemcpy(dst, sf.d_ring + e * sf.cells * 8, sf.cells * t_size(dt), mem == XM_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice));
+  if (mem == XM_MEM_DEVICE) HIP_TRY(hipStreamSynchronize(nullptr));
+  __atomic_thread_fence(__ATOMIC_ACQUIRE);
+  if (__atomic_load_n(tag, __ATOMIC_ACQUIRE) != t0) return 0;
+  if (stats) memcpy(stats, &st, sizeof st);
+  return 1;
+}
+
 int xm_ingest_flush(xm_ingest* g) {
   if (!g) return fail(XM_ERR_INVALID, "NULL argument");
   HIP_TRY(hipSetDevice(g->fx.h->cfg.device));
@@ -339,6 +417,9 @@ int xm_ingest_reset(xm_ingest* g) {
   z.last_t = 0;
   z.span_ok = 0;
   HIP_TRY(hipMemcpy(g->fx.dev.st, &z, sizeof z, hipMemcpyHostToDevice));
+  // the surface stage keeps its setting; what its ring holds belongs to the stream that ended (nothing is in flight: flushed)
+  if (g->sf.ready)
+    for (int e = 0; e < g->sf.ring; ++e) __atomic_store_n(g->sf.h_tag + e, 0ull, __ATOMIC_RELEASE);
   // The activity filter's history goes too: a reset is "the stream starts over" (the reference resets when a recording loops,
   // depth_reprojection.py:76) and its stamps then start below everything the history holds -- against the old history every
   // event with a neighbour that ever fired would pass.  (Metavision's filter object keeps its state there; the frames behind

@@ -122,6 +122,18 @@ struct SurfaceScratch {
   DevBuf in, depth, cloud;                                         // staging of XM_MEM_HOST calls
 };
 
+// The frame -> time surface entry (xm_api_framesurface.hpp): grow-only scratch, allocated by the first call and ordered between
+// calls like SurfaceScratch.  The winner maps and the accumulators are ALL ZERO between calls: their last readers leave them so
+// (xmaps_framesurface.hpp).  `dirty` is set while a call's launches are being issued: a call that fails between its event pass
+// and its last launch leaves it set, and the next call clears maps and accumulators before it uses them.
+struct FrameSurfScratch {
+  Event done;
+  hipStream_t last_stream = nullptr;
+  DevBuf maps, acc, stats;  // [<= FS_GROUP] winner maps / FsAcc; [frames of the call] FsStats
+  DevBuf in, out;           // staging of XM_MEM_HOST calls
+  bool dirty = false;
+};
+
 // ---- launch workers -------------------------------------------------------------------------------------------
 // A kernel launch costs the calling thread ~2.7 us in the HIP runtime, three launches per frame; with the GPU at ~12 us per
 // frame that single thread is what bounds the asynchronous device-pointer path (tools/only_kernel_eager.sh: 3.2 us per call
@@ -188,6 +200,7 @@ struct xm_handle {
   DevMem<u64> stage_frame;  // lazily allocated scratch for the stage API (max(rect, cam) cells)
   size_t stage_cells = 0;
   SurfaceScratch surf;      // xm_process_time_surfaces
+  FrameSurfScratch fsurf;   // xm_frames_to_time_surfaces
   std::vector<std::unique_ptr<Worker>> workers;  // one per slot stream (empty: launches happen in the calling thread)
   struct OwnSet {  // the device tables of the owner tiles' plan i (its scalars: plan().own[i])
     DevMem<uint16_t> d_xmap_own;

@@ -50,6 +50,27 @@ int ingest_issue_frame(xm_ingest* g, uint64_t push_no, u64 n) {
     la.frames_since_clear = 0;
   }
   la.frames_since_clear += 1;
+  // the surface stage the packet was pushed under: the cut frame's time surface into ring entry (frame number % ring), in front
+  // of everything else that reads the frame.  Its reads of the ring are over before the event the ingest stream waits for below
+  // (the filter stage's, else K1's) is recorded on this stream.  Stage off: nothing is launched
+  if (const int sfs = la.push_surface[vi]) {
+    IngestSurface& sf = g->sf;
+    const int e = (int)(la.frames_issued % (uint64_t)sf.ring), dt = sfs >> 2;
+    FsArgs a{};
+    a.desc = cut;
+    a.map = sf.d_map;
+    a.acc = sf.d_acc;
+    a.stats = sf.d_stats + e;
+    a.out = sf.d_ring + (size_t)e * sf.cells * 8;
+    a.tag = sf.h_tag + e;
+    a.tag_value = ((la.frames_issued + 1) << 2) | (u64)dt;
+    a.host_stats = sf.h_stats + e;
+    a.cells = (u32)sf.cells, a.map_stride = (u32)sf.stride;
+    a.cam_w = h->tb.cam_w, a.cam_h = h->tb.cam_h;
+    a.use_polarity = 0, a.select = sfs & 3;
+    a.max_chunk_blocks = sf.max_chunk_blocks;
+    launch_frame_surfaces(a, 1, n, dt, s);
+  }
   // one EventCD frame in descriptor form: grids from at least two events, the tiled K1's block from the frame itself
   if (flt) {
     launch_frame_filter(ingest_frame_filter_dev(g, vi, flt, la.push_filter[vi] >> 3), n, s);
@@ -217,6 +238,7 @@ int ingest_process(xm_ingest* g, const IngestJob& j, size_t n, const u32* n_dev 
   }
   la.push_t[vi] = j.t_push;
   la.push_filter[vi] = (unsigned char)(la.filter | (la.intended ? 8 : 0));
+  la.push_surface[vi] = (unsigned char)(la.surf_select ? la.surf_select | (la.surf_dtype << 2) : 0);
   la.dev.desc = fx.d_descs + vi;
   la.dev.info = fx.d_infos + vi;
   la.dev.verdict = fx.d_verdicts + vi;
@@ -304,6 +326,10 @@ int ingest_run_job(xm_ingest* g, const IngestJob& j) {
     case JobKind::set_filter:
       g->la.filter = j.filter;
       g->la.intended = j.intended;
+      break;
+    case JobKind::set_surface:
+      g->la.surf_select = j.surf_select;
+      g->la.surf_dtype = j.surf_dtype;
       break;
     case JobKind::stop:
     case JobKind::count_only: break;

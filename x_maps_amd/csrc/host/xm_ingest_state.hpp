@@ -71,6 +71,7 @@ enum class JobKind : int {
   flush,       // every verdict in, every frame's kernels launched and run
   count_only,  // nothing arrived (the copy side failed): the launch side only counts the job
   set_filter,  // the frame event filter for the frames cut by the packets behind this job (xm_ingest_set_frame_filter)
+  set_surface, // the surface stage's setting for the frames cut by the packets behind this job (xm_ingest_set_surface_output)
 };
 inline bool carries_packet(JobKind k) { return k == JobKind::records || k == JobKind::words || k == JobKind::on_device; }
 inline bool copy_side_has_work(JobKind k) { return k == JobKind::records || k == JobKind::words; }
@@ -87,6 +88,7 @@ struct IngestJob {
   uint64_t push_no = 0;              // number of the push (from 1; the caller's count = the launch side's `issued` + 1 when its turn comes)
   double t_push = 0.0;               // when the xm_ingest_push* call entered (steady clock)
   int filter = 0, intended = 0;      // set_filter: FILTER_* (0: none) and its semantics
+  int surf_select = 0, surf_dtype = 0;  // set_surface: XM_SURFACE_* (0: off) and XM_T_FLOAT32 / XM_T_FLOAT64
 };
 
 // launch side -> out thread: one cut frame.  Every cut frame is posted, so frame f is job f + 1 of the out queue.
@@ -188,6 +190,24 @@ struct IngestFrameFilter {
   DevMem<FrameFilterCtl> d_ctl;
 };
 
+// Time surfaces of the cut frames (xmaps_framesurface.hpp) on the frame stream, in front of any frame event filter.  Scratch and
+// ring, made ONCE by the caller's first xm_ingest_set_surface_output that switches the stage on, before it posts the set_surface
+// job: the launch side looks at them only for packets behind that job, and nothing of it changes afterwards.  Frame f goes to ring
+// entry f % ring.  An entry's tag (pinned host memory, written by the device): 0 while the entry is being rewritten, else
+// (the frame's number + 1) << 2 | its dtype (XM_T_FLOAT32 / XM_T_FLOAT64); its statistics lie beside it.
+struct IngestSurface {
+  bool ready = false;
+  int ring = 0;
+  size_t cells = 0, stride = 0;        // cam_w * cam_h; the same rounded up to FS_CPT (the winner map)
+  DevMem<u32> d_map;                   // one winner map, all zero between frames
+  DevMem<FsAcc> d_acc;                 // one accumulator, all zero between frames
+  DevMem<FsStats> d_stats;             // [ring] the statistics in device memory (the kernels' own copy)
+  DevMem<unsigned char> d_ring;        // [ring][cells] of 8 bytes: room for either dtype
+  PinnedMem<u64> h_tag;                // [ring]
+  PinnedMem<FsStats> h_stats;          // [ring]
+  u32 max_chunk_blocks = 4096;         // ("XM_FS_MAX_BLOCKS", read once)
+};
+
 // Caller side: the thread that calls xm_ingest_push* / poll* / backlog / flush (one at a time, by the API's contract).
 struct IngestCaller {
   uint64_t posted = 0;                 // pushes accepted so far
@@ -214,6 +234,8 @@ struct IngestLaunch {
   double push_t[ING_VRING] = {};       // IngestJob::t_push of packet p, p % ING_VRING, until its verdict says whether it cut a frame
   int filter = 0, intended = 0;        // the frame event filter selected by the last set_filter job (0: none) ...
   unsigned char push_filter[ING_VRING] = {};  // ... and what packet p was pushed under: filter | intended << 3 (its frame's filter)
+  int surf_select = 0, surf_dtype = 0; // the surface stage's setting from the last set_surface job (select 0: off) ...
+  unsigned char push_surface[ING_VRING] = {};  // ... and what packet p was pushed under: select | dtype << 2
   IngestDev dev{};                     // = IngestFixed::dev with the CURRENT packet's desc / info / verdict / act: passed by value to its kernels
   int act_toggle = 0;                  // the set of cells the next non-empty packet takes (ingest_act_set)
   uint64_t act_fused_push = 0;         // the packet whose k_act_first went out with its predecessor's k_ing_count (k_ing_count_act)
@@ -269,6 +291,7 @@ struct IngestShared {
 struct xm_ingest {
   IngestFixed fx;
   IngestFrameFilter ff;
+  IngestSurface sf;
   IngestCaller ca;
   IngestLaunch la;
   IngestOutSide out;

@@ -299,5 +299,23 @@ void launch_frame_filter(const FrameFilterDev& f, u64 n_bound, hipStream_t strea
   XM_LAUNCH(k_ff_emit, dim3(gc), dim3(FF_BLOCK), 0, stream, f, (u32)gc);
 }
 
+// ---- frames -> camera time surfaces (xmaps_framesurface.hpp): the group entry and the ingest's surface stage ---------------------
+// One launch sequence: n_frames (<= FS_GROUP) frames, the longest of n_max events (the ingest: the verdict's count).  The event
+// pass takes one block per FS_CHUNK events of the longest frame, at most a.max_chunk_blocks; the cell pass one per
+// FS_CELLS_PER_BLOCK cells of the fixed map.
+u32 fs_max_chunk_blocks() {  // ("XM_FS_MAX_BLOCKS": tests send short frames through the event pass's further trips)
+  const char* o = dbg_opt("XM_FS_MAX_BLOCKS");
+  const long v = o ? atol(o) : 0;
+  return v > 0 && v < 65535 ? (u32)v : 4096u;
+}
+void launch_frame_surfaces(const FsArgs& a, unsigned n_frames, u64 n_max, int dtype, hipStream_t stream) {
+  const unsigned ge = std::min<unsigned>(grid_for(n_max < 1 ? 1 : n_max, FS_CHUNK), a.max_chunk_blocks);
+  const unsigned gc = grid_for(a.cells, FS_CELLS_PER_BLOCK);
+  XM_LAUNCH(k_fs_events, dim3(ge, n_frames), dim3(FS_THREADS), 0, stream, a);
+  if (dtype == XM_T_FLOAT32) XM_LAUNCH(k_fs_pixels<float>, dim3(gc, n_frames), dim3(FS_THREADS), 0, stream, a);
+  else XM_LAUNCH(k_fs_pixels<double>, dim3(gc, n_frames), dim3(FS_THREADS), 0, stream, a);
+  XM_LAUNCH(k_fs_finish, dim3(grid_for(n_frames, 64)), dim3(64), 0, stream, a, (u32)n_frames);
+}
+
 
 }  // namespace

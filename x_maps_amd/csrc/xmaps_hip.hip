@@ -13,6 +13,7 @@
 #include "xmaps_evt3.hpp"           // EVT 3.0 decoder (xmaps_evt.hpp: what it shares with the next one)
 #include "xmaps_evt2.hpp"           // EVT 2.0 decoder
 #include "xmaps_surface.hpp"        // time surfaces -> depth maps + point clouds
+#include "xmaps_framesurface.hpp"   // frames of events -> camera time surfaces (the group entry and the ingest's surface stage)
 
 #include <hip/hip_ext.h>
 
@@ -73,6 +74,7 @@ using namespace xm;
 #include "host/xm_api_rigmaps.hpp"  // a rig's rectification maps, time map and X-map: the table builders' device path
 #include "host/xm_group.hpp"        // the skeleton of the group objects below: create / destroy, argument check, staging, dtype dispatch
 #include "host/xm_api_surface.hpp"  // a group of camera time surfaces -> depth maps + point clouds (the evaluation caller's entry)
+#include "host/xm_api_framesurface.hpp"  // a group of frames of events -> camera time surfaces: what joins the live half to the entries around it
 #include "host/xm_api_eslinit.hpp"  // the ESL-init baseline on the same surfaces: depth_init maps, disparity_init alone
 #include "host/xm_api_mc3d.hpp"     // the MC3D baseline on the same surfaces
 #include "host/xm_api_esloptim.hpp" // the ESL depth optimisation behind ESL-init: depth_optim maps

@@ -38,3 +38,5 @@
 #include "xmaps_esloptim.hpp"   // the ESL depth optimisation: one bounded scalar minimisation per camera pixel
 #include "xmaps_eslfilter.hpp"  // the ESL filters behind it: bilateral filter and TV denoiser (split Bregman around lsqr)
 #include "xmaps_evaltable.hpp"  // the evaluation table's scorer: combine, median, the metrics of every (method, scan) cell
+// (included by xmaps_hip.hip behind the ingest, whose frame descriptors it reads:)
+//       "xmaps_framesurface.hpp"  frames of events -> camera time surfaces: winners by integer atomics, one store per pixel

@@ -117,6 +117,7 @@ class DepthReprojectionPipe:
         self._ingest_filter_refused = False
         self._ingest_failed = False  # an ingest call has raised: the error has reached the caller, close() does not ask again
         self._closed = False
+        self._surface_callback = getattr(p, "surface_callback", None)
         if self.activity_filter is None and getattr(p, "activity_filter", True):
             _warn_activity_rule_unpinned()
         # a caller-supplied activity filter (Metavision's own, where the SDK is installed) runs on the host: so does the chain
@@ -128,6 +129,8 @@ class DepthReprojectionPipe:
                                        result_ring=int(getattr(p, "ingest_result_ring", 16)),
                                        lossless=not p.should_drop_frames)  # no_frame_dropping (the default): never lap the ring
             self._ingest_views = bool(getattr(p, "ingest_frame_views", False))
+            if self._surface_callback is not None:  # (before the first push: every frame of the stream gets a surface)
+                self.ingest.set_surface_output("last", np.float32)
         else:
             self._ensure_host_chain()
 
@@ -188,6 +191,12 @@ class DepthReprojectionPipe:
             if self._device_frame_filters and fr.n_events:
                 self.stats_printer.add_metric("frame evs filtered out [%]", 100 - fr.n_kept / fr.n_events * 100)
             self.last_ingest_frame = fr
+            if self._surface_callback is not None:
+                surf = self.ingest.surface(fr.seq)
+                if surf is None:  # (the surface ring is as long as the result ring: lapped only where the frame is lost too)
+                    self.stats_printer.count("surface lost")
+                else:
+                    self._surface_callback(surf)
             # a fresh array copied out of the pinned result ring, or (RuntimeParams.ingest_frame_views) a view into it that stays
             # valid until ingest_result_ring - 1 further frames have been produced
             self.frame_callback(fr.bgr)
@@ -269,6 +278,9 @@ class DepthReprojectionPipe:
     def process_ev_frame(self, evs):
         if len(evs) == 0:
             raise ValueError("zero-size array to reduction operation minimum which has no identity")  # xmd:12
+        if self._surface_callback is not None:  # (the cut frame's, in front of any frame event filter: as the ingest's stage)
+            surfs, _ = self.calib_maps.engine.frames_to_time_surfaces([evs], "last", np.float32)
+            self._surface_callback(surfs[0])
         if not isinstance(self.ev_filter_proc.selected_filter(), NoFilter):  # pipe:131-139
             with self.stats_printer.measure_time("frame ev filter"):
                 n_before = len(evs)

@@ -12,7 +12,7 @@ The window is pluggable; without Metavision's MTWindow the reference's own FakeW
 from __future__ import annotations
 
 from dataclasses import dataclass, field
-from typing import Any, Optional
+from typing import Any, Callable, Optional
 
 from .depth_reprojection_pipe import DepthReprojectionPipe
 from .stats import StatsPrinter
@@ -78,6 +78,12 @@ class RuntimeParams:
     # (calibration.build_tables(maps_on_device=True), x_maps_amd/rig_maps.py) instead of NumPy on the host.  The same tables,
     # bit for bit.
     tables_on_device: bool = False
+    # surface_callback(surface) for every shown frame, immediately before that frame's frame_callback: the frame's camera time
+    # surface (float32 [camera_height][camera_width]; per pixel the stamp of the frame's last event there as t - the frame's first
+    # stamp + 1, 0 = no event: XMapsEngine.frames_to_time_surfaces), built from the CUT frame, in front of any frame event filter.
+    # On the device ingest it is a stage of the ingest (DeviceIngest.set_surface_output); on the host chain one call of the
+    # group entry on the frame's events.  The same arrays either way.  What the evaluation entries take as `scans_np`.
+    surface_callback: Optional[Callable] = None
 
     @property
     def should_drop_frames(self):

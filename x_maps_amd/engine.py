@@ -51,6 +51,20 @@ class SurfaceStats:
                             float(s.t_min), float(s.t_max))
 
 
+@dataclass
+class FrameSurfaceStats:
+    """xm_frame_surface_stats of one frame's time surface (frames_to_time_surfaces, DeviceIngest.surface)."""
+    n_events: int = 0
+    n_pixels: int = 0
+    n_index_errors: int = 0
+    t_base: int = 0
+    t_span: int = 0
+
+    @staticmethod
+    def from_c(s: N.xm_frame_surface_stats) -> "FrameSurfaceStats":
+        return FrameSurfaceStats(int(s.n_events), int(s.n_pixels), int(s.n_index_errors), int(s.t_base), int(s.t_span))
+
+
 def _ptr(a) -> C.c_void_p:
     if a is None:
         return C.c_void_p(None)
@@ -524,6 +538,35 @@ class XMapsEngine:
             k = int(st[i].n_inliers)
             out.append((depth[i], cloud[i, :k].copy() if want_cloud else None, SurfaceStats.from_c(st[i])))
         return out
+
+    # ---- frames of events in, camera time surfaces out (what the calls above take) -------------------------------
+    def frames_to_time_surfaces(self, frames, select="last", dtype=np.float32, use_polarity=False):
+        """A list of EventCD arrays (one per frame; any may be empty) in ONE device call -> (surfaces [n][cam_h][cam_w] of
+        `dtype`, [FrameSurfaceStats]).  Per pixel the stamp of the last / first event of the frame that fired there (stream
+        order, `select`), as t - (the frame's smallest t) + 1; 0 = no event.  The definition: include/xmaps.h,
+        xm_frames_to_time_surfaces.  Engines of either view."""
+        from .synthetic import EVENT_CD_DTYPE
+        sel = {"last": N.XM_SURFACE_LAST, "first": N.XM_SURFACE_FIRST}.get(select)
+        if sel is None:
+            raise ValueError('select must be "last" or "first"')
+        dt = np.dtype(dtype)
+        if dt not in _T_DTYPES or dt == np.int64:
+            raise ValueError("dtype must be float32 or float64")
+        frames = [np.ascontiguousarray(f if f.dtype == EVENT_CD_DTYPE else f.astype(EVENT_CD_DTYPE)) for f in frames]
+        if not frames:
+            raise ValueError("no frames")
+        n = len(frames)
+        offsets = np.zeros(n + 1, np.uint64)
+        offsets[1:] = np.cumsum([len(f) for f in frames])
+        evs = np.zeros(int(offsets[-1]), EVENT_CD_DTYPE)  # (np.concatenate would hand back the packed 14-byte layout under NumPy 2)
+        for f, a in zip(frames, offsets[:-1]):
+            evs[int(a):int(a) + len(f)] = f
+        out = np.empty((n, self.cam_h, self.cam_w), dt)
+        st = (N.xm_frame_surface_stats * n)()
+        N.check(self._lib.xm_frames_to_time_surfaces(self._h, _ptr(evs) if len(evs) else None,
+                                                     offsets.ctypes.data_as(C.POINTER(C.c_uint64)), n, int(bool(use_polarity)), sel,
+                                                     _T_DTYPES[dt], N.XM_MEM_HOST, _ptr(out), C.cast(st, C.c_void_p)))
+        return out, [FrameSurfaceStats.from_c(s) for s in st]
 
     # ---- N3: per-frame de-duplication filters ------------------------------------------------------------
     def frame_event_filter(self, filter_id: int, evs: np.ndarray, xp_i16=None, map_shape=None,

@@ -16,8 +16,15 @@ this build's choice), and both give the same depth maps and clouds bit for bit.
 The baseline of the same evaluation, ESL-init (compute_depth_esl.py up to depth_init), takes the same surfaces: esl_init.py; so does the
 MC3D baseline (mc3d_baseline.py): mc3d.py.  ESL's depth optimisation behind ESL-init (depth_optimization): esl_optim.py.
 
-Out of scope: file handling, the bilateral and TV filters behind ESL's optimisation (which turn its maps into the
-table's ground truth), a projector-view surface path.  (The metrics of eval/ are in eval_metrics.py.)
+The other direction -- a frame of events -> its camera time surface, the `scans_np` image these routes start from -- is
+XMapsEngine.frames_to_time_surfaces (a group of frames in one device call), DeviceIngest.set_surface_output / surface (every cut
+frame of a live stream or a replay) and RuntimeParams.surface_callback; tools/run_esl_on_arrival.py --scans-from-raw writes the
+files.  Those surfaces are this build's definition (include/xmaps.h): the ESL dataset's own events-to-scan converter is not part
+of the reference, so they are not pinned against its scans_np files.  The filters behind ESL's optimisation, which
+turn its maps into the table's ground truth: esl_filter.py.
+
+Out of scope: a projector-view surface path; device-resident surfaces in the Python interface.  (The metrics of
+eval/ are in eval_metrics.py.)
 """
 from __future__ import annotations
 

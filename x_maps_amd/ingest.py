@@ -141,6 +141,39 @@ class DeviceIngest:
         ValueError: an unknown filter, or FirstEventPerYT on a rig whose (y, xr) cell map would be too large (nothing changes)."""
         N.check(self._lib.xm_ingest_set_frame_filter(self._g, int(filter_id), int(bool(intended_semantics))))
 
+    def set_surface_output(self, select="last", dtype=np.float32, ring: int = 0):
+        """The surface stage for the frames cut by the packets pushed from now on (ordered like a push): every cut frame's camera
+        time surface -- per pixel the stamp of its last / first event there as t - t_first_of_frame + 1, 0 = no event; built from
+        the CUT frame, in front of any frame event filter -- is kept in a ring of `ring` surfaces in device memory (0: as many as
+        the result ring) for surface(seq).  select: "last", "first", or None / "off" to switch the stage off.  The ring's length
+        is fixed by the first call that switches the stage on."""
+        sel = {"last": N.XM_SURFACE_LAST, "first": N.XM_SURFACE_FIRST, "off": 0, None: 0}.get(select, -1)
+        if sel < 0:
+            raise ValueError('select must be "last", "first" or None')
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise ValueError("dtype must be float32 or float64")
+        N.check(self._lib.xm_ingest_set_surface_output(self._g, sel, N.XM_T_FLOAT32 if dt == np.float32 else N.XM_T_FLOAT64, int(ring)))
+
+    def surface(self, seq: int, with_stats: bool = False):
+        """The time surface of frame `seq` (IngestFrame.seq) as the caller's own [cam_h][cam_w] array, or None when the ring does
+        not hold it (the stage was off when the frame was cut, or the ring has been lapped).  Complete once poll() has handed
+        the frame out.  with_stats: (surface, FrameSurfaceStats) instead."""
+        from .engine import FrameSurfaceStats
+        dt = self._lib.xm_ingest_surface_dtype(self._g, int(seq))
+        if dt < 0:
+            N.check(dt)
+        if dt == 0:
+            return None
+        out = np.empty((self._e.cam_h, self._e.cam_w), np.float32 if dt == N.XM_T_FLOAT32 else np.float64)
+        st = N.xm_frame_surface_stats()
+        rc = self._lib.xm_ingest_copy_surface(self._g, int(seq), C.c_void_p(out.ctypes.data), N.XM_MEM_HOST, C.byref(st))
+        if rc < 0:
+            N.check(rc)
+        if rc == 0 or self._lib.xm_ingest_surface_dtype(self._g, int(seq)) != dt:
+            return None
+        return (out, FrameSurfaceStats.from_c(st)) if with_stats else out
+
     def push_pinned(self, evs: np.ndarray):
         """A packet that already lives in pinned host memory (XMapsEngine.host_empty): no staging copy."""
         assert evs.dtype == EVENT_CD_DTYPE and evs.flags.c_contiguous
