@@ -847,6 +847,65 @@ int xm_ingest_copy_surface(xm_ingest* g, uint64_t seq, void* dst, int mem, xm_fr
 /* the dtype (XM_T_*) the surface of frame seq was built with, or 0 when the ring does not hold it */
 int xm_ingest_surface_dtype(xm_ingest* g, uint64_t seq);
 
+/* ---- frames of events in, per-event point clouds out: the live half's 3-D output ------------------------------------------------
+ * The reference's CamProjMaps.construct_point_cloud (cam_proj_calibration.py:319-331) as eval/compute_depth_x_maps.py:99-122
+ * applies it per event -- construct_point_cloud(xr_f32[mask], yr_f32[mask], disparity) -- on a frame of EventCD records, from the
+ * same int64 stamps and X-map columns as the frame's depth map.  Nothing of the definition is this build's own.  For one frame, on a
+ * handle of EITHER view:
+ *   - with use_polarity != 0 only the events with p == 1 exist at all (as in xm_process_frame_aos); otherwise every event exists;
+ *   - (t_min, t_max) are taken over ALL existing events, those left out below included;
+ *   - an existing event with x >= cam_width or y >= cam_height is LEFT OUT and counted in n_index_errors; so is one whose time
+ *     column falls outside the X-map;
+ *   - every other existing event goes through A1 and A2 -- the packed int16 rectify LUT, the int64 time normalisation (ties round
+ *     to even; t_max == t_min puts every event in column 0) and the X-map lookup, the code K1 runs -- and is an INLIER iff both
+ *     masks of x_maps_disparity.py:23,29 hold (0 <= yr < xmap_height - 1, disparity >= 0);
+ *   - the cloud holds one row per inlier event IN STREAM ORDER (stable, duplicates kept: the order of xr_f[mask]):
+ *     row = [x + d, y, -d, 1] through Q in float32, perspective divide, y and z negated, with x = mapx_f32[y][x],
+ *     y = mapy_f32[y][x] and d = (float)disparity -- xm_stage_point_cloud's arithmetic.  disparity == 0 gives the reference's
+ *     inf / nan row;
+ *   - an empty frame is defined: no rows, zero statistics.
+ * The result depends on the frame alone: not on the run, on the frame's place in a group or on earlier calls.  There is no
+ * floating-point atomic and no kernel waits for another block of its launch (x_maps_amd/csrc/xmaps_framecloud.hpp).
+ * Debug option "XM_FC_MAX_BLOCKS" (xm_debug_option): the most blocks per frame of the per-event passes, read at every group call
+ * and when an ingest's cloud stage is first switched on. */
+typedef struct xm_frame_cloud_stats {
+  uint64_t n_events;       /* existing events (all, or those with p == 1)                                              */
+  uint64_t n_inliers;      /* rows of the frame's cloud                                                                */
+  uint64_t n_index_errors; /* existing events left out (off the sensor, or a time column outside the X-map)            */
+  int64_t t_min;           /* the smallest / largest t over the existing events, those left out included (0, 0 for a   */
+  int64_t t_max;           /*   frame without any)                                                                     */
+} xm_frame_cloud_stats;
+/* The float rectify maps [cam_height][cam_width] and the 4x4 float64 Q (cast to float32 as xm_stage_point_cloud does) of the two
+ * entries below; copied.  Accepted on handles of either view (xm_surface_set_cloud_tables and its camera-view rule are another
+ * entry's and stay as they are).  Set them before an ingest on the handle switches its cloud stage on; a later call rewrites the
+ * same device tables once the device is idle. */
+int xm_cloud_set_tables(xm_handle* h, const float* mapx_f32, const float* mapy_f32, const double* Q);
+/* Frame f = records [offsets_host[f], offsets_host[f + 1]) of eventcd16 (16-byte EventCD records; 16-byte aligned in device
+ * memory).  cloud_out: f32 [offsets_host[n_frames] - offsets_host[0]][3]; frame f's rows start at row offsets_host[f] -
+ * offsets_host[0], the first n_inliers of them are valid, the rest are left untouched.  cloud_out == NULL: statistics only.
+ * stats_out (may be NULL): xm_frame_cloud_stats[n_frames].  mem == XM_MEM_HOST: records, cloud and statistics are host memory,
+ * the call is synchronous and only valid rows are copied back.  XM_MEM_DEVICE: all three are device memory; everything is enqueued
+ * on the next slot's stream, xm_sync() waits, the buffers stay valid and untouched until then (offsets_host is read inside the
+ * call).  Groups of any length are accepted (they go out as launch sequences of 32 frames).  Scratch is allocated by the first
+ * call and grown when a larger group arrives.  XM_ERR_INVALID: cloud_out without xm_cloud_set_tables, n_frames <= 0, decreasing
+ * offsets, a mem other than the two. */
+int xm_frames_to_point_clouds(xm_handle* h, const void* eventcd16, const uint64_t* offsets_host, int n_frames, int use_polarity,
+                              int mem, float* cloud_out, xm_frame_cloud_stats* stats_out);
+/* The same as a stage of the device ingest, ordered and ring-managed exactly like xm_ingest_set_surface_output: the frames cut by
+ * packets pushed AFTER the call get a cloud -- built on the frame stream from the CUT frame (polarity is not applied again), in
+ * front of any frame event filter -- in a ring of `ring` entries (0: the ingest's result_ring) of max_points rows in device memory.
+ * on != 0 needs max_points > 0 and the handle's xm_cloud_set_tables.  A frame with more inliers keeps its FIRST max_points rows in
+ * stream order; n_inliers reports the true count, so truncation is visible.  on == 0 switches the stage off: the ingest then
+ * launches nothing for it.  Scratch and ring are allocated by the first call that switches the stage on; a later call may not
+ * change max_points or the ring's length (XM_ERR_INVALID). */
+int xm_ingest_set_cloud_output(xm_ingest* g, int on, int64_t max_points, int ring);
+/* The cloud of frame `seq` (xm_ingest_frame.seq): its min(n_inliers, max_points) rows -> dst (f32 [..][3]; host or device memory
+ * by `mem`; NULL: statistics only), its statistics -> *stats (host memory, may be NULL).  Returns 1: copied, and the ring entry was
+ * still intact after the copy; 0: never produced, not complete yet, or already overwritten (dst may have been written); < 0: an
+ * error.  Once xm_ingest_poll* has handed out frame seq its cloud is complete.  xm_ingest_reset keeps the stage's setting and
+ * drops the ring's contents.  Synchronous. */
+int xm_ingest_copy_cloud(xm_ingest* g, uint64_t seq, float* dst, int mem, xm_frame_cloud_stats* stats);
+
 /* ---- ESL-init: the baseline of the reference's evaluation table, on the device ------------------------------------------------
  * What python/eval/compute_depth_esl.py:204-226 computes up to depth_init (the optimisation behind it: xm_esl_optim_* below; MC3D: xm_mc3d_*),
  * for a GROUP of camera time surfaces in one device call.  Per surface:

@@ -14,6 +14,8 @@ The bias file only configures a live camera (bias_events_iterator.py:69-78): acc
 With --scans-from-raw DIR part A also writes every shown frame's camera time surface to DIR/scans_np/scansNNN.npy (built on the
 device from the cut frame: RuntimeParams.surface_callback) and part B runs on DIR: a recording without the dataset's scans_np -- a
 rig of one's own -- gets its table rows from the RAW file alone.  They are this build's surfaces, not the ESL dataset's.
+With --clouds-from-raw DIR part A also writes every shown frame's per-event point cloud to DIR/pointcloud_live/frameNNNNNN.ply
+(the reference's construct_point_cloud on the cut frame's inlier events, built on the device: RuntimeParams.cloud_callback).
 
 Part B -- the accuracy row (eval/x-map-eval.sh:24-72 -> python/eval/compute_depth_x_maps.py:22-133 ->
 python/eval/create_evaluation_table.py:84-180): every `<scans>/scans_np/*.npy` time surface -> X-maps depth in camera view on
@@ -67,10 +69,12 @@ def raw_format(path: str) -> int:
 
 
 def replay_raw(raw, calib, proj_w, proj_h, fps, z_near, z_far, camera_perspective=False, device=0, chunk_words=1 << 20,
-               device_ingest=True, keep_frames=0, tables=None, max_chunks=0, scans_dir=None):
+               device_ingest=True, keep_frames=0, tables=None, max_chunks=0, scans_dir=None, clouds_dir=None):
     """Part A.  -> dict(report), list of (frame checksum, shape) per shown frame, the first `keep_frames` frames
     scans_dir: every shown frame's camera time surface (RuntimeParams.surface_callback: float32, this build's definition) is
-    written to <scans_dir>/scans_np/scansNNN.npy, N counting the shown frames from 0 -- what part B reads"""
+    written to <scans_dir>/scans_np/scansNNN.npy, N counting the shown frames from 0 -- what part B reads
+    clouds_dir: every shown frame's per-event point cloud (RuntimeParams.cloud_callback) is written to
+    <clouds_dir>/pointcloud_live/frameNNNNNN.ply, N counting the same way"""
     from x_maps_amd import evt2, evt3
     from x_maps_amd.depth_reprojection_processor import DepthReprojectionProcessor, RuntimeParams
     fmt = raw_format(raw)
@@ -95,11 +99,20 @@ def replay_raw(raw, calib, proj_w, proj_h, fps, z_near, z_far, camera_perspectiv
             np.save(os.path.join(scans_dir, "scans_np", scan_name(n_surfaces[0])), surf)
             n_surfaces[0] += 1
 
+    cloud_points = []
+    cloud_cb = None
+    if clouds_dir:
+        os.makedirs(os.path.join(clouds_dir, "pointcloud_live"), exist_ok=True)
+
+        def cloud_cb(cloud):
+            write_ply(os.path.join(clouds_dir, "pointcloud_live", cloud_name(len(cloud_points))), cloud)
+            cloud_points.append(len(cloud))
+
     t_setup = time.perf_counter()
     params = RuntimeParams(camera_width=640, camera_height=480, projector_width=proj_w, projector_height=proj_h, projector_fps=fps,
                            z_near=z_near, z_far=z_far, calib=calib, projector_time_map=None, no_frame_dropping=True,
                            camera_perspective=camera_perspective, tables=tables, device=device, device_ingest=device_ingest,
-                           surface_callback=surface_cb)
+                           surface_callback=surface_cb, cloud_callback=cloud_cb)
     n_words = n_chunks = 0
     with DepthReprojectionProcessor(params, window=Window()) as proc:
         t_setup = time.perf_counter() - t_setup
@@ -114,6 +127,7 @@ def replay_raw(raw, calib, proj_w, proj_h, fps, z_near, z_far, camera_perspectiv
         proc.flush()
         dt = time.perf_counter() - c0
         ds = proc._pipe.ingest.device_stats() if proc._pipe.ingest is not None else None
+        clouds_lost = int(proc._pipe.stats_printer.counters.get("cloud lost", 0)) if clouds_dir else 0
     rep = {"raw": raw, "format": f"EVT {fmt}.0", "words": n_words, "chunks": n_chunks, "chunk_words": chunk_words,
            "path": "device ingest (decode + filters + trigger finder + hot path on the GPU)" if device_ingest else
                    "host chain (NumPy decoder, filters, trigger finder; one fused GPU call per frame)",
@@ -125,6 +139,9 @@ def replay_raw(raw, calib, proj_w, proj_h, fps, z_near, z_far, camera_perspectiv
                                  "definition": "this build's surfaces (per pixel the stamp of the cut frame's last event there, t - the "
                                                "frame's first stamp + 1, float32; include/xmaps.h xm_frames_to_time_surfaces), NOT the ESL "
                                                "dataset's scans_np: ESL's own events-to-scan converter is not part of the reference"}
+    if clouds_dir:
+        rep["clouds_from_raw"] = {"dir": os.path.join(clouds_dir, "pointcloud_live"), "frames": len(cloud_points),
+                                  "points": int(sum(cloud_points)), "points_per_frame": cloud_points, "clouds_lost": clouds_lost}
     if ds is not None:
         rep["device"] = ds
         rep["events_behind_the_filters"] = ds["events_appended"]
@@ -210,6 +227,10 @@ def scan_groups(names, start_scan, num_scans, group):
     last = len(names) if not num_scans else min(len(names), start_scan + num_scans)
     for g0 in range(start_scan, last, max(1, group)):
         yield range(g0, min(last, g0 + max(1, group)))
+
+
+def cloud_name(i):
+    return "frame" + str(i).zfill(6) + ".ply"
 
 
 def scan_name(i):
@@ -396,6 +417,8 @@ def main(argv=None):
     ap.add_argument("--scans-from-raw", metavar="DIR",
                     help="part A also writes every shown frame's camera time surface to DIR/scans_np/scansNNN.npy (this build's "
                          "surfaces, not the ESL dataset's); part B then runs on --scans DIR unless --scans names another directory")
+    ap.add_argument("--clouds-from-raw", metavar="DIR",
+                    help="part A also writes every shown frame's per-event point cloud to DIR/pointcloud_live/frameNNNNNN.ply")
     ap.add_argument("--eval-calib", help="the ESL dataset's calib.yaml (cam_K, cam_kc, proj_K, proj_kc, R, T) for part B")
     ap.add_argument("--projector-width", type=int, default=1080)
     ap.add_argument("--projector-height", type=int, default=1920)
@@ -437,12 +460,15 @@ def main(argv=None):
         ap.error("nothing to do: give --raw and / or --scans")
     if a.scans_from_raw and not a.raw:
         ap.error("--scans-from-raw needs --raw")
+    if a.clouds_from_raw and not a.raw:
+        ap.error("--clouds-from-raw needs --raw")
     report = {"published": PUBLISHED}
     if a.raw:
         if a.bias:
             report["bias_file"] = {"path": a.bias, "present": os.path.exists(a.bias), "note": "configures a live camera only"}
         rep, shown, kept = replay_raw(a.raw, a.calib, a.projector_width, a.projector_height, a.projector_fps, a.z_near, a.z_far,
-                                      a.camera_perspective, a.device, a.chunk_words, True, a.save_frames, scans_dir=a.scans_from_raw)
+                                      a.camera_perspective, a.device, a.chunk_words, True, a.save_frames, scans_dir=a.scans_from_raw,
+                                      clouds_dir=a.clouds_from_raw)
         report["replay"] = rep
         if a.scans_from_raw and not a.scans and a.eval_calib:
             a.scans = a.scans_from_raw  # part B on the surfaces part A has just written

@@ -196,6 +196,11 @@ class xm_frame_surface_stats(C.Structure):
                 ("t_base", C.c_int64), ("t_span", C.c_int64)]
 
 
+class xm_frame_cloud_stats(C.Structure):
+    _fields_ = [("n_events", C.c_uint64), ("n_inliers", C.c_uint64), ("n_index_errors", C.c_uint64),
+                ("t_min", C.c_int64), ("t_max", C.c_int64)]
+
+
 class xm_esl_init_config(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("cam_width", C.c_int32), ("cam_height", C.c_int32),
                 ("rect_width", C.c_int32), ("rect_height", C.c_int32), ("min_disp", C.c_int32), ("max_disp", C.c_int32),
@@ -363,6 +368,10 @@ SYMBOLS = {
     "xm_ingest_set_surface_output": (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
     "xm_ingest_copy_surface": (C.c_int, [_P, C.c_uint64, _P, C.c_int, C.POINTER(xm_frame_surface_stats)]),
     "xm_ingest_surface_dtype": (C.c_int, [_P, C.c_uint64]),
+    "xm_cloud_set_tables": (C.c_int, [_P, _P, _P, _P]),
+    "xm_frames_to_point_clouds": (C.c_int, [_P, _P, C.POINTER(C.c_uint64), C.c_int, C.c_int, C.c_int, _P, _P]),
+    "xm_ingest_set_cloud_output": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int]),
+    "xm_ingest_copy_cloud": (C.c_int, [_P, C.c_uint64, _P, C.c_int, C.POINTER(xm_frame_cloud_stats)]),
     "xm_esl_init_create": (C.c_int, [C.c_int, C.POINTER(xm_esl_init_config), C.POINTER(_P)]),
     "xm_esl_init_destroy": (None, [_P]),
     "xm_esl_init_time_surfaces": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),

@@ -397,6 +397,79 @@ int xm_ingest_copy_surface(xm_ingest* g, uint64_t seq, void* dst, int mem, xm_fr
   return 1;
 }
 
+// the cloud stage's scratch and ring, once (IngestCloud)
+static int ingest_cloud_alloc(xm_ingest* g, size_t max_points, int ring) {
+  IngestCloud& cl = g->cl;
+  const xm_handle* h = g->fx.h;
+  cl.ring = ring;
+  cl.max_points = max_points;
+  cl.cap = (u32)g->fx.dev.mirror;  // (a cut frame is contiguous in the event ring: at most half of it)
+  cl.max_chunk_blocks = fc_max_chunk_blocks();
+  const size_t n_seg = (size_t)cl.cap / 64 + 1;
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  HIP_TRY(cl.d_acc.alloc(1));
+  HIP_TRY(cl.d_code.alloc(cl.cap));
+  HIP_TRY(cl.d_cnt.alloc(n_seg));
+  HIP_TRY(cl.d_off.alloc(n_seg));
+  HIP_TRY(cl.d_stats.alloc(ring));
+  HIP_TRY(cl.d_ring.alloc((size_t)ring * max_points * 3));
+  HIP_TRY(cl.h_tag.alloc(ring, hipHostMallocMapped));
+  HIP_TRY(cl.h_stats.alloc(ring, hipHostMallocMapped));
+  memset(cl.h_tag, 0, sizeof(u64) * ring);
+  memset(cl.h_stats, 0, sizeof(FcStats) * ring);
+  HIP_TRY(hipMemset(cl.d_acc, 0, sizeof(FcAcc)));
+  HIP_TRY(hipMemset(cl.d_stats, 0, sizeof(FcStats) * ring));
+  HIP_TRY(hipDeviceSynchronize());  // (default-stream memsets: the ingest's non-blocking streams do not wait for them)
+  cl.ready = true;
+  return XM_OK;
+}
+
+int xm_ingest_set_cloud_output(xm_ingest* g, int on, int64_t max_points, int ring) {
+  if (!g) return fail(XM_ERR_INVALID, "NULL argument");
+  if (ring < 0 || ring > 65536) return fail(XM_ERR_INVALID, "ring must lie in 0 .. 65536");
+  if (on && (max_points <= 0 || max_points >= (1ll << 31))) return fail(XM_ERR_INVALID, "max_points must lie in 1 .. 2^31 - 1");
+  if (on && !g->fx.h->fcloud.has_tables)
+    return fail(XM_ERR_INVALID, "the cloud stage needs the float rectify maps and Q: call xm_cloud_set_tables on the handle first");
+  int rc = ingest_take_error(g);
+  if (rc) return rc;
+  if (on) {
+    const int want = ring ? ring : g->fx.ring;
+    if (!g->cl.ready && (rc = ingest_cloud_alloc(g, (size_t)max_points, want))) return rc;
+    if (g->cl.ring != want || g->cl.max_points != (size_t)max_points)
+      return fail(XM_ERR_INVALID, "the cloud ring holds %d entries of %zu rows since the first call that switched the stage on", g->cl.ring,
+                  g->cl.max_points);
+  }
+  // ordered like a push: the packets handed in before this call keep the setting they were pushed under
+  IngestJob j;
+  j.kind = JobKind::set_cloud;
+  j.cloud_on = on ? 1 : 0;
+  return ingest_submit(g, j, false);
+}
+
+int xm_ingest_copy_cloud(xm_ingest* g, uint64_t seq, float* dst, int mem, xm_frame_cloud_stats* stats) {
+  if (!g || (!dst && !stats)) return fail(XM_ERR_INVALID, "NULL argument");
+  if (mem != XM_MEM_HOST && mem != XM_MEM_DEVICE) return fail(XM_ERR_INVALID, "mem must be XM_MEM_HOST or XM_MEM_DEVICE");
+  const IngestCloud& cl = g->cl;
+  if (!cl.ready) return 0;
+  const size_t e = (size_t)(seq % (uint64_t)cl.ring);
+  const u64* tag = cl.h_tag + e;
+  // the tag names the frame only between the stage's last launch for it and the first launch of the frame that takes the entry
+  // next (k_fc_extrema clears it in front of the pass that rewrites the entry): named before AND after the copy = intact
+  if (__atomic_load_n(tag, __ATOMIC_ACQUIRE) != seq + 1) return 0;
+  FcStats st;
+  memcpy(&st, cl.h_stats + e, sizeof st);
+  const size_t rows = (size_t)std::min<u64>(st.n_inliers, cl.max_points);
+  if (dst && rows) {
+    HIP_TRY(hipSetDevice(g->fx.h->cfg.device));
+    HIP_TRY(hipMemcpy(dst, cl.d_ring + e * cl.max_points * 3, rows * 12, mem == XM_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice));
+    if (mem == XM_MEM_DEVICE) HIP_TRY(hipStreamSynchronize(nullptr));
+  }
+  __atomic_thread_fence(__ATOMIC_ACQUIRE);
+  if (__atomic_load_n(tag, __ATOMIC_ACQUIRE) != seq + 1) return 0;
+  if (stats) memcpy(stats, &st, sizeof st);
+  return 1;
+}
+
 int xm_ingest_flush(xm_ingest* g) {
   if (!g) return fail(XM_ERR_INVALID, "NULL argument");
   HIP_TRY(hipSetDevice(g->fx.h->cfg.device));
@@ -420,6 +493,8 @@ int xm_ingest_reset(xm_ingest* g) {
   // the surface stage keeps its setting; what its ring holds belongs to the stream that ended (nothing is in flight: flushed)
   if (g->sf.ready)
     for (int e = 0; e < g->sf.ring; ++e) __atomic_store_n(g->sf.h_tag + e, 0ull, __ATOMIC_RELEASE);
+  if (g->cl.ready)
+    for (int e = 0; e < g->cl.ring; ++e) __atomic_store_n(g->cl.h_tag + e, 0ull, __ATOMIC_RELEASE);
   // The activity filter's history goes too: a reset is "the stream starts over" (the reference resets when a recording loops,
   // depth_reprojection.py:76) and its stamps then start below everything the history holds -- against the old history every
   // event with a neighbour that ever fired would pass.  (Metavision's filter object keeps its state there; the frames behind

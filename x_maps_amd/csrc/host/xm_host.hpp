@@ -134,6 +134,21 @@ struct FrameSurfScratch {
   bool dirty = false;
 };
 
+// The frame -> point cloud entry (xm_api_framecloud.hpp): its own cloud tables (handles of either view; the ingest's cloud stage
+// reads the same) + grow-only scratch, ordered between calls like SurfaceScratch.  The accumulators are ALL ZERO between calls
+// (k_fc_scan leaves them so); `dirty` as in FrameSurfScratch.  Codes, counts and offsets are rewritten by every call before it
+// reads them.
+struct FrameCloudScratch {
+  Event done;
+  hipStream_t last_stream = nullptr;
+  DevMem<float> mapx, mapy;  // float rectify maps [cam_h][cam_w] (xm_cloud_set_tables)
+  Mat4f q{};
+  bool has_tables = false;
+  DevBuf acc, code, cnt, off, stats;  // [<= FC_GROUP] FcAcc; per event u16; per 64 events uint2 / u32; [frames of the call] FcStats
+  DevBuf in, out;                     // staging of XM_MEM_HOST calls
+  bool dirty = false;
+};
+
 // ---- launch workers -------------------------------------------------------------------------------------------
 // A kernel launch costs the calling thread ~2.7 us in the HIP runtime, three launches per frame; with the GPU at ~12 us per
 // frame that single thread is what bounds the asynchronous device-pointer path (tools/only_kernel_eager.sh: 3.2 us per call
@@ -201,6 +216,7 @@ struct xm_handle {
   size_t stage_cells = 0;
   SurfaceScratch surf;      // xm_process_time_surfaces
   FrameSurfScratch fsurf;   // xm_frames_to_time_surfaces
+  FrameCloudScratch fcloud; // xm_cloud_set_tables, xm_frames_to_point_clouds
   std::vector<std::unique_ptr<Worker>> workers;  // one per slot stream (empty: launches happen in the calling thread)
   struct OwnSet {  // the device tables of the owner tiles' plan i (its scalars: plan().own[i])
     DevMem<uint16_t> d_xmap_own;

@@ -71,6 +71,31 @@ int ingest_issue_frame(xm_ingest* g, uint64_t push_no, u64 n) {
     a.max_chunk_blocks = sf.max_chunk_blocks;
     launch_frame_surfaces(a, 1, n, dt, s);
   }
+  // the cloud stage the packet was pushed under: the cut frame's point cloud (its first max_points rows) into ring entry (frame
+  // number % ring), behind the surface stage and in front of everything else that reads the frame, under the same ordering.
+  // Stage off: nothing is launched
+  if (la.push_cloud[vi]) {
+    IngestCloud& cl = g->cl;
+    const int e = (int)(la.frames_issued % (uint64_t)cl.ring);
+    FcArgs a{};
+    a.desc = cut;
+    a.cap = cl.cap;
+    a.max_rows = (u32)cl.max_points;
+    a.tb = h->tb;
+    a.mapx = h->fcloud.mapx.get(), a.mapy = h->fcloud.mapy.get(), a.Q = h->fcloud.q;
+    a.acc = cl.d_acc;
+    a.code = cl.d_code;
+    a.cnt = cl.d_cnt;
+    a.off = cl.d_off;
+    a.stats = cl.d_stats + e;
+    a.cloud = cl.d_ring + (size_t)e * cl.max_points * 3;
+    a.tag = cl.h_tag + e;
+    a.tag_value = la.frames_issued + 1;
+    a.host_stats = cl.h_stats + e;
+    a.use_polarity = 0;
+    a.max_chunk_blocks = cl.max_chunk_blocks;
+    launch_frame_clouds(a, 1, std::min<u64>(n, cl.cap), s);
+  }
   // one EventCD frame in descriptor form: grids from at least two events, the tiled K1's block from the frame itself
   if (flt) {
     launch_frame_filter(ingest_frame_filter_dev(g, vi, flt, la.push_filter[vi] >> 3), n, s);
@@ -239,6 +264,7 @@ int ingest_process(xm_ingest* g, const IngestJob& j, size_t n, const u32* n_dev 
   la.push_t[vi] = j.t_push;
   la.push_filter[vi] = (unsigned char)(la.filter | (la.intended ? 8 : 0));
   la.push_surface[vi] = (unsigned char)(la.surf_select ? la.surf_select | (la.surf_dtype << 2) : 0);
+  la.push_cloud[vi] = (unsigned char)(la.cloud_on ? 1 : 0);
   la.dev.desc = fx.d_descs + vi;
   la.dev.info = fx.d_infos + vi;
   la.dev.verdict = fx.d_verdicts + vi;
@@ -330,6 +356,9 @@ int ingest_run_job(xm_ingest* g, const IngestJob& j) {
     case JobKind::set_surface:
       g->la.surf_select = j.surf_select;
       g->la.surf_dtype = j.surf_dtype;
+      break;
+    case JobKind::set_cloud:
+      g->la.cloud_on = j.cloud_on;
       break;
     case JobKind::stop:
     case JobKind::count_only: break;

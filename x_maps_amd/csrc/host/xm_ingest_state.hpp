@@ -72,6 +72,7 @@ enum class JobKind : int {
   count_only,  // nothing arrived (the copy side failed): the launch side only counts the job
   set_filter,  // the frame event filter for the frames cut by the packets behind this job (xm_ingest_set_frame_filter)
   set_surface, // the surface stage's setting for the frames cut by the packets behind this job (xm_ingest_set_surface_output)
+  set_cloud,   // the cloud stage's setting for the frames cut by the packets behind this job (xm_ingest_set_cloud_output)
 };
 inline bool carries_packet(JobKind k) { return k == JobKind::records || k == JobKind::words || k == JobKind::on_device; }
 inline bool copy_side_has_work(JobKind k) { return k == JobKind::records || k == JobKind::words; }
@@ -89,6 +90,7 @@ struct IngestJob {
   double t_push = 0.0;               // when the xm_ingest_push* call entered (steady clock)
   int filter = 0, intended = 0;      // set_filter: FILTER_* (0: none) and its semantics
   int surf_select = 0, surf_dtype = 0;  // set_surface: XM_SURFACE_* (0: off) and XM_T_FLOAT32 / XM_T_FLOAT64
+  int cloud_on = 0;                  // set_cloud: 1 = on, 0 = off
 };
 
 // launch side -> out thread: one cut frame.  Every cut frame is posted, so frame f is job f + 1 of the out queue.
@@ -208,6 +210,26 @@ struct IngestSurface {
   u32 max_chunk_blocks = 4096;         // ("XM_FS_MAX_BLOCKS", read once)
 };
 
+// Point clouds of the cut frames (xmaps_framecloud.hpp) on the frame stream, in front of any frame event filter.  Scratch and ring,
+// made ONCE by the caller's first xm_ingest_set_cloud_output that switches the stage on, before it posts the set_cloud job, exactly
+// as IngestSurface.  Frame f goes to ring entry f % ring, which holds its first max_points rows.  An entry's tag (pinned host
+// memory, written by the device): 0 while the entry is being rewritten, else the frame's number + 1; its statistics lie beside it.
+struct IngestCloud {
+  bool ready = false;
+  int ring = 0;
+  size_t max_points = 0;
+  u32 cap = 0;                         // events the scratch holds: the longest frame the event ring can cut
+  DevMem<FcAcc> d_acc;                 // one accumulator, all zero between frames
+  DevMem<uint16_t> d_code;             // [cap]
+  DevMem<uint2> d_cnt;                 // [cap / 64 + 1]
+  DevMem<u32> d_off;                   // [cap / 64 + 1]
+  DevMem<FcStats> d_stats;             // [ring] the statistics in device memory (the kernels' own copy)
+  DevMem<float> d_ring;                // [ring][max_points][3]
+  PinnedMem<u64> h_tag;                // [ring]
+  PinnedMem<FcStats> h_stats;          // [ring]
+  u32 max_chunk_blocks = 4096;         // ("XM_FC_MAX_BLOCKS", read once)
+};
+
 // Caller side: the thread that calls xm_ingest_push* / poll* / backlog / flush (one at a time, by the API's contract).
 struct IngestCaller {
   uint64_t posted = 0;                 // pushes accepted so far
@@ -236,6 +258,8 @@ struct IngestLaunch {
   unsigned char push_filter[ING_VRING] = {};  // ... and what packet p was pushed under: filter | intended << 3 (its frame's filter)
   int surf_select = 0, surf_dtype = 0; // the surface stage's setting from the last set_surface job (select 0: off) ...
   unsigned char push_surface[ING_VRING] = {};  // ... and what packet p was pushed under: select | dtype << 2
+  int cloud_on = 0;                    // the cloud stage's setting from the last set_cloud job ...
+  unsigned char push_cloud[ING_VRING] = {};    // ... and what packet p was pushed under
   IngestDev dev{};                     // = IngestFixed::dev with the CURRENT packet's desc / info / verdict / act: passed by value to its kernels
   int act_toggle = 0;                  // the set of cells the next non-empty packet takes (ingest_act_set)
   uint64_t act_fused_push = 0;         // the packet whose k_act_first went out with its predecessor's k_ing_count (k_ing_count_act)
@@ -292,6 +316,7 @@ struct xm_ingest {
   IngestFixed fx;
   IngestFrameFilter ff;
   IngestSurface sf;
+  IngestCloud cl;
   IngestCaller ca;
   IngestLaunch la;
   IngestOutSide out;

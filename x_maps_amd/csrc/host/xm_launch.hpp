@@ -317,5 +317,22 @@ void launch_frame_surfaces(const FsArgs& a, unsigned n_frames, u64 n_max, int dt
   XM_LAUNCH(k_fs_finish, dim3(grid_for(n_frames, 64)), dim3(64), 0, stream, a, (u32)n_frames);
 }
 
+// ---- frames -> per-event point clouds (xmaps_framecloud.hpp): the group entry and the ingest's cloud stage ------------------------
+// One launch sequence: n_frames (<= FC_GROUP) frames, the longest of n_max events (the ingest: the verdict's count).  The three
+// per-event passes take one block per FC_CHUNK events of the longest frame, at most a.max_chunk_blocks; the scan one per frame.
+u32 fc_max_chunk_blocks() {  // ("XM_FC_MAX_BLOCKS": tests send short frames through the chunk loops' further trips)
+  const char* o = dbg_opt("XM_FC_MAX_BLOCKS");
+  const long v = o ? atol(o) : 0;
+  return v > 0 && v < 65535 ? (u32)v : 4096u;
+}
+void launch_frame_clouds(const FcArgs& a, unsigned n_frames, u64 n_max, hipStream_t stream) {
+  const unsigned ge = std::min<unsigned>(grid_for(n_max < 1 ? 1 : n_max, FC_CHUNK), a.max_chunk_blocks);
+  XM_LAUNCH(k_fc_extrema, dim3(ge, n_frames), dim3(FC_THREADS), 0, stream, a);
+  XM_LAUNCH(k_fc_events, dim3(ge, n_frames), dim3(FC_THREADS), 0, stream, a);
+  XM_LAUNCH(k_fc_scan, dim3(n_frames), dim3(FC_SCAN_BLOCK), 0, stream, a);
+  if (a.cloud) XM_LAUNCH(k_fc_points, dim3(ge, n_frames), dim3(FC_THREADS), 0, stream, a);
+  if (a.tag) XM_LAUNCH(k_fc_publish, dim3(1), dim3(64), 0, stream, a);
+}
+
 
 }  // namespace

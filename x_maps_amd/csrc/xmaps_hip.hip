@@ -14,6 +14,7 @@
 #include "xmaps_evt2.hpp"           // EVT 2.0 decoder
 #include "xmaps_surface.hpp"        // time surfaces -> depth maps + point clouds
 #include "xmaps_framesurface.hpp"   // frames of events -> camera time surfaces (the group entry and the ingest's surface stage)
+#include "xmaps_framecloud.hpp"     // frames of events -> per-event point clouds (the group entry and the ingest's cloud stage)
 
 #include <hip/hip_ext.h>
 
@@ -75,6 +76,7 @@ using namespace xm;
 #include "host/xm_group.hpp"        // the skeleton of the group objects below: create / destroy, argument check, staging, dtype dispatch
 #include "host/xm_api_surface.hpp"  // a group of camera time surfaces -> depth maps + point clouds (the evaluation caller's entry)
 #include "host/xm_api_framesurface.hpp"  // a group of frames of events -> camera time surfaces: what joins the live half to the entries around it
+#include "host/xm_api_framecloud.hpp"    // a group of frames of events -> per-event point clouds: the live half's 3-D output
 #include "host/xm_api_eslinit.hpp"  // the ESL-init baseline on the same surfaces: depth_init maps, disparity_init alone
 #include "host/xm_api_mc3d.hpp"     // the MC3D baseline on the same surfaces
 #include "host/xm_api_esloptim.hpp" // the ESL depth optimisation behind ESL-init: depth_optim maps

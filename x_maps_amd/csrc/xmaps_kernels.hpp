@@ -40,3 +40,4 @@
 #include "xmaps_evaltable.hpp"  // the evaluation table's scorer: combine, median, the metrics of every (method, scan) cell
 // (included by xmaps_hip.hip behind the ingest, whose frame descriptors it reads:)
 //       "xmaps_framesurface.hpp"  frames of events -> camera time surfaces: winners by integer atomics, one store per pixel
+//       "xmaps_framecloud.hpp"    frames of events -> per-event point clouds: codes per event, a scan, a stable compaction

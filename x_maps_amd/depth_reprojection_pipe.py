@@ -118,6 +118,9 @@ class DepthReprojectionPipe:
         self._ingest_failed = False  # an ingest call has raised: the error has reached the caller, close() does not ask again
         self._closed = False
         self._surface_callback = getattr(p, "surface_callback", None)
+        self._cloud_callback = getattr(p, "cloud_callback", None)
+        if self._cloud_callback is not None:  # (tables without the float rectify maps or Q: ValueError, here and not at the first frame)
+            self.calib_maps.engine.set_frame_cloud_tables()
         if self.activity_filter is None and getattr(p, "activity_filter", True):
             _warn_activity_rule_unpinned()
         # a caller-supplied activity filter (Metavision's own, where the SDK is installed) runs on the host: so does the chain
@@ -131,6 +134,8 @@ class DepthReprojectionPipe:
             self._ingest_views = bool(getattr(p, "ingest_frame_views", False))
             if self._surface_callback is not None:  # (before the first push: every frame of the stream gets a surface)
                 self.ingest.set_surface_output("last", np.float32)
+            if self._cloud_callback is not None:
+                self.ingest.set_cloud_output(True, int(getattr(p, "cloud_max_points", 262144)))
         else:
             self._ensure_host_chain()
 
@@ -197,6 +202,12 @@ class DepthReprojectionPipe:
                     self.stats_printer.count("surface lost")
                 else:
                     self._surface_callback(surf)
+            if self._cloud_callback is not None:
+                cloud = self.ingest.cloud(fr.seq)
+                if cloud is None:  # (the cloud ring is as long as the result ring: lapped only where the frame is lost too)
+                    self.stats_printer.count("cloud lost")
+                else:
+                    self._cloud_callback(cloud)
             # a fresh array copied out of the pinned result ring, or (RuntimeParams.ingest_frame_views) a view into it that stays
             # valid until ingest_result_ring - 1 further frames have been produced
             self.frame_callback(fr.bgr)
@@ -281,6 +292,9 @@ class DepthReprojectionPipe:
         if self._surface_callback is not None:  # (the cut frame's, in front of any frame event filter: as the ingest's stage)
             surfs, _ = self.calib_maps.engine.frames_to_time_surfaces([evs], "last", np.float32)
             self._surface_callback(surfs[0])
+        if self._cloud_callback is not None:  # (the same: a group of one through the group entry, the ingest stage's row limit)
+            cloud, _ = self.calib_maps.engine.frames_to_point_clouds([evs])[0]
+            self._cloud_callback(cloud[:int(getattr(self.params, "cloud_max_points", 262144))])
         if not isinstance(self.ev_filter_proc.selected_filter(), NoFilter):  # pipe:131-139
             with self.stats_printer.measure_time("frame ev filter"):
                 n_before = len(evs)

@@ -84,6 +84,14 @@ class RuntimeParams:
     # On the device ingest it is a stage of the ingest (DeviceIngest.set_surface_output); on the host chain one call of the
     # group entry on the frame's events.  The same arrays either way.  What the evaluation entries take as `scans_np`.
     surface_callback: Optional[Callable] = None
+    # cloud_callback(cloud) for every shown frame, immediately before that frame's frame_callback (behind its surface_callback,
+    # if both are set): the frame's per-event point cloud (float32 [n][3]: the reference's construct_point_cloud on the frame's
+    # inlier events in stream order, XMapsEngine.frames_to_point_clouds), built from the CUT frame, in front of any frame event
+    # filter; at most cloud_max_points rows, the frame's first.  On the device ingest it is a stage of the ingest
+    # (DeviceIngest.set_cloud_output); on the host chain one call of the group entry on the frame's events.  The same arrays
+    # either way.  Needs tables with cam_mapx_f32, cam_mapy_f32 and Q (ValueError at construction otherwise).
+    cloud_callback: Optional[Callable] = None
+    cloud_max_points: int = 262144
 
     @property
     def should_drop_frames(self):

@@ -65,6 +65,20 @@ class FrameSurfaceStats:
         return FrameSurfaceStats(int(s.n_events), int(s.n_pixels), int(s.n_index_errors), int(s.t_base), int(s.t_span))
 
 
+@dataclass
+class FrameCloudStats:
+    """xm_frame_cloud_stats of one frame's point cloud (frames_to_point_clouds, DeviceIngest.cloud)."""
+    n_events: int = 0
+    n_inliers: int = 0
+    n_index_errors: int = 0
+    t_min: int = 0
+    t_max: int = 0
+
+    @staticmethod
+    def from_c(s: N.xm_frame_cloud_stats) -> "FrameCloudStats":
+        return FrameCloudStats(int(s.n_events), int(s.n_inliers), int(s.n_index_errors), int(s.t_min), int(s.t_max))
+
+
 def _ptr(a) -> C.c_void_p:
     if a is None:
         return C.c_void_p(None)
@@ -166,6 +180,7 @@ class XMapsEngine:
         # process_time_surfaces(want_cloud=True): the float rectify maps and Q go to the device with the first such call
         self._has_cloud_tables = False
         self._cloud_tables = tuple(tables.get(k) for k in ("cam_mapx_f32", "cam_mapy_f32", "Q"))
+        self._has_frame_cloud_tables = False  # (frames_to_point_clouds / the ingest's cloud stage: the same tables, either view)
 
     # ---- lifetime ------------------------------------------------------------------------------
     def close(self):
@@ -567,6 +582,48 @@ class XMapsEngine:
                                                      offsets.ctypes.data_as(C.POINTER(C.c_uint64)), n, int(bool(use_polarity)), sel,
                                                      _T_DTYPES[dt], N.XM_MEM_HOST, _ptr(out), C.cast(st, C.c_void_p)))
         return out, [FrameSurfaceStats.from_c(s) for s in st]
+
+    # ---- frames of events in, per-event point clouds out (the live half's 3-D output) ------------------------------
+    def set_frame_cloud_tables(self, mapx_f32=None, mapy_f32=None, Q=None):
+        """The float rectify maps [cam_h][cam_w] and the 4x4 Q of frames_to_point_clouds and of the ingest's cloud stage
+        (xm_cloud_set_tables); engines of either view.  Without arguments: the engine's tables cam_mapx_f32, cam_mapy_f32, Q."""
+        if mapx_f32 is None and mapy_f32 is None and Q is None:
+            mapx_f32, mapy_f32, Q = self._cloud_tables
+        if mapx_f32 is None or mapy_f32 is None or Q is None:
+            raise ValueError("point clouds need the tables cam_mapx_f32, cam_mapy_f32 and Q")
+        mx = np.ascontiguousarray(mapx_f32, dtype=np.float32)
+        my = np.ascontiguousarray(mapy_f32, dtype=np.float32)
+        Q = np.ascontiguousarray(Q, dtype=np.float64)
+        if mx.shape != (self.cam_h, self.cam_w) or my.shape != mx.shape:
+            raise ValueError(f"float rectify maps must be ({self.cam_h}, {self.cam_w})")
+        if Q.shape != (4, 4):
+            raise ValueError("Q must be 4x4")
+        N.check(self._lib.xm_cloud_set_tables(self._h, _ptr(mx), _ptr(my), _ptr(Q)))
+        self._has_frame_cloud_tables = True
+
+    def frames_to_point_clouds(self, frames, use_polarity=False):
+        """A list of EventCD arrays (one per frame; any may be empty) in ONE device call -> [(cloud f32 [n_inliers][3],
+        FrameCloudStats)] per frame: the reference's construct_point_cloud(xr_f32[mask], yr_f32[mask], disparity) on the frame's
+        events, one row per inlier event in stream order.  The definition: include/xmaps.h, xm_frames_to_point_clouds.  Engines
+        of either view; the tables come from set_frame_cloud_tables (called with the engine's own tables if it has not been)."""
+        from .synthetic import EVENT_CD_DTYPE
+        if not self._has_frame_cloud_tables:
+            self.set_frame_cloud_tables()
+        frames = [np.ascontiguousarray(f if f.dtype == EVENT_CD_DTYPE else f.astype(EVENT_CD_DTYPE)) for f in frames]
+        if not frames:
+            raise ValueError("no frames")
+        n = len(frames)
+        offsets = np.zeros(n + 1, np.uint64)
+        offsets[1:] = np.cumsum([len(f) for f in frames])
+        evs = np.zeros(int(offsets[-1]), EVENT_CD_DTYPE)  # (np.concatenate would hand back the packed 14-byte layout under NumPy 2)
+        for f, a in zip(frames, offsets[:-1]):
+            evs[int(a):int(a) + len(f)] = f
+        cloud = np.empty((max(len(evs), 1), 3), np.float32)
+        st = (N.xm_frame_cloud_stats * n)()
+        N.check(self._lib.xm_frames_to_point_clouds(self._h, _ptr(evs) if len(evs) else None,
+                                                    offsets.ctypes.data_as(C.POINTER(C.c_uint64)), n, int(bool(use_polarity)),
+                                                    N.XM_MEM_HOST, _ptr(cloud), C.cast(st, C.c_void_p)))
+        return [(cloud[int(a):int(a) + int(s.n_inliers)].copy(), FrameCloudStats.from_c(s)) for a, s in zip(offsets[:-1], st)]
 
     # ---- N3: per-frame de-duplication filters ------------------------------------------------------------
     def frame_event_filter(self, filter_id: int, evs: np.ndarray, xp_i16=None, map_shape=None,

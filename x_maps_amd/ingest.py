@@ -174,6 +174,39 @@ class DeviceIngest:
             return None
         return (out, FrameSurfaceStats.from_c(st)) if with_stats else out
 
+    def set_cloud_output(self, on=True, max_points: int = 262144, ring: int = 0):
+        """The cloud stage for the frames cut by the packets pushed from now on (ordered like a push): every cut frame's per-event
+        point cloud -- XMapsEngine.frames_to_point_clouds on the CUT frame, in front of any frame event filter -- is kept in a
+        ring of `ring` entries (0: as many as the result ring) of `max_points` rows in device memory for cloud(seq).  A frame with
+        more inliers keeps its first max_points rows; its statistics report the true count.  max_points and the ring's length
+        are fixed by the first call that switches the stage on.  The engine's set_frame_cloud_tables is called if it has not been."""
+        if on and not self._e._has_frame_cloud_tables:
+            self._e.set_frame_cloud_tables()
+        N.check(self._lib.xm_ingest_set_cloud_output(self._g, int(bool(on)), int(max_points), int(ring)))
+        if on:
+            self._cloud_max_points = int(max_points)
+
+    def cloud(self, seq: int, with_stats: bool = False):
+        """The point cloud of frame `seq` (IngestFrame.seq) as the caller's own f32 [min(n_inliers, max_points)][3] array, or None
+        when the ring does not hold it (the stage was off when the frame was cut, or the ring has been lapped).  Complete once
+        poll() has handed the frame out.  with_stats: (cloud, FrameCloudStats) instead."""
+        from .engine import FrameCloudStats
+        st = N.xm_frame_cloud_stats()
+        rc = self._lib.xm_ingest_copy_cloud(self._g, int(seq), None, N.XM_MEM_HOST, C.byref(st))
+        if rc < 0:
+            N.check(rc)
+        if rc == 0:
+            return None
+        rows = min(int(st.n_inliers), getattr(self, "_cloud_max_points", 0))
+        out = np.empty((rows, 3), np.float32)
+        st2 = N.xm_frame_cloud_stats()
+        rc = self._lib.xm_ingest_copy_cloud(self._g, int(seq), C.c_void_p(out.ctypes.data) if rows else None, N.XM_MEM_HOST, C.byref(st2))
+        if rc < 0:
+            N.check(rc)
+        if rc == 0 or bytes(st2) != bytes(st):
+            return None
+        return (out, FrameCloudStats.from_c(st)) if with_stats else out
+
     def push_pinned(self, evs: np.ndarray):
         """A packet that already lives in pinned host memory (XMapsEngine.host_empty): no staging copy."""
         assert evs.dtype == EVENT_CD_DTYPE and evs.flags.c_contiguous
