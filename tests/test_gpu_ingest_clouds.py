@@ -120,6 +120,52 @@ def test_a_small_max_points_keeps_the_first_rows(want):
             assert _stats(st) == _stats(want[i][1]) and st.n_inliers > small, i  # the true count: truncation is visible
 
 
+def test_a_ring_of_two_is_lapped(want):
+    """the twin of tests/test_gpu_ingest_surfaces.py's test: five frames through a ring of two"""
+    packets, frames = _case()
+    small = 100
+    with XMapsEngine(_tables()) as eng, DeviceIngest(eng, 60, activity_filter=False, **INGEST) as ing:
+        ing.set_cloud_output(True, small, ring=2)
+        for p in packets:
+            ing.push(p)
+        ing.flush()
+        got = ing.poll()
+        assert len(got) == len(frames) == 5
+        held = [ing.cloud(fr.seq, with_stats=True) for fr in got]
+        assert [h is not None for h in held] == [False, False, False, True, True]
+        for i in (3, 4):
+            cloud, st = held[i]
+            assert cloud.shape == (small, 3) and np.array_equal(_bits(cloud), _bits(want[i][0][:small])), i
+            assert _stats(st) == _stats(want[i][1]), i
+        assert ing.cloud(17) is None and ing.cloud(5) is None
+        with pytest.raises(ValueError, match="the cloud ring holds 2 entries of 100 rows since the first call that switched the stage on"):
+            ing.set_cloud_output(True, small, ring=3)  # the ring's length is fixed by the first call
+        assert _same(ing.cloud(got[4].seq, with_stats=True), (want[4][0][:small], want[4][1]))  # the refused call changed nothing
+
+
+def test_reset_empties_both_stages_rings(want):
+    """one ingest with the surface and the cloud stage on: after reset() neither ring names any earlier frame"""
+    packets, frames = _case()
+    with XMapsEngine(_tables()) as eng, DeviceIngest(eng, 60, activity_filter=False, **INGEST) as ing:
+        ing.set_surface_output("last", np.float32)
+        ing.set_cloud_output(True, MAX_POINTS)
+        seen = []
+        for rnd in range(2):
+            for p in packets:
+                ing.push(p)
+            ing.flush()
+            got = ing.poll()
+            assert len(got) == len(frames)
+            for i, fr in enumerate(got):
+                assert _same(ing.cloud(fr.seq, with_stats=True), want[i]), (rnd, i)
+                surf, st = ing.surface(fr.seq, with_stats=True)
+                assert surf.shape == (CFG.cam_h, CFG.cam_w) and st.n_events == fr.n_events and st.n_pixels == np.count_nonzero(surf) > 0, (rnd, i)
+            seen += [fr.seq for fr in got]
+            ing.reset()
+            assert all(ing.cloud(s) is None and ing.surface(s) is None for s in seen), rnd
+        assert seen == list(range(10))
+
+
 def test_switched_off_and_reset(want):
     packets, frames = _case()
     with XMapsEngine(_tables()) as eng, DeviceIngest(eng, 60, activity_filter=False, **INGEST) as ing:

@@ -22,7 +22,6 @@ from __future__ import annotations
 import argparse
 import json
 import os
-import subprocess
 import sys
 import time
 
@@ -33,25 +32,16 @@ for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle"), os.pa
     if p not in sys.path:
         sys.path.insert(0, p)
 
+import _frame_stage as F  # noqa: E402
+from _frame_stage import GROUP, HBM_BYTES_PER_S  # noqa: E402
 from _timing import clock_state, timed  # noqa: E402
 
-HBM_BYTES_PER_S = 6.29e12  # measured streaming rate of an MI355X (float4 copy)
-GROUP = 32
 MAX_POINTS = 262144
-TRIED = "## Notes\n"
 NEW_SYMBOLS = ("xm_cloud_set_tables", "xm_frames_to_point_clouds", "xm_ingest_set_cloud_output", "xm_ingest_copy_cloud")
 
 
-def _gpu():
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("no GPU: this tool measures on the device and has no fallback")
-    torch.cuda.init()
-    return torch
-
-
 def step_group(repeats, device):
-    _gpu()
+    F.gpu()
     import ctypes as C
 
     import frame_cloud_cases as K
@@ -98,113 +88,28 @@ def step_group(repeats, device):
 
 
 def step_ingest(passes, device, with_stage):
-    _gpu()
-    if not with_stage:  # (the parent commit's build through XM_LIB: it does not export the entries this step never calls)
-        from x_maps_amd import _native as N
-        for name in NEW_SYMBOLS:
-            N.SYMBOLS.pop(name, None)
-    from x_maps_amd import XMapsEngine, rig
-    from x_maps_amd import synthetic as S
-    from x_maps_amd.ingest import DeviceIngest
-    cp, tables, _, _ = rig.make_esl_like(row_stride=13, device=device)
-    n_mean = int(np.mean([len(rig.render_events(cp, tables, row_stride=13, seed=f)[0]) for f in range(8)]))
-    n_frames = 48
-    stream, _ = rig.render_stream(cp, tables, n_frames=n_frames, row_stride=13, seed=9)
-    res = {"events": int(len(stream)), "frames_rendered": n_frames}
-    with XMapsEngine(tables, device=device, n_slots=4) as eng:
-        pin = eng.host_empty((len(stream),), S.EVENT_CD_DTYPE)
-        pin[:] = stream
-        packet = int(1e6 / 60 / 4)
-        cuts = np.searchsorted(pin["t"], np.arange(pin["t"][0], pin["t"][-1] + packet, packet))
-        packets = [pin[a:b] for a, b in zip(cuts[:-1], cuts[1:])]
-        with DeviceIngest(eng, 60, capacity_events=1 << 21, max_packet_events=1 << 18, expected_events_per_frame=n_mean,
-                          result_ring=n_frames + 2, want_depth=False, want_bgr=True, activity_filter=True) as ing:
-            def one_pass(on=False):
-                c0 = time.perf_counter()
-                for pk in packets:
-                    ing.push_pinned(pk)
-                ing.flush()
-                got = ing.poll(copy=False)
-                dt = time.perf_counter() - c0
-                if with_stage:  # (outside the timed window) the stage ran for the pass's frames, or for none of them
-                    held = [ing.cloud(fr.seq, with_stats=True) for fr in got]
-                    assert all((h is not None and len(h[0]) == min(h[1].n_inliers, MAX_POINTS) > 0) if on else h is None for h in held)
-                ing.reset()
-                return dt, len(got)
-            modes = [False, True] if with_stage else [False]
-            for on in modes * 2:  # warm-up: both settings twice (the first on-pass allocates the stage's ring)
-                if with_stage:
-                    ing.set_cloud_output(on, MAX_POINTS)
-                one_pass(on)
-            times = {m: [] for m in modes}
-            cut = None
-            for k in range(passes * len(modes)):  # alternating, in one process
-                on = modes[k % len(modes)]
-                if with_stage:
-                    ing.set_cloud_output(on, MAX_POINTS)
-                dt, n = one_pass(on)
-                times[on].append(dt)
-                cut = n if cut is None else cut
-                assert n == cut, "the passes cut different numbers of frames"
-            res["frames_cut"] = cut
-            for on, v in times.items():
-                med = float(np.median(v))
-                res["stage_on" if on else "stage_off"] = {"Mevents_per_s": round(len(stream) / med / 1e6, 1), "ms_per_pass_median": round(med * 1e3, 3),
-                                                          "passes_ms": [round(x * 1e3, 3) for x in v]}
-    print("FC_STEP " + json.dumps(res), flush=True)
+    def check(ing, got, on):  # the stage ran for the pass's frames, or for none of them
+        held = [ing.cloud(fr.seq, with_stats=True) for fr in got]
+        assert all((h is not None and len(h[0]) == min(h[1].n_inliers, MAX_POINTS) > 0) if on else h is None for h in held)
+    set_stage = (lambda ing, on: ing.set_cloud_output(on, MAX_POINTS)) if with_stage else None
+    print("FC_STEP " + json.dumps(F.ingest_passes(passes, device, NEW_SYMBOLS, set_stage, check)), flush=True)
 
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--md", help="write the profile (markdown) here")
-    ap.add_argument("--repeats", type=int, default=20)
-    ap.add_argument("--passes", type=int, default=7, help="timed passes of the stream per setting")
-    ap.add_argument("--device", type=int, default=0)
-    ap.add_argument("--parent-lib", help="a build of the parent commit's library: its stage-off passes, in processes of their own")
-    ap.add_argument("--step-timeout", type=float, default=240.0)
-    ap.add_argument("--step", help=argparse.SUPPRESS)  # (internal: one step in this process)
+    F.add_arguments(ap, "a build of the parent commit's library: its stage-off passes, in processes of their own")
     a = ap.parse_args(argv)
     if a.step == "group":
         return step_group(a.repeats, a.device)
     if a.step in ("ingest", "ingest_off_only"):
         return step_ingest(a.passes, a.device, a.step == "ingest")
-    res = {"frames": "rendered from rig.py's ESL-like stand-in, as bench.py --esl renders them; NOT the ESL recordings",
-           "clock_state": clock_state(), "repeats": a.repeats, "passes": a.passes}
+    res = {"frames": F.FRAMES_NOTE, "clock_state": clock_state(), "repeats": a.repeats, "passes": a.passes}
     steps = [("group", "group", None), ("ingest", "ingest", None)]
     if a.parent_lib:
         lib = os.path.abspath(a.parent_lib)
         steps += [("ingest_parent_build", "ingest_off_only", lib), ("ingest_again", "ingest", None), ("ingest_parent_build_again", "ingest_off_only", lib)]
-    ok = True
-    for name, step, lib in steps:
-        env = dict(os.environ)
-        env.pop("XM_LIB", None)
-        if lib:
-            env["XM_LIB"] = lib
-        cmd = [sys.executable, os.path.abspath(__file__), "--step", step, "--repeats", str(a.repeats), "--passes", str(a.passes),
-               "--device", str(a.device)]
-        try:
-            r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=a.step_timeout)
-        except subprocess.TimeoutExpired:
-            res[name] = {"error": f"no result within {a.step_timeout} s"}
-            ok = False
-            break
-        line = [ln for ln in r.stdout.splitlines() if ln.startswith("FC_STEP ")]
-        if r.returncode != 0 or not line:
-            res[name] = {"error": f"exit status {r.returncode}", "stderr_tail": r.stderr[-1500:]}
-            ok = False
-            break
-        res[name] = json.loads(line[-1][len("FC_STEP "):])
-    res["complete"] = ok
-    txt = json.dumps(res, indent=1)
-    print(txt)
-    if a.md and ok:
-        notes = ""
-        if os.path.exists(a.md):  # the hand-written section of an earlier profile stays
-            old = open(a.md).read()
-            if TRIED in old:
-                notes = old.split(TRIED, 1)[1]
-        with open(a.md, "w") as f:
-            f.write(markdown(res, notes))
+    if F.run_steps(__file__, "FC_STEP ", steps, a, res) and a.md:
+        F.write_md(a.md, res, markdown)
     return res
 
 
@@ -216,7 +121,6 @@ def markdown(r, notes="") -> str:
     if par:
         runs += [("parent commit's build (stage absent), run 1", par[0]), ("this build, stage off, run 2", r["ingest_again"]["stage_off"]),
                  ("this build, stage on, run 2", r["ingest_again"]["stage_on"]), ("parent commit's build, run 2", par[1])]
-    rows = "\n".join(f"| {k} | {v['Mevents_per_s']} | {v['ms_per_pass_median']} | {v['passes_ms']} |" for k, v in runs)
     if par:
         mine = np.mean([off["Mevents_per_s"], r["ingest_again"]["stage_off"]["Mevents_per_s"]])
         theirs = np.mean([p["Mevents_per_s"] for p in par])
@@ -224,14 +128,7 @@ def markdown(r, notes="") -> str:
                     f"(the README states a +-6 % run-to-run spread for this stream).")
     else:
         par_note = "The parent commit's build was not timed in this run (--parent-lib)."
-    return f"""# Frames of events -> per-event point clouds: times on the ESL-like stream
-
-Written by `tools/frame_clouds_time.py` on an MI355X.  **The frames are rendered** from `x_maps_amd/rig.py`'s ESL-like stand-in
-(640 x 480 camera, the frames `bench.py --esl` renders), not the ESL recordings.  Every step in a process of its own.
-Clock state of the box, queried idle before the first launch: {r['clock_state']}.
-
-**Nothing was measured before this**: the parent commit has no such entry.  These are first numbers, not a bar.
-
+    return F.md_head("Frames of events -> per-event point clouds", "frame_clouds_time.py", r["clock_state"]) + f"""
 ## The group entry (`xm_frames_to_point_clouds`)
 
 A group of {g['frames']} frames of {g['events_per_frame']} events ({g['rows_per_frame']} cloud rows per frame), records and clouds
@@ -251,21 +148,7 @@ streaming rate at which the entry consumes events.  "Moved" counts what the four
 code written and read, per row the record's first word, two map gathers and 12 bytes stored, and the 64-event counts and offsets.
 A group this small (about 5 M events, 80 MB) lies inside the Infinity Cache, and its four launches are a visible part of the time.
 
-## The ingest's stage (`xm_ingest_set_cloud_output`)
-
-The ESL-like stream ({i['events']} events, {i['frames_rendered']} frames rendered, {i['frames_cut']} cut), quarter-period packets of
-pinned records, activity filter on, BGR frames out; whole passes (push everything, flush, poll) alternating stage off / on in one
-process, {r['passes']} timed passes each, the median reported; max_points = {MAX_POINTS}.
-
-| setting | Mev/s | ms / pass (median) | passes, ms |
-|---|---|---|---|
-{rows}
-
-Stage on / off: {on['Mevents_per_s'] / off['Mevents_per_s']:.3f} of the rate.  {par_note}
-
-{TRIED}
-{notes.strip() or "(written by hand below this heading; kept when the tool rewrites the file)"}
-"""
+""" + F.md_ingest(r, "xm_ingest_set_cloud_output", f"; max_points = {MAX_POINTS}", F.run_rows(runs), par_note, notes)
 
 
 if __name__ == "__main__":

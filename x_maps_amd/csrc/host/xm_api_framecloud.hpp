@@ -12,8 +12,7 @@ int xm_cloud_set_tables(xm_handle* h, const float* mapx_f32, const float* mapy_f
   if (!h || !mapx_f32 || !mapy_f32 || !Q) return fail(XM_ERR_INVALID, "NULL argument");
   XM_ENTER(h);
   FrameCloudScratch& sc = h->fcloud;
-  if (sc.last_stream) HIP_TRY(hipStreamSynchronize(sc.last_stream));  // a group in flight may still read the old tables
-  sc.last_stream = nullptr;
+  if (int rc = sc.order.settle()) return rc;  // a group in flight may still read the old tables
   const size_t px = (size_t)h->cfg.cam_width * h->cfg.cam_height;
   if (sc.has_tables) {  // (same sizes: rewritten in place, so that an ingest's cloud stage keeps valid pointers)
     HIP_TRY(hipDeviceSynchronize());
@@ -37,16 +36,11 @@ int xm_frames_to_point_clouds(xm_handle* h, const void* eventcd16, const uint64_
   FrameCloudScratch& sc = h->fcloud;
   if (cloud_out && !sc.has_tables)
     return fail(XM_ERR_INVALID, "cloud_out needs the float rectify maps and Q: call xm_cloud_set_tables first");
-  u64 n_max = 0;
-  for (int f = 0; f < n_frames; ++f) {
-    if (offsets_host[f + 1] < offsets_host[f]) return fail(XM_ERR_INVALID, "offsets must not decrease (frame %d)", f);
-    n_max = std::max<u64>(n_max, offsets_host[f + 1] - offsets_host[f]);
-  }
-  const u64 ev0 = offsets_host[0], n_total = offsets_host[n_frames] - ev0;
-  if (n_max >= 0xffffffffull || n_total >= (1ull << 36)) return fail(XM_ERR_TOO_MANY, "group too large (a frame holds at most 2^32 - 2 events)");
-  if (n_total && !eventcd16) return fail(XM_ERR_INVALID, "NULL argument");
+  FrameSpans sp;
+  if ((rc = frame_spans(eventcd16, offsets_host, n_frames, mem, 1ull << 36, "group too large (a frame holds at most 2^32 - 2 events)", &sp)))
+    return rc;
+  const u64 ev0 = sp.ev0, n_total = sp.n_total;
   const bool host = mem == XM_MEM_HOST;
-  if (!host && ((uintptr_t)eventcd16 & 15)) return fail(XM_ERR_INVALID, "the record array must be 16-byte aligned");
   XM_ENTER(h);
   const size_t n = (size_t)n_frames, seq = std::min<size_t>(n, FC_GROUP);
   const size_t n_seg = (size_t)(n_total / 64) + n;  // >= the frames' ceil(n / 64) together
@@ -61,42 +55,30 @@ int xm_frames_to_point_clouds(xm_handle* h, const void* eventcd16, const uint64_
                                                 {sc.stats, n * sizeof(FcStats)},
                                                 {sc.in, host ? (size_t)n_total * 16 : 0},
                                                 {sc.out, host && cloud_out ? (size_t)n_total * 12 : 0}};
-  if (seq * sizeof(FcAcc) > sc.acc.cap) sc.dirty = true;  // (new accumulators are not zero yet)
-  if (any_grows(needs) && sc.last_stream) {
-    HIP_TRY(hipStreamSynchronize(sc.last_stream));
-    sc.last_stream = nullptr;
-  }
-  if ((rc = reserve_all(needs))) return rc;
-  if (!sc.done) HIP_TRY(sc.done.create());
-  if (sc.last_stream && sc.last_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, sc.done, 0));
-  if (sc.dirty) {  // the zero invariant, established once -- and again behind a call that failed half way
-    HIP_TRY(hipMemsetAsync(sc.acc.p, 0, sc.acc.cap, stream));
-    sc.dirty = false;
-  }
+  // (new accumulators are not zero yet; the zero invariant, established once -- and again behind a call that failed half way)
+  rc = sc.order.enter(
+      stream, any_grows(needs), seq * sizeof(FcAcc) > sc.acc.cap, [&] { return reserve_all(needs); },
+      [&] {
+        HIP_TRY(hipMemsetAsync(sc.acc.p, 0, sc.acc.cap, stream));
+        return (int)XM_OK;
+      });
+  if (rc) return rc;
 
-  const uint4* d_ev = (const uint4*)eventcd16 + (host ? 0 : ev0);
-  float* d_cloud = cloud_out;
+  const uint4* d_ev;
+  if ((rc = frame_records(eventcd16, sp, host, sc.in, stream, &d_ev))) return rc;
+  float* d_cloud = host && cloud_out ? (float*)sc.out.p : cloud_out;
   FcStats* d_stats = (FcStats*)sc.stats.p;
-  if (host) {
-    if (n_total) HIP_TRY(hipMemcpyAsync(sc.in.p, (const uint4*)eventcd16 + ev0, (size_t)n_total * 16, hipMemcpyHostToDevice, stream));
-    d_ev = (const uint4*)sc.in.p;
-    if (cloud_out) d_cloud = (float*)sc.out.p;
-  }
-  sc.dirty = true;
-  const u32 max_blocks = fc_max_chunk_blocks();
+  sc.order.launching();
+  const u32 max_blocks = frame_max_chunk_blocks("XM_FC_MAX_BLOCKS");
   u64 seg = 0;
   for (size_t f0 = 0; f0 < n; f0 += FC_GROUP) {  // launch sequences of at most FC_GROUP frames
     const unsigned nf = (unsigned)std::min<size_t>(FC_GROUP, n - f0);
     FcArgs a{};
     a.ev = d_ev;
-    u64 seq_max = 0;
+    const u64 seq_max = frame_seq_fill(offsets_host, ev0, f0, nf, a.first, a.n);
     for (unsigned k = 0; k < nf; ++k) {
-      const u64 nk = offsets_host[f0 + k + 1] - offsets_host[f0 + k];
-      a.first[k] = offsets_host[f0 + k] - ev0;
-      a.n[k] = (u32)nk;
       a.seg0[k] = (u32)seg;
-      seg += (nk + 63) / 64;
-      seq_max = std::max<u64>(seq_max, nk);
+      seg += ((u64)a.n[k] + 63) / 64;
     }
     a.max_rows = 0xffffffffu;
     a.tb = h->tb;
@@ -112,19 +94,17 @@ int xm_frames_to_point_clouds(xm_handle* h, const void* eventcd16, const uint64_
     launch_frame_clouds(a, nf, seq_max, stream);
     HIP_TRY(hipGetLastError());
   }
-  sc.dirty = false;
+  sc.order.launched();
   s.order.note_eager();
 
   if (!host) {
     if (stats_out) HIP_TRY(hipMemcpyAsync(stats_out, d_stats, n * sizeof(FcStats), hipMemcpyDeviceToDevice, stream));
-    HIP_TRY(hipEventRecord(sc.done, stream));
-    sc.last_stream = stream;
-    return XM_OK;
+    return sc.order.leave_async(stream);
   }
   std::vector<xm_frame_cloud_stats> st(n);
   HIP_TRY(hipMemcpyAsync(st.data(), d_stats, n * sizeof(FcStats), hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipStreamSynchronize(stream));
-  sc.last_stream = nullptr;
+  sc.order.leave_sync();
   if (cloud_out) {  // only the valid rows of every frame cross the bus
     for (size_t i = 0; i < n; ++i) {
       const size_t row0 = (size_t)(offsets_host[i] - ev0) * 3;

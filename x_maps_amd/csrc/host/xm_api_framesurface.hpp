@@ -16,16 +16,9 @@ int xm_frames_to_time_surfaces(xm_handle* h, const void* eventcd16, const uint64
   int rc;
   if ((rc = group_args(n_frames, mem, &dtype, "frames"))) return rc;
   if (!offsets_host || !surfaces_out) return fail(XM_ERR_INVALID, "NULL argument");
-  u64 n_max = 0;
-  for (int f = 0; f < n_frames; ++f) {
-    if (offsets_host[f + 1] < offsets_host[f]) return fail(XM_ERR_INVALID, "offsets must not decrease (frame %d)", f);
-    n_max = std::max<u64>(n_max, offsets_host[f + 1] - offsets_host[f]);
-  }
-  if (n_max >= 0xffffffffull) return fail(XM_ERR_TOO_MANY, "a frame holds at most 2^32 - 2 events");
-  const u64 ev0 = offsets_host[0], n_total = offsets_host[n_frames] - ev0;
-  if (n_total && !eventcd16) return fail(XM_ERR_INVALID, "NULL argument");
+  FrameSpans sp;
+  if ((rc = frame_spans(eventcd16, offsets_host, n_frames, mem, 0, "a frame holds at most 2^32 - 2 events", &sp))) return rc;
   const bool host = mem == XM_MEM_HOST;
-  if (!host && ((uintptr_t)eventcd16 & 15)) return fail(XM_ERR_INVALID, "the record array must be 16-byte aligned");
   XM_ENTER(h);
   const DevTables& tb = h->tb;
   const size_t n = (size_t)n_frames, px = (size_t)tb.cam_w * tb.cam_h, esz = t_size(dtype);
@@ -39,43 +32,30 @@ int xm_frames_to_time_surfaces(xm_handle* h, const void* eventcd16, const uint64
   const std::initializer_list<BufNeed> needs = {{sc.maps, seq * stride * 4},
                                                 {sc.acc, seq * sizeof(FsAcc)},
                                                 {sc.stats, n * sizeof(FsStats)},
-                                                {sc.in, host ? (size_t)n_total * 16 : 0},
+                                                {sc.in, host ? (size_t)sp.n_total * 16 : 0},
                                                 {sc.out, host ? n * px * esz : 0}};
-  // (new maps / accumulators are not zero yet -- noted before they are made, so that a call that fails below leaves the note)
-  if (seq * stride * 4 > sc.maps.cap || seq * sizeof(FsAcc) > sc.acc.cap) sc.dirty = true;
-  if (any_grows(needs) && sc.last_stream) {
-    HIP_TRY(hipStreamSynchronize(sc.last_stream));
-    sc.last_stream = nullptr;
-  }
-  if ((rc = reserve_all(needs))) return rc;
-  if (!sc.done) HIP_TRY(sc.done.create());
-  if (sc.last_stream && sc.last_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, sc.done, 0));
-  if (sc.dirty) {  // the zero invariant, established once -- and again behind a call that failed half way
-    HIP_TRY(hipMemsetAsync(sc.maps.p, 0, sc.maps.cap, stream));
-    HIP_TRY(hipMemsetAsync(sc.acc.p, 0, sc.acc.cap, stream));
-    sc.dirty = false;
-  }
+  // (new maps / accumulators are not zero yet; the zero invariant, established once -- and again behind a call that failed half way)
+  const bool zero_lost = seq * stride * 4 > sc.maps.cap || seq * sizeof(FsAcc) > sc.acc.cap;
+  rc = sc.order.enter(
+      stream, any_grows(needs), zero_lost, [&] { return reserve_all(needs); },
+      [&] {
+        HIP_TRY(hipMemsetAsync(sc.maps.p, 0, sc.maps.cap, stream));
+        HIP_TRY(hipMemsetAsync(sc.acc.p, 0, sc.acc.cap, stream));
+        return (int)XM_OK;
+      });
+  if (rc) return rc;
 
-  const uint4* d_ev = (const uint4*)eventcd16 + (host ? 0 : ev0);
-  char* d_out = (char*)surfaces_out;
+  const uint4* d_ev;
+  if ((rc = frame_records(eventcd16, sp, host, sc.in, stream, &d_ev))) return rc;
+  char* d_out = host ? (char*)sc.out.p : (char*)surfaces_out;
   FsStats* d_stats = (FsStats*)sc.stats.p;
-  if (host) {
-    if (n_total) HIP_TRY(hipMemcpyAsync(sc.in.p, (const uint4*)eventcd16 + ev0, (size_t)n_total * 16, hipMemcpyHostToDevice, stream));
-    d_ev = (const uint4*)sc.in.p;
-    d_out = (char*)sc.out.p;
-  }
-  sc.dirty = true;
-  const u32 max_blocks = fs_max_chunk_blocks();
+  sc.order.launching();
+  const u32 max_blocks = frame_max_chunk_blocks("XM_FS_MAX_BLOCKS");
   for (size_t f0 = 0; f0 < n; f0 += FS_GROUP) {  // launch sequences of at most FS_GROUP frames; they reuse the maps in stream order
     const unsigned nf = (unsigned)std::min<size_t>(FS_GROUP, n - f0);
     FsArgs a{};
     a.ev = d_ev;
-    u64 seq_max = 0;
-    for (unsigned k = 0; k < nf; ++k) {
-      a.first[k] = offsets_host[f0 + k] - ev0;
-      a.n[k] = (u32)(offsets_host[f0 + k + 1] - offsets_host[f0 + k]);
-      seq_max = std::max<u64>(seq_max, a.n[k]);
-    }
+    const u64 seq_max = frame_seq_fill(offsets_host, sp.ev0, f0, nf, a.first, a.n);
     a.map = (u32*)sc.maps.p;
     a.acc = (FsAcc*)sc.acc.p;
     a.stats = d_stats + f0;
@@ -87,19 +67,17 @@ int xm_frames_to_time_surfaces(xm_handle* h, const void* eventcd16, const uint64
     launch_frame_surfaces(a, nf, seq_max, dtype, stream);
     HIP_TRY(hipGetLastError());
   }
-  sc.dirty = false;
+  sc.order.launched();
   s.order.note_eager();
 
   if (!host) {
     if (stats_out) HIP_TRY(hipMemcpyAsync(stats_out, d_stats, n * sizeof(FsStats), hipMemcpyDeviceToDevice, stream));
-    HIP_TRY(hipEventRecord(sc.done, stream));
-    sc.last_stream = stream;
-    return XM_OK;
+    return sc.order.leave_async(stream);
   }
   HIP_TRY(hipMemcpyAsync(surfaces_out, d_out, n * px * esz, hipMemcpyDeviceToHost, stream));
   if (stats_out) HIP_TRY(hipMemcpyAsync(stats_out, d_stats, n * sizeof(FsStats), hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipStreamSynchronize(stream));
-  sc.last_stream = nullptr;
+  sc.order.leave_sync();
   return XM_OK;
 }
 

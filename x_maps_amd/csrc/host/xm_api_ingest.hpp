@@ -323,24 +323,18 @@ int xm_ingest_set_frame_filter(xm_ingest* g, int filter, int intended_semantics)
 static int ingest_surface_alloc(xm_ingest* g, int ring) {
   IngestSurface& sf = g->sf;
   const xm_handle* h = g->fx.h;
-  sf.ring = ring;
   sf.cells = (size_t)h->tb.cam_w * h->tb.cam_h;
   sf.stride = (sf.cells + FS_CPT - 1) / FS_CPT * FS_CPT;
-  sf.max_chunk_blocks = fs_max_chunk_blocks();
+  sf.max_chunk_blocks = frame_max_chunk_blocks("XM_FS_MAX_BLOCKS");
   HIP_TRY(hipSetDevice(h->cfg.device));
   HIP_TRY(sf.d_map.alloc(sf.stride));
   HIP_TRY(sf.d_acc.alloc(1));
-  HIP_TRY(sf.d_stats.alloc(ring));
   HIP_TRY(sf.d_ring.alloc((size_t)ring * sf.cells * 8));
-  HIP_TRY(sf.h_tag.alloc(ring, hipHostMallocMapped));
-  HIP_TRY(sf.h_stats.alloc(ring, hipHostMallocMapped));
-  memset(sf.h_tag, 0, sizeof(u64) * ring);
-  memset(sf.h_stats, 0, sizeof(FsStats) * ring);
+  if (int rc = sf.r.alloc(ring)) return rc;
   HIP_TRY(hipMemset(sf.d_map, 0, sf.stride * sizeof(u32)));
   HIP_TRY(hipMemset(sf.d_acc, 0, sizeof(FsAcc)));
-  HIP_TRY(hipMemset(sf.d_stats, 0, sizeof(FsStats) * ring));
   HIP_TRY(hipDeviceSynchronize());  // (default-stream memsets: the ingest's non-blocking streams do not wait for them)
-  sf.ready = true;
+  sf.r.ready = true;
   return XM_OK;
 }
 
@@ -353,9 +347,9 @@ int xm_ingest_set_surface_output(xm_ingest* g, int select, int dtype, int ring) 
   int rc = ingest_take_error(g);
   if (rc) return rc;
   if (select) {
-    const int want = ring ? ring : g->fx.ring;
-    if (!g->sf.ready && (rc = ingest_surface_alloc(g, want))) return rc;
-    if (g->sf.ring != want) return fail(XM_ERR_INVALID, "the surface ring holds %d entries since the first call that switched the stage on", g->sf.ring);
+    const int want = g->sf.r.want_ring(ring, g->fx.ring);
+    if (!g->sf.r.ready && (rc = ingest_surface_alloc(g, want))) return rc;
+    if (g->sf.r.ring != want) return fail(XM_ERR_INVALID, "the surface ring holds %d entries since the first call that switched the stage on", g->sf.r.ring);
   }
   // ordered like a push: the packets handed in before this call keep the setting they were pushed under
   IngestJob j;
@@ -368,59 +362,45 @@ int xm_ingest_set_surface_output(xm_ingest* g, int select, int dtype, int ring) 
 int xm_ingest_surface_dtype(xm_ingest* g, uint64_t seq) {
   if (!g) return fail(XM_ERR_INVALID, "NULL argument");
   const IngestSurface& sf = g->sf;
-  if (!sf.ready) return 0;
-  const size_t e = (size_t)(seq % (uint64_t)sf.ring);
-  const u64 t = __atomic_load_n(sf.h_tag + e, __ATOMIC_ACQUIRE);
-  return t >> 2 == seq + 1 ? (int)(t & 3) : 0;
+  if (!sf.r.ready) return 0;
+  const u64 t = __atomic_load_n(sf.r.h_tag + sf.r.entry(seq), __ATOMIC_ACQUIRE);
+  return surface_tag_names(t, seq) ? surface_tag_dtype(t) : 0;
 }
 
 int xm_ingest_copy_surface(xm_ingest* g, uint64_t seq, void* dst, int mem, xm_frame_surface_stats* stats) {
   if (!g || !dst) return fail(XM_ERR_INVALID, "NULL argument");
   if (mem != XM_MEM_HOST && mem != XM_MEM_DEVICE) return fail(XM_ERR_INVALID, "mem must be XM_MEM_HOST or XM_MEM_DEVICE");
   const IngestSurface& sf = g->sf;
-  if (!sf.ready) return 0;
-  const size_t e = (size_t)(seq % (uint64_t)sf.ring);
-  const u64* tag = sf.h_tag + e;
-  // the tag names the frame only between the stage's last launch for it and the first launch of the frame that takes the entry
-  // next (k_fs_events clears it in front of the pixel pass that rewrites the entry): named before AND after the copy = intact
-  const u64 t0 = __atomic_load_n(tag, __ATOMIC_ACQUIRE);
-  if (t0 >> 2 != seq + 1) return 0;
-  const int dt = (int)(t0 & 3);
-  FsStats st;
-  memcpy(&st, sf.h_stats + e, sizeof st);
-  HIP_TRY(hipSetDevice(g->fx.h->cfg.device));
-  HIP_TRY(hipMemcpy(dst, sf.d_ring + e * sf.cells * 8, sf.cells * t_size(dt), mem == XM_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice));
-  if (mem == XM_MEM_DEVICE) HIP_TRY(hipStreamSynchronize(nullptr));
-  __atomic_thread_fence(__ATOMIC_ACQUIRE);
-  if (__atomic_load_n(tag, __ATOMIC_ACQUIRE) != t0) return 0;
-  if (stats) memcpy(stats, &st, sizeof st);
-  return 1;
+  return sf.r.read(
+      seq, [&](u64 t) { return surface_tag_names(t, seq); },
+      [&](size_t e, u64 t, const FsStats&) {
+        HIP_TRY(hipSetDevice(g->fx.h->cfg.device));
+        HIP_TRY(hipMemcpy(dst, sf.d_ring + e * sf.cells * 8, sf.cells * t_size(surface_tag_dtype(t)),
+                          mem == XM_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice));
+        if (mem == XM_MEM_DEVICE) HIP_TRY(hipStreamSynchronize(nullptr));
+        return (int)XM_OK;
+      },
+      stats);
 }
 
 // the cloud stage's scratch and ring, once (IngestCloud)
 static int ingest_cloud_alloc(xm_ingest* g, size_t max_points, int ring) {
   IngestCloud& cl = g->cl;
   const xm_handle* h = g->fx.h;
-  cl.ring = ring;
   cl.max_points = max_points;
   cl.cap = (u32)g->fx.dev.mirror;  // (a cut frame is contiguous in the event ring: at most half of it)
-  cl.max_chunk_blocks = fc_max_chunk_blocks();
+  cl.max_chunk_blocks = frame_max_chunk_blocks("XM_FC_MAX_BLOCKS");
   const size_t n_seg = (size_t)cl.cap / 64 + 1;
   HIP_TRY(hipSetDevice(h->cfg.device));
   HIP_TRY(cl.d_acc.alloc(1));
   HIP_TRY(cl.d_code.alloc(cl.cap));
   HIP_TRY(cl.d_cnt.alloc(n_seg));
   HIP_TRY(cl.d_off.alloc(n_seg));
-  HIP_TRY(cl.d_stats.alloc(ring));
   HIP_TRY(cl.d_ring.alloc((size_t)ring * max_points * 3));
-  HIP_TRY(cl.h_tag.alloc(ring, hipHostMallocMapped));
-  HIP_TRY(cl.h_stats.alloc(ring, hipHostMallocMapped));
-  memset(cl.h_tag, 0, sizeof(u64) * ring);
-  memset(cl.h_stats, 0, sizeof(FcStats) * ring);
+  if (int rc = cl.r.alloc(ring)) return rc;
   HIP_TRY(hipMemset(cl.d_acc, 0, sizeof(FcAcc)));
-  HIP_TRY(hipMemset(cl.d_stats, 0, sizeof(FcStats) * ring));
   HIP_TRY(hipDeviceSynchronize());  // (default-stream memsets: the ingest's non-blocking streams do not wait for them)
-  cl.ready = true;
+  cl.r.ready = true;
   return XM_OK;
 }
 
@@ -433,10 +413,10 @@ int xm_ingest_set_cloud_output(xm_ingest* g, int on, int64_t max_points, int rin
   int rc = ingest_take_error(g);
   if (rc) return rc;
   if (on) {
-    const int want = ring ? ring : g->fx.ring;
-    if (!g->cl.ready && (rc = ingest_cloud_alloc(g, (size_t)max_points, want))) return rc;
-    if (g->cl.ring != want || g->cl.max_points != (size_t)max_points)
-      return fail(XM_ERR_INVALID, "the cloud ring holds %d entries of %zu rows since the first call that switched the stage on", g->cl.ring,
+    const int want = g->cl.r.want_ring(ring, g->fx.ring);
+    if (!g->cl.r.ready && (rc = ingest_cloud_alloc(g, (size_t)max_points, want))) return rc;
+    if (g->cl.r.ring != want || g->cl.max_points != (size_t)max_points)
+      return fail(XM_ERR_INVALID, "the cloud ring holds %d entries of %zu rows since the first call that switched the stage on", g->cl.r.ring,
                   g->cl.max_points);
   }
   // ordered like a push: the packets handed in before this call keep the setting they were pushed under
@@ -450,24 +430,17 @@ int xm_ingest_copy_cloud(xm_ingest* g, uint64_t seq, float* dst, int mem, xm_fra
   if (!g || (!dst && !stats)) return fail(XM_ERR_INVALID, "NULL argument");
   if (mem != XM_MEM_HOST && mem != XM_MEM_DEVICE) return fail(XM_ERR_INVALID, "mem must be XM_MEM_HOST or XM_MEM_DEVICE");
   const IngestCloud& cl = g->cl;
-  if (!cl.ready) return 0;
-  const size_t e = (size_t)(seq % (uint64_t)cl.ring);
-  const u64* tag = cl.h_tag + e;
-  // the tag names the frame only between the stage's last launch for it and the first launch of the frame that takes the entry
-  // next (k_fc_extrema clears it in front of the pass that rewrites the entry): named before AND after the copy = intact
-  if (__atomic_load_n(tag, __ATOMIC_ACQUIRE) != seq + 1) return 0;
-  FcStats st;
-  memcpy(&st, cl.h_stats + e, sizeof st);
-  const size_t rows = (size_t)std::min<u64>(st.n_inliers, cl.max_points);
-  if (dst && rows) {
-    HIP_TRY(hipSetDevice(g->fx.h->cfg.device));
-    HIP_TRY(hipMemcpy(dst, cl.d_ring + e * cl.max_points * 3, rows * 12, mem == XM_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice));
-    if (mem == XM_MEM_DEVICE) HIP_TRY(hipStreamSynchronize(nullptr));
-  }
-  __atomic_thread_fence(__ATOMIC_ACQUIRE);
-  if (__atomic_load_n(tag, __ATOMIC_ACQUIRE) != seq + 1) return 0;
-  if (stats) memcpy(stats, &st, sizeof st);
-  return 1;
+  return cl.r.read(
+      seq, [&](u64 t) { return cloud_tag_names(t, seq); },
+      [&](size_t e, u64, const FcStats& st) {
+        const size_t rows = (size_t)std::min<u64>(st.n_inliers, cl.max_points);
+        if (!dst || !rows) return (int)XM_OK;
+        HIP_TRY(hipSetDevice(g->fx.h->cfg.device));
+        HIP_TRY(hipMemcpy(dst, cl.d_ring + e * cl.max_points * 3, rows * 12, mem == XM_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice));
+        if (mem == XM_MEM_DEVICE) HIP_TRY(hipStreamSynchronize(nullptr));
+        return (int)XM_OK;
+      },
+      stats);
 }
 
 int xm_ingest_flush(xm_ingest* g) {
@@ -490,11 +463,9 @@ int xm_ingest_reset(xm_ingest* g) {
   z.last_t = 0;
   z.span_ok = 0;
   HIP_TRY(hipMemcpy(g->fx.dev.st, &z, sizeof z, hipMemcpyHostToDevice));
-  // the surface stage keeps its setting; what its ring holds belongs to the stream that ended (nothing is in flight: flushed)
-  if (g->sf.ready)
-    for (int e = 0; e < g->sf.ring; ++e) __atomic_store_n(g->sf.h_tag + e, 0ull, __ATOMIC_RELEASE);
-  if (g->cl.ready)
-    for (int e = 0; e < g->cl.ring; ++e) __atomic_store_n(g->cl.h_tag + e, 0ull, __ATOMIC_RELEASE);
+  // the surface and cloud stages keep their settings; their rings are emptied
+  g->sf.r.clear();
+  g->cl.r.clear();
   // The activity filter's history goes too: a reset is "the stream starts over" (the reference resets when a recording loops,
   // depth_reprojection.py:76) and its stamps then start below everything the history holds -- against the old history every
   // event with a neighbour that ever fired would pass.  (Metavision's filter object keeps its state there; the frames behind

@@ -12,8 +12,7 @@ int xm_surface_set_cloud_tables(xm_handle* h, const float* mapx_f32, const float
   if (h->cfg.view != XM_VIEW_CAMERA) return fail(XM_ERR_INVALID, "time surfaces need a camera-view handle (XM_VIEW_CAMERA)");
   XM_ENTER(h);
   SurfaceScratch& sc = h->surf;
-  if (sc.last_stream) HIP_TRY(hipStreamSynchronize(sc.last_stream));  // a group in flight may still read the old tables
-  sc.last_stream = nullptr;
+  if (int rc = sc.order.settle()) return rc;  // a group in flight may still read the old tables
   sc.has_cloud_tables = false;
   const size_t px = (size_t)h->cfg.cam_width * h->cfg.cam_height;
   HIP_TRY(sc.mapx.alloc(px));
@@ -58,13 +57,7 @@ int xm_process_time_surfaces(xm_handle* h, const void* surfaces, int dtype, int 
                                                 {sc.in, host ? n * px * esz : 0},
                                                 {sc.depth, host ? n * px * 4 : 0},
                                                 {sc.cloud, host && cloud_out ? n * px * 12 : 0}};
-  if (any_grows(needs) && sc.last_stream) {
-    HIP_TRY(hipStreamSynchronize(sc.last_stream));
-    sc.last_stream = nullptr;
-  }
-  if ((rc = reserve_all(needs))) return rc;
-  if (!sc.done) HIP_TRY(sc.done.create());
-  if (sc.last_stream && sc.last_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, sc.done, 0));
+  if ((rc = sc.order.enter(stream, any_grows(needs), false, [&] { return reserve_all(needs); }, [] { return 0; }))) return rc;
 
   const void* d_in = surfaces;
   float* d_depth = depth_out;
@@ -103,15 +96,13 @@ int xm_process_time_surfaces(xm_handle* h, const void* surfaces, int dtype, int 
 
   if (!host) {
     if (stats_out) HIP_TRY(hipMemcpyAsync(stats_out, d_stats, n * sizeof(SurfStats), hipMemcpyDeviceToDevice, stream));
-    HIP_TRY(hipEventRecord(sc.done, stream));
-    sc.last_stream = stream;
-    return XM_OK;
+    return sc.order.leave_async(stream);
   }
   std::vector<xm_surface_stats> st(n);
   HIP_TRY(hipMemcpyAsync(depth_out, d_depth, n * px * 4, hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipMemcpyAsync(st.data(), d_stats, n * sizeof(SurfStats), hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipStreamSynchronize(stream));
-  sc.last_stream = nullptr;
+  sc.order.leave_sync();
   if (cloud_out) {  // only the valid rows of every surface cross the bus
     for (size_t i = 0; i < n; ++i)
       if (st[i].n_inliers)

@@ -22,6 +22,9 @@
 // xm_profile_frame (g_prof, per thread) on a dispatch; that is a mode of the handle, which a group object does not have, and a
 // group call made on a thread while a handle's frame is being profiled there must not write into that frame's events.
 // xm_process_time_surfaces is a call on the handle and keeps XM_LAUNCH.
+//
+// Also here: the prologue of the two frame entries on the handle (xm_frames_to_time_surfaces, xm_frames_to_point_clouds), which
+// take a group of frames as offsets into one record array: frame_spans, frame_records, frame_seq_fill.
 #pragma once
 
 namespace {
@@ -109,6 +112,49 @@ int reserve_all(std::initializer_list<BufNeed> needs) {
     if (b.bytes)
       if (int rc = b.buf.reserve(b.bytes)) return rc;
   return XM_OK;
+}
+
+// ---- the frame entries' prologue: a group of frames in ONE array of EventCD records (xm_frames_to_time_surfaces / _point_clouds) ----
+
+struct FrameSpans {
+  u64 ev0 = 0, n_total = 0, n_max = 0;  // the group's first record, its records, the records of its longest frame
+};
+
+// offsets_host[0 .. n_frames] (not NULL) against the record array.  A frame holds at most 2^32 - 2 events, the group fewer than
+// total_limit (0: no limit of its own); `too_many` is the entry's own text for either.
+int frame_spans(const void* eventcd16, const uint64_t* offsets_host, int n_frames, int mem, u64 total_limit, const char* too_many,
+                FrameSpans* out) {
+  FrameSpans sp;
+  for (int f = 0; f < n_frames; ++f) {
+    if (offsets_host[f + 1] < offsets_host[f]) return fail(XM_ERR_INVALID, "offsets must not decrease (frame %d)", f);
+    sp.n_max = std::max<u64>(sp.n_max, offsets_host[f + 1] - offsets_host[f]);
+  }
+  sp.ev0 = offsets_host[0], sp.n_total = offsets_host[n_frames] - sp.ev0;
+  if (sp.n_max >= 0xffffffffull || (total_limit && sp.n_total >= total_limit)) return fail(XM_ERR_TOO_MANY, "%s", too_many);
+  if (sp.n_total && !eventcd16) return fail(XM_ERR_INVALID, "NULL argument");
+  if (mem != XM_MEM_HOST && ((uintptr_t)eventcd16 & 15)) return fail(XM_ERR_INVALID, "the record array must be 16-byte aligned");
+  *out = sp;
+  return XM_OK;
+}
+
+// the records the kernels read: the caller's from ev0 on, or their copy in `in` (host memory; enqueued on `stream`)
+int frame_records(const void* eventcd16, const FrameSpans& sp, bool host, DevBuf& in, hipStream_t stream, const uint4** d_ev) {
+  *d_ev = (const uint4*)eventcd16 + sp.ev0;
+  if (!host) return XM_OK;
+  if (sp.n_total) HIP_TRY(hipMemcpyAsync(in.p, *d_ev, (size_t)sp.n_total * 16, hipMemcpyHostToDevice, stream));
+  *d_ev = (const uint4*)in.p;
+  return XM_OK;
+}
+
+// frames [f0, f0 + nf) as one launch sequence: first[] relative to ev0 and n[]; returns the longest frame's count
+u64 frame_seq_fill(const uint64_t* offsets_host, u64 ev0, size_t f0, unsigned nf, u64* first, u32* n) {
+  u64 seq_max = 0;
+  for (unsigned k = 0; k < nf; ++k) {
+    first[k] = offsets_host[f0 + k] - ev0;
+    n[k] = (u32)(offsets_host[f0 + k + 1] - offsets_host[f0 + k]);
+    seq_max = std::max<u64>(seq_max, n[k]);
+  }
+  return seq_max;
 }
 
 // ---- staging of one synchronous call ----

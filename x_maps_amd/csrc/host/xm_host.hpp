@@ -55,7 +55,7 @@ struct DevBuf {  // grow-only device scratch: grows by a quarter beyond what was
   }
 };
 
-struct HipOrderOps {  // SlotOrder's calls on the HIP runtime
+struct HipOrderOps {  // SlotOrder's and ScratchOrder's calls on the HIP runtime
   static int rc(hipError_t e, const char* call) { return e == hipSuccess ? XM_OK : fail(XM_ERR_HIP, "%s failed: %s", call, hipGetErrorString(e)); }
   static hipEvent_t ev(void* e) { return static_cast<hipEvent_t>(e); }
   static hipStream_t st(void* s) { return static_cast<hipStream_t>(s); }
@@ -63,6 +63,7 @@ struct HipOrderOps {  // SlotOrder's calls on the HIP runtime
   static int wait(void* s, void* e) { return rc(hipStreamWaitEvent(st(s), ev(e), 0), "hipStreamWaitEvent"); }
   static int sync_event(void* e) { return rc(hipEventSynchronize(ev(e)), "hipEventSynchronize"); }
   static int sync_stream(void* s) { return rc(hipStreamSynchronize(st(s)), "hipStreamSynchronize"); }
+  static int create(Event& e) { return rc(e.create(), "hipEventCreateWithFlags"); }  // (ScratchOrder's end-of-call event)
 };
 
 struct Slot {
@@ -110,11 +111,12 @@ struct Slot {
   DevBuf ev_x, ev_y, ev_t, ev_p, ev_aos, out_depth, out_bgr, dbg[5];
 };
 
+using HipScratchOrder = ScratchOrder<HipOrderOps, Event>;
+
 // The time-surface entry (xm_api_surface.hpp): cloud tables + grow-only scratch, allocated by the first call.  One set per handle:
-// a call's launches wait for the previous call's (`done`, recorded on the stream that one ran on) before they touch it.
+// `order` makes a call's launches wait for the previous call's before they touch it (xm_scratch_order.hpp).
 struct SurfaceScratch {
-  Event done;
-  hipStream_t last_stream = nullptr;  // view: the slot stream of the most recent call (nullptr: none in flight since xm_sync)
+  HipScratchOrder order;
   DevMem<float> mapx, mapy;           // float rectify maps [cam_h][cam_w] (xm_surface_set_cloud_tables)
   Mat4f q{};
   bool has_cloud_tables = false;
@@ -124,29 +126,25 @@ struct SurfaceScratch {
 
 // The frame -> time surface entry (xm_api_framesurface.hpp): grow-only scratch, allocated by the first call and ordered between
 // calls like SurfaceScratch.  The winner maps and the accumulators are ALL ZERO between calls: their last readers leave them so
-// (xmaps_framesurface.hpp).  `dirty` is set while a call's launches are being issued: a call that fails between its event pass
-// and its last launch leaves it set, and the next call clears maps and accumulators before it uses them.
+// (xmaps_framesurface.hpp).  `order` is noted dirty while a call's launches are being issued: a call that fails between its event
+// pass and its last launch leaves the note, and the next call clears maps and accumulators before it uses them.
 struct FrameSurfScratch {
-  Event done;
-  hipStream_t last_stream = nullptr;
+  HipScratchOrder order;
   DevBuf maps, acc, stats;  // [<= FS_GROUP] winner maps / FsAcc; [frames of the call] FsStats
   DevBuf in, out;           // staging of XM_MEM_HOST calls
-  bool dirty = false;
 };
 
 // The frame -> point cloud entry (xm_api_framecloud.hpp): its own cloud tables (handles of either view; the ingest's cloud stage
 // reads the same) + grow-only scratch, ordered between calls like SurfaceScratch.  The accumulators are ALL ZERO between calls
-// (k_fc_scan leaves them so); `dirty` as in FrameSurfScratch.  Codes, counts and offsets are rewritten by every call before it
-// reads them.
+// (k_fc_scan leaves them so); the dirty note as in FrameSurfScratch.  Codes, counts and offsets are rewritten by every call before
+// it reads them.
 struct FrameCloudScratch {
-  Event done;
-  hipStream_t last_stream = nullptr;
+  HipScratchOrder order;
   DevMem<float> mapx, mapy;  // float rectify maps [cam_h][cam_w] (xm_cloud_set_tables)
   Mat4f q{};
   bool has_tables = false;
   DevBuf acc, code, cnt, off, stats;  // [<= FC_GROUP] FcAcc; per event u16; per 64 events uint2 / u32; [frames of the call] FcStats
   DevBuf in, out;                     // staging of XM_MEM_HOST calls
-  bool dirty = false;
 };
 
 // ---- launch workers -------------------------------------------------------------------------------------------

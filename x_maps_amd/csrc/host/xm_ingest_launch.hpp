@@ -55,16 +55,17 @@ int ingest_issue_frame(xm_ingest* g, uint64_t push_no, u64 n) {
   // (the filter stage's, else K1's) is recorded on this stream.  Stage off: nothing is launched
   if (const int sfs = la.push_surface[vi]) {
     IngestSurface& sf = g->sf;
-    const int e = (int)(la.frames_issued % (uint64_t)sf.ring), dt = sfs >> 2;
+    const size_t e = sf.r.entry(la.frames_issued);
+    const int dt = sfs >> 2;
     FsArgs a{};
     a.desc = cut;
     a.map = sf.d_map;
     a.acc = sf.d_acc;
-    a.stats = sf.d_stats + e;
-    a.out = sf.d_ring + (size_t)e * sf.cells * 8;
-    a.tag = sf.h_tag + e;
-    a.tag_value = ((la.frames_issued + 1) << 2) | (u64)dt;
-    a.host_stats = sf.h_stats + e;
+    a.stats = sf.r.d_stats + e;
+    a.out = sf.d_ring + e * sf.cells * 8;
+    a.tag = sf.r.h_tag + e;
+    a.tag_value = surface_tag(la.frames_issued, dt);
+    a.host_stats = sf.r.h_stats + e;
     a.cells = (u32)sf.cells, a.map_stride = (u32)sf.stride;
     a.cam_w = h->tb.cam_w, a.cam_h = h->tb.cam_h;
     a.use_polarity = 0, a.select = sfs & 3;
@@ -76,7 +77,7 @@ int ingest_issue_frame(xm_ingest* g, uint64_t push_no, u64 n) {
   // Stage off: nothing is launched
   if (la.push_cloud[vi]) {
     IngestCloud& cl = g->cl;
-    const int e = (int)(la.frames_issued % (uint64_t)cl.ring);
+    const size_t e = cl.r.entry(la.frames_issued);
     FcArgs a{};
     a.desc = cut;
     a.cap = cl.cap;
@@ -87,11 +88,11 @@ int ingest_issue_frame(xm_ingest* g, uint64_t push_no, u64 n) {
     a.code = cl.d_code;
     a.cnt = cl.d_cnt;
     a.off = cl.d_off;
-    a.stats = cl.d_stats + e;
-    a.cloud = cl.d_ring + (size_t)e * cl.max_points * 3;
-    a.tag = cl.h_tag + e;
-    a.tag_value = la.frames_issued + 1;
-    a.host_stats = cl.h_stats + e;
+    a.stats = cl.r.d_stats + e;
+    a.cloud = cl.d_ring + e * cl.max_points * 3;
+    a.tag = cl.r.h_tag + e;
+    a.tag_value = cloud_tag(la.frames_issued);
+    a.host_stats = cl.r.h_stats + e;
     a.use_polarity = 0;
     a.max_chunk_blocks = cl.max_chunk_blocks;
     launch_frame_clouds(a, 1, std::min<u64>(n, cl.cap), s);

@@ -192,41 +192,78 @@ struct IngestFrameFilter {
   DevMem<FrameFilterCtl> d_ctl;
 };
 
-// Time surfaces of the cut frames (xmaps_framesurface.hpp) on the frame stream, in front of any frame event filter.  Scratch and
-// ring, made ONCE by the caller's first xm_ingest_set_surface_output that switches the stage on, before it posts the set_surface
-// job: the launch side looks at them only for packets behind that job, and nothing of it changes afterwards.  Frame f goes to ring
-// entry f % ring.  An entry's tag (pinned host memory, written by the device): 0 while the entry is being rewritten, else
-// (the frame's number + 1) << 2 | its dtype (XM_T_FLOAT32 / XM_T_FLOAT64); its statistics lie beside it.
-struct IngestSurface {
+// A stage's ring of per-frame outputs (xm_ring_tag.hpp: entry and tag), as far as the surface and the cloud stage share it.  Made
+// ONCE by the caller's first xm_ingest_set_*_output that switches the stage on, before it posts the stage's job: the launch side
+// looks at it only for packets behind that job, and nothing of it changes afterwards.  An entry's tag lies in pinned host memory
+// and is written by the device; its statistics lie beside it.
+template <class Stats>
+struct IngestRing {
   bool ready = false;
   int ring = 0;
+  DevMem<Stats> d_stats;               // [ring] the statistics in device memory (the kernels' own copy)
+  PinnedMem<u64> h_tag;                // [ring]
+  PinnedMem<Stats> h_stats;            // [ring]
+
+  int alloc(int entries) {             // (the device is current; the caller synchronises the device behind the memset)
+    ring = entries;
+    HIP_TRY(d_stats.alloc(ring));
+    HIP_TRY(h_tag.alloc(ring, hipHostMallocMapped));
+    HIP_TRY(h_stats.alloc(ring, hipHostMallocMapped));
+    memset(h_tag, 0, sizeof(u64) * ring);
+    memset(h_stats, 0, sizeof(Stats) * ring);
+    HIP_TRY(hipMemset(d_stats, 0, sizeof(Stats) * ring));
+    return XM_OK;
+  }
+  // the ring length a call asks for (0: `dflt`); fixed by the first call that switched the stage on
+  int want_ring(int arg, int dflt) const { return arg ? arg : dflt; }
+  size_t entry(uint64_t seq) const { return ring_entry(seq, ring); }
+  // Frame seq's entry, if it still holds the frame: 1 and its statistics, else 0 (or copy's error).  The tag names the frame only
+  // between the stage's last launch for it and the first launch of the frame that takes the entry next (the stage's first kernel
+  // clears it in front of the pass that rewrites the entry): named before AND after the copy = intact.
+  // names(tag): does the tag name seq; copy(entry, tag, stats): takes the payload out of the entry, 0 = done.
+  template <class Names, class Copy>
+  int read(uint64_t seq, Names&& names, Copy&& copy, void* stats_out) const {
+    if (!ready) return 0;
+    const size_t e = entry(seq);
+    const u64* tag = h_tag + e;
+    const u64 t0 = __atomic_load_n(tag, __ATOMIC_ACQUIRE);
+    if (!names(t0)) return 0;
+    Stats st;
+    memcpy(&st, h_stats + e, sizeof st);
+    if (int rc = copy(e, t0, st)) return rc;
+    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    if (__atomic_load_n(tag, __ATOMIC_ACQUIRE) != t0) return 0;
+    if (stats_out) memcpy(stats_out, &st, sizeof st);
+    return 1;
+  }
+  void clear() {                       // reset: what the ring holds belongs to the stream that ended (nothing is in flight: flushed)
+    if (ready)
+      for (int e = 0; e < ring; ++e) __atomic_store_n(h_tag + e, 0ull, __ATOMIC_RELEASE);
+  }
+};
+
+// Time surfaces of the cut frames (xmaps_framesurface.hpp) on the frame stream, in front of any frame event filter.  Frame f goes
+// to ring entry f % ring; its tag carries its dtype (surface_tag).
+struct IngestSurface {
+  IngestRing<FsStats> r;
   size_t cells = 0, stride = 0;        // cam_w * cam_h; the same rounded up to FS_CPT (the winner map)
   DevMem<u32> d_map;                   // one winner map, all zero between frames
   DevMem<FsAcc> d_acc;                 // one accumulator, all zero between frames
-  DevMem<FsStats> d_stats;             // [ring] the statistics in device memory (the kernels' own copy)
   DevMem<unsigned char> d_ring;        // [ring][cells] of 8 bytes: room for either dtype
-  PinnedMem<u64> h_tag;                // [ring]
-  PinnedMem<FsStats> h_stats;          // [ring]
   u32 max_chunk_blocks = 4096;         // ("XM_FS_MAX_BLOCKS", read once)
 };
 
-// Point clouds of the cut frames (xmaps_framecloud.hpp) on the frame stream, in front of any frame event filter.  Scratch and ring,
-// made ONCE by the caller's first xm_ingest_set_cloud_output that switches the stage on, before it posts the set_cloud job, exactly
-// as IngestSurface.  Frame f goes to ring entry f % ring, which holds its first max_points rows.  An entry's tag (pinned host
-// memory, written by the device): 0 while the entry is being rewritten, else the frame's number + 1; its statistics lie beside it.
+// Point clouds of the cut frames (xmaps_framecloud.hpp) on the frame stream, behind the surface stage and in front of any frame
+// event filter.  Frame f goes to ring entry f % ring, which holds its first max_points rows (cloud_tag).
 struct IngestCloud {
-  bool ready = false;
-  int ring = 0;
+  IngestRing<FcStats> r;
   size_t max_points = 0;
   u32 cap = 0;                         // events the scratch holds: the longest frame the event ring can cut
   DevMem<FcAcc> d_acc;                 // one accumulator, all zero between frames
   DevMem<uint16_t> d_code;             // [cap]
   DevMem<uint2> d_cnt;                 // [cap / 64 + 1]
   DevMem<u32> d_off;                   // [cap / 64 + 1]
-  DevMem<FcStats> d_stats;             // [ring] the statistics in device memory (the kernels' own copy)
   DevMem<float> d_ring;                // [ring][max_points][3]
-  PinnedMem<u64> h_tag;                // [ring]
-  PinnedMem<FcStats> h_stats;          // [ring]
   u32 max_chunk_blocks = 4096;         // ("XM_FC_MAX_BLOCKS", read once)
 };
 

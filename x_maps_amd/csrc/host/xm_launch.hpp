@@ -303,8 +303,8 @@ void launch_frame_filter(const FrameFilterDev& f, u64 n_bound, hipStream_t strea
 // One launch sequence: n_frames (<= FS_GROUP) frames, the longest of n_max events (the ingest: the verdict's count).  The event
 // pass takes one block per FS_CHUNK events of the longest frame, at most a.max_chunk_blocks; the cell pass one per
 // FS_CELLS_PER_BLOCK cells of the fixed map.
-u32 fs_max_chunk_blocks() {  // ("XM_FS_MAX_BLOCKS": tests send short frames through the event pass's further trips)
-  const char* o = dbg_opt("XM_FS_MAX_BLOCKS");
+u32 frame_max_chunk_blocks(const char* option) {  // ("XM_FS_MAX_BLOCKS" / "XM_FC_MAX_BLOCKS": tests send short frames through the
+  const char* o = dbg_opt(option);                 // chunk loops' further trips)
   const long v = o ? atol(o) : 0;
   return v > 0 && v < 65535 ? (u32)v : 4096u;
 }
@@ -320,11 +320,6 @@ void launch_frame_surfaces(const FsArgs& a, unsigned n_frames, u64 n_max, int dt
 // ---- frames -> per-event point clouds (xmaps_framecloud.hpp): the group entry and the ingest's cloud stage ------------------------
 // One launch sequence: n_frames (<= FC_GROUP) frames, the longest of n_max events (the ingest: the verdict's count).  The three
 // per-event passes take one block per FC_CHUNK events of the longest frame, at most a.max_chunk_blocks; the scan one per frame.
-u32 fc_max_chunk_blocks() {  // ("XM_FC_MAX_BLOCKS": tests send short frames through the chunk loops' further trips)
-  const char* o = dbg_opt("XM_FC_MAX_BLOCKS");
-  const long v = o ? atol(o) : 0;
-  return v > 0 && v < 65535 ? (u32)v : 4096u;
-}
 void launch_frame_clouds(const FcArgs& a, unsigned n_frames, u64 n_max, hipStream_t stream) {
   const unsigned ge = std::min<unsigned>(grid_for(n_max < 1 ? 1 : n_max, FC_CHUNK), a.max_chunk_blocks);
   XM_LAUNCH(k_fc_extrema, dim3(ge, n_frames), dim3(FC_THREADS), 0, stream, a);

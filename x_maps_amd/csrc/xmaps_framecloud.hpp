@@ -7,7 +7,7 @@
 // Per launch sequence (at most FC_GROUP frames, grid = blocks x frames), every dependency between blocks a kernel boundary:
 //   C0 k_fc_extrema  per event: does it exist (polarity)?  Extrema of t over ALL existing events (those left out later included)
 //                    and their count: reduced per block, then ONE 64-bit integer atomic per value and block into the frame's
-//                    accumulator (the encoding of xmaps_framesurface.hpp: all-zero words are neutral for every field)
+//                    accumulator (xmaps_frameacc.hpp: all-zero words are neutral for every field)
 //   C1 k_fc_events   per existing event: A1 (packed int16 LUT) -> A2 (TimeNorm<long long> + event_disparity_col: the code K1 runs)
 //                    -> a 2-byte code, disparity + 1 of an inlier, else 0; per 64 consecutive events (one wave instruction) the
 //                    counts of inliers and of left-out events (off the sensor, or a column outside the X-map).  Every code and every
@@ -24,14 +24,15 @@
 // instruction in both.
 #pragma once
 #include "xmaps_common.hpp"
+#include "xmaps_frameacc.hpp"
 #include "xmaps_stage.hpp"  // Mat4f, point_from_disparity
 
 namespace xm {
 
-constexpr int FC_THREADS = 256;                // threads per block (C0, C1, C3)
-constexpr int FC_EPT = 4;                      // events per thread (independent 16-byte loads in flight)
-constexpr int FC_CHUNK = FC_THREADS * FC_EPT;  // events per block and trip of its chunk loop
-constexpr int FC_GROUP = 32;                   // frames per launch sequence
+constexpr int FC_THREADS = FRAME_THREADS;      // threads per block (C0, C1, C3)
+constexpr int FC_EPT = FRAME_EPT;              // events per thread
+constexpr int FC_CHUNK = FRAME_CHUNK;          // events per block and trip of its chunk loop
+constexpr int FC_GROUP = FRAME_GROUP;          // frames per launch sequence
 constexpr int FC_SCAN_BLOCK = 1024;            // C2
 
 struct FcAcc {   // device, one per frame of a sequence; all zero between calls
@@ -84,17 +85,14 @@ __device__ inline FcFrameRef fc_frame(const FcArgs& a, u32 f) {
   }
   return FcFrameRef{a.ev + a.first[f], a.n[f], a.first[f], a.seg0[f]};
 }
-__device__ inline u64 fc_enc(long long t) { return (u64)t ^ (1ull << 63); }
-__device__ inline long long fc_dec(u64 u) { return (long long)(u ^ (1ull << 63)); }
-__device__ inline bool fc_exists(const FcArgs& a, const uint4& r) { return !a.use_polarity || (short)(r.y & 0xffffu) == 1; }
 
 // C0 ------------------------------------------------------------------------------------------------------------------------
+// (k_fs_events without the winner map; both written out: see xmaps_frameacc.hpp)
 __global__ __launch_bounds__(FC_THREADS) void k_fc_extrema(FcArgs a) {
   __shared__ u64 s_min[FC_THREADS / 64], s_max[FC_THREADS / 64];
   __shared__ u32 s_n[FC_THREADS / 64];
   const u32 f = blockIdx.y, tid = threadIdx.x;
-  if (a.tag && blockIdx.x == 0 && tid == 0)  // ingest: the ring entry is about to be rewritten (C3 of this frame)
-    __hip_atomic_store(a.tag, 0ull, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  frame_tag_clear(a.tag);  // (C3 of this frame rewrites the ring entry)
   const FcFrameRef fr = fc_frame(a, f);
   u64 mn = 0, mx = 0;
   u32 n_ev = 0;
@@ -108,8 +106,8 @@ __global__ __launch_bounds__(FC_THREADS) void k_fc_extrema(FcArgs a) {
 #pragma unroll
     for (int k = 0; k < FC_EPT; ++k) {
       const u64 i = c0 + (u64)k * FC_THREADS + tid;
-      if (i >= fr.n || !fc_exists(a, r[k])) continue;
-      const u64 u = fc_enc(rec_t<long long>(r[k]));
+      if (i >= fr.n || !frame_exists(a.use_polarity, r[k])) continue;
+      const u64 u = frame_enc(rec_t<long long>(r[k]));
       mn = ~u > mn ? ~u : mn;
       mx = u > mx ? u : mx;
       n_ev += 1;
@@ -143,7 +141,7 @@ __global__ __launch_bounds__(FC_THREADS) void k_fc_events(FcArgs a) {
   const FcFrameRef fr = fc_frame(a, f);
   const FcAcc acc = a.acc[f];  // (C0 has finished: plain loads)
   const bool any = acc.n_events != 0;
-  const TimeNorm<long long> tn(any ? fc_dec(~acc.min_enc) : 0, any ? fc_dec(acc.max_enc) : 0, a.tb.t_px_scale);
+  const TimeNorm<long long> tn(any ? frame_dec(~acc.min_enc) : 0, any ? frame_dec(acc.max_enc) : 0, a.tb.t_px_scale);
   uint16_t* code = a.code + fr.base;
   uint2* cnt = a.cnt + fr.seg0;
   for (u64 c0 = (u64)blockIdx.x * FC_CHUNK; c0 < fr.n; c0 += (u64)gridDim.x * FC_CHUNK) {  // (block-uniform)
@@ -159,7 +157,7 @@ __global__ __launch_bounds__(FC_THREADS) void k_fc_events(FcArgs a) {
       if (w0 >= fr.n) break;                                                    // (wave-uniform)
       bool inl = false, oob = false;
       int dsp = 0;
-      if (i < fr.n && fc_exists(a, r[k])) {
+      if (i < fr.n && frame_exists(a.use_polarity, r[k])) {
         const EventResult e = event_disparity_col(a.tb, tn.column(rec_t<long long>(r[k])), rec_x(r[k]), rec_y(r[k]), oob);
         inl = e.inlier;
         dsp = e.disp;
@@ -215,7 +213,7 @@ __global__ __launch_bounds__(FC_SCAN_BLOCK) void k_fc_scan(FcArgs a) {
     const FcAcc v = *acc;
     *acc = FcAcc{0, 0, 0, {0, 0, 0}};  // its last reader leaves it zero
     FcStats s{0, 0, 0, 0, 0};
-    if (v.n_events) s = FcStats{v.n_events, total, oob_total, fc_dec(~v.min_enc), fc_dec(v.max_enc)};
+    if (v.n_events) s = FcStats{v.n_events, total, oob_total, frame_dec(~v.min_enc), frame_dec(v.max_enc)};
     a.stats[f] = s;
   }
 }

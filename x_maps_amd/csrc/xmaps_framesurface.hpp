@@ -16,8 +16,8 @@
 //                   it read ZERO: the map is all zero between calls, as the frame filters' maps are.  Non-zero pixels per block ->
 //                   one atomic add
 //   F2 k_fs_finish  one thread per frame: accumulator -> statistics; leaves the accumulator ZERO
-// Accumulator encoding: a time stamp t is ordered as u = t ^ 2^63; the accumulator keeps max(~u) (-> the minimum) and max(u) (-> the
-// maximum), so that all-zero words are neutral for every field and nothing has to be initialised per call.
+// Accumulator encoding (xmaps_frameacc.hpp, shared with xmaps_framecloud.hpp): all-zero words are neutral for every field, so
+// nothing has to be initialised per call.
 // No floating-point atomic anywhere: every result is a function of the frame alone.
 //
 // One winner map PER FRAME of the launch sequence (at most FS_GROUP frames, longer groups go out in several sequences that reuse the
@@ -26,15 +26,16 @@
 // frame after frame would force (two dependent launches per frame).
 #pragma once
 #include "xmaps_common.hpp"
+#include "xmaps_frameacc.hpp"
 
 namespace xm {
 
-constexpr int FS_THREADS = 256;                     // F0: threads per block
-constexpr int FS_EPT = 4;                           // F0: events per thread (independent 16-byte loads in flight)
-constexpr int FS_CHUNK = FS_THREADS * FS_EPT;       // F0: events per block and trip of its chunk loop
+constexpr int FS_THREADS = FRAME_THREADS;           // threads per block (F0, F1)
+constexpr int FS_EPT = FRAME_EPT;                   // F0: events per thread
+constexpr int FS_CHUNK = FRAME_CHUNK;               // F0: events per block and trip of its chunk loop
 constexpr int FS_CPT = 4;                           // F1: consecutive cells per thread (one 16-byte load of the map)
 constexpr int FS_CELLS_PER_BLOCK = FS_THREADS * FS_CPT;
-constexpr int FS_GROUP = 32;                        // frames per launch sequence
+constexpr int FS_GROUP = FRAME_GROUP;               // frames per launch sequence
 constexpr int FS_SELECT_LAST = 1, FS_SELECT_FIRST = 2;  // == XM_SURFACE_LAST / XM_SURFACE_FIRST
 
 struct FsAcc {   // device, one per frame of a sequence; all zero between calls
@@ -78,16 +79,13 @@ __device__ inline FsFrameRef fs_frame(const FsArgs& a, u32 f) {
   if (a.desc) return a.desc->valid ? FsFrameRef{a.desc->aos, a.desc->n} : FsFrameRef{nullptr, 0};
   return FsFrameRef{a.ev + a.first[f], a.n[f]};
 }
-__device__ inline u64 fs_enc(long long t) { return (u64)t ^ (1ull << 63); }
-__device__ inline long long fs_dec(u64 u) { return (long long)(u ^ (1ull << 63)); }
 
 // F0 ------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(FS_THREADS) void k_fs_events(FsArgs a) {
   __shared__ u64 s_min[FS_THREADS / 64], s_max[FS_THREADS / 64];
   __shared__ u32 s_n[FS_THREADS / 64], s_left[FS_THREADS / 64];
   const u32 f = blockIdx.y, tid = threadIdx.x;
-  if (a.tag && blockIdx.x == 0 && tid == 0)  // ingest: the ring entry is about to be rewritten (F1 of this frame, the next launch)
-    __hip_atomic_store(a.tag, 0ull, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  frame_tag_clear(a.tag);  // (F1 of this frame, the next launch, rewrites the ring entry)
   const FsFrameRef fr = fs_frame(a, f);
   u32* map = a.map + (size_t)f * a.map_stride;
   u64 mn = 0, mx = 0;
@@ -103,8 +101,8 @@ __global__ __launch_bounds__(FS_THREADS) void k_fs_events(FsArgs a) {
     for (int k = 0; k < FS_EPT; ++k) {
       const u64 i = c0 + (u64)k * FS_THREADS + tid;
       if (i >= fr.n) continue;
-      if (a.use_polarity && (short)(r[k].y & 0xffffu) != 1) continue;  // (such an event does not exist at all)
-      const u64 u = fs_enc(rec_t<long long>(r[k]));
+      if (!frame_exists(a.use_polarity, r[k])) continue;
+      const u64 u = frame_enc(rec_t<long long>(r[k]));
       mn = ~u > mn ? ~u : mn;
       mx = u > mx ? u : mx;
       n_ev += 1;
@@ -160,7 +158,7 @@ __global__ __launch_bounds__(FS_THREADS) void k_fs_pixels(FsArgs a) {
   const FsFrameRef fr = fs_frame(a, f);
   u32* map = a.map + (size_t)f * a.map_stride;
   T* out = (T*)a.out + (size_t)f * a.cells;
-  const long long base = fs_dec(~a.acc[f].min_enc);  // (F0 has finished: plain loads; unused when the frame has no event)
+  const long long base = frame_dec(~a.acc[f].min_enc);  // (F0 has finished: plain loads; unused when the frame has no event)
   const u32 c0 = (blockIdx.x * FS_THREADS + tid) * FS_CPT;
   u32 nz = 0;
   if (c0 < a.cells) {  // (map_stride is a multiple of FS_CPT: the 16-byte load stays inside the frame's map)
@@ -206,7 +204,7 @@ __global__ __launch_bounds__(64) void k_fs_finish(FsArgs a, u32 n_frames) {
   *acc = FsAcc{0, 0, 0, 0, 0, 0};  // its last reader leaves it zero
   FsStats s{0, 0, 0, 0, 0};
   if (v.n_events) {
-    const long long base = fs_dec(~v.min_enc), last = fs_dec(v.max_enc);
+    const long long base = frame_dec(~v.min_enc), last = frame_dec(v.max_enc);
     s = FsStats{v.n_events, v.n_pixels, v.n_left, base, (long long)((u64)last - (u64)base)};
   }
   a.stats[f] = s;

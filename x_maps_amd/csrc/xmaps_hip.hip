@@ -48,6 +48,7 @@ using namespace xm;
 #include "host/xm_agree.hpp"        // the agreement among a sharded handle's device threads (standard C++ only)
 #include "host/xm_res.hpp"          // owners of device / pinned memory, streams and events (RAII)
 #include "host/xm_slot_order.hpp"   // where a slot's last work ran; the only code that orders a stream or the host behind it (standard C++ only)
+#include "host/xm_scratch_order.hpp"  // how the calls on a handle's per-entry scratch follow each other (standard C++ only)
 #include "host/xm_host.hpp"         // errors, slots, launch workers, the handle (RigPlan + owners + run-time state), launch macros
 #include "host/xm_launch.hpp"       // launch helpers of every kernel variant
 #include "host/xm_own_plan.hpp"     // owner-tile tables (host analysis in xm_create)
@@ -66,6 +67,7 @@ using namespace xm;
 #include "host/xm_api_filters.hpp"  // frame event filters, pause detection
 #include "host/xm_api_activity.hpp" // the activity filter alone; its device state (shared with the ingest)
 #include "host/xm_api_evt3.hpp"     // EVT 3.0 / 2.0 decoder on the device
+#include "host/xm_ring_tag.hpp"     // the ingest's per-frame output rings: entry and tag arithmetic (standard C++ only)
 #include "host/xm_ingest_state.hpp" // device-side ingest: its state by owning thread, the jobs its threads hand each other
 #include "host/xm_ingest_out.hpp"   // ... the out side (result copies, sequence numbers) and the frame pool
 #include "host/xm_ingest_launch.hpp"  // ... the launch and copy sides (packets, verdicts, frames), the caller's door to them

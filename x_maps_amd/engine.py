@@ -6,7 +6,7 @@ pointers into the C-ABI and maps error codes to the exceptions the reference's N
 from __future__ import annotations
 
 import ctypes as C
-from dataclasses import dataclass
+from dataclasses import dataclass, fields
 
 import numpy as np
 
@@ -51,8 +51,16 @@ class SurfaceStats:
                             float(s.t_min), float(s.t_max))
 
 
+class _FrameStageStats:
+    """What the statistics of the two frame stages share: integer fields named as in the C struct, in its order."""
+
+    @classmethod
+    def from_c(cls, s):
+        return cls(*(int(getattr(s, f.name)) for f in fields(cls)))
+
+
 @dataclass
-class FrameSurfaceStats:
+class FrameSurfaceStats(_FrameStageStats):
     """xm_frame_surface_stats of one frame's time surface (frames_to_time_surfaces, DeviceIngest.surface)."""
     n_events: int = 0
     n_pixels: int = 0
@@ -60,13 +68,9 @@ class FrameSurfaceStats:
     t_base: int = 0
     t_span: int = 0
 
-    @staticmethod
-    def from_c(s: N.xm_frame_surface_stats) -> "FrameSurfaceStats":
-        return FrameSurfaceStats(int(s.n_events), int(s.n_pixels), int(s.n_index_errors), int(s.t_base), int(s.t_span))
-
 
 @dataclass
-class FrameCloudStats:
+class FrameCloudStats(_FrameStageStats):
     """xm_frame_cloud_stats of one frame's point cloud (frames_to_point_clouds, DeviceIngest.cloud)."""
     n_events: int = 0
     n_inliers: int = 0
@@ -74,9 +78,18 @@ class FrameCloudStats:
     t_min: int = 0
     t_max: int = 0
 
-    @staticmethod
-    def from_c(s: N.xm_frame_cloud_stats) -> "FrameCloudStats":
-        return FrameCloudStats(int(s.n_events), int(s.n_inliers), int(s.n_index_errors), int(s.t_min), int(s.t_max))
+
+def _concat_frames(frames):
+    """EventCD frames (host arrays; any may be empty) -> (one EVENT_CD_DTYPE array of all their records, u64 offsets [n + 1]:
+    frame f is records [offsets[f], offsets[f + 1])).  Filled frame by frame: np.concatenate would hand back the packed 14-byte
+    layout under NumPy 2."""
+    from .synthetic import EVENT_CD_DTYPE
+    offsets = np.zeros(len(frames) + 1, np.uint64)
+    offsets[1:] = np.cumsum([len(f) for f in frames])
+    evs = np.zeros(int(offsets[-1]), EVENT_CD_DTYPE)
+    for f, a in zip(frames, offsets[:-1]):
+        evs[int(a):int(a) + len(f)] = f if f.dtype == EVENT_CD_DTYPE else f.astype(EVENT_CD_DTYPE)
+    return evs, offsets
 
 
 def _ptr(a) -> C.c_void_p:
@@ -322,19 +335,14 @@ class XMapsEngine:
         """A list of EventCD frames (host arrays, as the trigger finder cuts them) in groups of <= n_slots frames through the
         multi-frame launches: [(depth | None, bgr | None)] per frame.  Synchronous; what an offline replay uses instead of one
         call per frame (the kernels of a group keep the chip full: DESIGN.md section 3)."""
-        from .synthetic import EVENT_CD_DTYPE
         out = []
         px = self.out_h * self.out_w
         G = max(1, self.n_slots)
         for g0 in range(0, len(frames), G):
-            grp = [np.ascontiguousarray(f if f.dtype == EVENT_CD_DTYPE else f.astype(EVENT_CD_DTYPE)) for f in frames[g0:g0 + G]]
+            grp = frames[g0:g0 + G]
             if any(len(f) == 0 for f in grp):
                 raise ValueError("empty frame in a group (t.min() of an empty frame raises in the reference)")
-            offs = np.zeros(len(grp) + 1, np.uint64)
-            offs[1:] = np.cumsum([len(f) for f in grp])
-            rec = np.empty(int(offs[-1]), EVENT_CD_DTYPE)  # (np.concatenate would hand back the packed 14-byte layout under NumPy 2)
-            for i, f in enumerate(grp):
-                rec[int(offs[i]):int(offs[i + 1])] = f
+            rec, offs = _concat_frames(grp)
             d_rec = self.to_device(rec)
             d_depth = self.dev_alloc(len(grp) * px * 4) if want_depth else None
             d_bgr = self.dev_alloc(len(grp) * px * 3) if want_bgr else None
@@ -560,22 +568,16 @@ class XMapsEngine:
         `dtype`, [FrameSurfaceStats]).  Per pixel the stamp of the last / first event of the frame that fired there (stream
         order, `select`), as t - (the frame's smallest t) + 1; 0 = no event.  The definition: include/xmaps.h,
         xm_frames_to_time_surfaces.  Engines of either view."""
-        from .synthetic import EVENT_CD_DTYPE
         sel = {"last": N.XM_SURFACE_LAST, "first": N.XM_SURFACE_FIRST}.get(select)
         if sel is None:
             raise ValueError('select must be "last" or "first"')
         dt = np.dtype(dtype)
         if dt not in _T_DTYPES or dt == np.int64:
             raise ValueError("dtype must be float32 or float64")
-        frames = [np.ascontiguousarray(f if f.dtype == EVENT_CD_DTYPE else f.astype(EVENT_CD_DTYPE)) for f in frames]
-        if not frames:
+        if not len(frames):
             raise ValueError("no frames")
         n = len(frames)
-        offsets = np.zeros(n + 1, np.uint64)
-        offsets[1:] = np.cumsum([len(f) for f in frames])
-        evs = np.zeros(int(offsets[-1]), EVENT_CD_DTYPE)  # (np.concatenate would hand back the packed 14-byte layout under NumPy 2)
-        for f, a in zip(frames, offsets[:-1]):
-            evs[int(a):int(a) + len(f)] = f
+        evs, offsets = _concat_frames(frames)
         out = np.empty((n, self.cam_h, self.cam_w), dt)
         st = (N.xm_frame_surface_stats * n)()
         N.check(self._lib.xm_frames_to_time_surfaces(self._h, _ptr(evs) if len(evs) else None,
@@ -606,18 +608,12 @@ class XMapsEngine:
         FrameCloudStats)] per frame: the reference's construct_point_cloud(xr_f32[mask], yr_f32[mask], disparity) on the frame's
         events, one row per inlier event in stream order.  The definition: include/xmaps.h, xm_frames_to_point_clouds.  Engines
         of either view; the tables come from set_frame_cloud_tables (called with the engine's own tables if it has not been)."""
-        from .synthetic import EVENT_CD_DTYPE
         if not self._has_frame_cloud_tables:
             self.set_frame_cloud_tables()
-        frames = [np.ascontiguousarray(f if f.dtype == EVENT_CD_DTYPE else f.astype(EVENT_CD_DTYPE)) for f in frames]
-        if not frames:
+        if not len(frames):
             raise ValueError("no frames")
         n = len(frames)
-        offsets = np.zeros(n + 1, np.uint64)
-        offsets[1:] = np.cumsum([len(f) for f in frames])
-        evs = np.zeros(int(offsets[-1]), EVENT_CD_DTYPE)  # (np.concatenate would hand back the packed 14-byte layout under NumPy 2)
-        for f, a in zip(frames, offsets[:-1]):
-            evs[int(a):int(a) + len(f)] = f
+        evs, offsets = _concat_frames(frames)
         cloud = np.empty((max(len(evs), 1), 3), np.float32)
         st = (N.xm_frame_cloud_stats * n)()
         N.check(self._lib.xm_frames_to_point_clouds(self._h, _ptr(evs) if len(evs) else None,

@@ -155,6 +155,14 @@ class DeviceIngest:
             raise ValueError("dtype must be float32 or float64")
         N.check(self._lib.xm_ingest_set_surface_output(self._g, sel, N.XM_T_FLOAT32 if dt == np.float32 else N.XM_T_FLOAT64, int(ring)))
 
+    def _ring_copy(self, copy, seq: int, out, st) -> bool:
+        """One xm_ingest_copy_surface / xm_ingest_copy_cloud call into the caller's `out` (None: statistics only) and `st`: did the
+        stage's ring hold frame `seq` from the call's first look at the entry to its last?"""
+        rc = copy(self._g, int(seq), C.c_void_p(out.ctypes.data) if out is not None and out.size else None, N.XM_MEM_HOST, C.byref(st))
+        if rc < 0:
+            N.check(rc)
+        return rc > 0
+
     def surface(self, seq: int, with_stats: bool = False):
         """The time surface of frame `seq` (IngestFrame.seq) as the caller's own [cam_h][cam_w] array, or None when the ring does
         not hold it (the stage was off when the frame was cut, or the ring has been lapped).  Complete once poll() has handed
@@ -167,10 +175,7 @@ class DeviceIngest:
             return None
         out = np.empty((self._e.cam_h, self._e.cam_w), np.float32 if dt == N.XM_T_FLOAT32 else np.float64)
         st = N.xm_frame_surface_stats()
-        rc = self._lib.xm_ingest_copy_surface(self._g, int(seq), C.c_void_p(out.ctypes.data), N.XM_MEM_HOST, C.byref(st))
-        if rc < 0:
-            N.check(rc)
-        if rc == 0 or self._lib.xm_ingest_surface_dtype(self._g, int(seq)) != dt:
+        if not self._ring_copy(self._lib.xm_ingest_copy_surface, seq, out, st) or self._lib.xm_ingest_surface_dtype(self._g, int(seq)) != dt:
             return None
         return (out, FrameSurfaceStats.from_c(st)) if with_stats else out
 
@@ -191,19 +196,12 @@ class DeviceIngest:
         when the ring does not hold it (the stage was off when the frame was cut, or the ring has been lapped).  Complete once
         poll() has handed the frame out.  with_stats: (cloud, FrameCloudStats) instead."""
         from .engine import FrameCloudStats
-        st = N.xm_frame_cloud_stats()
-        rc = self._lib.xm_ingest_copy_cloud(self._g, int(seq), None, N.XM_MEM_HOST, C.byref(st))
-        if rc < 0:
-            N.check(rc)
-        if rc == 0:
+        copy = self._lib.xm_ingest_copy_cloud
+        st, st2 = N.xm_frame_cloud_stats(), N.xm_frame_cloud_stats()
+        if not self._ring_copy(copy, seq, None, st):  # (the statistics first: they say how many rows there are)
             return None
-        rows = min(int(st.n_inliers), getattr(self, "_cloud_max_points", 0))
-        out = np.empty((rows, 3), np.float32)
-        st2 = N.xm_frame_cloud_stats()
-        rc = self._lib.xm_ingest_copy_cloud(self._g, int(seq), C.c_void_p(out.ctypes.data) if rows else None, N.XM_MEM_HOST, C.byref(st2))
-        if rc < 0:
-            N.check(rc)
-        if rc == 0 or bytes(st2) != bytes(st):
+        out = np.empty((min(int(st.n_inliers), getattr(self, "_cloud_max_points", 0)), 3), np.float32)
+        if not self._ring_copy(copy, seq, out, st2) or bytes(st2) != bytes(st):
             return None
         return (out, FrameCloudStats.from_c(st)) if with_stats else out
 
