@@ -746,7 +746,7 @@ int xm_evt3_decode(xm_evt3* d, const uint16_t* words_host, size_t n_words, const
  * n_events == NULL: nothing is waited for -- the ingest's kernels read the chunk's event count from device memory; a chunk that
  * decodes to more than max_packet_events is truncated to that and the excess counted in the frames' `overflow`. */
 int xm_ingest_push_evt3(xm_ingest* g, xm_evt3* d, const uint16_t* words_host, size_t n_words, int words_pinned, size_t* n_events);
-/* The same for EVT 2.0 ("EVT2/EVT3 RAW reader"), the older of Prophesee's two public RAW encodings: 32-bit
+/* The same for EVT 2.0 ("EVT2/EVT3 RAW reader"), the oldest of Prophesee's three public RAW encodings: 32-bit
  * little-endian words, [31:28] type -- 0x0 CD_OFF / 0x1 CD_ON {t[5:0], x[10:0], y[10:0]}: one event, p = type; 0x8 EVT_TIME_HIGH
  * {t[33:6]}: the time base of the words behind it; triggers and vendor words are skipped (x_maps_amd/csrc/xmaps_evt2.hpp; host
  * form x_maps_amd/evt2.py, independent checker oracle/evt2_oracle.py).  xm_evt2_create makes a decoder OBJECT OF THE SAME TYPE
@@ -756,6 +756,28 @@ typedef xm_evt3 xm_raw_decoder; /* the decoder object, whichever encoding it was
 int xm_evt2_create(xm_handle* h, size_t max_words, size_t max_events, xm_raw_decoder** out);
 int xm_evt2_decode(xm_raw_decoder* d, const uint32_t* words_host, size_t n_words, const void** events_dev, size_t* n_events);
 int xm_ingest_push_evt2(xm_ingest* g, xm_raw_decoder* d, const uint32_t* words_host, size_t n_words, int words_pinned, size_t* n_events);
+/* The same for EVT 2.1, the 64-bit vectorised RAW encoding of Gen4 / IMX636 cameras: little-endian 64-bit words, [63:60] type --
+ * 0x0 EVT_NEG / 0x1 EVT_POS {t[5:0] at 59:54, x_base[10:0] at 53:43, y[10:0] at 42:32, valid[31:0]}: one event at (x_base + n, y)
+ * for every set bit n of valid, in ascending n, p = type (x_base is decoded as it stands, a multiple of 32 or not); 0x8
+ * EVT_TIME_HIGH {t[33:6] at 59:32}: the time base of the words behind it, loops as in EVT 2.0; triggers and vendor words are
+ * skipped (x_maps_amd/csrc/xmaps_evt21.hpp; host form x_maps_amd/evt21.py, independent checker tests/evt21_ref.py).  A word is
+ * 0..32 events: max_words must be < 2^27, max_events = 0 means 4 * max_words, and a chunk that decodes to more than max_events is
+ * XM_ERR_TOO_MANY with the true count and the state unchanged, as for the other encodings.
+ * xm_evt21_set_legacy_halves(on): the file stores each word as two 32-bit little-endian halves with the HIGH half first
+ * ("endianness=legacy" in the header's format line); the halves are put back on the device where a word is loaded.  Takes effect
+ * from the next chunk; XM_ERR_INVALID on a decoder of another format. */
+int xm_evt21_create(xm_handle* h, size_t max_words, size_t max_events, xm_raw_decoder** out);
+int xm_evt21_set_legacy_halves(xm_raw_decoder* d, int on);
+int xm_evt21_decode(xm_raw_decoder* d, const uint64_t* words_host, size_t n_words, const void** events_dev, size_t* n_events);
+int xm_ingest_push_evt21(xm_ingest* g, xm_raw_decoder* d, const uint64_t* words_host, size_t n_words, int words_pinned, size_t* n_events);
+/* And for DAT (version 2, CD events), the other container the reference's --input takes: 8-byte records behind the header (its
+ * '%' lines and the two bytes event type 0x0C, event size 8 are the caller's to skip: x_maps_amd/dat.py), u32 ts (us) then u32
+ * data {x at 13:0, y at 27:14, p at 31:28}, every record one event; t = (loops << 32) | ts, a loop where ts falls back by more than
+ * 2^31 against the record before it (x_maps_amd/csrc/xmaps_dat.hpp; independent checker tests/dat_ref.py).  max_events = 0:
+ * max_words (= records).  xm_evt3_wait_for_time_base has nothing to wait for in this format. */
+int xm_dat_create(xm_handle* h, size_t max_records, size_t max_events, xm_raw_decoder** out);
+int xm_dat_decode(xm_raw_decoder* d, const void* records_host, size_t n_records, const void** events_dev, size_t* n_events);
+int xm_ingest_push_dat(xm_ingest* g, xm_raw_decoder* d, const void* records_host, size_t n_records, int records_pinned, size_t* n_events);
 
 /* ---- time surfaces in, depth maps and point clouds out ("next" row N4) --------------------------------------------------
  * The reference's offline evaluation (python/eval/compute_depth_x_maps.py:79-131) for a GROUP of camera time surfaces in one

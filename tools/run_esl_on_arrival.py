@@ -5,8 +5,8 @@
         --calib data/ESL_calib_hhi.yaml --scans /ESL_data/static/seq1/ --eval-calib data/calib.yaml --out report.json
 
 Part A -- the replay (`.vscode/launch.json:24-49`: depth_reprojection.py --projector-width 1080 --projector-height 1920 --calib
-data/ESL_calib_hhi.yaml --input data.raw --z-near 0.1 --z-far 1.2 --no-frame-dropping): the RAW file's words (EVT 3.0 or 2.0,
-by its header) go through `with DepthReprojectionProcessor(params)` in chunks -- decoded on the device, polarity / activity
+data/ESL_calib_hhi.yaml --input data.raw --z-near 0.1 --z-far 1.2 --no-frame-dropping): the recording's words (EVT 3.0, 2.0 or
+2.1 by a RAW file's header, or the records of a DAT file) go through `with DepthReprojectionProcessor(params)` in chunks -- decoded on the device, polarity / activity
 filter, trigger finder and the hot path there too (this build's default RuntimeParams) --; reported: frames shown, events, events/s,
 ms per shown frame next to the reference's published 2.67 ms (Threadripper PRO 5955WX, frame stage only), and -- with
 --compare-host-chain -- the same file through the opt-out host chain (NumPy decoder + filters + trigger finder), frame by frame.
@@ -59,13 +59,24 @@ PUBLISHED = {"ms_per_frame": 2.67, "ms_per_frame_sd": 0.31, "hardware": "AMD Ryz
              "seq1_book_duck": {"fill_rate": 0.91, "rmse_cm": 0.31}}
 
 
-def raw_format(path: str) -> int:
-    """3 or 2: the encoding a Prophesee RAW file's header declares"""
-    from x_maps_amd import evt2, evt3
+def raw_format(path: str):
+    """3, 2, 21 or "dat": what a Prophesee recording holds -- the encoding a RAW file's header declares (one that declares none is
+    EVT 3.0), or DAT by its suffix or its header fields.  An encoding this build does not know is a ValueError that names it."""
+    from x_maps_amd import dat, evt2, evt21, evt3
     with open(path, "rb") as f:
         head = f.read(1 << 16)
     fields, _ = evt3.split_raw_header(head)
-    return 2 if evt2._is_evt2(fields) else 3
+    if dat.is_dat(path, fields):
+        return "dat"
+    if evt2._is_evt2(fields):
+        return 2
+    if evt21._is_evt21(fields):
+        return 21
+    name = evt3.raw_format(fields, "3.0")
+    if name not in evt3._FORMAT_NAMES:
+        raise ValueError(f"{path}: the header names the encoding {fields.get('evt', fields.get('format'))!r}, which this build does not "
+                         f"decode (EVT 2.0, EVT 2.1, EVT 3.0 and DAT are)")
+    return 3
 
 
 def replay_raw(raw, calib, proj_w, proj_h, fps, z_near, z_far, camera_perspective=False, device=0, chunk_words=1 << 20,
@@ -75,10 +86,10 @@ def replay_raw(raw, calib, proj_w, proj_h, fps, z_near, z_far, camera_perspectiv
     written to <scans_dir>/scans_np/scansNNN.npy, N counting the shown frames from 0 -- what part B reads
     clouds_dir: every shown frame's per-event point cloud (RuntimeParams.cloud_callback) is written to
     <clouds_dir>/pointcloud_live/frameNNNNNN.ply, N counting the same way"""
-    from x_maps_amd import evt2, evt3
+    from x_maps_amd import dat, evt2, evt21, evt3
     from x_maps_amd.depth_reprojection_processor import DepthReprojectionProcessor, RuntimeParams
     fmt = raw_format(raw)
-    mod = evt2 if fmt == 2 else evt3
+    mod = {3: evt3, 2: evt2, 21: evt21, "dat": dat}[fmt]
     shown, kept = [], []
 
     class Window:
@@ -112,11 +123,12 @@ def replay_raw(raw, calib, proj_w, proj_h, fps, z_near, z_far, camera_perspectiv
     params = RuntimeParams(camera_width=640, camera_height=480, projector_width=proj_w, projector_height=proj_h, projector_fps=fps,
                            z_near=z_near, z_far=z_far, calib=calib, projector_time_map=None, no_frame_dropping=True,
                            camera_perspective=camera_perspective, tables=tables, device=device, device_ingest=device_ingest,
-                           surface_callback=surface_cb, cloud_callback=cloud_cb)
+                           surface_callback=surface_cb, cloud_callback=cloud_cb,
+                           raw_legacy_halves=fmt == 21 and evt21.raw_legacy_halves(raw))
     n_words = n_chunks = 0
     with DepthReprojectionProcessor(params, window=Window()) as proc:
         t_setup = time.perf_counter() - t_setup
-        push = proc.process_evt2_words if fmt == 2 else proc.process_evt3_words
+        push = {3: proc.process_evt3_words, 2: proc.process_evt2_words, 21: proc.process_evt21_words, "dat": proc.process_dat_records}[fmt]
         c0 = time.perf_counter()
         for words in mod.read_raw_words(raw, chunk_words=chunk_words):
             push(words)
@@ -128,7 +140,7 @@ def replay_raw(raw, calib, proj_w, proj_h, fps, z_near, z_far, camera_perspectiv
         dt = time.perf_counter() - c0
         ds = proc._pipe.ingest.device_stats() if proc._pipe.ingest is not None else None
         clouds_lost = int(proc._pipe.stats_printer.counters.get("cloud lost", 0)) if clouds_dir else 0
-    rep = {"raw": raw, "format": f"EVT {fmt}.0", "words": n_words, "chunks": n_chunks, "chunk_words": chunk_words,
+    rep = {"raw": raw, "format": {3: "EVT 3.0", 2: "EVT 2.0", 21: "EVT 2.1", "dat": "DAT"}[fmt], "words": n_words, "chunks": n_chunks, "chunk_words": chunk_words,
            "path": "device ingest (decode + filters + trigger finder + hot path on the GPU)" if device_ingest else
                    "host chain (NumPy decoder, filters, trigger finder; one fused GPU call per frame)",
            "setup_seconds": round(t_setup, 3), "replay_seconds": round(dt, 4), "frames_shown": len(shown),
@@ -409,7 +421,7 @@ def mc3d_from_scans(object_dir, eval_calib, proj_w, proj_h, num_scans=0, start_s
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--raw", help="Prophesee RAW recording (EVT 3.0 / 2.0), e.g. /ESL_data/static/seq1/data.raw")
+    ap.add_argument("--raw", help="Prophesee recording (RAW: EVT 3.0 / 2.0 / 2.1, or DAT), e.g. /ESL_data/static/seq1/data.raw")
     ap.add_argument("--bias", help="camera bias file of the recording (recorded in the report; a file replay does not use it)")
     ap.add_argument("--calib", default=os.path.join(ROOT, "..", "reference", "data", "ESL_calib_hhi.yaml"),
                     help="calibration YAML of the live pipe (the reference's data/ESL_calib_hhi.yaml)")

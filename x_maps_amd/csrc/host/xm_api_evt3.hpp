@@ -1,6 +1,7 @@
-// xm_api_evt3.hpp -- C-ABI: EVT 3.0 / EVT 2.0 words -> EventCD records on the device (xmaps_evt3.hpp, xmaps_evt2.hpp; xmaps_evt.hpp).  One decoder
-// object for both encodings (`format`): same buffers, same state record, same three launches.  Straight into the ingest:
-// xm_ingest_push_evt3 / _evt2 (xm_api_ingest.hpp), which enqueue the same launches (evt3_enqueue) from the ingest's copy side.
+// xm_api_evt3.hpp -- C-ABI: EVT 3.0 / EVT 2.0 / EVT 2.1 words and DAT records -> EventCD records on the device (xmaps_evt3.hpp,
+// xmaps_evt2.hpp, xmaps_evt21.hpp, xmaps_dat.hpp; xmaps_evt.hpp).  One decoder object for the four formats (`format`): same
+// buffers, same state record, same three launches.  Straight into the ingest: xm_ingest_push_evt3 / _evt2 / _evt21 / _dat
+// (xm_api_ingest.hpp), which enqueue the same launches (evt3_enqueue) from the ingest's copy side.
 // (part of libxmaps_hip.so's host side: included by ../xmaps_hip.hip, one translation unit; see that file for the order)
 #pragma once
 
@@ -9,7 +10,7 @@ struct xm_evt3 {
   int device = 0;  // (kept here: the decoder may be destroyed after its handle)
   Stream stream;
   size_t max_words = 0, max_events = 0;
-  int format = 3;                // 3: 16-bit EVT 3.0 words; 2: 32-bit EVT 2.0 words
+  int format = 3;                // 3: 16-bit EVT 3.0 words; 2: 32-bit EVT 2.0 words; EVT_FMT_21: 64-bit EVT 2.1 words; EVT_FMT_DAT: 8-byte DAT records
   size_t word_bytes = 2;
   PinnedMem<uint16_t> h_words;   // pinned staging (max_words * word_bytes)
   DevMem<uint16_t> d_words;
@@ -19,11 +20,21 @@ struct xm_evt3 {
   DevMem<uint4> d_out;           // records of the last xm_evt3_decode
   int cur = 0;
   int wait_tb = 0;               // xm_evt3_wait_for_time_base: events in front of the stream's first TIME_HIGH word are not emitted
+  int legacy_halves = 0;         // xm_evt21_set_legacy_halves: each 64-bit word is stored HIGH half first
+  int emit_by_word = 1;          // EVT 2.1: k_evt21_emit_words, the faster one (profiles/evt21.md); "XM_EVT21_EMIT_BY_WORD" = 0: k_evt21_emit
 };
 
 static_assert(sizeof(Evt2Scan) <= sizeof(Evt3Scan), "the decoders share the aggregates' buffer (d_agg)");
+static_assert(sizeof(Evt21Scan) <= sizeof(Evt3Scan), "the decoders share the aggregates' buffer (d_agg)");
+static_assert(sizeof(DatScan) <= sizeof(Evt3Scan), "the decoders share the aggregates' buffer (d_agg)");
+
+constexpr int EVT_FMT_21 = 21, EVT_FMT_DAT = 100;  // (xm_evt3::format beside 3 and 2)
 
 namespace {
+
+const char* evt_format_name(int format) {
+  return format == 3 ? "EVT 3.0 words" : format == 2 ? "EVT 2.0 words" : format == EVT_FMT_21 ? "EVT 2.1 words" : "DAT records";
+}
 
 // words (host) -> records at `out` (device, room for out_cap) enqueued on `stream`; the chunk's event count is left in
 // d->d_state[d->cur ^ 1].n_events (device memory) -- evt3_commit() flips `cur` once the caller has decided to keep the chunk
@@ -47,6 +58,31 @@ int evt3_enqueue(xm_evt3* d, const void* words_host, size_t n_words, bool pinned
     hipLaunchKernelGGL(k_evt2_prefix, dim3(1), dim3(EVT_THREADS), 0, stream, nb, agg, (const Evt3State*)st_in, st_out, count_out, d->wait_tb);
     hipLaunchKernelGGL(k_evt2_emit, dim3(nb), dim3(EVT_THREADS), 0, stream, w32, n, (const Evt2Scan*)agg, (const Evt3State*)st_in, out,
                        (u32)std::min<size_t>(out_cap, 0xffffffffu), d->wait_tb);
+    HIP_TRY(hipGetLastError());
+    return XM_OK;
+  }
+  if (d->format == EVT_FMT_21) {
+    const unsigned long long* w64 = reinterpret_cast<const unsigned long long*>(d->d_words.get());
+    Evt21Scan* agg = reinterpret_cast<Evt21Scan*>(d->d_agg.get());
+    const u32 cap = (u32)std::min<size_t>(out_cap, 0xffffffffu);
+    hipLaunchKernelGGL(k_evt21_aggregate, dim3(nb), dim3(EVT_THREADS), 0, stream, w64, n, agg, d->legacy_halves);
+    hipLaunchKernelGGL(k_evt21_prefix, dim3(1), dim3(EVT_THREADS), 0, stream, nb, agg, (const Evt3State*)st_in, st_out, count_out, d->wait_tb);
+    if (d->emit_by_word)
+      hipLaunchKernelGGL(k_evt21_emit_words, dim3(nb), dim3(EVT_THREADS), 0, stream, w64, n, (const Evt21Scan*)agg, (const Evt3State*)st_in, out, cap,
+                         d->wait_tb, d->legacy_halves);
+    else
+      hipLaunchKernelGGL(k_evt21_emit, dim3(nb), dim3(EVT_THREADS), 0, stream, w64, n, (const Evt21Scan*)agg, (const Evt3State*)st_in, out, cap,
+                         d->wait_tb, d->legacy_halves);
+    HIP_TRY(hipGetLastError());
+    return XM_OK;
+  }
+  if (d->format == EVT_FMT_DAT) {
+    const unsigned long long* r64 = reinterpret_cast<const unsigned long long*>(d->d_words.get());
+    DatScan* agg = reinterpret_cast<DatScan*>(d->d_agg.get());
+    hipLaunchKernelGGL(k_dat_aggregate, dim3(nb), dim3(EVT_THREADS), 0, stream, r64, n, agg);
+    hipLaunchKernelGGL(k_dat_prefix, dim3(1), dim3(EVT_THREADS), 0, stream, nb, agg, (const Evt3State*)st_in, st_out, count_out);
+    hipLaunchKernelGGL(k_dat_emit, dim3(nb), dim3(EVT_THREADS), 0, stream, r64, n, (const DatScan*)agg, (const Evt3State*)st_in, out,
+                       (u32)std::min<size_t>(out_cap, 0xffffffffu));
     HIP_TRY(hipGetLastError());
     return XM_OK;
   }
@@ -88,10 +124,13 @@ static int evt_create(xm_handle* h, int format, size_t max_words, size_t max_eve
   d->h = h;
   d->device = h->cfg.device;
   d->format = format;
-  d->word_bytes = format == 2 ? 4 : 2;
+  d->word_bytes = format == 3 ? 2 : format == 2 ? 4 : 8;
   d->max_words = max_words ? max_words : (size_t)1 << 20;
-  d->max_events = max_events ? max_events : (format == 2 ? d->max_words : 2 * d->max_words);
+  d->max_events = max_events ? max_events : (format == 3 ? 2 : format == EVT_FMT_21 ? 4 : 1) * d->max_words;
   if (d->max_words >= 0x7fffffffull || d->max_events >= 0x7fffffffull) return fail(XM_ERR_INVALID, "max_words and max_events must be < 2^31");
+  if (format == EVT_FMT_21 && d->max_words >= ((size_t)1 << 27))  // (a word is up to 32 events and a chunk's event counts are u32)
+    return fail(XM_ERR_INVALID, "max_words must be < 2^27 for EVT 2.1");
+  if (const char* e = dbg_opt("XM_EVT21_EMIT_BY_WORD")) d->emit_by_word = e[0] == '1';
   const size_t nb = grid_for(d->max_words, EVT_PER_BLOCK);
   const size_t n16 = d->max_words * d->word_bytes / sizeof(uint16_t);
   HIP_TRY(d->stream.create(hipStreamNonBlocking));
@@ -109,6 +148,8 @@ static int evt_create(xm_handle* h, int format, size_t max_words, size_t max_eve
 
 int xm_evt3_create(xm_handle* h, size_t max_words, size_t max_events, xm_evt3** out) { return evt_create(h, 3, max_words, max_events, out); }
 int xm_evt2_create(xm_handle* h, size_t max_words, size_t max_events, xm_evt3** out) { return evt_create(h, 2, max_words, max_events, out); }
+int xm_evt21_create(xm_handle* h, size_t max_words, size_t max_events, xm_evt3** out) { return evt_create(h, EVT_FMT_21, max_words, max_events, out); }
+int xm_dat_create(xm_handle* h, size_t max_words, size_t max_events, xm_evt3** out) { return evt_create(h, EVT_FMT_DAT, max_words, max_events, out); }
 
 void xm_evt3_destroy(xm_evt3* d) {
   if (!d) return;
@@ -120,6 +161,13 @@ void xm_evt3_destroy(xm_evt3* d) {
 int xm_evt3_wait_for_time_base(xm_evt3* d, int on) {
   if (!d) return fail(XM_ERR_INVALID, "NULL argument");
   d->wait_tb = on ? 1 : 0;
+  return XM_OK;
+}
+
+int xm_evt21_set_legacy_halves(xm_evt3* d, int on) {
+  if (!d) return fail(XM_ERR_INVALID, "NULL argument");
+  if (d->format != EVT_FMT_21) return fail(XM_ERR_INVALID, "this decoder was created for %s", evt_format_name(d->format));
+  d->legacy_halves = on ? 1 : 0;
   return XM_OK;
 }
 
@@ -135,7 +183,7 @@ int xm_evt3_reset(xm_evt3* d) {
 
 static int evt_decode(xm_evt3* d, int format, const void* words_host, size_t n_words, const void** events_dev, size_t* n_events) {
   if (!d || (n_words && !words_host) || !n_events) return fail(XM_ERR_INVALID, "NULL argument");
-  if (d->format != format) return fail(XM_ERR_INVALID, "this decoder was created for EVT %d.0 words", d->format);
+  if (d->format != format) return fail(XM_ERR_INVALID, "this decoder was created for %s", evt_format_name(d->format));
   HIP_TRY(hipSetDevice(d->device));
   if (events_dev) *events_dev = d->d_out;
   return evt3_run(d, words_host, n_words, false, d->d_out, d->max_events, d->stream, n_events);
@@ -146,6 +194,12 @@ int xm_evt3_decode(xm_evt3* d, const uint16_t* words_host, size_t n_words, const
 }
 int xm_evt2_decode(xm_evt3* d, const uint32_t* words_host, size_t n_words, const void** events_dev, size_t* n_events) {
   return evt_decode(d, 2, words_host, n_words, events_dev, n_events);
+}
+int xm_evt21_decode(xm_evt3* d, const uint64_t* words_host, size_t n_words, const void** events_dev, size_t* n_events) {
+  return evt_decode(d, EVT_FMT_21, words_host, n_words, events_dev, n_events);
+}
+int xm_dat_decode(xm_evt3* d, const void* records_host, size_t n_records, const void** events_dev, size_t* n_events) {
+  return evt_decode(d, EVT_FMT_DAT, records_host, n_records, events_dev, n_events);
 }
 
 }  // extern "C"

@@ -102,7 +102,7 @@ int xm_ingest_push_pinned(xm_ingest* g, const void* eventcd16_pinned, size_t n) 
 // the words are handed to the ingest's launch thread like a packet of records (pageable words: the call returns once they have been copied).
 static int ingest_push_words(xm_ingest* g, xm_evt3* d, int format, const void* words_host, size_t n_words, int words_pinned, size_t* n_events) {
   if (!g || !d || (n_words && !words_host)) return fail(XM_ERR_INVALID, "NULL argument");
-  if (d->format != format) return fail(XM_ERR_INVALID, "this decoder was created for EVT %d.0 words", d->format);
+  if (d->format != format) return fail(XM_ERR_INVALID, "this decoder was created for %s", evt_format_name(d->format));
   if (g->fx.h != d->h) return fail(XM_ERR_INVALID, "the decoder and the ingest belong to different handles");
   if (n_words > d->max_words) return fail(XM_ERR_TOO_MANY, "chunk of %zu words exceeds max_words %zu", n_words, d->max_words);
   const double c0 = ingest_now();
@@ -137,6 +137,12 @@ int xm_ingest_push_evt3(xm_ingest* g, xm_evt3* d, const uint16_t* words_host, si
 }
 int xm_ingest_push_evt2(xm_ingest* g, xm_evt3* d, const uint32_t* words_host, size_t n_words, int words_pinned, size_t* n_events) {
   return ingest_push_words(g, d, 2, words_host, n_words, words_pinned, n_events);
+}
+int xm_ingest_push_evt21(xm_ingest* g, xm_evt3* d, const uint64_t* words_host, size_t n_words, int words_pinned, size_t* n_events) {
+  return ingest_push_words(g, d, EVT_FMT_21, words_host, n_words, words_pinned, n_events);
+}
+int xm_ingest_push_dat(xm_ingest* g, xm_evt3* d, const void* records_host, size_t n_records, int records_pinned, size_t* n_events) {
+  return ingest_push_words(g, d, EVT_FMT_DAT, records_host, n_records, records_pinned, n_events);
 }
 
 static int ingest_poll(xm_ingest* g, xm_ingest_frame* out, bool owned) {

@@ -191,8 +191,11 @@ int ingest_handle_verdicts(xm_ingest* g, uint64_t block_upto) {
 // ---- packets ----------------------------------------------------------------------------------------------------------------
 
 // upper bound of the events one word of the decoder's format yields (for the host's bookkeeping: an EVT 3.0 vector word yields up
-// to 12, everything else at most one)
-int ingest_words_to_events(const xm_evt3* d) { return d && d->format == 2 ? 1 : 12; }
+// to 12, an EVT 2.1 word up to 32, an EVT 2.0 word or a DAT record at most one)
+int ingest_words_to_events(const xm_evt3* d) {
+  if (!d) return 12;
+  return d->format == 2 || d->format == EVT_FMT_DAT ? 1 : d->format == EVT_FMT_21 ? 32 : 12;
+}
 
 // the activity filter's state as a packet sees it: its set of cells and control words.  The packets that take part -- the
 // non-empty ones -- take the two sets strictly in turns (IngestLaunch::act_toggle, advanced by ingest_process; an empty push between

@@ -1,11 +1,12 @@
-// xmaps_evt.hpp -- what the device decoders of Prophesee's two RAW encodings share (xmaps_evt3.hpp: EVT 3.0, xmaps_evt2.hpp:
-// EVT 2.0; both include this file, neither includes the other).  (gfx950 / MI355X)
+// xmaps_evt.hpp -- what the device decoders of Prophesee's four recording formats share (xmaps_evt3.hpp: EVT 3.0, xmaps_evt2.hpp:
+// EVT 2.0, xmaps_evt21.hpp: EVT 2.1, xmaps_dat.hpp: DAT; each includes this file, none includes another).  (gfx950 / MI355X)
 //
-// Either format is a state machine over its words, and every piece of that state at word i is "the value of the last word of type T
+// Every format is a state machine over its words, and every piece of that state at word i is "the value of the last word of type T
 // at or before i" or a sum over the words before i: an inclusive scan with an associative combine, evaluated in three launches
 // per chunk of EVT_PER_BLOCK-word blocks: block aggregates -> their exclusive scan in one block, EVT_THREADS of them per trip with
 // the range read so far carried from trip to trip, seeded with the state the previous chunk left (which also writes the next state
-// and the chunk's event count) -> every block re-scans its words from its prefix and writes its records in word order.
+// and the chunk's event count) -> every block re-scans its words from its prefix and writes its records in word order (EVT 2.1,
+// whose words are up to 32 events each, has a second emit kernel that writes by output slot: xmaps_evt21.hpp).
 // Here: the block geometry, the state record a chunk hands to the next one, the start-of-stream rule and the block scan (over a
 // format's scan record and its evt_combine overload).  The three kernel bodies stay spelled out per format: shared as inlined
 // templates they compile to different device code (profiles/evt_skeleton_identity.md lists the shapes that were tried).
@@ -16,8 +17,8 @@ namespace xm {
 
 constexpr int EVT_THREADS = 256, EVT_IPT = 8, EVT_PER_BLOCK = EVT_THREADS * EVT_IPT;
 
-// What a chunk hands to the next one (Evt3Decoder's fields in x_maps_amd/evt3.py; EVT 2.0 uses t_high, t_loops, have_high and
-// n_events and leaves the rest 0).  The name is EVT 3.0's because the kernels' mangled names carry it.
+// What a chunk hands to the next one (Evt3Decoder's fields in x_maps_amd/evt3.py; EVT 2.0 and EVT 2.1 use t_high, t_loops,
+// have_high and n_events, DAT t_high -- its last stamp --, t_loops and n_events; they leave the rest 0).  The name is EVT 3.0's because the kernels' mangled names carry it.
 struct Evt3State {
   u32 y, base_x, base_p, t_high, t_low;
   u32 have_high;  // a TIME_HIGH word has been seen since the stream started (the "wait for the time base" option drops events before it)

@@ -109,7 +109,7 @@ class DepthReprojectionPipe:
         # device-side ingest (row N2): raw packets go to the GPU, which filters, buffers, cuts frames and runs the hot path on
         # them without the event stream (or any index into it) coming back to the host
         self.ingest = None
-        self._raw_dev, self._raw_host = {}, {}  # EVT 3.0 / 2.0 decoders (process_evt3_words / process_evt2_words), created on first use
+        self._raw_dev, self._raw_host = {}, {}  # RAW / DAT decoders (process_evt3_words / _evt2_words / _evt21_words / process_dat_records), created on first use
         self._own_act_filter = None
         self._host_chain_active = False
         self._device_frame_filters = bool(getattr(p, "device_frame_filters", False))
@@ -233,22 +233,44 @@ class DepthReprojectionPipe:
         """the same for EVT 2.0 words (x_maps_amd.evt2.read_raw_words): 32-bit words, the encoding of older sensors"""
         self._process_raw_words(words, 2)
 
+    def process_evt21_words(self, words):
+        """the same for EVT 2.1 words (x_maps_amd.evt21.read_raw_words): 64-bit words of up to 32 events, in the half order
+        RuntimeParams.raw_legacy_halves names"""
+        self._process_raw_words(words, 21)
+
+    def process_dat_records(self, records):
+        """the same for the records of a DAT file (x_maps_amd.dat.read_raw_words): 8 bytes per event"""
+        self._process_raw_words(records, "dat")
+
+    def _raw_format(self, fmt):
+        """-> (as_words, device decoder factory, host decoder factory) of a format process_*_words / _records takes"""
+        from . import dat, evt2, evt21, evt3
+        wait = bool(getattr(self.params, "raw_wait_for_time_base", False))
+        eng = self.calib_maps.engine
+        if fmt == 21:
+            legacy = bool(getattr(self.params, "raw_legacy_halves", False))
+            return (lambda w: np.ascontiguousarray(w, dtype="<u8"),
+                    lambda: evt21.DeviceEvt21Decoder(eng, max_words=1 << 20, wait_for_time_base=wait, legacy_halves=legacy),
+                    lambda: evt21.Evt21Decoder(wait, legacy))
+        if fmt == "dat":
+            return dat.as_records, lambda: dat.DeviceDatDecoder(eng, max_words=1 << 20), lambda: dat.DatDecoder()
+        mod, dt, cls, host = (evt2, "<u4", evt2.DeviceEvt2Decoder, evt2.Evt2Decoder) if fmt == 2 else (evt3, "<u2", evt3.DeviceEvt3Decoder, evt3.Evt3Decoder)
+        return (lambda w: np.ascontiguousarray(w, dtype=dt), lambda: cls(eng, max_words=1 << 20, wait_for_time_base=wait),
+                lambda: host(wait))
+
     def _process_raw_words(self, words, fmt):
-        from . import evt2, evt3
-        mod, dt = (evt2, "<u4") if fmt == 2 else (evt3, "<u2")
+        as_words, make_dev, make_host = self._raw_format(fmt)
         if self._use_ingest():
             dev = self._raw_dev.get(fmt)
             if dev is None:
-                cls = evt2.DeviceEvt2Decoder if fmt == 2 else evt3.DeviceEvt3Decoder
-                dev = self._raw_dev[fmt] = cls(self.calib_maps.engine, max_words=1 << 20,
-                                               wait_for_time_base=bool(getattr(self.params, "raw_wait_for_time_base", False)))
+                dev = self._raw_dev[fmt] = make_dev()
             from ._native import XMapsTooMany
-            w = np.ascontiguousarray(words, dtype=dt)
+            w = as_words(words)
 
             def push(piece):
                 try:
                     dev.push(self.ingest, piece)
-                except XMapsTooMany:  # (vector words: up to 12 events each -- more than a packet slot holds; nothing has advanced)
+                except XMapsTooMany:  # (vector words: up to 12 or 32 events each -- more than a packet slot holds; nothing has advanced)
                     if len(piece) < 2:
                         raise
                     push(piece[:len(piece) // 2])
@@ -264,8 +286,7 @@ class DepthReprojectionPipe:
             return
         host = self._raw_host.get(fmt)
         if host is None:
-            wait = bool(getattr(self.params, "raw_wait_for_time_base", False))
-            host = self._raw_host[fmt] = mod.Evt2Decoder(wait) if fmt == 2 else mod.Evt3Decoder(wait)
+            host = self._raw_host[fmt] = make_host()
         evs = host.decode(words)
         if len(evs):
             self.process_events(evs)

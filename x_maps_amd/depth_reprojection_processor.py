@@ -74,6 +74,9 @@ class RuntimeParams:
     # waits for the first time base) instead of emitted at time base 0.  Which of the two Metavision's reader does is unpinned
     # (tools/pin_thirdparty.py decides); it matters for the first few words of a file only.
     raw_wait_for_time_base: bool = False
+    # process_evt21_words: the recording stores every 64-bit word as two 32-bit halves with the HIGH half first ("endianness=legacy"
+    # in its header's format line: x_maps_amd.evt21.raw_legacy_halves); the decoders put the halves back where they load a word.
+    raw_legacy_halves: bool = False
     # `calib` is a calibration YAML: its rectification maps, the rectified time map and the X-map are built in one device call
     # (calibration.build_tables(maps_on_device=True), x_maps_amd/rig_maps.py) instead of NumPy on the host.  The same tables,
     # bit for bit.
@@ -206,6 +209,18 @@ class DepthReprojectionProcessor:
         """the same for a chunk of EVT 2.0 words (x_maps_amd.evt2.read_raw_words)"""
         self.stats_printer.print_stats_if_needed()
         self._pipe.process_evt2_words(words)
+        self.stats_printer.print_stats_if_needed()
+
+    def process_evt21_words(self, words):
+        """the same for a chunk of EVT 2.1 words (x_maps_amd.evt21.read_raw_words; RuntimeParams.raw_legacy_halves: their half order)"""
+        self.stats_printer.print_stats_if_needed()
+        self._pipe.process_evt21_words(words)
+        self.stats_printer.print_stats_if_needed()
+
+    def process_dat_records(self, records):
+        """the same for a chunk of a DAT file's records (x_maps_amd.dat.read_raw_words)"""
+        self.stats_printer.print_stats_if_needed()
+        self._pipe.process_dat_records(records)
         self.stats_printer.print_stats_if_needed()
 
     def flush(self):

@@ -1,7 +1,7 @@
-"""Prophesee EVT 2.0 RAW decoder ("next" row N4: "EVT2/EVT3 RAW reader"): the older of the two public RAW encodings.
+"""Prophesee EVT 2.0 RAW decoder ("next" row N4: "EVT2/EVT3 RAW reader"): the oldest of the three public RAW encodings.
 
 The reference reads its recordings through Metavision's closed readers (python/bias_events_iterator.py:53-96); which encoding a
-.raw file holds is the camera's choice (Gen3 sensors: EVT 2.0, Gen4: EVT 3.0; evt3.py is the other one).  EVT 2.0 is an ASCII
+.raw file holds is the camera's choice (Gen3 sensors: EVT 2.0, Gen4: EVT 3.0 or EVT 2.1; evt3.py and evt21.py are the other two).  EVT 2.0 is an ASCII
 header (lines starting with '%') followed by little-endian 32-bit words, type in the top four bits:
 
     0x0 CD_OFF / 0x1 CD_ON   [27:22] t[5:0]   [21:11] x   [10:0] y       one event, polarity = the type

@@ -158,8 +158,9 @@ def decode_evt3(words: np.ndarray, wait_for_time_base: bool = False) -> np.ndarr
 
 class DeviceEvtDecoder:
     """A RAW decoder as three kernels per chunk (csrc/xmaps_evt.hpp): the words cross PCIe as the recording stores them, the records
-    stay on the device.  One native decoder object serves both encodings (csrc/host/xm_api_evt3.hpp); a subclass names the word
-    dtype and the three entry points that differ: DeviceEvt3Decoder below, evt2.DeviceEvt2Decoder."""
+    stay on the device.  One native decoder object serves every format (csrc/host/xm_api_evt3.hpp); a subclass names the word
+    dtype and the three entry points that differ: DeviceEvt3Decoder below, evt2.DeviceEvt2Decoder, evt21.DeviceEvt21Decoder,
+    dat.DeviceDatDecoder."""
 
     _dtype = _create = _decode = _push = None
 
@@ -177,7 +178,7 @@ class DeviceEvtDecoder:
 
     def close(self):
         if getattr(self, "_d", None) is not None and self._d.value:
-            self._lib.xm_evt3_destroy(self._d)  # (one decoder type serves both encodings)
+            self._lib.xm_evt3_destroy(self._d)  # (one decoder type serves every format)
             self._d = self._C.c_void_p(None)
 
     def __del__(self):
@@ -196,16 +197,19 @@ class DeviceEvtDecoder:
     def reset(self):
         self._N.check(self._lib.xm_evt3_reset(self._d))
 
+    def _as_words(self, words) -> np.ndarray:
+        return np.ascontiguousarray(words, dtype=self._dtype)
+
     def decode_device(self, words: np.ndarray):
         C = self._C
-        w = np.ascontiguousarray(words, dtype=self._dtype)
+        w = self._as_words(words)
         ptr, n = C.c_void_p(None), C.c_size_t(0)
         self._N.check(getattr(self._lib, self._decode)(self._d, C.c_void_p(w.ctypes.data), len(w), C.byref(ptr), C.byref(n)))
         return int(ptr.value or 0), int(n.value)
 
     def decode(self, words: np.ndarray) -> np.ndarray:
         out = []
-        w = np.ascontiguousarray(words, dtype=self._dtype)
+        w = self._as_words(words)
         for a in range(0, max(len(w), 1), self.max_words):
             ptr, n = self.decode_device(w[a:a + self.max_words])
             ev = np.zeros(n, EVENT_CD_DTYPE)
@@ -224,7 +228,7 @@ class DeviceEvtDecoder:
         staging copy.  count=True: waits for the decoder and returns the chunk's event count; count=False: nothing is waited
         for (the ingest's kernels read the count on the device), returns None."""
         C = self._C
-        w = np.ascontiguousarray(words, dtype=self._dtype)
+        w = self._as_words(words)
         ingest._backpressure(1)
         n = C.c_size_t(0) if count else None
         self._N.check(getattr(self._lib, self._push)(ingest._g, self._d, C.c_void_p(w.ctypes.data), len(w), int(bool(pinned)),
