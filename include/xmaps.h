@@ -1204,6 +1204,65 @@ int xm_eval_table_score(xm_eval_table* e, const float* gt, const float* const* e
                         int n_scans, int mem, xm_eval_result* results_out, xm_eval_sums* sums_out, float* mask_out,
                         double* avg_depth_out);
 
+/* ---- projector time-map calibration: a white-frame recording's camera time surfaces -> the projector-space time map --------------
+ * The paper's recipe (section 3.3, "Time map calibration"): project a white image onto a plane, average several normalised camera
+ * time maps per pixel, find the projected frame's corners in a binary map, warp the quadrilateral to the projector's width x
+ * height with a projective transformation, interpolate missing values linearly between actual lines.  The reference ships no
+ * code for it: the arithmetic is THIS BUILD'S DEFINITION, pinned bit for bit to the NumPy oracle of tests/time_cal_cases.py.
+ * Float64 throughout, every expression in the order written, unfused; csrc/xmaps_timecal.hpp has the kernels.
+ *
+ *   accumulate : per surface lo / hi / nnz over its non-zero entries (as xm_process_time_surfaces takes them); a surface without
+ *                two distinct non-zero values is skipped and counted.  Otherwise per pixel with v != 0:
+ *                sum += max((f64(v) - lo) / (hi - lo), 0), cnt += 1.  Surfaces are taken in order -- inside a call by index, across
+ *                calls in call order -- by the one thread that owns the pixel: the sums depend on the sequence of surfaces only.
+ *   mean       : valid = cnt >= min_count (min_count >= 1); mean = valid ? sum / f64(cnt) : 0.
+ *   corners    : core = valid on the whole 3 x 3 neighbourhood (an image-border pixel is never core).  Over the core pixels
+ *                TL = argmin(x + y), TR = argmax(x - y), BR = argmax(x + y), BL = argmin(x - y), ties to the smallest raster index.
+ *                XM_ERR_INVALID (xm_last_error names the reason): no core pixel; two corners coincide; TL -> TR -> BR -> BL is not
+ *                strictly convex (the integer cross products of consecutive edges do not all have one sign).
+ *   warp       : h maps a projector pixel (u, v) to a camera position: X = h0 u + h1 v + h2, Y = h3 u + h4 v + h5,
+ *                D = h6 u + h7 v + h8, x = X / D, y = Y / D, x0 = floor(x), y0 = floor(y), fx = x - x0, fy = y - y0.  Taps (x0, y0),
+ *                (x0+1, y0), (x0, y0+1), (x0+1, y0+1) with weights (1-fx)(1-fy), fx(1-fy), (1-fx)fy, fx fy; a tap outside the image
+ *                or not valid has weight 0.  den = the weights, num = the products w * mean, both summed in tap order.  den > 0: the
+ *                value is num / den and the pixel is present; otherwise 0 and missing (so is NaN, D = 0, a position beyond the image).
+ *   fill       : along each projector row (a projector line is a column).  A missing pixel at u between the nearest present
+ *                u_l < u < u_r gets m_l + (m_r - m_l) * ((u - u_l) / (u_r - u_l)); with a present pixel on one side only, that
+ *                side's value; a row with no present pixel stays 0 and counts as one in n_unfilled.  One cast to float32.
+ *
+ * An object serves one thread at a time; every call is synchronous.  mem == XM_MEM_HOST: every array pointer is host memory,
+ * XM_MEM_DEVICE: device memory of the object's device; stats and h are host memory always. */
+typedef struct xm_timecal xm_timecal;
+typedef struct xm_timecal_stats {
+  uint64_t n_added;    /* surfaces handed in since create / reset, the skipped ones included */
+  uint64_t n_skipped;  /* ... of which not normalisable                                      */
+  uint32_t n_valid, n_core;      /* xm_timecal_mean / _set_mean                              */
+  int32_t corners[4][2];         /* TL, TR, BR, BL as (x, y); -1 where there is no core pixel */
+  uint32_t n_missing, n_unfilled; /* xm_timecal_warp: missing pixels before the fill; rows without a present pixel */
+} xm_timecal_stats;
+/* XM_ERR_INVALID: NULL, a non-positive side, cam_width * cam_height >= 2^31 */
+int xm_timecal_create(int device, int cam_width, int cam_height, xm_timecal** out);
+void xm_timecal_destroy(xm_timecal* tc);
+/* the accumulators and counters back to zero; the state of xm_timecal_mean is forgotten */
+int xm_timecal_reset(xm_timecal* tc);
+/* surfaces: [n][cam_height][cam_width], XM_T_FLOAT32 or XM_T_FLOAT64, 0 = no event.  At most 65535 surfaces per call. */
+int xm_timecal_add_surfaces(xm_timecal* tc, const void* surfaces, int dtype, int n, int mem);
+/* the counters alone (either may be NULL) */
+int xm_timecal_counts(xm_timecal* tc, uint64_t* n_added, uint64_t* n_skipped);
+/* the device time of the kernels, from HIP events around each launch of the last call that ran it, in ms: k_surf_extrema,
+ * k_tcal_accumulate (the last xm_timecal_add_surfaces), k_tcal_mean, k_tcal_corners, k_tcal_warp, k_tcal_fill */
+int xm_timecal_kernel_ms(xm_timecal* tc, float ms[6]);
+/* mean_out: f64 [cam_height][cam_width], valid_out: u8, the same shape; either may be NULL, and so may stats.  The corner errors
+ * are reported here, after the outputs and stats have been written: the mean and the mask stay in the object, so that
+ * xm_timecal_warp can follow with an h from corners of the caller's own.  XM_ERR_INVALID also for min_count == 0. */
+int xm_timecal_mean(xm_timecal* tc, uint32_t min_count, double* mean_out, uint8_t* valid_out, int mem, xm_timecal_stats* stats);
+/* the state xm_timecal_mean leaves, from the caller's arrays instead (mean must be 0 where valid is 0): the warp as a stage of its
+ * own.  Corners, errors and stats as xm_timecal_mean. */
+int xm_timecal_set_mean(xm_timecal* tc, const double* mean, const uint8_t* valid, int mem, xm_timecal_stats* stats);
+/* warp and fill on the state left by the last xm_timecal_mean / _set_mean (XM_ERR_INVALID without one).  time_map_out: f32
+ * [proj_height][proj_width]; present_out (may be NULL): u8, the mask before the fill.  Sides in 1 .. 2^24. */
+int xm_timecal_warp(xm_timecal* tc, const double h[9], int proj_width, int proj_height, float* time_map_out, uint8_t* present_out,
+                    int mem, xm_timecal_stats* stats);
+
 /* ---- pinned host memory for XM_MEM_HOST_PINNED ------------------------------------------------------------- */
 int xm_host_alloc(xm_handle* h, size_t bytes, void** out);
 int xm_host_free(xm_handle* h, void* p);

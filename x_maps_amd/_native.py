@@ -257,6 +257,11 @@ class xm_mc3d_stats(C.Structure):
                 ("n_poisoned", C.c_uint64), ("n_matched", C.c_uint64), ("n_disp_overflow", C.c_uint64)]
 
 
+class xm_timecal_stats(C.Structure):
+    _fields_ = [("n_added", C.c_uint64), ("n_skipped", C.c_uint64), ("n_valid", C.c_uint32), ("n_core", C.c_uint32),
+                ("corners", (C.c_int32 * 2) * 4), ("n_missing", C.c_uint32), ("n_unfilled", C.c_uint32)]
+
+
 # every symbol include/xmaps.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -397,6 +402,15 @@ SYMBOLS = {
     "xm_eval_table_destroy": (None, [_P]),
     "xm_eval_table_combine": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.POINTER(C.c_double)]),
     "xm_eval_table_score": (C.c_int, [_P, _P, C.POINTER(_P), C.c_int, C.c_uint32, C.c_int, C.c_int, _P, _P, _P, C.POINTER(C.c_double)]),
+    "xm_timecal_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(_P)]),
+    "xm_timecal_destroy": (None, [_P]),
+    "xm_timecal_reset": (C.c_int, [_P]),
+    "xm_timecal_add_surfaces": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int]),
+    "xm_timecal_counts": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "xm_timecal_kernel_ms": (C.c_int, [_P, C.POINTER(C.c_float)]),
+    "xm_timecal_mean": (C.c_int, [_P, C.c_uint32, _P, _P, C.c_int, C.POINTER(xm_timecal_stats)]),
+    "xm_timecal_set_mean": (C.c_int, [_P, _P, _P, C.c_int, C.POINTER(xm_timecal_stats)]),
+    "xm_timecal_warp": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int, C.c_int, _P, _P, C.c_int, C.POINTER(xm_timecal_stats)]),
     "xm_stream": (_P, [_P, C.c_int]),
     "xm_host_alloc": (C.c_int, [_P, C.c_size_t, C.POINTER(_P)]),
     "xm_host_free": (C.c_int, [_P, _P]),

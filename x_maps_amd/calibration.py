@@ -346,17 +346,34 @@ def build_eval_tables(cp: CamProjCalibrationParams, **kw) -> dict:
 def build_tables(cp: CamProjCalibrationParams, z_near=0.1, z_far=1.2, scan_upwards=True, device: int = 0,
                  x_map_on_gpu: bool = True, projector_time_map_rectified: Optional[np.ndarray] = None,
                  zero_undistort_proj_map: bool = False, time_map_border: str = "replicate", x_map_fn=None,
-                 maps_on_device: bool = False) -> dict:
+                 maps_on_device: bool = False, projector_time_map: Optional[np.ndarray] = None) -> dict:
     """Everything DepthReprojectionPipe.__post_init__ builds (python/depth_reprojection_pipe.py:69-99), as the
     tables dict XMapsEngine / RuntimeParams.tables take.  Projector = camera 1 of the stereo pair (calib:194-217).
     maps_on_device: the maps, the rectified time map and the X-map in one device call (x_maps_amd.rig_maps.build_xmaps_tables:
-    the same dict, bit for bit; stereo_rectify stays here)."""
+    the same dict, bit for bit; stereo_rectify stays here).
+    projector_time_map: an UNRECTIFIED [proj_h][proj_w] time map (x_maps_amd.time_map_calibration) in place of the linear one: it
+    is rectified with remap_nearest through the projector's forward maps and time_map_border (with maps_on_device through
+    rig_maps.forward_map(src=)), then used exactly as projector_time_map_rectified is."""
     if maps_on_device and x_map_fn is not None:
         raise ValueError("x_map_fn builds the X-map on the host: it does not go with maps_on_device=True")
+    if projector_time_map is not None and projector_time_map_rectified is not None:
+        raise ValueError("projector_time_map and projector_time_map_rectified are two forms of one input: pass one")
     size = (cp.rect_image_width, cp.rect_image_height)
     R1, R2, P1, P2, Q = stereo_rectify(cp.projector_K, cp.projector_D, cp.camera_K, cp.camera_D, size, cp.cam2proj_R,
                                        cp.cam2proj_T)
     x_off, xw = 4242, cp.projector_width
+    if projector_time_map is not None:
+        tm = np.ascontiguousarray(projector_time_map, dtype=np.float32)
+        if tm.shape != (cp.projector_height, cp.projector_width):
+            raise ValueError(f"projector_time_map must be {cp.projector_height} x {cp.projector_width}, not {tm.shape}")
+        proj_fwd_D = np.zeros(5) if zero_undistort_proj_map else cp.projector_D
+        if maps_on_device:
+            from .rig_maps import forward_map
+            projector_time_map_rectified = forward_map(cp.projector_K, proj_fwd_D, R2, P2, size, want_maps=False, src=tm,
+                                                       border=time_map_border, device=device)["remap"]
+        else:
+            projector_time_map_rectified = remap_nearest(tm, *init_undistort_rectify_map(cp.projector_K, proj_fwd_D, R2, P2, size),
+                                                         time_map_border)
     if maps_on_device:
         from .rig_maps import build_xmaps_tables
         dev = build_xmaps_tables(cp, R1, R2, P1, P2, scan_upwards=scan_upwards, zero_undistort_proj_map=zero_undistort_proj_map,

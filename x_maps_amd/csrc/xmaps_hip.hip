@@ -17,6 +17,7 @@
 #include "xmaps_surface.hpp"        // time surfaces -> depth maps + point clouds
 #include "xmaps_framesurface.hpp"   // frames of events -> camera time surfaces (the group entry and the ingest's surface stage)
 #include "xmaps_framecloud.hpp"     // frames of events -> per-event point clouds (the group entry and the ingest's cloud stage)
+#include "xmaps_timecal.hpp"        // projector time-map calibration: white-frame time surfaces -> the projector-space time map
 
 #include <hip/hip_ext.h>
 
@@ -86,3 +87,4 @@ using namespace xm;
 #include "host/xm_api_esloptim.hpp" // the ESL depth optimisation behind ESL-init: depth_optim maps
 #include "host/xm_api_eslfilter.hpp" // the bilateral filter and the TV denoiser behind it: depth_optim_filtered maps
 #include "host/xm_api_evaltable.hpp" // the evaluation table's scorer: ground truth + every method's maps -> the cells of Table 1
+#include "host/xm_api_timecal.hpp"  // the projector time-map calibration: accumulate, mean, corners, warp, fill

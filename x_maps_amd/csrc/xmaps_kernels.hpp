@@ -41,3 +41,4 @@
 // (included by xmaps_hip.hip behind the ingest, whose frame descriptors it reads:)
 //       "xmaps_framesurface.hpp"  frames of events -> camera time surfaces: winners by integer atomics, one store per pixel
 //       "xmaps_framecloud.hpp"    frames of events -> per-event point clouds: codes per event, a scan, a stable compaction
+//       "xmaps_timecal.hpp"       projector time-map calibration: accumulate, mean, corners, projective warp, fill along rows

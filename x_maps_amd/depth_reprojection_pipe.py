@@ -118,6 +118,7 @@ class DepthReprojectionPipe:
         self._ingest_failed = False  # an ingest call has raised: the error has reached the caller, close() does not ask again
         self._closed = False
         self._surface_callback = getattr(p, "surface_callback", None)
+        self._surface_kind = (getattr(p, "surface_select", "last"), getattr(p, "surface_dtype", np.float32))
         self._cloud_callback = getattr(p, "cloud_callback", None)
         if self._cloud_callback is not None:  # (tables without the float rectify maps or Q: ValueError, here and not at the first frame)
             self.calib_maps.engine.set_frame_cloud_tables()
@@ -133,7 +134,7 @@ class DepthReprojectionPipe:
                                        lossless=not p.should_drop_frames)  # no_frame_dropping (the default): never lap the ring
             self._ingest_views = bool(getattr(p, "ingest_frame_views", False))
             if self._surface_callback is not None:  # (before the first push: every frame of the stream gets a surface)
-                self.ingest.set_surface_output("last", np.float32)
+                self.ingest.set_surface_output(*self._surface_kind)
             if self._cloud_callback is not None:
                 self.ingest.set_cloud_output(True, int(getattr(p, "cloud_max_points", 262144)))
         else:
@@ -311,7 +312,7 @@ class DepthReprojectionPipe:
         if len(evs) == 0:
             raise ValueError("zero-size array to reduction operation minimum which has no identity")  # xmd:12
         if self._surface_callback is not None:  # (the cut frame's, in front of any frame event filter: as the ingest's stage)
-            surfs, _ = self.calib_maps.engine.frames_to_time_surfaces([evs], "last", np.float32)
+            surfs, _ = self.calib_maps.engine.frames_to_time_surfaces([evs], *self._surface_kind)
             self._surface_callback(surfs[0])
         if self._cloud_callback is not None:  # (the same: a group of one through the group entry, the ingest stage's row limit)
             cloud, _ = self.calib_maps.engine.frames_to_point_clouds([evs])[0]

@@ -87,6 +87,10 @@ class RuntimeParams:
     # On the device ingest it is a stage of the ingest (DeviceIngest.set_surface_output); on the host chain one call of the
     # group entry on the frame's events.  The same arrays either way.  What the evaluation entries take as `scans_np`.
     surface_callback: Optional[Callable] = None
+    # which event of a pixel stamps the surface ("last" or "first") and the surface's dtype (float32 or float64): the time-map
+    # calibration (tools/calibrate_time_map.py) takes first events in float64
+    surface_select: str = "last"
+    surface_dtype: Any = "float32"
     # cloud_callback(cloud) for every shown frame, immediately before that frame's frame_callback (behind its surface_callback,
     # if both are set): the frame's per-event point cloud (float32 [n][3]: the reference's construct_point_cloud on the frame's
     # inlier events in stream order, XMapsEngine.frames_to_point_clouds), built from the CUT frame, in front of any frame event
