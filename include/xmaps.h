@@ -779,6 +779,90 @@ int xm_dat_create(xm_handle* h, size_t max_records, size_t max_events, xm_raw_de
 int xm_dat_decode(xm_raw_decoder* d, const void* records_host, size_t n_records, const void** events_dev, size_t* n_events);
 int xm_ingest_push_dat(xm_ingest* g, xm_raw_decoder* d, const void* records_host, size_t n_records, int records_pinned, size_t* n_events);
 
+/* ---- frames cut at a recording's external trigger events -----------------------------------------------------------
+ * A rig whose projector is wired to the camera's sync jack records one EXT_TRIGGER word (type 0xA) per pulse: the exact frame
+ * boundaries, in stream order (the paper's section 3.4: the pause finder is the fallback for rigs without a sync line).  The
+ * word, per encoding (the vendor's published format description; unpinned against Metavision, like the decoders):
+ *   EVT 3.0  [15:12] = 0xA, id [11:8], value [0]; the time is the state machine's current TIME_HIGH / TIME_LOW exactly as for a CD
+ *            event at that word (a TIME_HIGH that changed the field restarts the low field at 0; the 24-bit wrap count applies)
+ *   EVT 2.0  [31:28] = 0xA, t[5:0] at [27:22], id [12:8], value [0]; t = (loops << 34) | (time_high << 6) | t[5:0], as for CD words
+ *   EVT 2.1  [63:60] = 0xA, t[5:0] at [59:54], id [44:40], value [32]; composed as in EVT 2.0 (legacy halves swapped back first)
+ * A trigger word changes no decoder state.  event_index = the number of records the decoder writes for the chunk IN FRONT of the
+ * word: the boundary is exact in stream order whatever the time stamps are.  Records come out in word order.  Start-of-stream
+ * rule as for the events (xm_evt3_wait_for_time_base): in front of the stream's first TIME_HIGH a trigger carries the time
+ * base 0 (off) or is not emitted (on).  (x_maps_amd/csrc/xmaps_exttrigger.hpp: two further launches per chunk; host form
+ * x_maps_amd/ext_trigger.py, independent checker tests/ext_trigger_ref.py) */
+typedef struct xm_ext_trigger {
+  int64_t t;            /* us                                                             */
+  uint32_t event_index; /* records of the chunk in front of the word                      */
+  uint8_t id;           /* the trigger channel                                            */
+  uint8_t value;        /* 1: rising edge, 0: falling edge                                */
+  uint16_t reserved;    /* 0                                                              */
+} xm_ext_trigger;
+/* max_triggers = room for one chunk's records; 0 (default) = off: the two launches are not issued, nothing is allocated.  Takes
+ * effect from the next chunk.  XM_ERR_INVALID on a DAT decoder (CD DAT files carry no trigger words).  Only the synchronous
+ * decode entries (xm_evt3_decode / xm_evt2_decode / xm_evt21_decode, xm_trigframes_push) extract; xm_ingest_push_evt* ignore it.
+ * A chunk with more trigger words than max_triggers: the decode returns XM_ERR_TOO_MANY with the decoder's state unchanged, as
+ * for too many events (decode it again in halves). */
+int xm_evt_set_ext_triggers(xm_raw_decoder* d, size_t max_triggers);
+/* The records of the last successful xm_evt*_decode (at most cap of them are copied, *n = their number): *n = 0 when extraction
+ * is off, after xm_evt3_reset and after an empty chunk. */
+int xm_evt_last_ext_triggers(xm_raw_decoder* d, xm_ext_trigger* out_host, size_t cap, size_t* n);
+
+/* THE CUT RULE of this build (pure host code: x_maps_amd/csrc/host/xm_trigger_cut.hpp; Python mirror TriggerFrameCutter).
+ *  - A trigger is SELECTED when (cfg.id < 0 || id == cfg.id) and its value matches cfg.edge (XM_TRIG_RISING: 1, XM_TRIG_FALLING:
+ *    0, XM_TRIG_BOTH: either).
+ *  - I_k = the absolute stream index of the k-th selected trigger since create / reset: the events kept so far plus the trigger's
+ *    index among the chunk's kept events.  Frame k holds the kept events [I_k, I_k+1).  Nothing is trimmed (the reference's +-2
+ *    events belong to its pause heuristic).
+ *  - Events in front of the first selected trigger belong to no frame: events_before_first_trigger.
+ *  - min_events > 0: a frame with n <= min_events is not delivered: frames_skipped.  min_events = 0: every frame is delivered,
+ *    empty ones included (an empty frame is defined in xm_process_batch_aos, xm_frames_to_time_surfaces, xm_frames_to_point_clouds).
+ *  - The buffer holds cap_events records; its live part is the undelivered and unreleased frames and the open one.  A chunk of n
+ *    decoded events needs n records of room behind the live part ("a chunk's worth": the count BEFORE positive_only, so that
+ *    nothing waits for the compaction).  If live + n > cap_events the open frame is dropped -- its events so far and those up to
+ *    the next selected trigger are counted in events_dropped_open_frame, cutting resumes at that trigger (the analogue of the
+ *    ingest's "stream without a usable pause": bookkeeping, not an error).  If the ready frames alone leave no room, the push
+ *    returns XM_ERR_TOO_MANY (release them first; the chunk is decoded and lost: reset).  Otherwise, only if the chunk does not
+ *    fit behind the live part, that part is first moved to the buffer's front (front_moves; non-overlapping copies).
+ *  - The open frame at reset / destroy is not a frame.
+ * xm_trigframes_push: decodes the chunk with the decoder's synchronous path (extraction must be on: XM_ERR_INVALID otherwise),
+ * appends the chunk's records behind the live ones -- positive_only: a stable compaction that keeps the p == 1 records (count per
+ * block, fold of the earlier blocks' counts, write; the chunk's trigger indices are remapped in the same pass to "kept records
+ * with chunk index < event_index", the chunk's event count to the kept total); otherwise a plain copy -- and runs the cutter.
+ * *n_ready = frames waiting.  Synchronous.
+ * xm_trigframes_ready: the next run of ready frames that lie back to back in the buffer (a skipped frame ends a run), at most
+ * min(cap_frames, max_frames_ready if > 0): *events_dev = the buffer's base (16-byte aligned), offsets_host[0 .. *n_frames] ascending
+ * record offsets into it -- ready for the three frame entries with XM_MEM_DEVICE --, opening[f] (nullable) = frame f's opening
+ * trigger (event_index: its index among its chunk's kept events).  Valid until the next push / release / reset.
+ * xm_trigframes_release(n): the first n ready frames are done with (call it after xm_sync). */
+#define XM_TRIG_RISING 0
+#define XM_TRIG_FALLING 1
+#define XM_TRIG_BOTH 2
+typedef struct xm_trigframes_config {
+  uint32_t struct_size;     /* sizeof(xm_trigframes_config)                                  */
+  int32_t id;               /* the trigger channel, < 0: any                                 */
+  int32_t edge;             /* XM_TRIG_*                                                     */
+  int32_t positive_only;    /* != 0: keep p == 1 records only                                */
+  uint64_t cap_events;      /* the buffer, in records (0 = 2^22)                             */
+  uint64_t min_events;      /* see above                                                     */
+  int32_t max_frames_ready; /* per xm_trigframes_ready, 0: no limit                          */
+  int32_t reserved;         /* 0                                                             */
+} xm_trigframes_config;
+typedef struct xm_trigframes_counters {
+  uint64_t events_in, events_kept, triggers_seen, triggers_selected, frames_cut /* delivered to the ready queue */;
+  uint64_t frames_skipped, events_before_first_trigger, events_dropped_open_frame, front_moves;
+} xm_trigframes_counters;
+typedef struct xm_trigframes xm_trigframes;
+int xm_trigframes_create(xm_handle* h, const xm_trigframes_config* cfg, xm_trigframes** out);
+void xm_trigframes_destroy(xm_trigframes* tf);
+int xm_trigframes_reset(xm_trigframes* tf); /* drops every frame, open or ready, and the stream position; the counters stay */
+int xm_trigframes_push(xm_trigframes* tf, xm_raw_decoder* d, const void* words_host, size_t n_words, int words_pinned, int* n_ready);
+int xm_trigframes_ready(xm_trigframes* tf, const void** events_dev, uint64_t* offsets_host, int cap_frames, int* n_frames,
+                        xm_ext_trigger* opening /* nullable */);
+int xm_trigframes_release(xm_trigframes* tf, int n_frames);
+int xm_trigframes_stats(xm_trigframes* tf, xm_trigframes_counters* out);
+
 /* ---- time surfaces in, depth maps and point clouds out ("next" row N4) --------------------------------------------------
  * The reference's offline evaluation (python/eval/compute_depth_x_maps.py:79-131) for a GROUP of camera time surfaces in one
  * device call: each surface is [cam_height][cam_width] row-major, XM_T_FLOAT32 or XM_T_FLOAT64, 0 = no event.  Per surface:

@@ -125,6 +125,21 @@ class xm_ingest_frame(C.Structure):
     ]
 
 
+XM_TRIG_RISING, XM_TRIG_FALLING, XM_TRIG_BOTH = 0, 1, 2
+
+
+class xm_trigframes_config(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("id", C.c_int32), ("edge", C.c_int32), ("positive_only", C.c_int32),
+        ("cap_events", C.c_uint64), ("min_events", C.c_uint64), ("max_frames_ready", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+class xm_trigframes_counters(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("events_in", "events_kept", "triggers_seen", "triggers_selected", "frames_cut", "frames_skipped",
+                                          "events_before_first_trigger", "events_dropped_open_frame", "front_moves")]
+
+
 class xm_eval_result(C.Structure):
     _fields_ = [("fillrate", C.c_double), ("rmse", C.c_double), ("perc_1", C.c_double), ("perc_5", C.c_double),
                 ("perc_10", C.c_double), ("margin", C.c_double), ("n_valid", C.c_uint64), ("n_gt_zero", C.c_uint64)]
@@ -366,6 +381,15 @@ SYMBOLS = {
     "xm_evt21_set_legacy_halves": (C.c_int, [_P, C.c_int]),
     "xm_evt21_decode": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
     "xm_ingest_push_evt21": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_int, C.POINTER(C.c_size_t)]),
+    "xm_evt_set_ext_triggers": (C.c_int, [_P, C.c_size_t]),
+    "xm_evt_last_ext_triggers": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "xm_trigframes_create": (C.c_int, [_P, C.POINTER(xm_trigframes_config), C.POINTER(_P)]),
+    "xm_trigframes_destroy": (None, [_P]),
+    "xm_trigframes_reset": (C.c_int, [_P]),
+    "xm_trigframes_push": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_int, C.POINTER(C.c_int)]),
+    "xm_trigframes_ready": (C.c_int, [_P, C.POINTER(_P), _P, C.c_int, C.POINTER(C.c_int), _P]),
+    "xm_trigframes_release": (C.c_int, [_P, C.c_int]),
+    "xm_trigframes_stats": (C.c_int, [_P, C.POINTER(xm_trigframes_counters)]),
     "xm_dat_create": (C.c_int, [_P, C.c_size_t, C.c_size_t, C.POINTER(C.c_void_p)]),
     "xm_dat_decode": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
     "xm_ingest_push_dat": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_int, C.POINTER(C.c_size_t)]),

@@ -22,6 +22,13 @@ struct xm_evt3 {
   int wait_tb = 0;               // xm_evt3_wait_for_time_base: events in front of the stream's first TIME_HIGH word are not emitted
   int legacy_halves = 0;         // xm_evt21_set_legacy_halves: each 64-bit word is stored HIGH half first
   int emit_by_word = 1;          // EVT 2.1: k_evt21_emit_words, the faster one (profiles/evt21.md); "XM_EVT21_EMIT_BY_WORD" = 0: k_evt21_emit
+  // EXT_TRIGGER extraction (xm_evt_set_ext_triggers, xm_api_exttrigger.hpp); max_triggers = 0: off, nothing below is allocated
+  size_t max_triggers = 0;
+  DevMem<u32> d_trig_counts;     // per block of the chunk, + the chunk's total behind them
+  DevMem<uint4> d_trig;          // the chunk's records (xm_ext_trigger)
+  PinnedMem<u32> h_trig_n;       // the chunk's total comes back here
+  PinnedMem<uint4> h_trig;       // records of the last successful decode
+  size_t n_trig = 0;
 };
 
 static_assert(sizeof(Evt2Scan) <= sizeof(Evt3Scan), "the decoders share the aggregates' buffer (d_agg)");
@@ -31,6 +38,11 @@ static_assert(sizeof(DatScan) <= sizeof(Evt3Scan), "the decoders share the aggre
 constexpr int EVT_FMT_21 = 21, EVT_FMT_DAT = 100;  // (xm_evt3::format beside 3 and 2)
 
 namespace {
+
+// xm_api_exttrigger.hpp: the two extraction launches behind the chunk's emit kernel (+ the copy of their total), and the
+// download of the records once the chunk is kept
+int evt_ext_enqueue(xm_evt3* d, u32 n, u32 nb, hipStream_t stream);
+int evt_ext_collect(xm_evt3* d, hipStream_t stream);
 
 const char* evt_format_name(int format) {
   return format == 3 ? "EVT 3.0 words" : format == 2 ? "EVT 2.0 words" : format == EVT_FMT_21 ? "EVT 2.1 words" : "DAT records";
@@ -96,17 +108,32 @@ int evt3_enqueue(xm_evt3* d, const void* words_host, size_t n_words, bool pinned
 }
 
 // the synchronous form: *n_events once the count is back (synchronises the stream)
-int evt3_run(xm_evt3* d, const void* words_host, size_t n_words, bool pinned, uint4* out, size_t out_cap, hipStream_t stream, size_t* n_events) {
+// ext: the chunk's EXT_TRIGGER records as well, when the decoder has them on (the synchronous decode entries; the ingest's does not)
+int evt3_run(xm_evt3* d, const void* words_host, size_t n_words, bool pinned, uint4* out, size_t out_cap, hipStream_t stream, size_t* n_events,
+             bool ext = false) {
   *n_events = 0;
-  if (!n_words) return XM_OK;
+  if (!n_words) {
+    if (ext) d->n_trig = 0;  // (an empty chunk holds no trigger)
+    return XM_OK;
+  }
   int rc = evt3_enqueue(d, words_host, n_words, pinned, out, out_cap, stream);
   if (rc) return rc;
+  ext = ext && d->max_triggers;
+  if (ext) {
+    rc = evt_ext_enqueue(d, (u32)n_words, (u32)grid_for(n_words, EVT_PER_BLOCK), stream);
+    if (rc) return rc;
+  }
   HIP_TRY(hipMemcpyAsync(d->h_state, d->d_state + (d->cur ^ 1), sizeof(Evt3State), hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipStreamSynchronize(stream));
   *n_events = (size_t)d->h_state->n_events;
   // Too many events for `out`: the decoder's state is NOT advanced (st_in is still current), so the caller can decode the same
   // chunk again into a larger buffer or in halves; the records written so far are a truncated prefix and must not be used.
   if (*n_events > out_cap) return fail(XM_ERR_TOO_MANY, "the chunk decodes to %zu events, room for %zu (decoder state unchanged: decode it again in smaller pieces)", *n_events, out_cap);
+  if (ext) {  // too many trigger words for the records' buffer: the same contract
+    if (*d->h_trig_n > d->max_triggers) return fail(XM_ERR_TOO_MANY, "the chunk holds %u trigger words, room for %zu (decoder state unchanged: decode it again in smaller pieces)", *d->h_trig_n, d->max_triggers);
+    rc = evt_ext_collect(d, stream);
+    if (rc) return rc;
+  }
   d->cur ^= 1;
   return XM_OK;
 }
@@ -178,6 +205,7 @@ int xm_evt3_reset(xm_evt3* d) {
   HIP_TRY(hipMemsetAsync(d->d_state, 0, 2 * sizeof(Evt3State), d->stream));  // (a memset on the default stream could be overtaken by the next chunk's kernels)
   HIP_TRY(hipStreamSynchronize(d->stream));
   d->cur = 0;
+  d->n_trig = 0;
   return XM_OK;
 }
 
@@ -186,7 +214,7 @@ static int evt_decode(xm_evt3* d, int format, const void* words_host, size_t n_w
   if (d->format != format) return fail(XM_ERR_INVALID, "this decoder was created for %s", evt_format_name(d->format));
   HIP_TRY(hipSetDevice(d->device));
   if (events_dev) *events_dev = d->d_out;
-  return evt3_run(d, words_host, n_words, false, d->d_out, d->max_events, d->stream, n_events);
+  return evt3_run(d, words_host, n_words, false, d->d_out, d->max_events, d->stream, n_events, true);
 }
 
 int xm_evt3_decode(xm_evt3* d, const uint16_t* words_host, size_t n_words, const void** events_dev, size_t* n_events) {

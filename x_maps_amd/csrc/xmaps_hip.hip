@@ -14,6 +14,7 @@
 #include "xmaps_evt2.hpp"           // EVT 2.0 decoder
 #include "xmaps_evt21.hpp"          // EVT 2.1 decoder
 #include "xmaps_dat.hpp"            // DAT (version 2, CD) decoder
+#include "xmaps_exttrigger.hpp"     // EXT_TRIGGER words -> trigger records behind the decoders' emit; the triggered frames' append
 #include "xmaps_surface.hpp"        // time surfaces -> depth maps + point clouds
 #include "xmaps_framesurface.hpp"   // frames of events -> camera time surfaces (the group entry and the ingest's surface stage)
 #include "xmaps_framecloud.hpp"     // frames of events -> per-event point clouds (the group entry and the ingest's cloud stage)
@@ -70,6 +71,7 @@ using namespace xm;
 #include "host/xm_api_filters.hpp"  // frame event filters, pause detection
 #include "host/xm_api_activity.hpp" // the activity filter alone; its device state (shared with the ingest)
 #include "host/xm_api_evt3.hpp"     // EVT 3.0 / 2.0 / 2.1 / DAT decoder on the device
+#include "host/xm_api_exttrigger.hpp"  // ... its EXT_TRIGGER records; frames cut at them (xm_trigger_cut.hpp: the rule, standard C++ only)
 #include "host/xm_ring_tag.hpp"     // the ingest's per-frame output rings: entry and tag arithmetic (standard C++ only)
 #include "host/xm_ingest_state.hpp" // device-side ingest: its state by owning thread, the jobs its threads hand each other
 #include "host/xm_ingest_out.hpp"   // ... the out side (result copies, sequence numbers) and the frame pool

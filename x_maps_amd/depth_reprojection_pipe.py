@@ -70,6 +70,11 @@ class DepthReprojectionPipe:
 
     def __post_init__(self):
         p = self.params
+        self._frame_sync = getattr(p, "frame_sync", "pauses")  # (checked before anything is made on the device)
+        if self._frame_sync not in ("pauses", "ext_trigger"):
+            raise ValueError('RuntimeParams.frame_sync must be "pauses" or "ext_trigger"')
+        if getattr(p, "ext_trigger_edge", "rising") not in ("rising", "falling", "both"):
+            raise ValueError('RuntimeParams.ext_trigger_edge must be "rising", "falling" or "both"')
         tables = getattr(p, "tables", None)
         if tables is None:
             if isinstance(p.calib, str) and p.calib.endswith(".npz"):
@@ -122,6 +127,12 @@ class DepthReprojectionPipe:
         self._cloud_callback = getattr(p, "cloud_callback", None)
         if self._cloud_callback is not None:  # (tables without the float rectify maps or Q: ValueError, here and not at the first frame)
             self.calib_maps.engine.set_frame_cloud_tables()
+        # frames cut at the recording's EXT_TRIGGER words instead of pauses (RuntimeParams.frame_sync; ext_trigger.py): a chain of its
+        # own behind process_*_words -- decoder with extraction on, TriggeredFrames, the group entries on the device buffer --
+        # made on first use; neither the ingest nor the host chain exists in this mode
+        self._trig, self._trig_dev, self._trig_bgr = None, {}, None
+        if self._frame_sync == "ext_trigger":
+            return
         if self.activity_filter is None and getattr(p, "activity_filter", True):
             _warn_activity_rule_unpinned()
         # a caller-supplied activity filter (Metavision's own, where the SDK is installed) runs on the host: so does the chain
@@ -259,7 +270,105 @@ class DepthReprojectionPipe:
         return (lambda w: np.ascontiguousarray(w, dtype=dt), lambda: cls(eng, max_words=1 << 20, wait_for_time_base=wait),
                 lambda: host(wait))
 
+    # ---- frame_sync = "ext_trigger": words -> trigger records + events -> frames cut at the triggers, all on the device ----
+    MIN_EVENTS_PER_FRAME = 1000  # the reference's (python/trigger_finder.py): frames of that many events or fewer are not shown
+
+    def _triggered_chain(self, fmt):
+        """-> (decoder of `fmt` with extraction on, the TriggeredFrames), made on first use"""
+        p = self.params
+        eng = self.calib_maps.engine
+        cap = int(getattr(p, "ext_trigger_cap_events", 1 << 22))
+        if self._trig is None:
+            from .ext_trigger import TriggeredFrames
+            self._trig = TriggeredFrames(eng, cap_events=cap, id=int(getattr(p, "ext_trigger_id", -1)),
+                                         edge=getattr(p, "ext_trigger_edge", "rising"), min_events=self.MIN_EVENTS_PER_FRAME,
+                                         positive_only=True)  # PolarityFilterAlgorithm(1), pipe:43,114
+        dev = self._trig_dev.get(fmt)
+        if dev is None:
+            from . import evt2, evt21, evt3
+            wait = bool(getattr(p, "raw_wait_for_time_base", False))
+            max_words = 1 << 20
+            # (a chunk never decodes to more events than the buffer holds: XM_ERR_TOO_MANY then leaves the decoder where it was)
+            per_word = {3: 2, 2: 1, 21: 4}[fmt]
+            kw = dict(max_words=max_words, max_events=min(per_word * max_words, cap), wait_for_time_base=wait)
+            if fmt == 21:
+                dev = evt21.DeviceEvt21Decoder(eng, legacy_halves=bool(getattr(p, "raw_legacy_halves", False)), **kw)
+            else:
+                dev = (evt2.DeviceEvt2Decoder if fmt == 2 else evt3.DeviceEvt3Decoder)(eng, **kw)
+            dev.set_ext_triggers(1 << 16)
+            self._trig_dev[fmt] = dev
+        return dev, self._trig
+
+    def _group_engine(self):
+        """the engine of process_ev_frames: the library's default flags and a slot per frame of a group"""
+        if getattr(self, "_replay_engine", None) is None:
+            from .engine import XMapsEngine
+            self._replay_engine = XMapsEngine(self.calib_maps.tables, camera_perspective=self.params.camera_perspective,
+                                              device=getattr(self.params, "device", 0), n_slots=self.replay_group)
+        return self._replay_engine
+
+    def _deliver_triggered_frames(self):
+        """Every ready frame, in runs of at most replay_group: surfaces, clouds and the frames' launches on the device buffer, one
+        xm_sync, then per frame surface_callback, cloud_callback, frame_callback; the run is released behind its last callback."""
+        tf = self._trig
+        while True:
+            ptr, offs, _ = tf.ready(self.replay_group)
+            n = len(offs) - 1
+            if n == 0:
+                return
+            if not self.fused or not isinstance(self.ev_filter_proc.selected_filter(), NoFilter):
+                frames = tf.download(ptr, offs)  # (the frame event filters re-order a frame's events on the host: pipe:131-139)
+                tf.release(n)
+                for evs in frames:
+                    self.stats_printer.count("trig ✅")
+                    self.process_ev_frame(evs)
+                continue
+            eng = self._group_engine()
+            px = eng.out_h * eng.out_w * 3
+            if self._trig_bgr is None:
+                self._trig_bgr = eng.dev_alloc(self.replay_group * px)
+            surfs = clouds = None
+            with self.stats_printer.measure_time("x-maps frames (fused, groups)"):
+                if self._surface_callback is not None:
+                    surfs, _ = eng.frames_to_time_surfaces_device(ptr, offs, *self._surface_kind)
+                if self._cloud_callback is not None:
+                    clouds = eng.frames_to_point_clouds_device(ptr, offs)
+                eng.process_events_batch_device(ptr, offs, None, self._trig_bgr)
+                eng.sync()  # (also redoes frames whose verified shortcut failed)
+                bgr = np.empty((n, eng.out_h, eng.out_w, 3), np.uint8)
+                eng.dev_download(bgr, self._trig_bgr)
+            for f in range(n):
+                self.stats_printer.count("trig ✅")
+                if surfs is not None:
+                    self._surface_callback(surfs[f])
+                if clouds is not None:
+                    self._cloud_callback(clouds[f][0][:int(getattr(self.params, "cloud_max_points", 262144))])
+                self.frame_callback(bgr[f])
+            tf.release(n)
+
+    def _process_raw_words_triggered(self, words, fmt):
+        if fmt == "dat":
+            raise ValueError('frame_sync="ext_trigger": CD DAT records carry no trigger words')
+        dev, tf = self._triggered_chain(fmt)
+        from ._native import XMapsTooMany
+        w = dev._as_words(words)
+
+        def push(piece):
+            try:
+                tf.push(dev, piece)
+            except XMapsTooMany:  # (more events or trigger words than a chunk's buffers hold; nothing has advanced)
+                if len(piece) < 2:
+                    raise
+                push(piece[:len(piece) // 2])
+                push(piece[len(piece) // 2:])
+                return
+            self._deliver_triggered_frames()
+        for a in range(0, len(w), dev.max_words):
+            push(w[a:a + dev.max_words])
+
     def _process_raw_words(self, words, fmt):
+        if self._frame_sync == "ext_trigger":
+            return self._process_raw_words_triggered(words, fmt)
         as_words, make_dev, make_host = self._raw_format(fmt)
         if self._use_ingest():
             dev = self._raw_dev.get(fmt)
@@ -293,6 +402,8 @@ class DepthReprojectionPipe:
             self.process_events(evs)
 
     def process_events(self, evs):
+        if self._frame_sync == "ext_trigger":
+            raise ValueError('frame_sync="ext_trigger": EventCD packets carry no trigger words (process_evt3_words / _evt2_words / _evt21_words do)')
         if self._use_ingest():
             # asynchronous: the frames this packet cuts are delivered by a later call -- at the latest by reset() / close()
             try:
@@ -340,14 +451,10 @@ class DepthReprojectionPipe:
             for evs in frames:
                 self.process_ev_frame(evs)
             return
-        if getattr(self, "_replay_engine", None) is None:
-            # an engine of its own with the library's default flags (verified shortcut with automatic redo: the mode in which
-            # groups take the column tiles) and enough slots for a group; the per-frame engine declares its frames sorted
-            from .engine import XMapsEngine
-            self._replay_engine = XMapsEngine(self.calib_maps.tables, camera_perspective=self.params.camera_perspective,
-                                              device=getattr(self.params, "device", 0), n_slots=self.replay_group)
+        # an engine of its own with the library's default flags (verified shortcut with automatic redo: the mode in which
+        # groups take the column tiles) and enough slots for a group; the per-frame engine declares its frames sorted
         with self.stats_printer.measure_time("x-maps frames (fused, groups)"):
-            outs = self._replay_engine.process_event_frames(list(frames), want_depth=False)
+            outs = self._group_engine().process_event_frames(list(frames), want_depth=False)
         for _, bgr in outs:
             self.frame_callback(bgr)
 
@@ -385,6 +492,10 @@ class DepthReprojectionPipe:
         # deliver them before the stream starts over
         self.flush()
         self.trigger_finder.reset()
+        if self._trig is not None:  # (frame_sync = "ext_trigger": the open frame is not a frame; the decoders start a stream)
+            self._trig.reset()
+            for dev in self._trig_dev.values():
+                dev.reset()
         if self.ingest is not None:
             self.ingest.reset()  # (buffered events and the activity filter's history: the stream starts over)
         if self._own_act_filter is not None:
@@ -403,7 +514,16 @@ class DepthReprojectionPipe:
         try:
             self.flush()  # (before the decoders, the ingest and its result ring go: views are delivered while they are valid)
         finally:
+            if getattr(self, "_trig", None) is not None:
+                self._trig.close()
+                self._trig = None
+            for dev in getattr(self, "_trig_dev", {}).values():
+                dev.close()
+            self._trig_dev = {}
             if getattr(self, "_replay_engine", None) is not None:
+                if getattr(self, "_trig_bgr", None):
+                    self._replay_engine.dev_free(self._trig_bgr)
+                    self._trig_bgr = None
                 self._replay_engine.close()
                 self._replay_engine = None
             for dev in getattr(self, "_raw_dev", {}).values():  # (before the engine they belong to)

@@ -99,6 +99,22 @@ class RuntimeParams:
     # either way.  Needs tables with cam_mapx_f32, cam_mapy_f32 and Q (ValueError at construction otherwise).
     cloud_callback: Optional[Callable] = None
     cloud_max_points: int = 262144
+    # How the stream is cut into projector frames.  "pauses" (the default; nothing changes): the reference's software trigger finder,
+    # on the device ingest or the host chain.  "ext_trigger": at the recording's EXT_TRIGGER words -- the pulses of the camera's
+    # sync jack, for rigs whose projector is wired to it (the paper's section 3.4; x_maps_amd/ext_trigger.py).  Only
+    # process_evt3_words / _evt2_words / _evt21_words carry those words: process_events and process_dat_records raise ValueError
+    # in this mode.  Frame k = the positive events (PolarityFilterAlgorithm(1)) between the k-th and the next selected trigger,
+    # nothing trimmed; frames of MIN_EVENTS_PER_FRAME = 1000 events or fewer are skipped, as the reference's trigger finder skips
+    # them.  THE ACTIVITY FILTER IS NOT PART OF THIS CHAIN (activity_filter is ignored).  DELIVERY is synchronous, as in the
+    # reference: a frame reaches frame_callback (its surface_callback and cloud_callback in front) inside the call whose words hold
+    # its closing trigger.  While a frame event filter (key E) is selected every frame is downloaded and goes through
+    # process_ev_frame.  ext_trigger_id: the trigger channel (-1: any); ext_trigger_edge: "rising", "falling" or "both";
+    # ext_trigger_cap_events: the device buffer the frames are cut from, in events -- an open frame that cannot keep its events
+    # plus one more chunk's inside it is dropped (counted; cutting resumes at the next trigger).
+    frame_sync: str = "pauses"
+    ext_trigger_id: int = -1
+    ext_trigger_edge: str = "rising"
+    ext_trigger_cap_events: int = 1 << 22
 
     @property
     def should_drop_frames(self):

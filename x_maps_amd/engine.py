@@ -621,6 +621,62 @@ class XMapsEngine:
                                                     N.XM_MEM_HOST, _ptr(cloud), C.cast(st, C.c_void_p)))
         return [(cloud[int(a):int(a) + int(s.n_inliers)].copy(), FrameCloudStats.from_c(s)) for a, s in zip(offsets[:-1], st)]
 
+    # ---- the same two entries on frames that are in device memory already (ext_trigger.TriggeredFrames) ----------
+    def frames_to_time_surfaces_device(self, aos_ptr, offsets, select="last", dtype=np.float32, use_polarity=False):
+        """frames [offsets[f], offsets[f + 1]) of device-resident EventCD records -> (surfaces, [FrameSurfaceStats]) on the host:
+        xm_frames_to_time_surfaces with XM_MEM_DEVICE, waited for and downloaded.  Same results as frames_to_time_surfaces."""
+        sel = {"last": N.XM_SURFACE_LAST, "first": N.XM_SURFACE_FIRST}.get(select)
+        if sel is None:
+            raise ValueError('select must be "last" or "first"')
+        dt = np.dtype(dtype)
+        if dt not in _T_DTYPES or dt == np.int64:
+            raise ValueError("dtype must be float32 or float64")
+        offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offs) - 1
+        if n <= 0:
+            raise ValueError("no frames")
+        out = np.empty((n, self.cam_h, self.cam_w), dt)
+        st = (N.xm_frame_surface_stats * n)()
+        d_out, d_st = self.dev_alloc(out.nbytes), self.dev_alloc(C.sizeof(st))
+        try:
+            N.check(self._lib.xm_frames_to_time_surfaces(self._h, _ptr(aos_ptr), offs.ctypes.data_as(C.POINTER(C.c_uint64)), n,
+                                                         int(bool(use_polarity)), sel, _T_DTYPES[dt], N.XM_MEM_DEVICE, _ptr(d_out), _ptr(d_st)))
+            self.sync()
+            self.dev_download(out, d_out)
+            N.check(self._lib.xm_dev_download(self._h, C.cast(st, C.c_void_p), _ptr(d_st), C.sizeof(st)))
+        finally:
+            self.dev_free(d_out)
+            self.dev_free(d_st)
+        return out, [FrameSurfaceStats.from_c(s) for s in st]
+
+    def frames_to_point_clouds_device(self, aos_ptr, offsets, use_polarity=False):
+        """frames of device-resident EventCD records -> [(cloud, FrameCloudStats)] on the host: xm_frames_to_point_clouds with
+        XM_MEM_DEVICE, waited for and downloaded.  Same results as frames_to_point_clouds."""
+        if not self._has_frame_cloud_tables:
+            self.set_frame_cloud_tables()
+        offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offs) - 1
+        if n <= 0:
+            raise ValueError("no frames")
+        rows = max(int(offs[-1] - offs[0]), 1)
+        st = (N.xm_frame_cloud_stats * n)()
+        d_cloud, d_st = self.dev_alloc(rows * 12), self.dev_alloc(C.sizeof(st))
+        try:
+            N.check(self._lib.xm_frames_to_point_clouds(self._h, _ptr(aos_ptr), offs.ctypes.data_as(C.POINTER(C.c_uint64)), n,
+                                                        int(bool(use_polarity)), N.XM_MEM_DEVICE, _ptr(d_cloud), _ptr(d_st)))
+            self.sync()
+            N.check(self._lib.xm_dev_download(self._h, C.cast(st, C.c_void_p), _ptr(d_st), C.sizeof(st)))
+            out = []
+            for a, s in zip(offs[:-1], st):
+                cloud = np.empty((int(s.n_inliers), 3), np.float32)
+                if len(cloud):
+                    self.dev_download(cloud, d_cloud + 12 * int(a - offs[0]))
+                out.append((cloud, FrameCloudStats.from_c(s)))
+        finally:
+            self.dev_free(d_cloud)
+            self.dev_free(d_st)
+        return out
+
     # ---- N3: per-frame de-duplication filters ------------------------------------------------------------
     def frame_event_filter(self, filter_id: int, evs: np.ndarray, xp_i16=None, map_shape=None,
                            intended_semantics: bool = False) -> np.ndarray:

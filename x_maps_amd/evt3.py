@@ -25,6 +25,9 @@ from .synthetic import EVENT_CD_DTYPE
 
 T_ADDR_Y, T_ADDR_X, T_VECT_BASE_X, T_VECT_12, T_VECT_8, T_TIME_LOW, T_TIME_HIGH = 0x0, 0x2, 0x3, 0x4, 0x5, 0x6, 0x8
 _FORMAT_NAMES = ("3.0", "3", "EVT3", "EVT3.0")
+# one EXT_TRIGGER word as a record (include/xmaps.h: xm_ext_trigger; ext_trigger.py)
+EXT_TRIGGER_DTYPE = np.dtype({"names": ["t", "event_index", "id", "value", "reserved"], "formats": ["<i8", "<u4", "u1", "u1", "<u2"],
+                              "offsets": [0, 8, 12, 13, 14], "itemsize": 16})
 
 
 def split_raw_header(blob: bytes) -> tuple[dict, int]:
@@ -199,6 +202,20 @@ class DeviceEvtDecoder:
 
     def _as_words(self, words) -> np.ndarray:
         return np.ascontiguousarray(words, dtype=self._dtype)
+
+    def set_ext_triggers(self, max_triggers: int):
+        """EXT_TRIGGER words -> trigger records beside the events (xm_evt_set_ext_triggers; ext_trigger.py): max_triggers = room for
+        one chunk's records, 0 = off (the default).  From the next chunk on; decode / decode_device only, push ignores it."""
+        self._N.check(self._lib.xm_evt_set_ext_triggers(self._d, int(max_triggers)))
+        self._max_triggers = int(max_triggers)
+
+    def last_ext_triggers(self) -> np.ndarray:
+        """the trigger records of the last decode_device (fields t, event_index, id, value); empty when extraction is off"""
+        C = self._C
+        out = np.zeros(getattr(self, "_max_triggers", 0), EXT_TRIGGER_DTYPE)
+        n = C.c_size_t(0)
+        self._N.check(self._lib.xm_evt_last_ext_triggers(self._d, C.c_void_p(out.ctypes.data), len(out), C.byref(n)))
+        return out[:int(n.value)]
 
     def decode_device(self, words: np.ndarray):
         C = self._C
