@@ -863,6 +863,50 @@ int xm_trigframes_ready(xm_trigframes* tf, const void** events_dev, uint64_t* of
 int xm_trigframes_release(xm_trigframes* tf, int n_frames);
 int xm_trigframes_stats(xm_trigframes* tf, xm_trigframes_counters* out);
 
+/* THE TWO FILTERS of the triggered chain (x_maps_amd/csrc/xmaps_trigfilter.hpp), what the reference's pipe does to every packet in
+ * front of the cut and to every cut frame (python/depth_reprojection_pipe.py:110-119, :130-139).  Both are off by default; with
+ * both off xm_trigframes_push and xm_trigframes_ready do exactly what is said above.
+ * STAGE 1, the activity filter, inside xm_trigframes_push (in place of the two append launches: the first pass over the chunk,
+ * the sequential judge, count, write -- four launches):
+ *  - A record of the chunk is KEPT iff p == 1, it lies on the sensor (x < cam_width, y < cam_height) and the rule keeps it: some
+ *    positive on-sensor record EARLIER IN THE STREAM at one of the 8 neighbouring pixels (self_counts != 0: or at its own) has
+ *    t - t' <= thresh_us.  This build's definition, the ingest's (oracle/ingest_oracle.py); unpinned against Metavision.
+ *  - Every positive on-sensor record joins its pixel's history, kept or not.  A record off the sensor is not kept and joins none.
+ *  - The history lives in device memory between pushes: the result does not depend on how the stream is cut into chunks.
+ *    xm_trigframes_reset empties it; switching the stage on starts from an empty one.
+ *  - A chunk whose stamps run backwards by more than a bucket of thresh_us + 1 us, or that spans more than 8 such buckets, is
+ *    judged sequentially by one block (exact, slow: ~20 ms per million records): chunks_sequential.
+ *  - Everything behind it sees the filtered stream: the trigger remap ("kept records with chunk index < event_index", kept = both
+ *    filters), xm_trigframes_counters.events_kept, min_events and every other line of the cut rule.  The room rule still uses the
+ *    chunk's count before any filter.
+ * STAGE 2, the frame event filters (the reference's key E), on the run of ready frames xm_trigframes_ready_filtered hands out:
+ *  - Per frame, xm_ingest_set_frame_filter's semantics: one record per cell that fired, in raster order of the cells, cells (y, x)
+ *    or -- XM_FILTER_FIRST_PER_YT -- (y, xr) on a map as wide as the frame's own max(xr) + 1 with NumPy's negative-index wrap.
+ *  - An event whose cell lies outside the map is left out and counted in the frame's n_index_errors.
+ *  - The survivors of the run's frames lie back to back in a buffer of the stage's own; the buffer of records is untouched (the
+ *    unfiltered run stays available through xm_trigframes_ready until it is released).
+ *  - Four launches for the whole run (three without the wrap), one copy of the per-frame totals back. */
+/* thresh_us < 0: off (default).  Otherwise the ingest's activity rule (this build's definition, xmaps_ingest.hpp /
+ * oracle/ingest_oracle.py) on the POSITIVE events of the stream, in stream order, across chunks; requires positive_only
+ * (XM_ERR_INVALID otherwise; thresh_us must lie in [0, 2^31 - 2)).  Ordered like a push: takes effect with the next chunk;
+ * switching it on starts from an empty history. */
+int xm_trigframes_set_activity(xm_trigframes* tf, int64_t thresh_us, int self_counts);
+typedef struct xm_trigframes_filter_counters {
+  uint64_t events_positive, events_active, chunks_sequential;        /* stage 1: p == 1 records judged, records kept, see above */
+  uint64_t frames_filtered, events_after_frame_filter, index_errors; /* stage 2 */
+} xm_trigframes_filter_counters;
+int xm_trigframes_filter_stats(xm_trigframes* tf, xm_trigframes_filter_counters* out);
+/* filter: 0 (none, default) or XM_FILTER_*, both values of intended_semantics, with xm_ingest_set_frame_filter's cells, wrap rule,
+ * XM_INGEST_YT_MAX_CELLS limit and XM_ERR_INVALID cases (nothing changes then).  max_frames (1 .. 4096): the longest run one call
+ * filters (scratch: two u32 maps of max_frames x cells, a survivors buffer; allocated here). */
+int xm_trigframes_set_frame_filter(xm_trigframes* tf, int filter, int intended_semantics, int max_frames);
+/* xm_trigframes_ready's run (also capped by max_frames), each frame replaced by what the selected filter hands on: *events_dev =
+ * the survivors buffer, offsets_host[0] = 0, frame f = [offsets_host[f], offsets_host[f+1]) in raster order of its cells;
+ * n_index_errors[f] (nullable) = events of frame f whose cell lies outside the map.  filter 0: exactly xm_trigframes_ready.
+ * Synchronous (one copy of the per-frame totals back).  Valid until the next push / release / reset / ready*. */
+int xm_trigframes_ready_filtered(xm_trigframes* tf, const void** events_dev, uint64_t* offsets_host, int cap_frames, int* n_frames,
+                                 xm_ext_trigger* opening /* nullable */, uint64_t* n_index_errors /* nullable */);
+
 /* ---- time surfaces in, depth maps and point clouds out ("next" row N4) --------------------------------------------------
  * The reference's offline evaluation (python/eval/compute_depth_x_maps.py:79-131) for a GROUP of camera time surfaces in one
  * device call: each surface is [cam_height][cam_width] row-major, XM_T_FLOAT32 or XM_T_FLOAT64, 0 = no event.  Per surface:

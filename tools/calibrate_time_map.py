@@ -42,7 +42,8 @@ def _corners(text):
 
 
 def calibrate(recording, calib, out_dir, camera=(640, 480), projector=(1080, 1920), fps=60, min_share=0.5, corners=None, corner_order=0,
-              chunk_words=1 << 20, device=0, activity_filter=True, group=16, frame_sync="pauses", trigger_id=-1, trigger_edge="rising"):
+              chunk_words=1 << 20, device=0, activity_filter=True, group=16, frame_sync="pauses", trigger_id=-1, trigger_edge="rising",
+              trigger_activity_filter=False):
     from run_esl_on_arrival import raw_format
     from x_maps_amd import calibration as C
     from x_maps_amd import dat, evt2, evt21, evt3
@@ -78,7 +79,8 @@ def calibrate(recording, calib, out_dir, camera=(640, 480), projector=(1080, 192
                                camera_perspective=False, tables=tables, device=device, device_ingest=True, activity_filter=activity_filter,
                                surface_callback=surface_cb, surface_select="first", surface_dtype=np.float64,
                                raw_legacy_halves=fmt == 21 and evt21.raw_legacy_halves(recording), frame_sync=frame_sync,
-                               ext_trigger_id=trigger_id, ext_trigger_edge=trigger_edge)  # ("ext_trigger": a frame per trigger-to-trigger span)
+                               ext_trigger_id=trigger_id, ext_trigger_edge=trigger_edge,  # ("ext_trigger": a frame per trigger-to-trigger span)
+                               ext_trigger_activity_filter=bool(trigger_activity_filter))
         with DepthReprojectionProcessor(params, window=Window()) as proc:
             push = {3: proc.process_evt3_words, 2: proc.process_evt2_words, 21: proc.process_evt21_words, "dat": proc.process_dat_records}[fmt]
             for words in mod.read_raw_words(recording, chunk_words=chunk_words):
@@ -120,10 +122,12 @@ def main(argv=None):
                     help="cut the white frames at pauses (the trigger finder) or at the recording's EXT_TRIGGER words (sync jack wired)")
     ap.add_argument("--trigger-id", type=int, default=-1, help="--frame-sync ext-trigger: the trigger channel (-1: any)")
     ap.add_argument("--trigger-edge", choices=("rising", "falling", "both"), default="rising")
+    ap.add_argument("--trigger-activity-filter", action="store_true",
+                    help="--frame-sync ext-trigger: the activity filter in front of the cut, so that noise is not averaged into the map (off by default)")
     a = ap.parse_args(argv)
     rep = calibrate(a.recording, a.calib, a.out, a.camera, a.projector, a.fps, a.min_share, a.corners, a.corner_order, a.chunk_words,
                     a.device, not a.no_activity_filter, frame_sync=a.frame_sync.replace("-", "_"), trigger_id=a.trigger_id,
-                    trigger_edge=a.trigger_edge)
+                    trigger_edge=a.trigger_edge, trigger_activity_filter=a.trigger_activity_filter)
     print(json.dumps(rep))
     return rep
 

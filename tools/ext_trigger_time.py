@@ -15,7 +15,10 @@ time limit, and no further step is started after one that failed or ran out of t
   chain    the ESL-like stream (rig.render_stream, as benchmodes/esl.py renders it) with a trigger per frame as EVT 3.0 words in
            period chunks through DepthReprojectionPipe with frame_sync = "ext_trigger", beside the device ingest's pause finder
            on the same stream without the trigger words: frames/s and ms per frame, whole passes.
-  kernels  the two extraction launches and the append under rocprofv3 --kernel-trace --stats (a child of its own)."""
+  kernels  the two extraction launches and the append under rocprofv3 --kernel-trace --stats (a child of its own).
+With --filters-md FILE the tool measures the chain's two filters instead (profiles/ext_trigger_filters.md): xm_trigframes_push with
+both stages off beside three runs of --parent-lib, the activity stage on minus off and its kernels beside the ingest's, the frame
+event filters' device stage against the download path per shown frame, and one pass at the reference's threshold."""
 from __future__ import annotations
 
 import argparse
@@ -238,6 +241,240 @@ def step_kernels(a):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+# ---- the chain's two filters (--filters-md): xm_trigframes_set_activity / xm_trigframes_set_frame_filter ---------------------------
+FILTER_SYMBOLS = ("xm_trigframes_set_activity", "xm_trigframes_filter_stats", "xm_trigframes_set_frame_filter", "xm_trigframes_ready_filtered")
+ACT_T = int(1e6 / 60)  # the reference's threshold at 60 Hz
+
+
+def step_push(repeats, device, off_only=False):
+    """xm_trigframes_push over the chain stream's period chunks, whole passes (reset, every chunk), the median of `repeats` passes
+    after two: both stages off (what the parent's build can run; this build: off_only, the same process shape as the parent's runs)
+    or, on this build, alternating with the activity stage on"""
+    F.gpu()
+    from x_maps_amd import _native as N
+    parent = bool(os.environ.get("XM_LIB"))
+    off_only = off_only or parent
+    if parent:
+        for name in FILTER_SYMBOLS:
+            N.SYMBOLS.pop(name, None)
+    from x_maps_amd import XMapsEngine, evt3
+    from x_maps_amd import ext_trigger as X
+    tables, stream, _, chunks = _chain_stream(device)
+    res = {"events": int(len(stream)), "chunks": len(chunks)}
+    with XMapsEngine(tables, device=device) as eng, evt3.DeviceEvt3Decoder(eng, max_words=max(len(c) for c in chunks)) as dec:
+        dec.set_ext_triggers(4096)
+        with X.TriggeredFrames(eng, cap_events=1 << 22, min_events=1000, positive_only=True) as tf:
+            def one_pass():
+                dec.reset(), tf.reset()
+                c0 = time.perf_counter()
+                for w in chunks:
+                    tf.push(dec, w)
+                    tf.release(len(tf.ready(64)[1]) - 1)
+                return time.perf_counter() - c0
+            modes = ["off"] if off_only else ["off", "activity"]
+            times = {m: [] for m in modes}
+            for k in range((repeats + 2) * len(modes)):  # alternating, in one process; the first two rounds are warm-up
+                m = modes[k % len(modes)]
+                if not off_only:
+                    tf.set_activity(ACT_T if m == "activity" else None)
+                dt = one_pass()
+                if k >= 2 * len(modes):
+                    times[m].append(dt)
+            for m, v in times.items():
+                res[m] = {"ms_per_chunk": round(float(np.median(v)) * 1e3 / len(chunks), 4), "ms_per_pass_median": round(float(np.median(v)) * 1e3, 3),
+                          "ms_per_pass_min_max": [round(min(v) * 1e3, 3), round(max(v) * 1e3, 3)]}
+            if not off_only:  # one pass at the reference's T on the period chunks, counted on its own
+                tf.set_activity(None), tf.set_activity(ACT_T)
+                before = tf.filter_stats()
+                one_pass()
+                after, st = tf.filter_stats(), tf.stats()
+                res["one_pass_at_T"] = {"thresh_us": ACT_T, "chunks_sequential": after["chunks_sequential"] - before["chunks_sequential"],
+                                        "events_positive": after["events_positive"] - before["events_positive"],
+                                        "events_active": after["events_active"] - before["events_active"], "frames_cut_total": st["frames_cut"]}
+    print(TAG + json.dumps(res), flush=True)
+
+
+def step_frame_filters(passes, device):
+    """the chain per shown frame with a frame event filter selected: device stage against download path, alternating passes"""
+    F.gpu()
+    from x_maps_amd.depth_reprojection_processor import DepthReprojectionProcessor, RuntimeParams
+    tables, stream, _, chunks = _chain_stream(device)
+    res = {"events": int(len(stream)), "chunks": len(chunks)}
+
+    class Window:
+        n = 0
+
+        def should_close(self):
+            return False
+
+        def show_async(self, img):
+            Window.n += 1
+
+    for label, presses in (("LastEventPerXY", 3), ("FirstEventPerYT", 1)):
+        procs = {}
+        for mode in ("download", "device"):
+            params = RuntimeParams(camera_width=640, camera_height=480, projector_width=1080, projector_height=1920, projector_fps=60, z_near=0.1,
+                                   z_far=1.2, calib=None, tables=tables, device=device, frame_sync="ext_trigger", device_frame_filters=mode == "device")
+            procs[mode] = DepthReprojectionProcessor(params, window=Window()).__enter__()
+            for _ in range(presses):
+                procs[mode]._pipe.select_next_frame_event_filter()
+        assert type(procs["device"]._pipe.ev_filter_proc.selected_filter()).__name__.startswith(label)
+
+        def one_pass(proc):
+            Window.n = 0
+            c0 = time.perf_counter()
+            for w in chunks:
+                proc.process_evt3_words(w)
+            dt = time.perf_counter() - c0
+            proc._pipe.reset()
+            return dt, Window.n
+        times = {m: [] for m in procs}
+        shown = None
+        for k in range((passes + 2) * 2):
+            m = ("download", "device")[k % 2]
+            dt, n = one_pass(procs[m])
+            shown = n if shown is None else shown
+            assert n == shown, "the two paths showed different numbers of frames"
+            if k >= 4:
+                times[m].append(dt)
+        res[label] = {"frames_shown": shown, "filter_stats": procs["device"]._pipe._trig.filter_stats()}
+        for m, v in times.items():
+            res[label][m] = {"ms_per_frame": round(float(np.median(v)) * 1e3 / max(shown, 1), 4), "passes_ms": [round(x * 1e3, 2) for x in v]}
+        for p in procs.values():
+            p.__exit__(None, None, None)
+    print(TAG + json.dumps(res), flush=True)
+
+
+def step_filter_kernels_child(device, which):
+    """what the two kernel traces look at: pushes with the activity stage on (`trig`), or the same chunks' positive events as packets
+    through the activity filter alone, the ingest's kernels (`alone`)"""
+    F.gpu()
+    from x_maps_amd import XMapsEngine, evt3
+    from x_maps_amd import ext_trigger as X
+    tables, stream, _, chunks = _chain_stream(device)
+    with XMapsEngine(tables, device=device) as eng:
+        if which == "trig":
+            with evt3.DeviceEvt3Decoder(eng, max_words=max(len(c) for c in chunks)) as dec:
+                dec.set_ext_triggers(4096)
+                with X.TriggeredFrames(eng, cap_events=1 << 22, positive_only=True, activity_thresh_us=ACT_T) as tf:
+                    for _ in range(3):
+                        dec.reset(), tf.reset()
+                        for w in chunks:
+                            tf.push(dec, w)
+                            tf.release(len(tf.ready(64)[1]) - 1)
+        else:
+            from x_maps_amd.activity_filter import ActivityNoiseFilterAlgorithm
+            ext = X.ExtTriggerExtractor(3)
+            packets = [ext.extract(w)[0] for w in chunks]
+            packets = [p[p["p"] == 1] for p in packets]
+            flt = ActivityNoiseFilterAlgorithm(eng, ACT_T)
+            for _ in range(3):
+                flt.reset()
+                for p in packets:
+                    flt.process_events(p)
+    print(TAG + json.dumps({"events": int(len(stream)), "chunks": len(chunks)}), flush=True)
+
+
+def step_filter_kernels(a, which):
+    prof = shutil.which("rocprofv3")
+    if prof is None:
+        return {"error": "rocprofv3 not found"}
+    tmp = tempfile.mkdtemp(prefix="trigflt_")
+    try:
+        cmd = [prof, "--kernel-trace", "--stats", "-d", tmp, "-o", "trig", "--", sys.executable, os.path.abspath(__file__), "--step", "filter_kernels_" + which,
+               "--device", str(a.device)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=a.step_timeout)
+        line = [ln for ln in r.stdout.splitlines() if ln.startswith(TAG)]
+        if r.returncode != 0 or not line:
+            return {"error": f"exit status {r.returncode}", "stderr_tail": r.stderr[-1500:]}
+        rows = {}
+        for db in glob.glob(os.path.join(tmp, "**", "*.db"), recursive=True):
+            c = sqlite3.connect(db)
+            for name, d in c.execute("select name, end - start from kernels"):
+                short = name.split("(")[0].replace("void ", "").replace("xm::", "")
+                if short.startswith(("k_act_", "k_trigact_", "k_trig_keep")):
+                    rows.setdefault(short, []).append(d)
+        rows = {k: {"calls": len(v), "avg_us": round(sum(v) / len(v) / 1e3, 2), "min_us": round(min(v) / 1e3, 2), "max_us": round(max(v) / 1e3, 2)}
+                for k, v in sorted(rows.items())}
+        return rows or {"error": "no kernel rows in the trace"}
+    except (subprocess.TimeoutExpired, sqlite3.Error) as e:
+        return {"error": repr(e)}
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
+def filters_markdown(r, notes="") -> str:
+    parents = [r[k] for k in ("parent_1", "parent_2", "parent_3") if k in r and "error" not in r[k]]
+    p, pa = r["push"], [q["off"]["ms_per_chunk"] for q in parents]
+    offs = [r[k] for k in ("off_1", "off_2", "off_3") if k in r and "error" not in r[k]]
+    mine = float(np.median([q["off"]["ms_per_chunk"] for q in offs]))
+    inside = ("inside" if min(pa) <= mine <= max(pa) else
+              f"OUTSIDE ({mine / (sum(pa) / len(pa)):.3f} of the parent's mean)") if pa else "not measured (no --parent-lib)"
+    one = p["one_pass_at_T"]
+    ff = r["frame_filters"]
+    ff_rows = "\n".join(f"| {k} | {v['frames_shown']} | {v['download']['ms_per_frame']} | {v['device']['ms_per_frame']} | "
+                        f"{v['device']['ms_per_frame'] / v['download']['ms_per_frame']:.3f} | {v['download']['passes_ms']} | {v['device']['passes_ms']} |"
+                        for k, v in ff.items() if isinstance(v, dict))
+
+    def ktable(k):
+        if "error" in k:
+            return f"Not measured in this run: {k['error']}."
+        return "| kernel | calls | avg us | min us | max us |\n|---|---|---|---|---|\n" + "\n".join(
+            f"| `{n}` | {v['calls']} | {v['avg_us']} | {v['min_us']} | {v['max_us']} |" for n, v in k.items())
+    return f"""# The triggered chain's two filters: times
+
+Written by `tools/ext_trigger_time.py --filters-md` on an MI355X.  **No real triggered recording exists beside this project: the
+stream is rendered** -- the ESL-like stream of `profiles/ext_trigger.md` ({p['events']} events, {CHAIN_FRAMES} frames, a trigger 100 us in
+front of every frame) as EVT 3.0 words in {p['chunks']} period chunks.  Every step in a process of its own, all in one call.
+Clock state of the box, queried idle before the first launch: {r['clock_state']}.
+
+## 1. Stages off against the parent commit's library
+
+`xm_trigframes_push` (+ ready / release) over the chunks, whole passes, the median of {r['repeats']} passes after two.  The parent's
+build three times (three processes): its own spread is the margin.  This build with both stages off three times too, in processes of
+the same shape, the two builds taking turns (parent, this, parent, this, ...): a box's rate drifts from process to process by more
+than the two builds differ.  Compared: the median of this build's three runs.
+
+| build | ms / chunk | ms / pass (median) | pass min .. max, ms |
+|---|---|---|---|
+{chr(10).join(f"| parent, run {i + 1} | {q['off']['ms_per_chunk']} | {q['off']['ms_per_pass_median']} | {q['off']['ms_per_pass_min_max']} |" for i, q in enumerate(parents))}
+{chr(10).join(f"| this build, both stages off, run {i + 1} | {q['off']['ms_per_chunk']} | {q['off']['ms_per_pass_median']} | {q['off']['ms_per_pass_min_max']} |" for i, q in enumerate(offs))}
+
+In the order they ran: {", ".join(f"{k} {r[k]['off']['ms_per_chunk']}" for k in ("parent_1", "off_1", "parent_2", "off_2", "parent_3", "off_3") if k in r and "error" not in r[k])}.
+This build (median {mine:.4f} ms / chunk) lies **{inside}** the parent's spread{f" ({min(pa)} .. {max(pa)} ms / chunk)" if pa else ""}.
+
+## 2. The activity stage on minus off
+
+The same passes alternating off / on (T = {ACT_T} us) in one process: off {p['off']['ms_per_chunk']} ms / chunk, on
+{p['activity']['ms_per_chunk']} ms / chunk: **{p['activity']['ms_per_chunk'] - p['off']['ms_per_chunk']:+.4f} ms per chunk**
+({p['activity']['ms_per_chunk'] / p['off']['ms_per_chunk']:.3f} x).
+
+The stage's kernels, `rocprofv3 --kernel-trace --stats` of three passes in a process of its own:
+
+{ktable(r['kernels_trig'])}
+
+Beside them the ingest's activity kernels (`xm_activity_process`: `k_act_first`, `k_act_mark`, `k_act_update`) on the same chunks'
+positive events, a trace of its own:
+
+{ktable(r['kernels_alone'])}
+
+## 3. Frame event filter: device stage against download path
+
+The chain through `DepthReprojectionPipe` with the filter selected, ms per shown frame, the median of {r['passes']} whole passes
+after two, the two paths alternating in one process.  Reported, not gated: the stream stays on the device either way.
+
+| filter | frames shown | download path, ms / frame | device stage, ms / frame | device / download | download passes, ms | device passes, ms |
+|---|---|---|---|---|---|---|
+{ff_rows}
+
+## 4. One pass at the reference's T = {one['thresh_us']} us on period chunks
+
+`chunks_sequential` = **{one['chunks_sequential']}** (must be 0: a period chunk of 16.6 ms is one bucket of T + 1 us);
+{one['events_active']} of {one['events_positive']} positive events kept.
+
+{F.TRIED}{notes}"""
+
+
 def markdown(r, notes="") -> str:
     d, parents = r["decode"], [r[k] for k in ("parent_1", "parent_2", "parent_3") if k in r and "error" not in r[k]]
     rows = []
@@ -299,8 +536,28 @@ construction (trigger-to-trigger spans against pause-to-pause spans): the figure
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    F.add_arguments(ap, "the parent commit's libxmaps_hip.so: (a) of the decode table")
+    F.add_arguments(ap, "the parent commit's libxmaps_hip.so: (a) of the decode table; with --filters-md the three parent runs of its first table")
+    ap.add_argument("--filters-md", help="measure the chain's two filters instead (profiles/ext_trigger_filters.md) and write the profile here")
     a = ap.parse_args(argv)
+    if a.step in ("push", "push_off"):
+        return step_push(a.repeats, a.device, off_only=a.step == "push_off")
+    if a.step == "frame_filters":
+        return step_frame_filters(a.passes, a.device)
+    if a.step in ("filter_kernels_trig", "filter_kernels_alone"):
+        return step_filter_kernels_child(a.device, a.step.rsplit("_", 1)[1])
+    if a.filters_md:
+        res = {"clock_state": clock_state(), "repeats": a.repeats, "passes": a.passes}
+        steps = []
+        for i in (1, 2, 3):  # (the box's rate drifts from process to process: the two builds take turns)
+            steps += [(f"parent_{i}", "push", a.parent_lib)] if a.parent_lib else []
+            steps += [(f"off_{i}", "push_off", None)]
+        steps += [("push", "push", None), ("frame_filters", "frame_filters", None)]
+        if F.run_steps(__file__, TAG, steps, a, res):
+            res["kernels_trig"] = step_filter_kernels(a, "trig")
+            res["kernels_alone"] = step_filter_kernels(a, "alone") if "error" not in res["kernels_trig"] else {"error": "not started: the trace in front of it failed"}
+            print(json.dumps({k: res[k] for k in ("kernels_trig", "kernels_alone")}, indent=1))
+            F.write_md(a.filters_md, res, filters_markdown)
+        return res
     if a.step == "decode":
         return step_decode(a.repeats, a.device)
     if a.step == "chain":

@@ -81,14 +81,15 @@ def raw_format(path: str):
 
 def replay_raw(raw, calib, proj_w, proj_h, fps, z_near, z_far, camera_perspective=False, device=0, chunk_words=1 << 20,
                device_ingest=True, keep_frames=0, tables=None, max_chunks=0, scans_dir=None, clouds_dir=None, frame_sync="pauses",
-               trigger_id=-1, trigger_edge="rising"):
+               trigger_id=-1, trigger_edge="rising", trigger_activity_filter=False):
     """Part A.  -> dict(report), list of (frame checksum, shape) per shown frame, the first `keep_frames` frames
     scans_dir: every shown frame's camera time surface (RuntimeParams.surface_callback: float32, this build's definition) is
     written to <scans_dir>/scans_np/scansNNN.npy, N counting the shown frames from 0 -- what part B reads
     clouds_dir: every shown frame's per-event point cloud (RuntimeParams.cloud_callback) is written to
     <clouds_dir>/pointcloud_live/frameNNNNNN.ply, N counting the same way
     frame_sync: "pauses" (the trigger finder) or "ext_trigger" (RuntimeParams.frame_sync: the frames are cut at the recording's
-    EXT_TRIGGER words of channel trigger_id / edge trigger_edge -- one surface / cloud file per trigger-to-trigger frame)"""
+    EXT_TRIGGER words of channel trigger_id / edge trigger_edge -- one surface / cloud file per trigger-to-trigger frame)
+    trigger_activity_filter: frame_sync="ext_trigger" only -- the activity filter in front of the cut (RuntimeParams.ext_trigger_activity_filter)"""
     from x_maps_amd import dat, evt2, evt21, evt3
     from x_maps_amd.depth_reprojection_processor import DepthReprojectionProcessor, RuntimeParams
     fmt = raw_format(raw)
@@ -128,7 +129,7 @@ def replay_raw(raw, calib, proj_w, proj_h, fps, z_near, z_far, camera_perspectiv
                            camera_perspective=camera_perspective, tables=tables, device=device, device_ingest=device_ingest,
                            surface_callback=surface_cb, cloud_callback=cloud_cb,
                            raw_legacy_halves=fmt == 21 and evt21.raw_legacy_halves(raw), frame_sync=frame_sync,
-                           ext_trigger_id=trigger_id, ext_trigger_edge=trigger_edge)
+                           ext_trigger_id=trigger_id, ext_trigger_edge=trigger_edge, ext_trigger_activity_filter=bool(trigger_activity_filter))
     n_words = n_chunks = 0
     with DepthReprojectionProcessor(params, window=Window()) as proc:
         t_setup = time.perf_counter() - t_setup
@@ -144,6 +145,7 @@ def replay_raw(raw, calib, proj_w, proj_h, fps, z_near, z_far, camera_perspectiv
         dt = time.perf_counter() - c0
         ds = proc._pipe.ingest.device_stats() if proc._pipe.ingest is not None else None
         trig_stats = proc._pipe._trig.stats() if proc._pipe._trig is not None else None
+        trig_filter_stats = proc._pipe._trig.filter_stats() if proc._pipe._trig is not None else None
         clouds_lost = int(proc._pipe.stats_printer.counters.get("cloud lost", 0)) if clouds_dir else 0
     rep = {"raw": raw, "format": {3: "EVT 3.0", 2: "EVT 2.0", 21: "EVT 2.1", "dat": "DAT"}[fmt], "words": n_words, "chunks": n_chunks, "chunk_words": chunk_words,
            "path": "external triggers (decode + trigger records + polarity + frames cut at the trigger words + hot path on the GPU)"
@@ -162,7 +164,7 @@ def replay_raw(raw, calib, proj_w, proj_h, fps, z_near, z_far, camera_perspectiv
         rep["clouds_from_raw"] = {"dir": os.path.join(clouds_dir, "pointcloud_live"), "frames": len(cloud_points),
                                   "points": int(sum(cloud_points)), "points_per_frame": cloud_points, "clouds_lost": clouds_lost}
     if trig_stats is not None:
-        rep["ext_trigger"] = dict(trig_stats, id=trigger_id, edge=trigger_edge)
+        rep["ext_trigger"] = dict(trig_stats, id=trigger_id, edge=trigger_edge, activity_filter=bool(trigger_activity_filter), filters=trig_filter_stats)
     if ds is not None:
         rep["device"] = ds
         rep["events_behind_the_filters"] = ds["events_appended"]
@@ -444,6 +446,8 @@ def main(argv=None):
                     help="part A: cut the frames at pauses (the trigger finder) or at the recording's EXT_TRIGGER words (a rig with the sync jack wired)")
     ap.add_argument("--trigger-id", type=int, default=-1, help="--frame-sync ext-trigger: the trigger channel (-1: any)")
     ap.add_argument("--trigger-edge", choices=("rising", "falling", "both"), default="rising")
+    ap.add_argument("--trigger-activity-filter", action="store_true",
+                    help="--frame-sync ext-trigger: the activity filter in front of the cut, as the reference's pipe has it (off by default)")
     ap.add_argument("--eval-calib", help="the ESL dataset's calib.yaml (cam_K, cam_kc, proj_K, proj_kc, R, T) for part B")
     ap.add_argument("--projector-width", type=int, default=1080)
     ap.add_argument("--projector-height", type=int, default=1920)
@@ -494,7 +498,7 @@ def main(argv=None):
         rep, shown, kept = replay_raw(a.raw, a.calib, a.projector_width, a.projector_height, a.projector_fps, a.z_near, a.z_far,
                                       a.camera_perspective, a.device, a.chunk_words, True, a.save_frames, scans_dir=a.scans_from_raw,
                                       clouds_dir=a.clouds_from_raw, frame_sync=a.frame_sync.replace("-", "_"), trigger_id=a.trigger_id,
-                                      trigger_edge=a.trigger_edge)
+                                      trigger_edge=a.trigger_edge, trigger_activity_filter=a.trigger_activity_filter)
         report["replay"] = rep
         if a.scans_from_raw and not a.scans and a.eval_calib:
             a.scans = a.scans_from_raw  # part B on the surfaces part A has just written

@@ -140,6 +140,11 @@ class xm_trigframes_counters(C.Structure):
                                           "events_before_first_trigger", "events_dropped_open_frame", "front_moves")]
 
 
+class xm_trigframes_filter_counters(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("events_positive", "events_active", "chunks_sequential",
+                                          "frames_filtered", "events_after_frame_filter", "index_errors")]
+
+
 class xm_eval_result(C.Structure):
     _fields_ = [("fillrate", C.c_double), ("rmse", C.c_double), ("perc_1", C.c_double), ("perc_5", C.c_double),
                 ("perc_10", C.c_double), ("margin", C.c_double), ("n_valid", C.c_uint64), ("n_gt_zero", C.c_uint64)]
@@ -390,6 +395,10 @@ SYMBOLS = {
     "xm_trigframes_ready": (C.c_int, [_P, C.POINTER(_P), _P, C.c_int, C.POINTER(C.c_int), _P]),
     "xm_trigframes_release": (C.c_int, [_P, C.c_int]),
     "xm_trigframes_stats": (C.c_int, [_P, C.POINTER(xm_trigframes_counters)]),
+    "xm_trigframes_set_activity": (C.c_int, [_P, C.c_int64, C.c_int]),
+    "xm_trigframes_filter_stats": (C.c_int, [_P, C.POINTER(xm_trigframes_filter_counters)]),
+    "xm_trigframes_set_frame_filter": (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
+    "xm_trigframes_ready_filtered": (C.c_int, [_P, C.POINTER(_P), _P, C.c_int, C.POINTER(C.c_int), _P, _P]),
     "xm_dat_create": (C.c_int, [_P, C.c_size_t, C.c_size_t, C.POINTER(C.c_void_p)]),
     "xm_dat_decode": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
     "xm_ingest_push_dat": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_int, C.POINTER(C.c_size_t)]),

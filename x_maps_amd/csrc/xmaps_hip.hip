@@ -15,6 +15,7 @@
 #include "xmaps_evt21.hpp"          // EVT 2.1 decoder
 #include "xmaps_dat.hpp"            // DAT (version 2, CD) decoder
 #include "xmaps_exttrigger.hpp"     // EXT_TRIGGER words -> trigger records behind the decoders' emit; the triggered frames' append
+#include "xmaps_trigfilter.hpp"     // ... their two filters: the activity rule inside the append, the frame event filters on runs of frames
 #include "xmaps_surface.hpp"        // time surfaces -> depth maps + point clouds
 #include "xmaps_framesurface.hpp"   // frames of events -> camera time surfaces (the group entry and the ingest's surface stage)
 #include "xmaps_framecloud.hpp"     // frames of events -> per-event point clouds (the group entry and the ingest's cloud stage)

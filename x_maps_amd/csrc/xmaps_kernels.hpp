@@ -42,3 +42,7 @@
 //       "xmaps_framesurface.hpp"  frames of events -> camera time surfaces: winners by integer atomics, one store per pixel
 //       "xmaps_framecloud.hpp"    frames of events -> per-event point clouds: codes per event, a scan, a stable compaction
 //       "xmaps_timecal.hpp"       projector time-map calibration: accumulate, mean, corners, projective warp, fill along rows
+// (and behind the decoders:)
+//       "xmaps_exttrigger.hpp"    EXT_TRIGGER words -> trigger records; the triggered frames' append (p == 1 compaction + trigger remap)
+//       "xmaps_trigfilter.hpp"    the triggered frames' two filters: the activity rule inside the append (first pass, sequential
+//                                 judge, count, write + retire), the frame event filters on a run of ready frames (blockIdx.y = frame)

@@ -131,6 +131,7 @@ class DepthReprojectionPipe:
         # own behind process_*_words -- decoder with extraction on, TriggeredFrames, the group entries on the device buffer --
         # made on first use; neither the ingest nor the host chain exists in this mode
         self._trig, self._trig_dev, self._trig_bgr = None, {}, None
+        self._trig_filter, self._trig_filter_refused = (0, False), False  # what the buffer has been told (TriggeredFrames.set_frame_filter)
         if self._frame_sync == "ext_trigger":
             return
         if self.activity_filter is None and getattr(p, "activity_filter", True):
@@ -283,6 +284,9 @@ class DepthReprojectionPipe:
             self._trig = TriggeredFrames(eng, cap_events=cap, id=int(getattr(p, "ext_trigger_id", -1)),
                                          edge=getattr(p, "ext_trigger_edge", "rising"), min_events=self.MIN_EVENTS_PER_FRAME,
                                          positive_only=True)  # PolarityFilterAlgorithm(1), pipe:43,114
+            if getattr(p, "ext_trigger_activity_filter", False) and getattr(p, "activity_filter", True):  # pipe:65-68,116-117
+                _warn_activity_rule_unpinned()
+                self._trig.set_activity(self._activity_thresh_us(), bool(getattr(p, "activity_include_self", False)))
         dev = self._trig_dev.get(fmt)
         if dev is None:
             from . import evt2, evt21, evt3
@@ -311,12 +315,25 @@ class DepthReprojectionPipe:
         """Every ready frame, in runs of at most replay_group: surfaces, clouds and the frames' launches on the device buffer, one
         xm_sync, then per frame surface_callback, cloud_callback, frame_callback; the run is released behind its last callback."""
         tf = self._trig
+        sel = self.ev_filter_proc.selected_filter()
+        on_device = False  # RuntimeParams.device_frame_filters: the selected filter is a stage on the run, the stream stays on the device
+        if self.fused and self._device_frame_filters:
+            want = (0, False) if isinstance(sel, NoFilter) else (int(getattr(sel, "filter_id", 0)), bool(getattr(sel, "intended_semantics", False)))
+            if want != self._trig_filter:
+                try:
+                    tf.set_frame_filter(want[0], want[1], max_frames=self.replay_group)
+                    self._trig_filter_refused = False
+                except ValueError as e:
+                    self._trig_filter_refused = True
+                    self.stats_printer.log(f"{sel}: not available on the device ({e}); the frames go through the host path")
+                self._trig_filter = want
+            on_device = want[0] != 0 and not self._trig_filter_refused
         while True:
             ptr, offs, _ = tf.ready(self.replay_group)
             n = len(offs) - 1
             if n == 0:
                 return
-            if not self.fused or not isinstance(self.ev_filter_proc.selected_filter(), NoFilter):
+            if not on_device and (not self.fused or not isinstance(sel, NoFilter)):
                 frames = tf.download(ptr, offs)  # (the frame event filters re-order a frame's events on the host: pipe:131-139)
                 tf.release(n)
                 for evs in frames:
@@ -333,7 +350,14 @@ class DepthReprojectionPipe:
                     surfs, _ = eng.frames_to_time_surfaces_device(ptr, offs, *self._surface_kind)
                 if self._cloud_callback is not None:
                     clouds = eng.frames_to_point_clouds_device(ptr, offs)
-                eng.process_events_batch_device(ptr, offs, None, self._trig_bgr)
+                fptr, foffs = ptr, offs
+                if on_device:  # (surfaces and clouds are the cut frames', in front of the filter: as the ingest orders its stages)
+                    fptr, foffs, _, _ = tf.ready_filtered(n)
+                    assert len(foffs) == n + 1
+                    for f in range(n):
+                        self.stats_printer.add_metric("frame evs filtered out [%]",
+                                                      100 - int(foffs[f + 1] - foffs[f]) / max(int(offs[f + 1] - offs[f]), 1) * 100)
+                eng.process_events_batch_device(fptr, foffs, None, self._trig_bgr)
                 eng.sync()  # (also redoes frames whose verified shortcut failed)
                 bgr = np.empty((n, eng.out_h, eng.out_w, 3), np.uint8)
                 eng.dev_download(bgr, self._trig_bgr)

@@ -105,16 +105,25 @@ class RuntimeParams:
     # process_evt3_words / _evt2_words / _evt21_words carry those words: process_events and process_dat_records raise ValueError
     # in this mode.  Frame k = the positive events (PolarityFilterAlgorithm(1)) between the k-th and the next selected trigger,
     # nothing trimmed; frames of MIN_EVENTS_PER_FRAME = 1000 events or fewer are skipped, as the reference's trigger finder skips
-    # them.  THE ACTIVITY FILTER IS NOT PART OF THIS CHAIN (activity_filter is ignored).  DELIVERY is synchronous, as in the
+    # them.  The activity filter is a stage of this chain when ext_trigger_activity_filter is set (below); without it the chain
+    # has none and activity_filter is ignored, as before.  DELIVERY is synchronous, as in the
     # reference: a frame reaches frame_callback (its surface_callback and cloud_callback in front) inside the call whose words hold
     # its closing trigger.  While a frame event filter (key E) is selected every frame is downloaded and goes through
-    # process_ev_frame.  ext_trigger_id: the trigger channel (-1: any); ext_trigger_edge: "rising", "falling" or "both";
+    # process_ev_frame -- or, with device_frame_filters, is filtered where it lies (TriggeredFrames.ready_filtered: the run's
+    # surfaces and clouds from the cut frames, its launches on the survivors; the same frames).
+    # ext_trigger_id: the trigger channel (-1: any); ext_trigger_edge: "rising", "falling" or "both";
     # ext_trigger_cap_events: the device buffer the frames are cut from, in events -- an open frame that cannot keep its events
     # plus one more chunk's inside it is dropped (counted; cutting resumes at the next trigger).
     frame_sync: str = "pauses"
     ext_trigger_id: int = -1
     ext_trigger_edge: str = "rising"
     ext_trigger_cap_events: int = 1 << 22
+    # frame_sync = "ext_trigger" only: polarity filter -> ACTIVITY FILTER -> cut, what the reference's pipe does to every packet
+    # (pipe:110-119), on the device inside the append.  False (the default) is the chain as it was: no activity filter.  True:
+    # activity_filter, activity_strict, activity_include_self and int(1e6 / projector_fps) apply to this chain as they do to the
+    # ingest (this build's rule; unpinned against Metavision, like the ingest's), and MIN_EVENTS_PER_FRAME applies to the filtered
+    # frames.
+    ext_trigger_activity_filter: bool = False
 
     @property
     def should_drop_frames(self):

@@ -16,7 +16,11 @@ frame boundary is exact in stream order whatever the stamps are.
                              DeviceEvtDecoder.set_ext_triggers / last_ext_triggers (csrc/xmaps_exttrigger.hpp)
     insert_ext_triggers      puts trigger words into an encoded stream in front of given events (tests, rendered recordings)
     TriggerFrameCutter       THE CUT RULE of this build (include/xmaps.h states it; csrc/host/xm_trigger_cut.hpp is the same in C++)
-    TriggeredFrames          the device-resident buffer the rule cuts from (xm_trigframes): frames as (device records, host offsets)
+    TriggeredFrames          the device-resident buffer the rule cuts from (xm_trigframes): frames as (device records, host offsets);
+                             its two filters, both off by default (csrc/xmaps_trigfilter.hpp): the activity filter in front of the
+                             cut (set_activity: this build's rule, the ingest's) and the frame event filters on a run of ready
+                             frames (set_frame_filter / ready_filtered)
+    keep_where               the host form of the buffer's append for an arbitrary keep mask (keep_positive: p == 1)
 """
 from __future__ import annotations
 
@@ -168,16 +172,24 @@ def insert_ext_triggers(words, fmt, at_event, id=0, value=1, t=None, legacy_halv
     return evt21.swap_halves(res) if f == 21 and legacy_halves else res
 
 
-def keep_positive(events: np.ndarray, triggers: np.ndarray):
-    """PolarityFilterAlgorithm(1) on a chunk and its triggers: (the p == 1 events, the triggers with event_index remapped to "kept
-    events with chunk index < event_index") -- what xm_trigframes_push does with positive_only"""
-    keep = events["p"] == 1
+def keep_where(events: np.ndarray, triggers: np.ndarray, mask):
+    """The append of xm_trigframes_push for an arbitrary keep mask (one bool per event of the chunk): (the kept events in stream
+    order, the triggers with event_index remapped to "kept events with chunk index < event_index")"""
+    keep = np.asarray(mask, dtype=bool)
+    if keep.shape != (len(events),):
+        raise ValueError("one keep flag per event of the chunk")
     before = np.concatenate(([0], np.cumsum(keep)))
     out = triggers.copy()
     out["event_index"] = before[np.minimum(triggers["event_index"].astype(np.int64), len(events))]
     kept = np.zeros(int(keep.sum()), EVENT_CD_DTYPE)
     kept[:] = events[keep]
     return kept, out
+
+
+def keep_positive(events: np.ndarray, triggers: np.ndarray):
+    """PolarityFilterAlgorithm(1) on a chunk and its triggers: keep_where(p == 1) -- what xm_trigframes_push does with
+    positive_only (and no activity filter)"""
+    return keep_where(events, triggers, events["p"] == 1)
 
 
 class TriggerFrameCutter:
@@ -328,8 +340,11 @@ class TriggeredFrames:
 
     created = 0  # objects made in this process (the pipe's default mode makes none)
 
+    FILTER_COUNTERS = ("events_positive", "events_active", "chunks_sequential", "frames_filtered", "events_after_frame_filter",
+                       "index_errors")
+
     def __init__(self, engine, cap_events: int = 1 << 22, id: int = -1, edge: str = "rising", min_events: int = 0,
-                 positive_only: bool = False, max_frames_ready: int = 0):
+                 positive_only: bool = False, max_frames_ready: int = 0, activity_thresh_us=None, activity_include_self: bool = False):
         from . import _native as N
         if edge not in EDGES:
             raise ValueError('edge must be "rising", "falling" or "both"')
@@ -339,6 +354,38 @@ class TriggeredFrames:
         self._tf = C.c_void_p(None)
         N.check(self._lib.xm_trigframes_create(engine._h, C.byref(cfg), C.byref(self._tf)))
         TriggeredFrames.created += 1
+        if activity_thresh_us is not None:
+            try:
+                self.set_activity(activity_thresh_us, activity_include_self)
+            except Exception:
+                self.close()
+                raise
+
+    def set_activity(self, thresh_us, include_self: bool = False):
+        """The activity filter as a stage of push (this build's rule, the ingest's: oracle/ingest_oracle.py), from the next chunk on;
+        thresh_us None or < 0: off.  Needs positive_only; switching it on starts from an empty history."""
+        self._N.check(self._lib.xm_trigframes_set_activity(self._tf, -1 if thresh_us is None else int(thresh_us), int(bool(include_self))))
+
+    def set_frame_filter(self, filter_id: int, intended_semantics: bool = False, max_frames: int = 16):
+        """The frame event filter ready_filtered applies (0: none; frame_event_filter's filter_id numbers), on runs of at most
+        max_frames frames.  ValueError (nothing changes): an unknown filter, FirstEventPerYT on a rig whose cell map is too large."""
+        self._N.check(self._lib.xm_trigframes_set_frame_filter(self._tf, int(filter_id), int(bool(intended_semantics)), int(max_frames)))
+
+    def ready_filtered(self, cap_frames: int = 64):
+        """ready()'s run with each frame replaced by what the selected filter hands on -> (device pointer of the survivors buffer,
+        offsets uint64 [n + 1] from 0, opening triggers [n], n_index_errors uint64 [n]); no filter selected: ready()'s values"""
+        ptr, n = C.c_void_p(None), C.c_int(0)
+        offs = np.zeros(cap_frames + 1, np.uint64)
+        opening = np.zeros(cap_frames, EXT_TRIGGER_DTYPE)
+        bad = np.zeros(cap_frames, np.uint64)
+        self._N.check(self._lib.xm_trigframes_ready_filtered(self._tf, C.byref(ptr), C.c_void_p(offs.ctypes.data), int(cap_frames), C.byref(n),
+                                                             C.c_void_p(opening.ctypes.data), C.c_void_p(bad.ctypes.data)))
+        return int(ptr.value or 0), offs[:n.value + 1].copy(), opening[:n.value].copy(), bad[:n.value].copy()
+
+    def filter_stats(self) -> dict:
+        st = self._N.xm_trigframes_filter_counters()
+        self._N.check(self._lib.xm_trigframes_filter_stats(self._tf, C.byref(st)))
+        return {k: int(getattr(st, k)) for k in self.FILTER_COUNTERS}
 
     def close(self):
         if getattr(self, "_tf", None) is not None and self._tf.value:
