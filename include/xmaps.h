@@ -206,6 +206,9 @@ int xm_own_plan_info(const xm_config* cfg, int32_t info[12]);
  * mem == XM_MEM_DEVICE: asynchronous on the next slot's stream; the buffers must stay valid until
  *                       xm_sync(); stats of the most recent frame via xm_last_frame_stats() after it.
  * n == 0 and t_max == t_min are defined: an empty frame, resp. every event in X-map column 0.
+ * Time stamps: any finite values whose t_max - t_min does not overflow their type -- int64 frames of up to 2^63 - 1 us from any
+ * (also negative) base, float32 / float64 of any order -- give NumPy's columns bit for bit; the column and owner tiles take
+ * frames of up to 2^32 - 2 us and longer ones are redone on the 64-bit path.  Overflowing spans, NaN and inf are undefined.
  */
 int xm_process_frame(xm_handle* h, const uint16_t* x, const uint16_t* y, const void* t, const int16_t* p,
                      size_t n, int t_dtype, int mem, float* depth_out, uint8_t* bgr_out, xm_frame_stats* stats);

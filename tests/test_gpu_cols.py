@@ -525,7 +525,9 @@ def test_integer_thresholds_reproduce_the_float64_column_of_every_time_stamp(xma
                 col = O.time_to_xmap_column(t0 + a, xmap_w - 1).astype(np.int64)  # tmin, tmax = the array's first / last element
                 want = np.searchsorted(col, np.arange(xmap_w + 1), side="left")    # first a with column >= c; span + 1 if none
                 assert np.array_equal(thr, want.astype(np.uint32)), (span, t0)
-        for span in (2 ** 31 + 12_345, 4_000_000_000, 999_999_937):  # too long to enumerate: check around every threshold
+        # too long to enumerate: check around every threshold (2^32 - 2 is the largest span the tiles take: span + 1 = "no such a"
+        # must still fit 32 bits)
+        for span in (2 ** 31 + 12_345, 4_000_000_000, 999_999_937, 2 ** 32 - 3, 2 ** 32 - 2):
             t0 = 7_777
             thr = eng.debug_cols_thresholds(t0, t0 + span).astype(np.int64)
             probe = np.unique(np.clip(np.concatenate([thr - 1, thr, thr + 1, [0, span]]), 0, span))
@@ -533,3 +535,8 @@ def test_integer_thresholds_reproduce_the_float64_column_of_every_time_stamp(xma
             for c in range(xmap_w + 1):
                 below, at = probe < thr[c], probe >= thr[c]
                 assert (col[below] < c).all() and (col[at] >= c).all(), (span, c)
+        # from a span of 0xffffffff on, a = t - tmin (or span + 1) leaves 32 bits: the entry refuses, as the boundary pass does
+        for span in (2 ** 32 - 1, 2 ** 32, 2 ** 40, 2 ** 63 - 1):
+            with pytest.raises(ValueError, match="do not take the column tiles"):
+                eng.debug_cols_thresholds(-5, -5 + span)
+        assert len(eng.debug_cols_thresholds(3, 1)) == xmap_w + 1  # (t_last < t_first, an unsorted frame: treated as span 0, not refused)
