@@ -1059,6 +1059,63 @@ int xm_ingest_set_cloud_output(xm_ingest* g, int on, int64_t max_points, int rin
  * drops the ring's contents.  Synchronous. */
 int xm_ingest_copy_cloud(xm_ingest* g, uint64_t seq, float* dst, int mem, xm_frame_cloud_stats* stats);
 
+/* ---- frames of events in, EVT 3.0 words out: a replayable recording of what the pipeline processed -------------------------------
+ * For one frame of 16-byte EventCD records in stream order the words are exactly x_maps_amd.evt3.encode_evt3(frame, use_vectors)
+ * -- the host encoder is the definition, its state fresh for every frame, so a frame's words begin with its own EVT_TIME_HIGH,
+ * EVT_TIME_LOW and EVT_ADDR_Y.  The same rule in the form that evaluates in parallel (x, y the raw u16, p the raw int16, t the
+ * int64 of the record; hi = (t >> 12) & 0xfff, lo = t & 0xfff):
+ *   - LINKS: event i >= 1 is linked to event i - 1 iff t, y and p are equal and x[i] > x[i - 1].  A CHAIN is a maximal sequence of
+ *     linked events; its head is the frame's first event or an event that is not linked.  With use_vectors == 0 nothing is linked;
+ *   - RUN STARTS: within a chain, the orbit of the head under next(i) = the first j of the chain with x[j] - x[i] >= 12.  A run is
+ *     a start and the chain's events in front of its next; its columns grow strictly, so next(i) <= i + 12, and a chain holds at
+ *     most 65 536 events (x is u16): the walk is bounded, and it may cross any 64-event segment or block of the kernels;
+ *   - a run of one event is EVT_ADDR_X (x & 0x7ff, p & 1 in bit 11); a run of >= 2 events is VECT_BASE_X (the same fields) and ONE
+ *     VECT_12 with bit x[k] - x[start] set for every event k of the run.  use_vectors == 0: every event is a run of one
+ *     (= encode_evt3_singles);
+ *   - in front of run start i: EVT_TIME_HIGH (hi) iff i is the frame's first event or hi differs from event i - 1's;
+ *     EVT_TIME_LOW (lo) iff EVT_TIME_HIGH is sent or lo differs; EVT_ADDR_Y (y & 0x7ff) iff i is the first event or y differs.  (Only a
+ *     chain's head can have any: a linked event shares t and y with its predecessor.)  Events that start no run send nothing;
+ *   - fields are masked as the host encoder masks them and bits of t above bit 23 are dropped: two events whose stamps differ
+ *     only there are not linked, and no time word separates them.  What that loses is counted, not refused: n_out_of_range;
+ *   - a frame of n events encodes to at most 4 * n words; an empty frame is defined: no words, zero statistics.
+ * The result depends on the frame alone: not on the run, on the frame's place in a group or on earlier calls.  No atomics, and no
+ * kernel waits for another block of its launch (x_maps_amd/csrc/xmaps_evt3enc.hpp).  Debug option "XM_ENC_MAX_BLOCKS"
+ * (xm_debug_option): the most blocks per frame of the per-event passes, read at every group call and when an ingest's record stage
+ * is first switched on. */
+typedef struct xm_evt3_record_stats {
+  uint64_t n_events;       /* records of the frame                                                                      */
+  uint64_t n_words;        /* words of the frame                                                                        */
+  uint64_t n_vector_runs;  /* runs of >= 2 events (VECT_BASE_X + VECT_12)                                               */
+  uint64_t n_out_of_range; /* events with x > 2047, y > 2047, p not in {0, 1} or t < 0 (encoded with their fields masked) */
+  int64_t t_first;         /* the first / last record's stamp in stream order (0, 0 for an empty frame)                 */
+  int64_t t_last;
+} xm_evt3_record_stats;
+/* Frame f = records [offsets_host[f], offsets_host[f + 1]) of eventcd16, as in xm_frames_to_point_clouds.  words_out: u16
+ * [4 * (offsets_host[n_frames] - offsets_host[0])]; frame f's words start at word 4 * (offsets_host[f] - offsets_host[0]), the
+ * first n_words of them are valid, the rest are left untouched.  stats_out (may be NULL): xm_evt3_record_stats[n_frames].
+ * mem == XM_MEM_HOST: records, words and statistics are host memory, the call is synchronous and only valid words are copied back.
+ * XM_MEM_DEVICE: all three are device memory; everything is enqueued on the next slot's stream, xm_sync() waits, the buffers stay
+ * valid and untouched until then (offsets_host is read inside the call).  Handles of either view; groups of any length (launch
+ * sequences of 32 frames) of fewer than 2^30 events together (XM_ERR_TOO_MANY).  Scratch is allocated by the first call and grown
+ * when a larger group arrives.  XM_ERR_INVALID: n_frames <= 0, decreasing offsets, a mem other than the two, a NULL array that
+ * would be used. */
+int xm_frames_to_evt3_words(xm_handle* h, const void* eventcd16, const uint64_t* offsets_host, int n_frames, int use_vectors, int mem,
+                            uint16_t* words_out, xm_evt3_record_stats* stats_out);
+/* The same as a stage of the device ingest, ordered and ring-managed exactly like xm_ingest_set_cloud_output: the frames cut by
+ * packets pushed AFTER the call get their words -- built on the frame stream from the CUT frame (behind the polarity and activity
+ * filters, in front of any frame event filter) -- in a ring of `ring` entries (0: the ingest's result_ring) of max_words words in
+ * device memory.  on != 0 needs max_words > 0.  Overflow is all or nothing (a truncated word stream is worse than none): a frame
+ * with n_words > max_words publishes its statistics with the true n_words and no word.  on == 0 switches the stage off: the ingest
+ * then launches nothing for it.  use_vectors may change from call to call; scratch and ring are allocated by the first call that
+ * switches the stage on, and a later call may not change max_words or the ring's length (XM_ERR_INVALID). */
+int xm_ingest_set_record_output(xm_ingest* g, int on, int use_vectors, int64_t max_words, int ring);
+/* The words of frame `seq` (xm_ingest_frame.seq): its n_words words -> dst (u16; host or device memory by `mem`; NULL: statistics
+ * only) unless n_words > max_words (then none), its statistics -> *stats (host memory, may be NULL).  Returns 1: copied, and the
+ * ring entry was still intact after the copy; 0: never produced, not complete yet, or already overwritten (dst may have been
+ * written); < 0: an error.  Once xm_ingest_poll* has handed out frame seq its words are complete.  xm_ingest_reset keeps the
+ * stage's setting and drops the ring's contents.  Synchronous. */
+int xm_ingest_copy_record(xm_ingest* g, uint64_t seq, uint16_t* dst, int mem, xm_evt3_record_stats* stats);
+
 /* ---- ESL-init: the baseline of the reference's evaluation table, on the device ------------------------------------------------
  * What python/eval/compute_depth_esl.py:204-226 computes up to depth_init (the optimisation behind it: xm_esl_optim_* below; MC3D: xm_mc3d_*),
  * for a GROUP of camera time surfaces in one device call.  Per surface:

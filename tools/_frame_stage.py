@@ -1,6 +1,6 @@
-"""What tools/frame_surfaces_time.py and tools/frame_clouds_time.py share: the child-step runner, the ingest pass loop with the
-stage alternating off / on, and the pieces of the markdown both write.  Imported by the two tools (tools/ is the script's
-directory, so `import _frame_stage` finds it); no tool imports another tool."""
+"""What tools/frame_surfaces_time.py, tools/frame_clouds_time.py and tools/evt3_record_time.py share: the child-step runner, the
+ingest pass loop with the stage alternating off / on, and the pieces of the markdown they write.  Imported by the three tools
+(tools/ is the script's directory, so `import _frame_stage` finds it); no tool imports another tool."""
 from __future__ import annotations
 
 import argparse

@@ -6,7 +6,7 @@
 
 emit uses the library's own flags (x_maps_amd/_native.py) with -shared replaced by --cuda-device-only -S and a fixed -cuid=, which
 makes the text deterministic.  compare reports identical texts, or -- when only the order of the functions differs -- compares them
-by name with the function index taken out of the local labels, and lists every function whose body differs with the number of
+by name with the function index taken out of the local labels and of the loop comments that quote them, and lists every function whose body differs with the number of
 differing lines.  It compares texts and looks for no instruction in particular.  Results: profiles/device_split_identity.md.
 """
 import difflib
@@ -43,7 +43,9 @@ def functions(text):
         if m:
             name = m.group(1)
             out[name] = []
-        out[name].append(re.sub(r"\.L(BB|tmp|func_[a-z]+)\d+", r".L\1", line))
+        line = re.sub(r"\.L(BB|tmp|func_[a-z]+)\d+", r".L\1", line)
+        line = re.sub(r"\bBB\d+_", "BB_", line)  # (the loop comments name blocks as BB<function index>_<block> ...
+        out[name].append(re.sub(r"[ \t]+;", " ;", line))  # ... behind padding that depends on the label's length)
         if name and re.match(r"\s*\.size\s+" + re.escape(name) + ",", line):
             name = ""
     return out

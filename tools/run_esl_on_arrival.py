@@ -16,6 +16,9 @@ device from the cut frame: RuntimeParams.surface_callback) and part B runs on DI
 rig of one's own -- gets its table rows from the RAW file alone.  They are this build's surfaces, not the ESL dataset's.
 With --clouds-from-raw DIR part A also writes every shown frame's per-event point cloud to DIR/pointcloud_live/frameNNNNNN.ply
 (the reference's construct_point_cloud on the cut frame's inlier events, built on the device: RuntimeParams.cloud_callback).
+With --record-frames FILE.raw part A also writes the frames it shows to FILE.raw -- EVT 3.0 words encoded on the device from the cut
+frames, behind the filters, one EXT_TRIGGER word in front of each (RuntimeParams.record_callback, evt3.FrameRecordingWriter) --,
+a recording that `--raw FILE.raw --frame-sync ext-trigger --trigger-id 0` replays to the same frames.
 
 Part B -- the accuracy row (eval/x-map-eval.sh:24-72 -> python/eval/compute_depth_x_maps.py:22-133 ->
 python/eval/create_evaluation_table.py:84-180): every `<scans>/scans_np/*.npy` time surface -> X-maps depth in camera view on
@@ -81,7 +84,7 @@ def raw_format(path: str):
 
 def replay_raw(raw, calib, proj_w, proj_h, fps, z_near, z_far, camera_perspective=False, device=0, chunk_words=1 << 20,
                device_ingest=True, keep_frames=0, tables=None, max_chunks=0, scans_dir=None, clouds_dir=None, frame_sync="pauses",
-               trigger_id=-1, trigger_edge="rising", trigger_activity_filter=False):
+               trigger_id=-1, trigger_edge="rising", trigger_activity_filter=False, record_frames=None):
     """Part A.  -> dict(report), list of (frame checksum, shape) per shown frame, the first `keep_frames` frames
     scans_dir: every shown frame's camera time surface (RuntimeParams.surface_callback: float32, this build's definition) is
     written to <scans_dir>/scans_np/scansNNN.npy, N counting the shown frames from 0 -- what part B reads
@@ -89,7 +92,9 @@ def replay_raw(raw, calib, proj_w, proj_h, fps, z_near, z_far, camera_perspectiv
     <clouds_dir>/pointcloud_live/frameNNNNNN.ply, N counting the same way
     frame_sync: "pauses" (the trigger finder) or "ext_trigger" (RuntimeParams.frame_sync: the frames are cut at the recording's
     EXT_TRIGGER words of channel trigger_id / edge trigger_edge -- one surface / cloud file per trigger-to-trigger frame)
-    trigger_activity_filter: frame_sync="ext_trigger" only -- the activity filter in front of the cut (RuntimeParams.ext_trigger_activity_filter)"""
+    trigger_activity_filter: frame_sync="ext_trigger" only -- the activity filter in front of the cut (RuntimeParams.ext_trigger_activity_filter)
+    record_frames: a .raw file that receives the shown frames as EVT 3.0 words encoded on the device (RuntimeParams.record_callback
+    through evt3.FrameRecordingWriter): a recording that --frame-sync ext-trigger --trigger-id 0 replays to the same frames"""
     from x_maps_amd import dat, evt2, evt21, evt3
     from x_maps_amd.depth_reprojection_processor import DepthReprojectionProcessor, RuntimeParams
     fmt = raw_format(raw)
@@ -123,11 +128,12 @@ def replay_raw(raw, calib, proj_w, proj_h, fps, z_near, z_far, camera_perspectiv
             write_ply(os.path.join(clouds_dir, "pointcloud_live", cloud_name(len(cloud_points))), cloud)
             cloud_points.append(len(cloud))
 
+    recorder = evt3.FrameRecordingWriter(record_frames, 640, 480) if record_frames else None
     t_setup = time.perf_counter()
     params = RuntimeParams(camera_width=640, camera_height=480, projector_width=proj_w, projector_height=proj_h, projector_fps=fps,
                            z_near=z_near, z_far=z_far, calib=calib, projector_time_map=None, no_frame_dropping=True,
                            camera_perspective=camera_perspective, tables=tables, device=device, device_ingest=device_ingest,
-                           surface_callback=surface_cb, cloud_callback=cloud_cb,
+                           surface_callback=surface_cb, cloud_callback=cloud_cb, record_callback=recorder,
                            raw_legacy_halves=fmt == 21 and evt21.raw_legacy_halves(raw), frame_sync=frame_sync,
                            ext_trigger_id=trigger_id, ext_trigger_edge=trigger_edge, ext_trigger_activity_filter=bool(trigger_activity_filter))
     n_words = n_chunks = 0
@@ -147,6 +153,9 @@ def replay_raw(raw, calib, proj_w, proj_h, fps, z_near, z_far, camera_perspectiv
         trig_stats = proc._pipe._trig.stats() if proc._pipe._trig is not None else None
         trig_filter_stats = proc._pipe._trig.filter_stats() if proc._pipe._trig is not None else None
         clouds_lost = int(proc._pipe.stats_printer.counters.get("cloud lost", 0)) if clouds_dir else 0
+        records_lost = int(proc._pipe.stats_printer.counters.get("record lost", 0)) if recorder else 0
+    if recorder:
+        recorder.close()
     rep = {"raw": raw, "format": {3: "EVT 3.0", 2: "EVT 2.0", 21: "EVT 2.1", "dat": "DAT"}[fmt], "words": n_words, "chunks": n_chunks, "chunk_words": chunk_words,
            "path": "external triggers (decode + trigger records + polarity + frames cut at the trigger words + hot path on the GPU)"
                    if frame_sync == "ext_trigger" else
@@ -163,6 +172,11 @@ def replay_raw(raw, calib, proj_w, proj_h, fps, z_near, z_far, camera_perspectiv
     if clouds_dir:
         rep["clouds_from_raw"] = {"dir": os.path.join(clouds_dir, "pointcloud_live"), "frames": len(cloud_points),
                                   "points": int(sum(cloud_points)), "points_per_frame": cloud_points, "clouds_lost": clouds_lost}
+    if recorder:
+        rep["record_frames"] = {"file": record_frames, "frames": recorder.frames, "words": recorder.words_written,
+                                "frames_below_replay_minimum": recorder.frames_below_replay_minimum,
+                                "frames_without_words": recorder.frames_without_words, "records_lost": records_lost,
+                                "replay_with": "--frame-sync ext-trigger --trigger-id 0"}
     if trig_stats is not None:
         rep["ext_trigger"] = dict(trig_stats, id=trigger_id, edge=trigger_edge, activity_filter=bool(trigger_activity_filter), filters=trig_filter_stats)
     if ds is not None:
@@ -442,6 +456,9 @@ def main(argv=None):
                          "surfaces, not the ESL dataset's); part B then runs on --scans DIR unless --scans names another directory")
     ap.add_argument("--clouds-from-raw", metavar="DIR",
                     help="part A also writes every shown frame's per-event point cloud to DIR/pointcloud_live/frameNNNNNN.ply")
+    ap.add_argument("--record-frames", metavar="FILE.raw",
+                    help="part A also writes the frames it shows to FILE.raw as EVT 3.0 words encoded on the device, one EXT_TRIGGER word "
+                         "(id 0) in front of each: replays to the same frames with --frame-sync ext-trigger --trigger-id 0")
     ap.add_argument("--frame-sync", choices=("pauses", "ext-trigger"), default="pauses",
                     help="part A: cut the frames at pauses (the trigger finder) or at the recording's EXT_TRIGGER words (a rig with the sync jack wired)")
     ap.add_argument("--trigger-id", type=int, default=-1, help="--frame-sync ext-trigger: the trigger channel (-1: any)")
@@ -491,6 +508,8 @@ def main(argv=None):
         ap.error("--scans-from-raw needs --raw")
     if a.clouds_from_raw and not a.raw:
         ap.error("--clouds-from-raw needs --raw")
+    if a.record_frames and not a.raw:
+        ap.error("--record-frames needs --raw")
     report = {"published": PUBLISHED}
     if a.raw:
         if a.bias:
@@ -498,7 +517,8 @@ def main(argv=None):
         rep, shown, kept = replay_raw(a.raw, a.calib, a.projector_width, a.projector_height, a.projector_fps, a.z_near, a.z_far,
                                       a.camera_perspective, a.device, a.chunk_words, True, a.save_frames, scans_dir=a.scans_from_raw,
                                       clouds_dir=a.clouds_from_raw, frame_sync=a.frame_sync.replace("-", "_"), trigger_id=a.trigger_id,
-                                      trigger_edge=a.trigger_edge, trigger_activity_filter=a.trigger_activity_filter)
+                                      trigger_edge=a.trigger_edge, trigger_activity_filter=a.trigger_activity_filter,
+                                      record_frames=a.record_frames)
         report["replay"] = rep
         if a.scans_from_raw and not a.scans and a.eval_calib:
             a.scans = a.scans_from_raw  # part B on the surfaces part A has just written

@@ -221,6 +221,11 @@ class xm_frame_cloud_stats(C.Structure):
                 ("t_min", C.c_int64), ("t_max", C.c_int64)]
 
 
+class xm_evt3_record_stats(C.Structure):
+    _fields_ = [("n_events", C.c_uint64), ("n_words", C.c_uint64), ("n_vector_runs", C.c_uint64), ("n_out_of_range", C.c_uint64),
+                ("t_first", C.c_int64), ("t_last", C.c_int64)]
+
+
 class xm_esl_init_config(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("cam_width", C.c_int32), ("cam_height", C.c_int32),
                 ("rect_width", C.c_int32), ("rect_height", C.c_int32), ("min_disp", C.c_int32), ("max_disp", C.c_int32),
@@ -417,6 +422,9 @@ SYMBOLS = {
     "xm_frames_to_point_clouds": (C.c_int, [_P, _P, C.POINTER(C.c_uint64), C.c_int, C.c_int, C.c_int, _P, _P]),
     "xm_ingest_set_cloud_output": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int]),
     "xm_ingest_copy_cloud": (C.c_int, [_P, C.c_uint64, _P, C.c_int, C.POINTER(xm_frame_cloud_stats)]),
+    "xm_frames_to_evt3_words": (C.c_int, [_P, _P, C.POINTER(C.c_uint64), C.c_int, C.c_int, C.c_int, _P, _P]),
+    "xm_ingest_set_record_output": (C.c_int, [_P, C.c_int, C.c_int, C.c_int64, C.c_int]),
+    "xm_ingest_copy_record": (C.c_int, [_P, C.c_uint64, _P, C.c_int, C.POINTER(xm_evt3_record_stats)]),
     "xm_esl_init_create": (C.c_int, [C.c_int, C.POINTER(xm_esl_init_config), C.POINTER(_P)]),
     "xm_esl_init_destroy": (None, [_P]),
     "xm_esl_init_time_surfaces": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),

@@ -449,6 +449,61 @@ int xm_ingest_copy_cloud(xm_ingest* g, uint64_t seq, float* dst, int mem, xm_fra
       stats);
 }
 
+// the record stage's scratch and ring, once (IngestRecord)
+static int ingest_record_alloc(xm_ingest* g, size_t max_words, int ring) {
+  IngestRecord& rec = g->rec;
+  rec.max_words = max_words;
+  rec.cap = (u32)g->fx.dev.mirror;  // (a cut frame is contiguous in the event ring: at most half of it)
+  rec.max_chunk_blocks = frame_max_chunk_blocks("XM_ENC_MAX_BLOCKS");
+  const size_t n_seg = (size_t)rec.cap / 64 + 1;
+  HIP_TRY(hipSetDevice(g->fx.h->cfg.device));
+  HIP_TRY(rec.d_code.alloc(rec.cap));
+  HIP_TRY(rec.d_cnt.alloc(n_seg));
+  HIP_TRY(rec.d_off.alloc(n_seg));
+  HIP_TRY(rec.d_ring.alloc((size_t)ring * max_words));
+  if (int rc = rec.r.alloc(ring)) return rc;
+  HIP_TRY(hipDeviceSynchronize());  // (default-stream memsets: the ingest's non-blocking streams do not wait for them)
+  rec.r.ready = true;
+  return XM_OK;
+}
+
+int xm_ingest_set_record_output(xm_ingest* g, int on, int use_vectors, int64_t max_words, int ring) {
+  if (!g) return fail(XM_ERR_INVALID, "NULL argument");
+  if (ring < 0 || ring > 65536) return fail(XM_ERR_INVALID, "ring must lie in 0 .. 65536");
+  if (on && (max_words <= 0 || max_words >= (1ll << 31))) return fail(XM_ERR_INVALID, "max_words must lie in 1 .. 2^31 - 1");
+  int rc = ingest_take_error(g);
+  if (rc) return rc;
+  if (on) {
+    const int want = g->rec.r.want_ring(ring, g->fx.ring);
+    if (!g->rec.r.ready && (rc = ingest_record_alloc(g, (size_t)max_words, want))) return rc;
+    if (g->rec.r.ring != want || g->rec.max_words != (size_t)max_words)
+      return fail(XM_ERR_INVALID, "the record ring holds %d entries of %zu words since the first call that switched the stage on", g->rec.r.ring,
+                  g->rec.max_words);
+  }
+  // ordered like a push: the packets handed in before this call keep the setting they were pushed under
+  IngestJob j;
+  j.kind = JobKind::set_record;
+  j.record_on = on ? 1 : 0;
+  j.record_vectors = use_vectors ? 1 : 0;
+  return ingest_submit(g, j, false);
+}
+
+int xm_ingest_copy_record(xm_ingest* g, uint64_t seq, uint16_t* dst, int mem, xm_evt3_record_stats* stats) {
+  if (!g || (!dst && !stats)) return fail(XM_ERR_INVALID, "NULL argument");
+  if (mem != XM_MEM_HOST && mem != XM_MEM_DEVICE) return fail(XM_ERR_INVALID, "mem must be XM_MEM_HOST or XM_MEM_DEVICE");
+  const IngestRecord& rec = g->rec;
+  return rec.r.read(
+      seq, [&](u64 t) { return cloud_tag_names(t, seq); },
+      [&](size_t e, u64, const EncStats& st) {
+        if (!dst || !st.n_words || st.n_words > rec.max_words) return (int)XM_OK;  // (all or nothing: the entry holds no word of such a frame)
+        HIP_TRY(hipSetDevice(g->fx.h->cfg.device));
+        HIP_TRY(hipMemcpy(dst, rec.d_ring + e * rec.max_words, (size_t)st.n_words * 2, mem == XM_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice));
+        if (mem == XM_MEM_DEVICE) HIP_TRY(hipStreamSynchronize(nullptr));
+        return (int)XM_OK;
+      },
+      stats);
+}
+
 int xm_ingest_flush(xm_ingest* g) {
   if (!g) return fail(XM_ERR_INVALID, "NULL argument");
   HIP_TRY(hipSetDevice(g->fx.h->cfg.device));
@@ -469,9 +524,10 @@ int xm_ingest_reset(xm_ingest* g) {
   z.last_t = 0;
   z.span_ok = 0;
   HIP_TRY(hipMemcpy(g->fx.dev.st, &z, sizeof z, hipMemcpyHostToDevice));
-  // the surface and cloud stages keep their settings; their rings are emptied
+  // the surface, cloud and record stages keep their settings; their rings are emptied
   g->sf.r.clear();
   g->cl.r.clear();
+  g->rec.r.clear();
   // The activity filter's history goes too: a reset is "the stream starts over" (the reference resets when a recording loops,
   // depth_reprojection.py:76) and its stamps then start below everything the history holds -- against the old history every
   // event with a neighbour that ever fired would pass.  (Metavision's filter object keeps its state there; the frames behind

@@ -147,6 +147,14 @@ struct FrameCloudScratch {
   DevBuf in, out;                     // staging of XM_MEM_HOST calls
 };
 
+// The frame -> EVT 3.0 entry (xm_api_evt3enc.hpp): grow-only scratch, ordered between calls like SurfaceScratch.  Nothing of it is
+// under a zero invariant: codes, counts, offsets and statistics are rewritten by every call before it reads them.
+struct FrameRecordScratch {
+  HipScratchOrder order;
+  DevBuf code, cnt, off, stats;  // per event u16; per 64 events uint2 / u32; [frames of the call] EncStats
+  DevBuf in, out;                // staging of XM_MEM_HOST calls
+};
+
 // ---- launch workers -------------------------------------------------------------------------------------------
 // A kernel launch costs the calling thread ~2.7 us in the HIP runtime, three launches per frame; with the GPU at ~12 us per
 // frame that single thread is what bounds the asynchronous device-pointer path (tools/only_kernel_eager.sh: 3.2 us per call
@@ -215,6 +223,7 @@ struct xm_handle {
   SurfaceScratch surf;      // xm_process_time_surfaces
   FrameSurfScratch fsurf;   // xm_frames_to_time_surfaces
   FrameCloudScratch fcloud; // xm_cloud_set_tables, xm_frames_to_point_clouds
+  FrameRecordScratch frecord; // xm_frames_to_evt3_words
   std::vector<std::unique_ptr<Worker>> workers;  // one per slot stream (empty: launches happen in the calling thread)
   struct OwnSet {  // the device tables of the owner tiles' plan i (its scalars: plan().own[i])
     DevMem<uint16_t> d_xmap_own;

@@ -97,6 +97,28 @@ int ingest_issue_frame(xm_ingest* g, uint64_t push_no, u64 n) {
     a.max_chunk_blocks = cl.max_chunk_blocks;
     launch_frame_clouds(a, 1, std::min<u64>(n, cl.cap), s);
   }
+  // the record stage the packet was pushed under: the cut frame's EVT 3.0 words (all of them, or none where they exceed max_words)
+  // into ring entry (frame number % ring), behind the cloud stage and in front of everything else that reads the frame, under the
+  // same ordering.  Stage off: nothing is launched
+  if (const int rcs = la.push_record[vi]) {
+    IngestRecord& rec = g->rec;
+    const size_t e = rec.r.entry(la.frames_issued);
+    EncArgs a{};
+    a.desc = cut;
+    a.cap = rec.cap;
+    a.max_words = (u32)rec.max_words;
+    a.code = rec.d_code;
+    a.cnt = rec.d_cnt;
+    a.off = rec.d_off;
+    a.stats = rec.r.d_stats + e;
+    a.words = rec.d_ring + e * rec.max_words;
+    a.tag = rec.r.h_tag + e;
+    a.tag_value = cloud_tag(la.frames_issued);
+    a.host_stats = rec.r.h_stats + e;
+    a.use_vectors = rcs >> 1;
+    a.max_chunk_blocks = rec.max_chunk_blocks;
+    launch_frame_records(a, 1, std::min<u64>(n, rec.cap), s);
+  }
   // one EventCD frame in descriptor form: grids from at least two events, the tiled K1's block from the frame itself
   if (flt) {
     launch_frame_filter(ingest_frame_filter_dev(g, vi, flt, la.push_filter[vi] >> 3), n, s);
@@ -269,6 +291,7 @@ int ingest_process(xm_ingest* g, const IngestJob& j, size_t n, const u32* n_dev 
   la.push_filter[vi] = (unsigned char)(la.filter | (la.intended ? 8 : 0));
   la.push_surface[vi] = (unsigned char)(la.surf_select ? la.surf_select | (la.surf_dtype << 2) : 0);
   la.push_cloud[vi] = (unsigned char)(la.cloud_on ? 1 : 0);
+  la.push_record[vi] = (unsigned char)(la.record_on ? 1 | (la.record_vectors ? 2 : 0) : 0);
   la.dev.desc = fx.d_descs + vi;
   la.dev.info = fx.d_infos + vi;
   la.dev.verdict = fx.d_verdicts + vi;
@@ -363,6 +386,10 @@ int ingest_run_job(xm_ingest* g, const IngestJob& j) {
       break;
     case JobKind::set_cloud:
       g->la.cloud_on = j.cloud_on;
+      break;
+    case JobKind::set_record:
+      g->la.record_on = j.record_on;
+      g->la.record_vectors = j.record_vectors;
       break;
     case JobKind::stop:
     case JobKind::count_only: break;

@@ -73,6 +73,7 @@ enum class JobKind : int {
   set_filter,  // the frame event filter for the frames cut by the packets behind this job (xm_ingest_set_frame_filter)
   set_surface, // the surface stage's setting for the frames cut by the packets behind this job (xm_ingest_set_surface_output)
   set_cloud,   // the cloud stage's setting for the frames cut by the packets behind this job (xm_ingest_set_cloud_output)
+  set_record,  // the record stage's setting for the frames cut by the packets behind this job (xm_ingest_set_record_output)
 };
 inline bool carries_packet(JobKind k) { return k == JobKind::records || k == JobKind::words || k == JobKind::on_device; }
 inline bool copy_side_has_work(JobKind k) { return k == JobKind::records || k == JobKind::words; }
@@ -91,6 +92,7 @@ struct IngestJob {
   int filter = 0, intended = 0;      // set_filter: FILTER_* (0: none) and its semantics
   int surf_select = 0, surf_dtype = 0;  // set_surface: XM_SURFACE_* (0: off) and XM_T_FLOAT32 / XM_T_FLOAT64
   int cloud_on = 0;                  // set_cloud: 1 = on, 0 = off
+  int record_on = 0, record_vectors = 0;  // set_record: 1 = on, 0 = off; vector words or single events only
 };
 
 // launch side -> out thread: one cut frame.  Every cut frame is posted, so frame f is job f + 1 of the out queue.
@@ -267,6 +269,19 @@ struct IngestCloud {
   u32 max_chunk_blocks = 4096;         // ("XM_FC_MAX_BLOCKS", read once)
 };
 
+// EVT 3.0 words of the cut frames (xmaps_evt3enc.hpp) on the frame stream, behind the cloud stage and in front of any frame event
+// filter.  Frame f goes to ring entry f % ring, which holds max_words words: all of the frame's or none (cloud_tag names it).
+struct IngestRecord {
+  IngestRing<EncStats> r;
+  size_t max_words = 0;
+  u32 cap = 0;                         // events the scratch holds: the longest frame the event ring can cut
+  DevMem<uint16_t> d_code;             // [cap]
+  DevMem<uint2> d_cnt;                 // [cap / 64 + 1]
+  DevMem<u32> d_off;                   // [cap / 64 + 1]
+  DevMem<uint16_t> d_ring;             // [ring][max_words]
+  u32 max_chunk_blocks = 4096;         // ("XM_ENC_MAX_BLOCKS", read once)
+};
+
 // Caller side: the thread that calls xm_ingest_push* / poll* / backlog / flush (one at a time, by the API's contract).
 struct IngestCaller {
   uint64_t posted = 0;                 // pushes accepted so far
@@ -297,6 +312,8 @@ struct IngestLaunch {
   unsigned char push_surface[ING_VRING] = {};  // ... and what packet p was pushed under: select | dtype << 2
   int cloud_on = 0;                    // the cloud stage's setting from the last set_cloud job ...
   unsigned char push_cloud[ING_VRING] = {};    // ... and what packet p was pushed under
+  int record_on = 0, record_vectors = 0;       // the record stage's setting from the last set_record job ...
+  unsigned char push_record[ING_VRING] = {};   // ... and what packet p was pushed under: on | use_vectors << 1
   IngestDev dev{};                     // = IngestFixed::dev with the CURRENT packet's desc / info / verdict / act: passed by value to its kernels
   int act_toggle = 0;                  // the set of cells the next non-empty packet takes (ingest_act_set)
   uint64_t act_fused_push = 0;         // the packet whose k_act_first went out with its predecessor's k_ing_count (k_ing_count_act)
@@ -354,6 +371,7 @@ struct xm_ingest {
   IngestFrameFilter ff;
   IngestSurface sf;
   IngestCloud cl;
+  IngestRecord rec;
   IngestCaller ca;
   IngestLaunch la;
   IngestOutSide out;

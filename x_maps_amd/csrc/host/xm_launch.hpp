@@ -303,7 +303,7 @@ void launch_frame_filter(const FrameFilterDev& f, u64 n_bound, hipStream_t strea
 // One launch sequence: n_frames (<= FS_GROUP) frames, the longest of n_max events (the ingest: the verdict's count).  The event
 // pass takes one block per FS_CHUNK events of the longest frame, at most a.max_chunk_blocks; the cell pass one per
 // FS_CELLS_PER_BLOCK cells of the fixed map.
-u32 frame_max_chunk_blocks(const char* option) {  // ("XM_FS_MAX_BLOCKS" / "XM_FC_MAX_BLOCKS": tests send short frames through the
+u32 frame_max_chunk_blocks(const char* option) {  // ("XM_FS_MAX_BLOCKS" / "XM_FC_MAX_BLOCKS" / "XM_ENC_MAX_BLOCKS": tests send short frames through the
   const char* o = dbg_opt(option);                 // chunk loops' further trips)
   const long v = o ? atol(o) : 0;
   return v > 0 && v < 65535 ? (u32)v : 4096u;
@@ -327,6 +327,19 @@ void launch_frame_clouds(const FcArgs& a, unsigned n_frames, u64 n_max, hipStrea
   XM_LAUNCH(k_fc_scan, dim3(n_frames), dim3(FC_SCAN_BLOCK), 0, stream, a);
   if (a.cloud) XM_LAUNCH(k_fc_points, dim3(ge, n_frames), dim3(FC_THREADS), 0, stream, a);
   if (a.tag) XM_LAUNCH(k_fc_publish, dim3(1), dim3(64), 0, stream, a);
+}
+
+// ---- frames -> EVT 3.0 words (xmaps_evt3enc.hpp): the group entry and the ingest's record stage ---------------------------------
+// One launch sequence: n_frames (<= ENC_GROUP) frames, the longest of n_max events (the ingest: the verdict's count).  The three
+// per-event passes take one block per ENC_CHUNK events of the longest frame, at most a.max_chunk_blocks ("XM_ENC_MAX_BLOCKS"); the
+// scan one per frame.
+void launch_frame_records(const EncArgs& a, unsigned n_frames, u64 n_max, hipStream_t stream) {
+  const unsigned ge = std::min<unsigned>(grid_for(n_max < 1 ? 1 : n_max, ENC_CHUNK), a.max_chunk_blocks);
+  XM_LAUNCH(k_enc_runs, dim3(ge, n_frames), dim3(ENC_THREADS), 0, stream, a);
+  XM_LAUNCH(k_enc_count, dim3(ge, n_frames), dim3(ENC_THREADS), 0, stream, a);
+  XM_LAUNCH(k_enc_scan, dim3(n_frames), dim3(ENC_SCAN_BLOCK), 0, stream, a);
+  XM_LAUNCH(k_enc_emit, dim3(ge, n_frames), dim3(ENC_THREADS), 0, stream, a);
+  if (a.tag) XM_LAUNCH(k_enc_publish, dim3(1), dim3(64), 0, stream, a);
 }
 
 

@@ -19,6 +19,7 @@
 #include "xmaps_surface.hpp"        // time surfaces -> depth maps + point clouds
 #include "xmaps_framesurface.hpp"   // frames of events -> camera time surfaces (the group entry and the ingest's surface stage)
 #include "xmaps_framecloud.hpp"     // frames of events -> per-event point clouds (the group entry and the ingest's cloud stage)
+#include "xmaps_evt3enc.hpp"        // frames of events -> EVT 3.0 words (the group entry and the ingest's record stage)
 #include "xmaps_timecal.hpp"        // projector time-map calibration: white-frame time surfaces -> the projector-space time map
 
 #include <hip/hip_ext.h>
@@ -85,6 +86,7 @@ using namespace xm;
 #include "host/xm_api_surface.hpp"  // a group of camera time surfaces -> depth maps + point clouds (the evaluation caller's entry)
 #include "host/xm_api_framesurface.hpp"  // a group of frames of events -> camera time surfaces: what joins the live half to the entries around it
 #include "host/xm_api_framecloud.hpp"    // a group of frames of events -> per-event point clouds: the live half's 3-D output
+#include "host/xm_api_evt3enc.hpp"       // a group of frames of events -> EVT 3.0 words: the way out for the events themselves
 #include "host/xm_api_eslinit.hpp"  // the ESL-init baseline on the same surfaces: depth_init maps, disparity_init alone
 #include "host/xm_api_mc3d.hpp"     // the MC3D baseline on the same surfaces
 #include "host/xm_api_esloptim.hpp" // the ESL depth optimisation behind ESL-init: depth_optim maps

@@ -41,6 +41,7 @@
 // (included by xmaps_hip.hip behind the ingest, whose frame descriptors it reads:)
 //       "xmaps_framesurface.hpp"  frames of events -> camera time surfaces: winners by integer atomics, one store per pixel
 //       "xmaps_framecloud.hpp"    frames of events -> per-event point clouds: codes per event, a scan, a stable compaction
+//       "xmaps_evt3enc.hpp"       frames of events -> EVT 3.0 words: run starts per chain, counts per 64 events, a scan, a stable emit
 //       "xmaps_timecal.hpp"       projector time-map calibration: accumulate, mean, corners, projective warp, fill along rows
 // (and behind the decoders:)
 //       "xmaps_exttrigger.hpp"    EXT_TRIGGER words -> trigger records; the triggered frames' append (p == 1 compaction + trigger remap)

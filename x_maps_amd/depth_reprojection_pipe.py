@@ -127,6 +127,8 @@ class DepthReprojectionPipe:
         self._cloud_callback = getattr(p, "cloud_callback", None)
         if self._cloud_callback is not None:  # (tables without the float rectify maps or Q: ValueError, here and not at the first frame)
             self.calib_maps.engine.set_frame_cloud_tables()
+        self._record_callback = getattr(p, "record_callback", None)
+        self._record_kind = (bool(getattr(p, "record_use_vectors", True)), int(getattr(p, "record_max_words", 1 << 21)))
         # frames cut at the recording's EXT_TRIGGER words instead of pauses (RuntimeParams.frame_sync; ext_trigger.py): a chain of its
         # own behind process_*_words -- decoder with extraction on, TriggeredFrames, the group entries on the device buffer --
         # made on first use; neither the ingest nor the host chain exists in this mode
@@ -149,6 +151,8 @@ class DepthReprojectionPipe:
                 self.ingest.set_surface_output(*self._surface_kind)
             if self._cloud_callback is not None:
                 self.ingest.set_cloud_output(True, int(getattr(p, "cloud_max_points", 262144)))
+            if self._record_callback is not None:
+                self.ingest.set_record_output(True, *self._record_kind)
         else:
             self._ensure_host_chain()
 
@@ -221,6 +225,12 @@ class DepthReprojectionPipe:
                     self.stats_printer.count("cloud lost")
                 else:
                     self._cloud_callback(cloud)
+            if self._record_callback is not None:
+                rec = self.ingest.record(fr.seq)
+                if rec is None:  # (the record ring is as long as the result ring: lapped only where the frame is lost too)
+                    self.stats_printer.count("record lost")
+                else:
+                    self._record_callback(*rec)
             # a fresh array copied out of the pinned result ring, or (RuntimeParams.ingest_frame_views) a view into it that stays
             # valid until ingest_result_ring - 1 further frames have been produced
             self.frame_callback(fr.bgr)
@@ -344,12 +354,14 @@ class DepthReprojectionPipe:
             px = eng.out_h * eng.out_w * 3
             if self._trig_bgr is None:
                 self._trig_bgr = eng.dev_alloc(self.replay_group * px)
-            surfs = clouds = None
+            surfs = clouds = recs = None
             with self.stats_printer.measure_time("x-maps frames (fused, groups)"):
                 if self._surface_callback is not None:
                     surfs, _ = eng.frames_to_time_surfaces_device(ptr, offs, *self._surface_kind)
                 if self._cloud_callback is not None:
                     clouds = eng.frames_to_point_clouds_device(ptr, offs)
+                if self._record_callback is not None:
+                    recs = eng.frames_to_evt3_words(ptr, offs, self._record_kind[0], device=True)
                 fptr, foffs = ptr, offs
                 if on_device:  # (surfaces and clouds are the cut frames', in front of the filter: as the ingest orders its stages)
                     fptr, foffs, _, _ = tf.ready_filtered(n)
@@ -367,6 +379,8 @@ class DepthReprojectionPipe:
                     self._surface_callback(surfs[f])
                 if clouds is not None:
                     self._cloud_callback(clouds[f][0][:int(getattr(self.params, "cloud_max_points", 262144))])
+                if recs is not None:
+                    self._record(recs[0][f], recs[1][f])
                 self.frame_callback(bgr[f])
             tf.release(n)
 
@@ -442,6 +456,10 @@ class DepthReprojectionPipe:
             pos = self.activity_filter(pos)
         self.trigger_finder.process_events(pos)
 
+    def _record(self, words, st):
+        """record_callback as the ingest's record stage calls it: no words (None) for a frame with more than record_max_words"""
+        self._record_callback(words if st.n_words <= self._record_kind[1] else None, st)
+
     # ---- one frame of events -> BGR frame (the hot path) ------------------------------------------------
     def process_ev_frame(self, evs):
         if len(evs) == 0:
@@ -452,6 +470,9 @@ class DepthReprojectionPipe:
         if self._cloud_callback is not None:  # (the same: a group of one through the group entry, the ingest stage's row limit)
             cloud, _ = self.calib_maps.engine.frames_to_point_clouds([evs])[0]
             self._cloud_callback(cloud[:int(getattr(self.params, "cloud_max_points", 262144))])
+        if self._record_callback is not None:  # (the same: a group of one, the ingest stage's all-or-nothing word limit)
+            words, st = self.calib_maps.engine.frames_to_evt3_words([evs], use_vectors=self._record_kind[0])
+            self._record(words[0], st[0])
         if not isinstance(self.ev_filter_proc.selected_filter(), NoFilter):  # pipe:131-139
             with self.stats_printer.measure_time("frame ev filter"):
                 n_before = len(evs)

@@ -99,6 +99,17 @@ class RuntimeParams:
     # either way.  Needs tables with cam_mapx_f32, cam_mapy_f32 and Q (ValueError at construction otherwise).
     cloud_callback: Optional[Callable] = None
     cloud_max_points: int = 262144
+    # record_callback(words, stats) for every shown frame, immediately before that frame's frame_callback (behind its surface and
+    # cloud callbacks): the frame's EVT 3.0 words (uint16: evt3.encode_evt3(frame, record_use_vectors), the encoder's state fresh
+    # for the frame, XMapsEngine.frames_to_evt3_words) and its Evt3RecordStats, built from the CUT frame -- behind the polarity and
+    # activity filters, in front of any frame event filter.  A frame with more than record_max_words words comes with words None
+    # (all or nothing; stats.n_words is the true count).  On the device ingest it is a stage of the ingest
+    # (DeviceIngest.set_record_output); on the host chain, and on the ext_trigger chain, one call of the group entry on the frame's
+    # events or device records.  The same arrays either way.  evt3.FrameRecordingWriter turns the calls into a .raw file that
+    # frame_sync="ext_trigger" replays to the same frames.
+    record_callback: Optional[Callable] = None
+    record_use_vectors: bool = True
+    record_max_words: int = 1 << 21
     # How the stream is cut into projector frames.  "pauses" (the default; nothing changes): the reference's software trigger finder,
     # on the device ingest or the host chain.  "ext_trigger": at the recording's EXT_TRIGGER words -- the pulses of the camera's
     # sync jack, for rigs whose projector is wired to it (the paper's section 3.4; x_maps_amd/ext_trigger.py).  Only

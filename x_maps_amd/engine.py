@@ -79,6 +79,17 @@ class FrameCloudStats(_FrameStageStats):
     t_max: int = 0
 
 
+@dataclass
+class Evt3RecordStats(_FrameStageStats):
+    """xm_evt3_record_stats of one frame's EVT 3.0 words (frames_to_evt3_words, DeviceIngest.record)."""
+    n_events: int = 0
+    n_words: int = 0
+    n_vector_runs: int = 0
+    n_out_of_range: int = 0
+    t_first: int = 0
+    t_last: int = 0
+
+
 def _concat_frames(frames):
     """EventCD frames (host arrays; any may be empty) -> (one EVENT_CD_DTYPE array of all their records, u64 offsets [n + 1]:
     frame f is records [offsets[f], offsets[f + 1])).  Filled frame by frame: np.concatenate would hand back the packed 14-byte
@@ -676,6 +687,60 @@ class XMapsEngine:
             self.dev_free(d_cloud)
             self.dev_free(d_st)
         return out
+
+    # ---- frames of events in, EVT 3.0 words out (a replayable recording of what the pipeline processed) -----------
+    def frames_to_evt3_words(self, events, offsets=None, use_vectors=True, device=False):
+        """Frames of EventCD records in ONE device call -> ([u16 words per frame], [Evt3RecordStats]): per frame exactly
+        evt3.encode_evt3(frame, use_vectors), the encoder's state fresh for every frame (include/xmaps.h, xm_frames_to_evt3_words).
+        events: a list of EventCD arrays (offsets None; any may be empty), or ONE array with u64 offsets [n + 1], frame f =
+        records [offsets[f], offsets[f + 1]).  device=True: `events` is a device pointer to such records (16-byte aligned) and
+        offsets is required: XM_MEM_DEVICE, waited for, and the valid words downloaded."""
+        if device:
+            if offsets is None:
+                raise ValueError("device records need offsets")
+            return self._frames_to_evt3_words_device(events, offsets, use_vectors)
+        if offsets is None:
+            if not len(events):
+                raise ValueError("no frames")
+            evs, offs = _concat_frames(list(events))
+        else:
+            from .synthetic import EVENT_CD_DTYPE
+            evs = np.ascontiguousarray(events if events.dtype == EVENT_CD_DTYPE else events.astype(EVENT_CD_DTYPE))
+            offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offs) - 1
+        if n <= 0:
+            raise ValueError("no frames")
+        if len(offs) and int(offs[-1]) > len(evs):
+            raise ValueError("offsets reach past the records")
+        words = np.empty(max(4 * int(offs[-1] - offs[0]), 1), np.uint16)
+        st = (N.xm_evt3_record_stats * n)()
+        N.check(self._lib.xm_frames_to_evt3_words(self._h, _ptr(evs) if len(evs) else None, offs.ctypes.data_as(C.POINTER(C.c_uint64)), n,
+                                                  int(bool(use_vectors)), N.XM_MEM_HOST, _ptr(words), C.cast(st, C.c_void_p)))
+        out = [words[4 * int(a - offs[0]):4 * int(a - offs[0]) + int(s.n_words)].copy() for a, s in zip(offs[:-1], st)]
+        return out, [Evt3RecordStats.from_c(s) for s in st]
+
+    def _frames_to_evt3_words_device(self, aos_ptr, offsets, use_vectors=True):
+        offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offs) - 1
+        if n <= 0:
+            raise ValueError("no frames")
+        st = (N.xm_evt3_record_stats * n)()
+        d_words, d_st = self.dev_alloc(max(int(offs[-1] - offs[0]), 1) * 8), self.dev_alloc(C.sizeof(st))
+        try:
+            N.check(self._lib.xm_frames_to_evt3_words(self._h, _ptr(aos_ptr), offs.ctypes.data_as(C.POINTER(C.c_uint64)), n,
+                                                      int(bool(use_vectors)), N.XM_MEM_DEVICE, _ptr(d_words), _ptr(d_st)))
+            self.sync()
+            N.check(self._lib.xm_dev_download(self._h, C.cast(st, C.c_void_p), _ptr(d_st), C.sizeof(st)))
+            out = []
+            for a, s in zip(offs[:-1], st):
+                w = np.empty(int(s.n_words), np.uint16)
+                if len(w):
+                    self.dev_download(w, d_words + 8 * int(a - offs[0]))
+                out.append(w)
+        finally:
+            self.dev_free(d_words)
+            self.dev_free(d_st)
+        return out, [Evt3RecordStats.from_c(s) for s in st]
 
     # ---- N3: per-frame de-duplication filters ------------------------------------------------------------
     def frame_event_filter(self, filter_id: int, evs: np.ndarray, xp_i16=None, map_shape=None,

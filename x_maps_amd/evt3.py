@@ -343,8 +343,86 @@ def encode_evt3_singles(evs: np.ndarray) -> np.ndarray:
     return words.astype("<u2")
 
 
+def _raw_header(width: int, height: int) -> bytes:
+    return f"% evt 3.0\n% format EVT3;height={height};width={width}\n% geometry {width}x{height}\n% end\n".encode("ascii")
+
+
 def write_raw(path: str, evs: np.ndarray, width: int = 640, height: int = 480):
-    hdr = f"% evt 3.0\n% format EVT3;height={height};width={width}\n% geometry {width}x{height}\n% end\n".encode("ascii")
     with open(path, "wb") as f:
-        f.write(hdr)
+        f.write(_raw_header(width, height))
         f.write(encode_evt3(evs).tobytes())
+
+
+T_EXT_TRIGGER = 0xA
+REPLAY_MIN_EVENTS = 1000  # frame_sync="ext_trigger" skips frames of this many events or fewer (MIN_EVENTS_PER_FRAME)
+
+
+class FrameRecordingWriter:
+    """A recording of the frames a pipeline SHOWED, replayable through frame_sync="ext_trigger" (ext_trigger_id=0): host code only.
+
+        with FrameRecordingWriter("session.raw", width, height) as rec:
+            params = RuntimeParams(..., record_callback=rec)      # record_callback(words, stats) = rec.write_frame(words, stats)
+
+    Per frame: the two time words of stats.t_first, one EXT_TRIGGER word (id 0, value 1), then the frame's words as the device
+    encoded them (XMapsEngine.frames_to_evt3_words / the ingest's record stage: they begin with their own EVT_TIME_HIGH,
+    EVT_TIME_LOW and EVT_ADDR_Y, so nothing of the previous frame reaches into them).  close() writes the time words of the last
+    frame's t_last and a closing trigger.  The header is write_raw's.  What is recorded is the stream behind the polarity and
+    activity filters and behind the cut: it replays to the same frames whatever the filters' rules are by then.
+
+    Two things a reader of the file must know:
+     - STAMPS come back shifted by a multiple of 2^24 us: EVT 3.0 carries 24 bits of time and a decoder counts a recording's first
+       loop as 0, so a session whose stamps start at 40 000 000 replays from 40 000 000 - 2 * 2^24.  Every output of the pipeline
+       depends on differences inside a frame only.
+     - a pause-cut frame may hold 997 .. 1000 events (the reference's trigger finder asks for more than 1000 and then trims 4),
+       while the ext_trigger chain skips frames of <= 1000 events: such a frame is written like every other, comes back from a
+       cutter with min_events=0, and is NOT shown by the replaying pipeline.  `frames_below_replay_minimum` counts them.
+    Frames that came without words (more than record_max_words: all or nothing) cannot be written: `frames_without_words`."""
+
+    def __init__(self, path: str, width: int, height: int):
+        self._f = open(path, "wb")
+        self._f.write(_raw_header(width, height))
+        self.frames = 0
+        self.frames_below_replay_minimum = 0
+        self.frames_without_words = 0
+        self.words_written = 0
+        self._t_last = None
+
+    def _put(self, words):
+        w = np.ascontiguousarray(words, dtype="<u2")
+        self._f.write(w.tobytes())
+        self.words_written += len(w)
+
+    @staticmethod
+    def _trigger_at(t: int) -> list:
+        return [(T_TIME_HIGH << 12) | ((int(t) >> 12) & 0xfff), (T_TIME_LOW << 12) | (int(t) & 0xfff), (T_EXT_TRIGGER << 12) | 1]
+
+    def write_frame(self, words, stats):
+        if self._f is None:
+            raise ValueError("the recording is closed")
+        if words is None or not stats.n_events:
+            self.frames_without_words += 1
+            return
+        if len(words) != stats.n_words:
+            raise ValueError(f"{len(words)} words, the statistics say {stats.n_words}")
+        self._put(self._trigger_at(stats.t_first))
+        self._put(words)
+        self._t_last = int(stats.t_last)
+        self.frames += 1
+        self.frames_below_replay_minimum += int(stats.n_events <= REPLAY_MIN_EVENTS)
+
+    __call__ = write_frame
+
+    def close(self):
+        if self._f is None:
+            return
+        if self._t_last is not None:
+            self._put(self._trigger_at(self._t_last))
+        self._f.close()
+        self._f = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False

@@ -156,7 +156,7 @@ class DeviceIngest:
         N.check(self._lib.xm_ingest_set_surface_output(self._g, sel, N.XM_T_FLOAT32 if dt == np.float32 else N.XM_T_FLOAT64, int(ring)))
 
     def _ring_copy(self, copy, seq: int, out, st) -> bool:
-        """One xm_ingest_copy_surface / xm_ingest_copy_cloud call into the caller's `out` (None: statistics only) and `st`: did the
+        """One xm_ingest_copy_surface / xm_ingest_copy_cloud / xm_ingest_copy_record call into the caller's `out` (None: statistics only) and `st`: did the
         stage's ring hold frame `seq` from the call's first look at the entry to its last?"""
         rc = copy(self._g, int(seq), C.c_void_p(out.ctypes.data) if out is not None and out.size else None, N.XM_MEM_HOST, C.byref(st))
         if rc < 0:
@@ -204,6 +204,32 @@ class DeviceIngest:
         if not self._ring_copy(copy, seq, out, st2) or bytes(st2) != bytes(st):
             return None
         return (out, FrameCloudStats.from_c(st)) if with_stats else out
+
+    def set_record_output(self, on=True, use_vectors=True, max_words: int = 1 << 21, ring: int = 0):
+        """The record stage for the frames cut by the packets pushed from now on (ordered like a push): every cut frame's EVT 3.0
+        words -- XMapsEngine.frames_to_evt3_words on the CUT frame, in front of any frame event filter -- are kept in a ring of
+        `ring` entries (0: as many as the result ring) of `max_words` words in device memory for record(seq).  All or nothing: a
+        frame with more words keeps none; its statistics report the true count.  max_words and the ring's length are fixed by
+        the first call that switches the stage on."""
+        N.check(self._lib.xm_ingest_set_record_output(self._g, int(bool(on)), int(bool(use_vectors)), int(max_words), int(ring)))
+        if on:
+            self._record_max_words = int(max_words)
+
+    def record(self, seq: int):
+        """(words, Evt3RecordStats) of frame `seq` (IngestFrame.seq): its EVT 3.0 words as the caller's own u16 array -- None in
+        their place when the frame has more than max_words of them --, or None when the ring does not hold the frame (the stage
+        was off when the frame was cut, or the ring has been lapped).  Complete once poll() has handed the frame out."""
+        from .engine import Evt3RecordStats
+        copy = self._lib.xm_ingest_copy_record
+        st, st2 = N.xm_evt3_record_stats(), N.xm_evt3_record_stats()
+        if not self._ring_copy(copy, seq, None, st):  # (the statistics first: they say how many words there are)
+            return None
+        if int(st.n_words) > getattr(self, "_record_max_words", 0):
+            return None, Evt3RecordStats.from_c(st)
+        out = np.empty(int(st.n_words), np.uint16)
+        if not self._ring_copy(copy, seq, out, st2) or bytes(st2) != bytes(st):
+            return None
+        return out, Evt3RecordStats.from_c(st)
 
     def push_pinned(self, evs: np.ndarray):
         """A packet that already lives in pinned host memory (XMapsEngine.host_empty): no staging copy."""
